@@ -13,6 +13,13 @@ step's pages start in pinned HOST memory and are uploaded inside the timed regio
 --resident-pages --vary-pages 1 = rounds 1-3: one set, resident in HBM).  Weights are seed-0 synthetic (no checkpoints exist
 offline) - throughput is weight independent.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the --steps steps and prints the line.  Everything else the benchmark measures (the per-op
+profiling pass and its roofline, the other rec mode, the fp32 precision mode, the formula stage, the backbone alone, the S2 drop-in
+seam, the CPU baseline, the standalone upload and v2-gather timings) runs only with --full:
+
+    python bench.py --full --steps 20 --warmup 5
+    python bench.py --dump-outputs DIR      # + the last timed step's result as DIR/*.npy (same arguments -> same inputs)
 """
 import argparse
 import json
@@ -47,6 +54,36 @@ def _strict_rule(n_lines):
     return ("the reference's batching result: one global np.argsort of all %d lines, chunks of 6, every line padded to int(48 * max ratio of "
             "ITS chunk) (rapid_ocr.py:404-449); launches are runs of that sorted list sized by rd_rec_plan_chunks, every line computed at its "
             "own padded width inside the launch tensor (rd_rec_backbone_forward_lines)" % n_lines)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out, dirname):
+    """--dump-outputs: the last timed step's gathered, page-ordered result - what the timed path hands its caller, one row per text
+    line: its global page index, its confidence and its text as Unicode code points (-1 after the end of the string).  Above
+    DUMP_LIMIT_BYTES a fixed seeded sample of the lines is written; `line_index` says which."""
+    pages_, scores, texts = [], [], []
+    for page, lines in out:
+        for text, score in lines:
+            pages_.append(page)
+            scores.append(score)
+            texts.append(text)
+    n = len(texts)
+    width = max([len(t) for t in texts], default=0)
+    keep = np.arange(n)
+    row_bytes = 8 * (3 + width)
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    codes = np.full((len(keep), width), -1.0, dtype=np.float64)
+    for r, i in enumerate(keep):
+        codes[r, :len(texts[i])] = [ord(c) for c in texts[i]]
+    arrays = {"line_index": keep.astype(np.float64), "line_page": np.asarray(pages_, dtype=np.float64)[keep],
+              "line_score": np.asarray(scores, dtype=np.float64)[keep], "line_text_codepoints": codes}
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / (name + ".npy"), a)
 
 
 def load_states():
@@ -353,6 +390,13 @@ def main():
                          "every step start in pinned HOST memory, like the arrays the reference hands to a batch (batch_analyze.py:108-111), "
                          "and are uploaded inside the timed region by PageUploader (copy stream, batch i + 1 under batch i)")
     ap.add_argument("--no-extra-passes", action="store_true", help="skip the post-passes (other rec mode, fp32 precision, backbone alone)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: the per-op profiling pass (roofline), the "
+                         "post-passes (unless --no-extra-passes), the CPU baseline (unless --no-cpu-baseline), the standalone upload and "
+                         "v2-gather timings.  Off: only what pages/s and ms_per_step need (--dump-profile still runs the profiling pass)")
+    ap.add_argument("--dump-outputs", type=str, default="",
+                    help="write the last timed step's gathered, page-ordered result to DIR/*.npy (rank 0): line_index, line_page, "
+                         "line_score, line_text_codepoints (float64; a fixed seeded sample of the lines if the arrays would exceed 64 MB)")
     args = ap.parse_args()
 
     if not torch.cuda.is_available():
@@ -368,15 +412,18 @@ def main():
         raise SystemExit("bench.py: --gpus %d asked for, %d device(s) visible: one rank per GPU over RCCL needs %d devices"
                          % (args.gpus, n_dev, args.gpus))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # a bare `python bench.py --gpus N`: start the N ranks ourselves, exactly as the driver's torchrun line does
+        # a bare `python bench.py --gpus N`: start the N ranks ourselves, exactly as the driver's torchrun line does.
+        # The launcher is a child process, never an exec of this one: this process has already opened the GPU (device count above)
         import socket
+        import subprocess
         with socket.socket() as s_:
             s_.bind(("127.0.0.1", 0))
             port = s_.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(port), str(Path(__file__).resolve())] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        rc = subprocess.run(cmd).returncode
+        raise SystemExit(rc if rc >= 0 else 128 - rc)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -586,17 +633,21 @@ def main():
     out = run_steps(args.steps)
     fence()
     dt = time.perf_counter() - t0
-    # the product's gather of whole per-page results (dist.gather_page_dets, wire format v2 - what PageAnalyzer's List[List[dict]] travels
-    # in): one call on this step's lines as OcrText-span dicts, every rank, outside the timed region (the timed
-    # region gathers the flat (text, score) format v1)
-    from rapiddoc_amd.dist import gather_page_dets
-    last_local = [(i, [{"category_id": 15, "poly": [float(k) for k in range(8)], "score": s_, "text": t_} for t_, s_ in lines])
-                  for i, lines in out if i in set(my_pages)]
-    fence()
-    tg = time.perf_counter()
-    v2 = gather_page_dets(last_local, dist)
-    gather_v2_ms = (time.perf_counter() - tg) * 1e3
-    assert [i for i, _ in v2] == [i for i, _ in out]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+    gather_v2_ms = None
+    if args.full:
+        # the product's gather of whole per-page results (dist.gather_page_dets, wire format v2 - what PageAnalyzer's List[List[dict]] travels
+        # in): one call on this step's lines as OcrText-span dicts, every rank, outside the timed region (the timed
+        # region gathers the flat (text, score) format v1)
+        from rapiddoc_amd.dist import gather_page_dets
+        last_local = [(i, [{"category_id": 15, "poly": [float(k) for k in range(8)], "score": s_, "text": t_} for t_, s_ in lines])
+                      for i, lines in out if i in set(my_pages)]
+        fence()
+        tg = time.perf_counter()
+        v2 = gather_page_dets(last_local, dist)
+        gather_v2_ms = (time.perf_counter() - tg) * 1e3
+        assert [i for i, _ in v2] == [i for i, _ in out]
     if os.environ.get("RD_BENCH_STOP_AFTER_TIMED") == "1":      # developer: a kernel trace whose tail is the timed steps (tools/trace_gaps.py)
         print("timed region: %.2f ms per step" % (dt / args.steps * 1e3), file=sys.stderr)
         return
@@ -604,7 +655,7 @@ def main():
     plan_misses = sum(p["plans_built"] for p in plan_stats) - plans_before
     captures_timed = sum(p["graph_captures"] for p in plan_stats) - captures_before
     h2d_ms = None
-    if upload:          # one batch's upload alone, outside the timed region (inside it the copies run under the previous batch)
+    if upload and args.full:          # one batch's upload alone, outside the timed region (inside it the copies run under the previous batch)
         torch.cuda.synchronize()
         th = time.perf_counter()
         uploader.wait(uploader.submit(page_sets[0][0]))
@@ -634,7 +685,7 @@ def main():
             pp.rec_width_sync = None
     # ---- roofline of the dominant kernel: per-op HIP events (recorded by the library on the launch stream)
     roof = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.dump_profile):
         engines = pool.engines
         for e in engines:
             e.set_profiling(True)
@@ -731,7 +782,7 @@ def main():
     # ---- post-passes (N = 1 only, rank 0, after the timed region; each a few steps): the OTHER rec batching mode, the pure
     # fp32-MFMA precision mode, the layout backbone alone.  All measured in this very run - no constants in the line.
     extra = {}
-    if rank == 0 and world == 1 and not args.no_extra_passes:
+    if args.full and rank == 0 and world == 1 and not args.no_extra_passes:
         def timed_steps(fn, n, w):
             for _ in range(w):
                 fn()
@@ -794,7 +845,7 @@ def main():
                        "rec_mode": args.rec_mode,
                        "rec_launch_batches": int(pool.stats.get("rec_batches", 0)),
                        "pages_per_gpu": P, "global_pages": n_global, "pages_gathered": len(out), "result_crc32": result_crc,
-                       "gather_page_dets_v2_ms": round(gather_v2_ms, 2),      # one gather of this step's results as per-page dict lists (wire format v2), all ranks
+                       "gather_page_dets_v2_ms": None if gather_v2_ms is None else round(gather_v2_ms, 2),      # (--full) one gather of this step's results as per-page dict lists (wire format v2), all ranks
                        "rec_width_sync": (None if width_sync is None else {"collective_calls": width_sync.calls,
                                           "what": "global argsort / chunks of 6 over the lines of all ranks (dist.GlobalLineWidths)"}),
                        "page_sets_cycled": K_sets, "setup_steps": max(0, args.setup_steps), "setup_passes_over_all_page_sets": max(0, args.setup_passes),
@@ -824,7 +875,7 @@ def main():
             "roofline": roof,
         }
         rec.update(extra)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(states, cores_per_rank or os.cpu_count() or 1)
         print(json.dumps(rec), flush=True)
     if dist:

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-timeout 600 python bench.py --steps 20 --warmup 5 --dump-profile $O/${TAG}_bench_per_kernel.csv 2>/dev/null | tail -1 > $O/${TAG}_bench.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 --dump-profile $O/${TAG}_bench_per_kernel.csv 2>/dev/null | tail -1 > $O/${TAG}_bench.json
 cd /tmp && export TMPDIR=/tmp
 # (the profiled passes run the round-1..3 form of the workload - one resident page set - so that per-kernel figures stay comparable
 #  across rounds and a pass does not spend 20 s synthesising eight page sets; the kernels and their launch sizes are the same)

@@ -21,7 +21,7 @@ python $R/tools/pmc_traffic.py $O/${TAG}_pmc_FETCH_SIZE.csv $O/${TAG}_pmc_WRITE_
 cp $O/${TAG}_pmc_traffic.json $R/profiles/pmc_traffic.json          # what bench.py reads (committed from gpurun_out afterwards)
 unset RD_BENCH_STOP_AFTER_TIMED
 cd $R
-timeout 900 python bench.py --steps 20 --warmup 5 --dump-profile $O/${TAG}_bench_per_kernel.csv 2>/dev/null | tail -1 > $O/${TAG}_bench.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 --dump-profile $O/${TAG}_bench_per_kernel.csv 2>/dev/null | tail -1 > $O/${TAG}_bench.json
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$TAG -o s -- python $R/bench.py --no-cpu-baseline --no-extra-passes $ONE > /tmp/rp.log 2>&1
 cp /tmp/rp_$TAG/s_kernel_stats.csv $O/${TAG}_rocprofv3_kernel_stats.csv

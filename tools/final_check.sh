@@ -2,7 +2,7 @@ set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; cd $R
 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 > $O/r4_gputest_final.log
 cat $O/r4_gputest_final.log
-timeout 600 python bench.py --steps 20 --warmup 5 --dump-profile $O/r4_bench_per_kernel.csv 2>/dev/null | tail -1 > $O/r4_bench.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 --dump-profile $O/r4_bench_per_kernel.csv 2>/dev/null | tail -1 > $O/r4_bench.json
 python -c "
 import json; r=json.load(open('$O/r4_bench.json')); print(r['value'], r['ms_per_step'], r['config']['step_wall_ms'], r['roofline']['kernel'], r['roofline']['frac'], r['roofline']['traffic'], r['formula'] if 'formula' in r else None)"
 {
