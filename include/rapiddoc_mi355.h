@@ -38,9 +38,12 @@ typedef struct rd_handle rd_handle;
 #define RD_REC_UNFUSED_CTC 1  /* materialise logits, then row statistics (validation path)              */
 #define RD_REC_WANT_SOFTMAX 2 /* also write softmax probabilities [B,T,C] (the reference session output) */
 #define RD_REC_WANT_LOGITS 4  /* also write raw logits [B,T,C]                                          */
+#define RD_REC_WANT_NECK 64   /* "ppocrv5_rec_server" only, instead of the two above: full_btc_dev receives the neck's output
+                               * [B,T,120] (the CTC classifier's input); idx / prob come from the fused head as with flags 0 */
 
 const char* rd_version(void);
-/* model_kind: "ppocrv6_det" | "ppocrv6_rec" | "pphgnetv2_b4" | "pphgnetv2_b6_formula" | "ppformulanet_head".  NULL on failure -> rd_create_error(). */
+/* model_kind: "ppocrv6_det" | "ppocrv6_rec" | "ppocrv5_rec_server" (PPHGNetV2-B4 + SVTR neck + CTC; every rd_rec_* call except
+ * rd_rec_backbone_forward_lines) | "pphgnetv2_b4" | "pphgnetv2_b6_formula" | "ppformulanet_head".  NULL on failure -> rd_create_error(). */
 rd_handle* rd_create(int device_id, const char* model_kind);
 const char* rd_create_error(void);
 void rd_destroy(rd_handle* h);

@@ -38,6 +38,9 @@ static int guarded(rd_handle* h, F&& f) {
     }
 }
 
+// the recogniser kinds share one C surface (rd_rec_*)
+static bool is_rec_kind(const std::string& k) { return k == "ppocrv6_rec" || k == "ppocrv5_rec_server"; }
+
 extern "C" {
 
 const char* rd_version(void) { return "rapiddoc_mi355 0.3 (gfx950; fp32 results, split-fp16 + fp32 MFMA kernels)"; }
@@ -89,7 +92,7 @@ int rd_query_workspace(rd_handle* h, int B, int H, int W, int flags, size_t* ws_
     return guarded(h, [&] {
         RD_CHECK(ws_bytes, "ws_bytes is NULL");
         RD_CHECK(h->eng, "this model kind owns its workspace");
-        if (h->eng->kind() == "ppocrv6_rec" && !(flags & rd::REC_STAGE_TAIL)) H = 48;
+        if (is_rec_kind(h->eng->kind()) && !(flags & rd::REC_STAGE_TAIL)) H = 48;
         *ws_bytes = h->eng->workspace_bytes(B, H, W, flags);
     });
 }
@@ -105,17 +108,18 @@ int rd_det_forward(rd_handle* h, const float* x, int B, int H, int W, float* pro
 int rd_rec_forward(rd_handle* h, const float* x, int B, int W, int32_t* idx, float* prob, float* full, int flags, void* ws,
                    size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && h->eng->kind() == "ppocrv6_rec", "handle is not a ppocrv6_rec model");
+        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server) model");
         RD_CHECK(x && idx && prob && B > 0, "null input/output");
-        if (flags & (RD_REC_WANT_SOFTMAX | RD_REC_WANT_LOGITS)) RD_CHECK(full, "full_btc_dev is NULL");
+        if (flags & (RD_REC_WANT_SOFTMAX | RD_REC_WANT_LOGITS | RD_REC_WANT_NECK)) RD_CHECK(full, "full_btc_dev is NULL");
         RD_CHECK(!((flags & RD_REC_WANT_SOFTMAX) && (flags & RD_REC_WANT_LOGITS)), "choose softmax OR logits");
+        RD_CHECK(!(flags & RD_REC_WANT_NECK) || flags == RD_REC_WANT_NECK, "RD_REC_WANT_NECK goes with no other flag");
         h->eng->run(B, 48, W, flags, {(void*)x, (void*)idx, (void*)prob, (void*)full}, ws, ws_bytes, (hipStream_t)stream);
     });
 }
-int rd_rec_token_dim(rd_handle* h) { return (h && h->eng && h->eng->kind() == "ppocrv6_rec") ? h->eng->rec_token_dim() : -1; }
+int rd_rec_token_dim(rd_handle* h) { return (h && h->eng && is_rec_kind(h->eng->kind())) ? h->eng->rec_token_dim() : -1; }
 int rd_rec_backbone_forward(rd_handle* h, const float* x, int B, int W, float* tokens, void* ws, size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && h->eng->kind() == "ppocrv6_rec", "handle is not a ppocrv6_rec model");
+        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server) model");
         RD_CHECK(x && tokens && B > 0, "null input/output");
         h->eng->run(B, 48, W, rd::REC_STAGE_BACKBONE, {(void*)x, (void*)tokens}, ws, ws_bytes, (hipStream_t)stream);
     });
@@ -123,6 +127,9 @@ int rd_rec_backbone_forward(rd_handle* h, const float* x, int B, int W, float* t
 int rd_rec_backbone_forward_lines(rd_handle* h, const float* x, int B, int W, const int32_t* line_tab, float* tokens, void* ws, size_t ws_bytes,
                                   void* stream) {
     return guarded(h, [&] {
+        RD_CHECK(!(h->eng && h->eng->kind() == "ppocrv5_rec_server"),
+                 "rd_rec_backbone_forward_lines: per-line widths inside one backbone launch are out of scope for ppocrv5_rec_server "
+                 "(run the backbone stage once per padded width)");
         RD_CHECK(h->eng && h->eng->kind() == "ppocrv6_rec", "handle is not a ppocrv6_rec model");
         RD_CHECK(x && tokens && line_tab && B > 0, "null input/output");
         h->eng->run(B, 48, W, rd::REC_STAGE_BACKBONE | rd::REC_LINE_WIDTHS, {(void*)x, (void*)tokens, (void*)line_tab}, ws, ws_bytes,
@@ -132,7 +139,7 @@ int rd_rec_backbone_forward_lines(rd_handle* h, const float* x, int B, int W, co
 int rd_rec_tail_forward(rd_handle* h, const float* tokens, int n_tokens, int n_lines, int max_tokens, const int32_t* seg,
                         const int32_t* tokinfo, int32_t* idx, float* prob, void* ws, size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && h->eng->kind() == "ppocrv6_rec", "handle is not a ppocrv6_rec model");
+        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server) model");
         RD_CHECK(tokens && seg && tokinfo && idx && prob && n_tokens > 0 && n_lines > 0 && max_tokens > 0, "null input/output");
         h->eng->run(n_lines, max_tokens, n_tokens, rd::REC_STAGE_TAIL,
                     {(void*)tokens, (void*)idx, (void*)prob, nullptr, (void*)seg, (void*)tokinfo}, ws, ws_bytes, (hipStream_t)stream);
@@ -496,6 +503,52 @@ float rd_debug_gemm_h1(int M, int K, int N, int act, int iters, float* x, int xl
     if (range_out) *range_out = (int)*flag;
     (void)hipHostFree(flag);
     (void)hipFree(img);
+    return ms;
+}
+
+// developer entry: the 1 x 3 sequence convolution alone (kernels_seqconv.hip).  x0 [M][ld0] / x1 [M][ld1] (or null) = the two K segments,
+// w [N][3 (C0 + C1)] fp32 in the kernel's order (tap, then segment 0 | segment 1 channels), tokinfo [M] (or null: uniform lines of T
+// tokens), split != 0: the split-fp16 route (the weights are split here the way the engine splits them), else native fp32.
+// Returns ms per launch (iters timed launches after one untimed), or -1 when the kernel does not take the shape.
+float rd_debug_seqconv(int M, int C0, int C1, int N, int T, int act, int split, int iters, float* x0, int ld0, float* x1, int ld1, float* w, float* b,
+                       const int32_t* tokinfo, float* y, int yld, int* range_out) {
+    if (M <= 0 || !rd::seqconv_shape_ok(C0, C1, N) || ld0 % 4 || ld1 % 4 || (!tokinfo && T <= 0)) return -1.f;
+    rd::SeqConvParams p{};
+    p.x0 = x0; p.ld0 = ld0; p.C0 = C0; p.x1 = C1 ? x1 : nullptr; p.ld1 = C1 ? ld1 : 0; p.C1 = C1;
+    p.w = w; p.bias = b; p.y = y; p.yld = yld; p.M = M; p.N = N; p.T = T; p.tokinfo = tokinfo; p.act = act;
+    const int K = 3 * (C0 + C1);
+    void *dh = nullptr, *dl = nullptr;
+    unsigned* flag = nullptr;
+    (void)hipHostMalloc((void**)&flag, sizeof(unsigned), hipHostMallocMapped);
+    *flag = 0;
+    if (split) {
+        std::vector<float> hw((size_t)N * K);
+        if (hipMemcpy(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+        std::vector<uint16_t> hi, lo;
+        rd::split_weights_h3(hw.data(), N, K, hi, lo);
+        if (hipMalloc(&dh, hi.size() * 2) != hipSuccess || hipMalloc(&dl, lo.size() * 2) != hipSuccess) return -1.f;
+        (void)hipMemcpy(dh, hi.data(), hi.size() * 2, hipMemcpyHostToDevice);
+        (void)hipMemcpy(dl, lo.data(), lo.size() * 2, hipMemcpyHostToDevice);
+        p.wh = (const uint16_t*)dh; p.wl = (const uint16_t*)dl;
+        p.range_flag = flag;
+    }
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    rd::launch_seqconv(p, nullptr);
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) rd::launch_seqconv(p, nullptr);
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    ms = iters > 0 ? ms / iters : 0.f;
+    (void)hipDeviceSynchronize();
+    if (hipGetLastError() != hipSuccess) ms = -1.f;
+    if (range_out) *range_out = (int)*flag;
+    (void)hipHostFree(flag);
+    if (dh) (void)hipFree(dh);
+    if (dl) (void)hipFree(dl);
     return ms;
 }
 

@@ -803,13 +803,19 @@ TView Builder::stem_front(const std::string& w1, const std::string& bn1, const s
 }
 
 TView Builder::stem_tail(const std::string& w3, const std::string& bn3, const std::string& w4, const std::string& bn4, const TView& x, int act3,
-                         int act4, const TView* out) {
+                         int act4, const TView* out, int s3) {
     const int n1 = weight_dim(w3, 0), cin = weight_dim(w3, 1), n2 = weight_dim(w4, 0);
     ConvGeom g3;
     g3.kh = g3.kw = 3;
-    g3.sh = g3.sw = 2;
+    g3.sh = g3.sw = s3;
     g3.pt = g3.pl = g3.pb = g3.pr = 1;
     ConvGeom g1;
+    if (s3 != 2) {       // the fused kernel (and its weight image) is a stride-2 kernel
+        TView s3v = conv(w3, "", bn3, x, g3, act3);
+        TView s4v = conv(w4, "", bn4, s3v, g1, act4, out);
+        release(s3v);
+        return s4v;
+    }
     const std::string fkey = w3 + "|" + bn3 + "|" + w4 + "|" + bn4 + "|stemtail";
     const int oh = out_dim(x.h, 3, 2, 1, 1), ow = out_dim(x.w, 3, 2, 1, 1);
     // (fused: 16-byte float4 accesses on both sides - channel strides and the output view's channel offset are multiples of four floats;
@@ -870,6 +876,77 @@ TView Builder::stem_tail(const std::string& w3, const std::string& bn3, const st
         q.x = pl.vptr(xv, c);
         q.y = pl.vptr(yv, c);
         launch_stem34(q, c.stream);
+    };
+    emit(std::move(r));
+    return y;
+}
+
+TView Builder::seqconv(const std::string& wname, const std::string& bn, const TView& x0, const TView* x1, int act, const TView* tokinfo) {
+    const HostTensor& w = ws_->get(wname);
+    RD_CHECK(w.shape.size() == 4 && w.shape[3] == 3 && (w.shape[2] == 1 || w.shape[2] == 3), "seqconv weight shape [Cout][Cin][1|3][3]: " + wname);
+    const int cout = (int)w.shape[0], cin = (int)w.shape[1], kh = (int)w.shape[2];
+    const int c0 = x0.c, c1 = x1 ? x1->c : 0;
+    RD_CHECK(cin == c0 + c1, "seqconv Cin mismatch: " + wname);
+    RD_CHECK(seqconv_shape_ok(c0, c1, cout), "seqconv: channel counts (segments % 16, Cout % 64): " + wname);
+    RD_CHECK(x0.h == 1 && (!x1 || (x1->h == 1 && x1->n == x0.n && x1->w == x0.w)), "seqconv: one row of tokens per line: " + wname);
+    const bool ragged = tokinfo != nullptr;
+    RD_CHECK(!ragged || x0.n == 1, "ragged seqconv: one token row");
+    TView y = alloc(x0.n, 1, x0.w, cout);
+    const int K = 3 * cin;
+    const std::string key = wname + "|" + bn + "|seq";
+    if (!planning()) {
+        if (!pb_->has(key + "#w")) {
+            std::vector<float> shift;
+            std::vector<float> scale = bn_scale_shift(bn, cout, shift);
+            std::vector<float> wf((size_t)cout * K);
+            const float* src = w.f32();
+            const int mid = kh / 2;
+            for (int co = 0; co < cout; ++co)
+                for (int ci = 0; ci < cin; ++ci)
+                    for (int t = 0; t < 3; ++t) wf[(size_t)co * K + (size_t)t * cin + ci] = src[(((size_t)co * cin + ci) * kh + mid) * 3 + t] * scale[co];
+            pb_->add(key + "#w", wf);
+            pb_->add(key + "#b", shift);
+            if (fits_fp16_range(wf)) {      // (both split precision modes take the split route: the layer is the tail's widest)
+                std::vector<uint16_t> hi, lo;
+                split_weights_h3(wf.data(), cout, K, hi, lo);
+                pb_->add_u16(key + "#wh", hi);
+                pb_->add_u16(key + "#wl", lo);
+            }
+        }
+        return y;
+    }
+    SeqConvParams p{};
+    p.ld0 = plan_->ld(x0); p.C0 = c0;
+    p.ld1 = x1 ? plan_->ld(*x1) : 0; p.C1 = c1;
+    RD_CHECK(p.ld0 % 4 == 0 && x0.coff % 4 == 0 && p.ld1 % 4 == 0 && (!x1 || x1->coff % 4 == 0), "seqconv: 16-byte aligned token rows");
+    p.w = pb_->ptr(key + "#w");
+    p.bias = pb_->ptr(key + "#b");
+    const bool split = (h3_ || mixer_h3_) && pb_->has(key + "#wh");
+    if (split) {
+        p.wh = reinterpret_cast<const uint16_t*>(pb_->ptr(key + "#wh"));
+        p.wl = reinterpret_cast<const uint16_t*>(pb_->ptr(key + "#wl"));
+        p.range_flag = range_flag_;
+    }
+    p.yld = plan_->ld(y);
+    p.M = (int)x0.pixels(); p.N = cout;
+    p.T = x0.w;
+    p.act = act;
+    OpRecord r;
+    r.name = wname;
+    r.kind = "seqconv1x3";
+    r.cfg = std::string(c1 ? "2seg" : "1seg") + (ragged ? "/ragged" : "/uniform") + (split ? "/h3" : "/f32");
+    r.shape = "M" + std::to_string(p.M) + "_K" + std::to_string(K) + "_N" + std::to_string(cout);
+    r.flops = 2.0 * p.M * (double)K * cout;
+    r.bytes = 4.0 * ((double)p.M * cin + (double)p.M * cout) + 4.0 * (double)cout * K;
+    const TView x0v = x0, x1v = x1 ? *x1 : TView{}, yv = y, tiv = ragged ? *tokinfo : TView{};
+    const bool has1 = x1 != nullptr;
+    r.run = [p, x0v, x1v, yv, tiv, has1, ragged](const Plan& pl, const RunCtx& c) {
+        SeqConvParams q = p;
+        q.x0 = pl.vptr(x0v, c);
+        q.x1 = has1 ? pl.vptr(x1v, c) : nullptr;
+        q.y = pl.vptr(yv, c);
+        q.tokinfo = ragged ? reinterpret_cast<const int32_t*>(pl.vptr(tiv, c)) : nullptr;
+        launch_seqconv(q, c.stream);
     };
     emit(std::move(r));
     return y;
@@ -1300,7 +1377,7 @@ Engine::Engine(int device, const std::string& kind) : device_(device), kind_(kin
         RD_CHECK(v == "auto" || v == "fp32" || v == "h3", "RD_PRECISION must be auto, fp32 or h3");
         precision_ = v == "h3" ? PREC_H3 : v == "fp32" ? PREC_FP32 : PREC_AUTO;
     }
-    RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "pphgnetv2_b4" || kind == "pphgnetv2_b6_formula",
+    RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "pphgnetv2_b4" || kind == "pphgnetv2_b6_formula",
              "unknown model kind '" + kind + "'");
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
@@ -1346,6 +1423,7 @@ Engine::~Engine() {
 void Engine::build(Builder& b, int B, int H, int W, int flags) {
     if (kind_ == "ppocrv6_det") build_ppocrv6_det(b, B, H, W);
     else if (kind_ == "ppocrv6_rec") build_ppocrv6_rec(b, B, H, W, flags);
+    else if (kind_ == "ppocrv5_rec_server") build_ppocrv5_rec_server(b, B, H, W, flags);
     else if (kind_ == "pphgnetv2_b6_formula") build_pphgnetv2_b6_formula(b, B, H, W, flags);
     else build_pphgnetv2_b4(b, B, H, W);
 }
@@ -1357,6 +1435,9 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
     if (kind_ == "ppocrv6_rec") {
         n_classes_ = (int)store_.get("head.head.weight").shape[0];  // torch.py:112-116
         rec_token_dim_ = (int)store_.get("head.encoder.conv_block.0.convolution.weight").shape[1];
+    } else if (kind_ == "ppocrv5_rec_server") {
+        n_classes_ = (int)store_.get("head.ctc_head.fc.weight").shape[0];
+        rec_token_dim_ = (int)store_.get("head.ctc_encoder.encoder.conv1.conv.weight").shape[1];
     }
     Plan dummy;
     h3_prepared_ = precision_ == PREC_H3;
@@ -1367,7 +1448,7 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
     RD_HIP(hipHostGetDevicePointer((void**)&range_flag_, (void*)range_flag_host_, 0));
     Builder b(Mode::PREPARE, &store_, &params_, &dummy, h3_prepared_, true);
     // smallest legal geometry; only weight names/shapes matter in PREPARE mode
-    if (kind_ == "ppocrv6_rec") build(b, 1, 48, 64, 0), build(b, 1, 48, 64, REC_UNFUSED_CTC);
+    if (kind_ == "ppocrv6_rec" || kind_ == "ppocrv5_rec_server") build(b, 1, 48, 64, 0), build(b, 1, 48, 64, REC_UNFUSED_CTC);
     else build(b, 1, 64, 64, 0);
     params_.upload();
     loaded_ = true;

@@ -191,8 +191,14 @@ class Builder {
                      const std::string& w2b, const std::string& bn2b, const TView& x_nchw);
     // stem3 (3x3 / stride 2 / pad 1 + BN + act) -> stem4 (1x1 + BN + act): one fused kernel in the split-fp16 precision modes
     // (kernels_stem34.hip, round 6), the two convolutions otherwise.  `out`: where stem4's output goes (a channel slot of a concat buffer)
+    // `s3`: stride of stem3 (2; 1 in the text-recognition geometry of PPHGNetV2 - the fused kernel is a stride-2 kernel, stride 1 takes
+    // the two convolutions)
     TView stem_tail(const std::string& w3, const std::string& bn3, const std::string& w4, const std::string& bn4, const TView& x, int act3,
-                    int act4, const TView* out = nullptr);
+                    int act4, const TView* out = nullptr, int s3 = 2);
+    // 1 x 3 sequence convolution over token rows (kernels_seqconv.hip): weight `wname` [Cout][C0 + C1][1 | 3][3] (of a 3 x 3 only the middle
+    // row: the map is one row high, the other two only ever meet padding) + BatchNorm `bn`; x0 / x1 = the two K segments (x1 may be null).
+    // Uniform form: x0 is [B][1][T][C0]; ragged form: [1][1][W][C0] with tokinfo (as Builder::dwconv)
+    TView seqconv(const std::string& wname, const std::string& bn, const TView& x0, const TView* x1, int act, const TView* tokinfo = nullptr);
     struct GapOut { TView partial; int chunks = 0; };  // per-image partial sums of a layer's output (SE pooling)
     TView dwconv(const std::string& wname, const std::string& bname, const std::string& bn, const TView& x,
                  const ConvGeom& g, int act, const TView* out = nullptr, const TView* res = nullptr, GapOut* gap = nullptr,
@@ -316,8 +322,10 @@ void build_ppocrv6_det(Builder& b, int B, int H, int W);
 // 2 prob, 4 seg int32 [B][2], 5 tokinfo int32 [W]) - see build_ppocrv6_rec
 // REC_LINE_WIDTHS (with REC_STAGE_BACKBONE): ext[2] = LineTab int32 [B][4] (rd_kernels.h) - every line is computed at ITS OWN padded
 // width inside the shared [B,3,48,W] tensor and writes its own number of tokens at its own offset of ext[1]
-enum RecFlags : int { REC_UNFUSED_CTC = 1, REC_WANT_SOFTMAX = 2, REC_WANT_LOGITS = 4, REC_STAGE_BACKBONE = 8, REC_STAGE_TAIL = 16, REC_LINE_WIDTHS = 32 };
+enum RecFlags : int { REC_UNFUSED_CTC = 1, REC_WANT_SOFTMAX = 2, REC_WANT_LOGITS = 4, REC_STAGE_BACKBONE = 8, REC_STAGE_TAIL = 16, REC_LINE_WIDTHS = 32, REC_WANT_NECK = 64 };
 void build_ppocrv6_rec(Builder& b, int B, int H, int W, int flags);
+// PP-OCRv5 server recogniser (PPHGNetV2-B4 text_rec + SVTR neck + CTC): same externals, flags and stages; REC_LINE_WIDTHS is refused
+void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags);
 void build_pphgnetv2_b4(Builder& b, int B, int H, int W);
 // PP-FormulaNet_plus encoder; flags bit 0: the caller's image has 1 channel (replicated to 3 like the reference)
 void build_pphgnetv2_b6_formula(Builder& b, int B, int H, int W, int flags);

@@ -194,6 +194,7 @@ void build_ppocrv6_det(Builder& b, int B, int H, int W) {
 void build_ppocrv6_rec(Builder& b, int B, int H, int W, int flags) {
     const bool tail_only = (flags & REC_STAGE_TAIL) != 0, backbone_only = (flags & REC_STAGE_BACKBONE) != 0;
     RD_CHECK(!(tail_only && backbone_only), "rec: choose one stage");
+    RD_CHECK(!(flags & REC_WANT_NECK), "RD_REC_WANT_NECK is offered by ppocrv5_rec_server only");
     const std::string e = "head.encoder";
     auto cw = [&](int i) { return e + ".conv_block." + std::to_string(i) + ".convolution.weight"; };
     auto cbn = [&](int i) { return e + ".conv_block." + std::to_string(i) + ".normalization"; };
@@ -295,12 +296,20 @@ void build_ppocrv6_rec(Builder& b, int B, int H, int W, int flags) {
 // PPHGNetV2-B4 (det=True): the PP-DocLayout-L / plus-L / V2 / V3 backbone.
 // ext[0] = x NCHW [B,3,H,W]; ext[1..4] = stage outputs NCHW (strides 4/8/16/32; 128/512/1024/2048 ch)
 // ---------------------------------------------------------------------------------------------------
-struct HgStageCfg { int cin, mid, cout, blocks; bool down, light; int k, layers; };
+struct HgStageCfg { int cin, mid, cout, blocks; bool down, light; int k, layers; int sh = 2, sw = 2; };   // (sh, sw): strides of the depthwise downsample
 static const HgStageCfg kB4Det[4] = {
     {48, 48, 128, 1, false, false, 3, 6},
     {128, 96, 512, 1, true, false, 3, 6},
     {512, 192, 1024, 3, true, true, 5, 6},
     {1024, 384, 2048, 1, true, true, 5, 6},
+};
+
+// text_rec=True geometry (ocr .../backbones/rec_pphgnetv2.py:1437-1443): every stage downsamples, one axis at a time; stem3 has stride 1
+static const HgStageCfg kB4Rec[4] = {
+    {48, 48, 128, 1, true, false, 3, 6, 2, 1},
+    {128, 96, 512, 1, true, false, 3, 6, 1, 2},
+    {512, 192, 1024, 3, true, true, 5, 6, 2, 1},
+    {1024, 384, 2048, 1, true, true, 5, 6, 2, 1},
 };
 
 static const HgStageCfg kB6Formula[4] = {   // rec_pphgnetv2.py:1601-1607
@@ -313,7 +322,7 @@ static const HgStageCfg kB6Formula[4] = {   // rec_pphgnetv2.py:1601-1607
 // Shared PPHGNetV2 body.  `pre` = state-dict prefix ("" or "backbone.pphgnet_b6.").  Every stage output listed in
 // `want` is handed to `emit(stage, view)`.
 template <typename Emit>
-static void build_pphgnetv2(Builder& b, const TView& x, const HgStageCfg (&cfg)[4], const std::string& pre, Emit emit) {
+static void build_pphgnetv2(Builder& b, const TView& x, const HgStageCfg (&cfg)[4], const std::string& pre, Emit emit, int stem3_stride = 2) {
     const int B = x.n;
     auto cw = [&](const std::string& p) { return pre + p + ".conv.weight"; };
     auto bn = [&](const std::string& p) { return pre + p + ".bn"; };
@@ -326,22 +335,25 @@ static void build_pphgnetv2(Builder& b, const TView& x, const HgStageCfg (&cfg)[
     auto new_cat = [&](int n, int h, int w, const HgStageCfg& c, int cin) { return b.alloc(n, h, w, cin + c.layers * c.mid); };
     {
         const HgStageCfg& c = cfg[0];
-        RD_CHECK(!c.down, "PPHGNetV2: the first stage does not downsample");
-        const int s3h = (cat.h + 2 - 3) / 2 + 1, s3w = (cat.w + 2 - 3) / 2 + 1;      // stem3: 3x3 / stride 2 / pad 1
-        cur_cat = new_cat(B, s3h, s3w, c, c.cin);
+        const int s3h = (cat.h + 2 - 3) / stem3_stride + 1, s3w = (cat.w + 2 - 3) / stem3_stride + 1;      // stem3: 3x3 / pad 1
+        // (a first stage that downsamples takes the stem's output from a plain buffer; its own concat buffer is made below)
+        cur_cat = c.down ? b.alloc(B, s3h, s3w, c.cin) : new_cat(B, s3h, s3w, c, c.cin);
         cur = b.slice(cur_cat, 0, c.cin);
-        b.stem_tail(cw("stem.stem3"), bn("stem.stem3"), cw("stem.stem4"), bn("stem.stem4"), cat, ACT_RELU, ACT_RELU, &cur);
+        b.stem_tail(cw("stem.stem3"), bn("stem.stem3"), cw("stem.stem4"), bn("stem.stem4"), cat, ACT_RELU, ACT_RELU, &cur, stem3_stride);
         b.release(cat);
     }
     for (int si = 0; si < 4; ++si) {
         const HgStageCfg& c = cfg[si];
         const std::string sp = "stages." + std::to_string(si);
         RD_CHECK(si == 0 || c.down, "PPHGNetV2: stages 2-4 downsample");
-        if (c.down) {  // depthwise 3x3 stride 2 + BN, no activation (HGV2_Stage.downsample)
-            const int oh = (cur.h + 2 - 3) / 2 + 1, ow = (cur.w + 2 - 3) / 2 + 1;
+        if (c.down) {  // depthwise 3x3 stride (sh, sw) + BN, no activation (HGV2_Stage.downsample)
+            const int oh = (cur.h + 2 - 3) / c.sh + 1, ow = (cur.w + 2 - 3) / c.sw + 1;
             TView ncat = new_cat(B, oh, ow, c, c.cin);
             TView nin = b.slice(ncat, 0, c.cin);
-            b.dwconv(cw(sp + ".downsample"), "", bn(sp + ".downsample"), cur, geom(3, 2), ACT_NONE, &nin);
+            G gd = geom(3, 2);
+            gd.sh = c.sh;
+            gd.sw = c.sw;
+            b.dwconv(cw(sp + ".downsample"), "", bn(sp + ".downsample"), cur, gd, ACT_NONE, &nin);
             b.release(cur_cat);
             cur_cat = ncat;
             cur = nin;
@@ -409,6 +421,115 @@ void build_pphgnetv2_b6_formula(Builder& b, int B, int H, int W, int flags) {
         TView o = b.external(1, B, v.h, v.w, v.c);
         b.copy(v, o);
     });
+}
+
+// ---------------------------------------------------------------------------------------------------
+// PP-OCRv5 server rec (arch_config.yaml ch_PP-OCRv5_rec_server): PPHGNetV2_B4(text_rec=True) -> EncoderWithSVTR (necks/rnn.py:90-200,
+// dims 120, depth 2, kernel [1, 3], use_guide) -> CTCHead Linear(120, classes).  Externals and the two-stage form as build_ppocrv6_rec
+// (tokens are [.][2048]); per-line widths inside one backbone launch (REC_LINE_WIDTHS) are not offered for this kind.
+// ---------------------------------------------------------------------------------------------------
+void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags) {
+    const bool tail_only = (flags & REC_STAGE_TAIL) != 0, backbone_only = (flags & REC_STAGE_BACKBONE) != 0;
+    RD_CHECK(!(tail_only && backbone_only), "rec: choose one stage");
+    RD_CHECK(!(flags & REC_LINE_WIDTHS), "ppocrv5_rec_server: per-line widths inside one backbone launch are out of scope for this kind");
+    const std::string e = "head.ctc_encoder.encoder";
+    auto cw = [&](const char* n) { return e + "." + n + ".conv.weight"; };
+    auto cbn = [&](const char* n) { return e + "." + n + ".norm"; };
+    const int Cb = b.weight_dim(cw("conv1"), 1);
+    TView h, seg, tokinfo;
+    int T, n_seq = B;
+    if (tail_only) {
+        RD_CHECK((flags & ~REC_STAGE_TAIL) == 0, "rec tail: fused CTC only");
+        RD_CHECK(B >= 1 && H >= 1 && H < 32768 && W >= B, "rec tail: B lines, H = longest line (tokens), W = all tokens");
+        h = b.external(0, 1, 1, W, Cb);
+        seg = b.external(4, B, 1, 1, 2);
+        tokinfo = b.external(5, 1, 1, W, 1);
+        T = H;
+    } else {
+        RD_CHECK(H == 48, "rec input height must be 48");
+        RD_CHECK(W >= 16, "rec input width must be >= 16");
+        TView x = b.external(0, B, H, W, 3);
+        if (backbone_only) RD_CHECK((flags & ~REC_STAGE_BACKBONE) == 0, "rec backbone stage takes no other flag");
+        // the height collapse avg_pool2d([3, 2]) runs while the last stage's buffer is live
+        build_pphgnetv2(b, x, kB4Rec, "backbone.", [&](int si, const TView& v) {
+            if (si != 3) return;
+            RD_CHECK(v.c == Cb, "rec server: backbone width");
+            if (backbone_only) {
+                TView out = b.external(1, B, 1, (v.w - 2) / 2 + 1, v.c);
+                b.avgpool3x2(v, &out);
+            } else {
+                h = b.avgpool3x2(v);
+            }
+        }, 1);
+        if (backbone_only) return;
+        T = h.w;
+        RD_CHECK(h.h == 1, "rec: pooled height");
+    }
+    const TView* ti = tail_only ? &tokinfo : nullptr;
+    const TView* sg = tail_only ? &seg : nullptr;
+
+    TView z1 = b.seqconv(cw("conv1"), cbn("conv1"), h, nullptr, ACT_SILU, ti);
+    TView t = b.conv(cw("conv2"), "", cbn("conv2"), z1, geom(1), ACT_SILU);
+    b.release(z1);
+    const int C = t.c, heads = 8, hd = C / heads;
+    int depth = 0;
+    while (b.has_weight(e + ".svtr_block." + std::to_string(depth) + ".norm1.weight")) ++depth;
+    for (int d = 0; d < depth; ++d) {    // Block(prenorm=False) of THIS reference: x + mixer(norm1(x)); x + mlp(norm2(x)) (rec_svtrnet.py:255-262)
+        const std::string p = e + ".svtr_block." + std::to_string(d);
+        TView y = b.layernorm(p + ".norm1", t, 1e-5f);
+        TView qkv = b.linear(p + ".mixer.qkv", y, ACT_NONE);
+        b.release(y);
+        TView a = b.attention(qkv, n_seq, T, heads, hd, sg);
+        b.release(qkv);
+        TView t2 = b.linear(p + ".mixer.proj", a, ACT_NONE, nullptr, &t);
+        b.release(a);
+        b.release(t);
+        TView y2 = b.layernorm(p + ".norm2", t2, 1e-5f);
+        TView m = b.linear(p + ".mlp.fc1", y2, ACT_SILU);
+        b.release(y2);
+        t = b.linear(p + ".mlp.fc2", m, ACT_NONE, nullptr, &t2);
+        b.release(m);
+        b.release(t2);
+    }
+    TView n = b.layernorm(e + ".norm", t, 1e-6f);
+    b.release(t);
+    TView z3 = b.conv(cw("conv3"), "", cbn("conv3"), n, geom(1), ACT_SILU);
+    b.release(n);
+    TView z4 = b.seqconv(cw("conv4"), cbn("conv4"), h, &z3, ACT_SILU, ti);   // cat(h, z3) is never written: two K segments
+    b.release(z3);
+    b.release(h);
+    TView seq = b.conv(cw("conv1x1"), "", cbn("conv1x1"), z4, geom(1), ACT_SILU);
+    b.release(z4);
+
+    if (flags & REC_WANT_NECK) {         // the classifier's input, for the parity tests of the neck
+        RD_CHECK(flags == REC_WANT_NECK, "rec: RD_REC_WANT_NECK goes with no other flag");
+        TView o = b.external(3, B, 1, T, seq.c);
+        b.copy(seq, o);
+    }
+    const std::string fc = "head.ctc_head.fc";
+    const int ncls = b.weight_dim(fc + ".weight", 0);
+    TView idx = tail_only ? b.external(1, 1, 1, W, 1) : b.external(1, B, 1, T, 1);
+    TView prob = tail_only ? b.external(2, 1, 1, W, 1) : b.external(2, B, 1, T, 1);
+    const bool want_full = (flags & (REC_WANT_SOFTMAX | REC_WANT_LOGITS)) != 0;
+    if ((flags & REC_UNFUSED_CTC) || want_full) {
+        if (flags & REC_WANT_LOGITS) {
+            TView lg = b.external(3, B, 1, T, ncls);
+            b.linear(fc, seq, ACT_NONE, &lg);
+            b.ctc_stats(lg, idx, prob);
+        } else {
+            TView lg = b.linear(fc, seq, ACT_NONE);
+            if (flags & REC_WANT_SOFTMAX) {
+                TView sm = b.external(3, B, 1, T, ncls);
+                b.softmax_rows(lg, sm, &idx, &prob);
+            } else {
+                b.ctc_stats(lg, idx, prob);
+            }
+            b.release(lg);
+        }
+    } else {
+        b.ctc_head(fc, seq, idx, prob);
+    }
+    b.release(seq);
 }
 
 }  // namespace rd

@@ -115,6 +115,24 @@ void launch_conv_stream_h3(const ConvParams& p, hipStream_t s);
 inline bool conv_stream_h3_shape_ok(int kh, int kw, int cin, int cout) {
     return cin % 4 == 0 && cin <= 64 && kh * kw * ((cin + 15) / 16 * 16) <= 256 && cout <= 96;
 }
+// 1 x 3 sequence convolution over token rows with two K segments (kernels_seqconv.hip): the SVTR neck's conv1 / conv4 of the PP-OCRv5
+// server recogniser.  Y[m][n] = act(sum_tap sum_c X[m + tap - 1][c] W[n][tap Cin + c] + bias[n]), Cin = C0 + C1, channels [0, C0) read
+// from x0 and [C0, Cin) from x1; row m + tap - 1 counts as zero where it leaves m's text line.
+struct SeqConvParams {
+    const float* x0; int ld0, C0;     // token rows [M][ld0]; pointers and row strides 16-byte aligned, C0 % 16 == 0
+    const float* x1; int ld1, C1;     // second K segment, or nullptr / 0 / 0
+    const float* w;                   // fp32 [N][3 Cin], BN folded (the native fp32 route)
+    const uint16_t* wh; const uint16_t* wl;   // the same matrix as (hi, lo) fp16 planes (split_weights_h3: rows padded to 32), or nullptr: fp32 route
+    const float* bias;                // [N] or nullptr
+    float* y; int yld;
+    int M, N;                         // N % 64 == 0
+    int T;                            // uniform form: M = B T rows, every line has T tokens
+    const int32_t* tokinfo;           // ragged form (or nullptr): [M] position in the line | tokens of the line << 16
+    int act;
+    unsigned* range_flag;             // split route: raised when an operand leaves the fp16 range
+};
+bool seqconv_shape_ok(int C0, int C1, int N);
+void launch_seqconv(const SeqConvParams& p, hipStream_t s);
 // a short human-readable tag of the tile configuration chosen for p (for the per-op profile)
 const char* conv_igemm_config_name(const ConvParams& p);
 

@@ -13,7 +13,8 @@ import torch
 from . import _lib, weights as W
 
 REC_UNFUSED_CTC, REC_WANT_SOFTMAX, REC_WANT_LOGITS = 1, 2, 4
-KINDS = ("ppocrv6_det", "ppocrv6_rec", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
+REC_WANT_NECK = 64          # ppocrv5_rec_server: `full` receives the neck's output [B, T, 120] instead
+KINDS = ("ppocrv6_det", "ppocrv6_rec", "ppocrv5_rec_server", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
 
 
 def rec_line_table(widths, first_tokens) -> np.ndarray:
@@ -181,19 +182,20 @@ class RdEngine:
         if H != 48:
             raise EngineError("rec input height must be 48")
         T = self._l.rd_rec_seq_len(W_)
-        want_full = bool(flags & (REC_WANT_SOFTMAX | REC_WANT_LOGITS))
+        want_full = bool(flags & (REC_WANT_SOFTMAX | REC_WANT_LOGITS | REC_WANT_NECK))
+        n_full = 120 if flags & REC_WANT_NECK else None       # (the SVTR neck's `dims`; every other flag: the class count)
         if out is not None:
             idx, prob, full = out
             ok = (idx.shape == (B, T) and idx.dtype == torch.int32 and idx.is_contiguous() and prob.shape == (B, T)
                   and prob.dtype == torch.float32 and prob.is_contiguous()
-                  and (not want_full or (full is not None and full.shape == (B, T, self.num_classes) and full.dtype == torch.float32
+                  and (not want_full or (full is not None and full.shape == (B, T, n_full or self.num_classes) and full.dtype == torch.float32
                                          and full.is_contiguous())))
             if not ok:
                 raise EngineError("rec_forward: `out` tensors do not match the forward's shapes")
         else:
             idx = torch.empty((B, T), dtype=torch.int32, device=x.device)
             prob = torch.empty((B, T), dtype=torch.float32, device=x.device)
-            full = torch.empty((B, T, self.num_classes), dtype=torch.float32, device=x.device) if want_full else None
+            full = torch.empty((B, T, n_full or self.num_classes), dtype=torch.float32, device=x.device) if want_full else None
 
         def launch():
             self._chk(self._l.rd_rec_forward(self._h, x.data_ptr(), B, W_, idx.data_ptr(), prob.data_ptr(),

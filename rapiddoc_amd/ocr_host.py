@@ -300,6 +300,25 @@ def rec_batches_lines(wh_ratios: Sequence[float], rec_batch_num: int = 6, img_h:
     return out, line_w
 
 
+def rec_batches_equal_width(order: np.ndarray, line_w: np.ndarray, max_columns: int = 64 * 1088, n_max: int = 160) -> List[Tuple[np.ndarray, int]]:
+    """Launches of ONE padded width each from `rec_batches_lines`' sorted list (`order` = its concatenated indices, `line_w` = the
+    reference width per line in that order): runs of equal width, cut into launches of at most `n_max` lines and `max_columns` pixel
+    columns (never fewer than 6 lines, the reference's own chunk).  For a recogniser that has no per-line widths inside a launch."""
+    order, line_w = np.asarray(order), np.asarray(line_w, dtype=np.int64)
+    out: List[Tuple[np.ndarray, int]] = []
+    i, n = 0, len(order)
+    while i < n:
+        w = int(line_w[i])
+        j = i
+        while j < n and int(line_w[j]) == w:
+            j += 1
+        cap = max(6, min(n_max, max_columns // max(w, 1)))
+        for a in range(i, j, cap):
+            out.append((order[a: min(a + cap, j)], w))
+        i = j
+    return out
+
+
 def rec_resized_width(w: float, h: float, wpad: int, img_h: int = REC_IMG_H) -> int:
     """resize_norm_img: resized_w = min(imgW, ceil(imgH * w/h))."""
     return int(min(wpad, math.ceil(img_h * (w / h))))

@@ -117,7 +117,9 @@ class PagePipeline:
                  rec_batch_num: Optional[int] = None, rec_width_multiple: int = 32, keep_feats: bool = False, n_rec_streams: int = 4,
                  rec_mode: Optional[str] = None, rec_chunking: Optional[str] = None):
         """`states`: {'ppocrv6_det': ..., 'ppocrv6_rec': ..., 'pphgnetv2_b4': ...}, each a .safetensors path,
-        bytes, or name->ndarray dict.
+        bytes, or name->ndarray dict.  The recogniser may be given as 'ppocrv5_rec_server' instead of 'ppocrv6_rec' (PPHGNetV2-B4 +
+        SVTR neck + CTC): strict mode then runs the backbone stage once per distinct reference width (that kind has no per-line widths
+        inside a launch), everything behind the token buffer - the ragged tail, the collapse, word boxes - is the same.
 
         `rec_mode`: how the text lines are batched for the recogniser.  A line's logits depend on its batch's padded width
         (LightSVTR attends over the zero-padded columns), so the batching is part of the result:
@@ -160,11 +162,17 @@ class PagePipeline:
         self.det = RdEngine("ppocrv6_det", device, guard="deferred", reuse_outputs=True).load_weights(states["ppocrv6_det"])
         # rec batches are independent: they alternate between `n_rec_streams` HIP streams (one engine handle = one
         # workspace per stream) so that the launch gaps / tails of one batch are filled by kernels of the other
-        self.rec_engines = [RdEngine("ppocrv6_rec", device, guard="deferred").load_weights(states["ppocrv6_rec"]) for _ in range(max(1, n_rec_streams))]
+        rec_kinds = [k for k in ("ppocrv6_rec", "ppocrv5_rec_server") if k in states]
+        if len(rec_kinds) != 1:
+            raise ValueError("states must carry exactly one recogniser: 'ppocrv6_rec' or 'ppocrv5_rec_server'")
+        self.rec_kind = rec_kinds[0]
+        # strict mode: lines of different reference widths share a launch only where the kind computes per-line widths inside one
+        self.rec_lines_in_launch = self.rec_kind == "ppocrv6_rec"
+        self.rec_engines = [RdEngine(self.rec_kind, device, guard="deferred").load_weights(states[self.rec_kind]) for _ in range(max(1, n_rec_streams))]
         self.rec = self.rec_engines[0]
         self.rec_streams = [torch.cuda.Stream(device=self.tdev) for _ in self.rec_engines]
         # neck + CTC head of the two-stage recogniser: own handle (own workspace) and stream, it runs under the next backbones
-        self.rec_tail = RdEngine("ppocrv6_rec", device, guard="deferred").load_weights(states["ppocrv6_rec"])
+        self.rec_tail = RdEngine(self.rec_kind, device, guard="deferred").load_weights(states[self.rec_kind])
         self.tail_stream = torch.cuda.Stream(device=self.tdev)
         self.layout_stream = torch.cuda.Stream(device=self.tdev)
         # det runs on a stream of its own, so that the NEXT batch's det + layout forwards can be enqueued under this batch's
@@ -387,6 +395,10 @@ class PagePipeline:
                 line_keys = key[keep] if image_keys is not None else page_of[keep].astype(np.int64)
                 given = self._synced_widths(sync, line_keys, np.asarray(ratios, dtype=np.float64))
             batches, line_w, line_ratio = ocr_host.rec_batches_lines(ratios, n_cu=self.n_cu, with_ratio=True, given=given)
+            if not self.rec_lines_in_launch:
+                # same lines, same order, same reference width per line - but a launch holds lines of ONE width (a line's result depends
+                # on its pixels and its padded width only, so the launch boundaries do not enter the result)
+                batches = ocr_host.rec_batches_equal_width(np.concatenate([c for c, _w in batches]), line_w)
         elif not strict and self.rec_chunking == "adaptive":
             batches = ocr_host.rec_batches_adaptive(ratios, width_multiple=self.rec_width_multiple, n_cu=self.n_cu)
         else:
@@ -473,7 +485,7 @@ class PagePipeline:
                 tokens[int(group_base[gi]) + int(group_lens[gi].sum()): int(group_base[gi + 1])].zero_()
             group_tables = [self.rec_tail.rec_tail_tables(lp, dev, out=self._buf(("tail_tab", gi), 2 * len(lp) + int(lp.sum()), torch.int32))
                             for gi, (lp, _t) in enumerate(group_pad)]   # uploaded now, used later
-            if lines_mode:
+            if lines_mode and self.rec_lines_in_launch:
                 tab_h = torch.from_numpy(rec_line_table(line_w, first_tok)).pin_memory()
                 linetab = self._buf("rec_linetab", 4 * n, torch.int32).view(n, 4)
                 linetab.copy_(tab_h, non_blocking=True)
@@ -542,7 +554,7 @@ class PagePipeline:
                                                          ocr_host.REC_IMG_H, wpad, 1, x.data_ptr(), st.cuda_stream)   # stage 2
                 if rc != 0:
                     raise RuntimeError("rd_line_resize_norm_batch failed")
-                if lines_mode:
+                if lines_mode and self.rec_lines_in_launch:
                     self.rec_engines[k].rec_backbone_forward_lines(x, linetab[pos: pos + nb], tokens)
                     ev = torch.cuda.Event()
                     ev.record(st)

@@ -224,15 +224,53 @@ class LazySoftmax(np.lib.mixins.NDArrayOperatorsMixin):
         return "LazySoftmax(shape=%s, %s)" % (self.shape, "materialized" if self.materialized else "on device")
 
 
+# Recogniser architectures this engine serves, by weight-file stem - the reference picks the graph the same way, from the stem through
+# arch_config.yaml (rapid_doc/model/ocr/torch.py:69-76; "ch_PP-OCRv6_small_rec_infer" is the yaml's own key for the v6 file).
+REC_ARCH_BY_STEM = {
+    "ch_PP-OCRv6_rec_small": "ppocrv6_rec",
+    "ch_PP-OCRv6_small_rec_infer": "ppocrv6_rec",
+    "ch_PP-OCRv5_rec_server": "ppocrv5_rec_server",
+}
+
+
+def resolve_rec_kind(weights: WeightSrc) -> str:
+    """Engine kind of a recogniser's weights: a file goes by its stem (an unknown one is an error, as in the reference - never a guess at
+    the graph), a state dict or a safetensors byte image without a name by the CTC classifier it carries (`head.ctc_head.fc.weight`:
+    the v5 server MultiHead; `head.head.weight`: the v6 LightSVTR head)."""
+    if isinstance(weights, (str, Path)):
+        stem = Path(str(weights)).stem
+        if stem not in REC_ARCH_BY_STEM:
+            raise ValueError(f"architecture {stem} is not in the recognisers this engine serves {sorted(REC_ARCH_BY_STEM)}")
+        return REC_ARCH_BY_STEM[stem]
+    if isinstance(weights, (bytes, bytearray, memoryview)):
+        import json
+        import struct
+        blob = bytes(weights[:8])
+        (hlen,) = struct.unpack("<Q", blob)
+        keys = set(json.loads(bytes(weights[8:8 + hlen])))
+    else:
+        keys = set(weights)
+    keys = {k[len("model."):] if k.startswith("model.") else k for k in keys}
+    if "head.ctc_head.fc.weight" in keys:
+        return "ppocrv5_rec_server"
+    if "head.head.weight" in keys:
+        return "ppocrv6_rec"
+    raise ValueError("architecture of the recogniser weights is not in the recognisers this engine serves "
+                     "(neither head.ctc_head.fc.weight nor head.head.weight among the tensors)")
+
+
 class Mi355RecSession(_BaseSession):
-    """PP-OCRv6 rec: [B,3,48,W] -> softmax(ctc_logits) [B,T,C] (ocr/torch.py:185-187).
+    """PP-OCRv6 small / PP-OCRv5 server rec: [B,3,48,W] -> softmax(ctc_logits) [B,T,C] (ocr/torch.py:185-187; the v5 CTCHead applies
+    the softmax itself, rec_ctc_head.py:51-53 - the session's result is the same tensor for both).  The kind follows from the weights
+    (`resolve_rec_kind`) unless `kind` names it.
 
     `lazy_softmax` (default True): the result is a `LazySoftmax` - an array-like that holds the tensor in HBM, answers the CTC decode's
     `argmax(axis=2)` / `max(axis=2)` from the device's own reductions of it, and turns into the exact ndarray on any other access.
     False: a plain ndarray per call (the round-1..5 behaviour; `copy_out` then picks between a fresh array and a pinned view)."""
     kind = "ppocrv6_rec"
 
-    def __init__(self, weights: WeightSrc, device: int = 0, lazy_softmax: bool = True):
+    def __init__(self, weights: WeightSrc, device: int = 0, lazy_softmax: bool = True, kind: Optional[str] = None):
+        self.kind = kind or resolve_rec_kind(weights)
         super().__init__(weights, device)
         self.lazy_softmax = lazy_softmax
         self.softmax_materialized = 0          # LazySoftmax results that were copied off the device after all

@@ -67,6 +67,8 @@ def synth_tensor(name: str, shape: Tuple[int, ...], dtype: str, seed: int) -> np
             std *= 0.5
         if name == "head.head.weight":  # CTC classifier: spread the logits so argmax varies over time
             std *= 6.0
+        if name == "head.ctc_head.fc.weight":  # PP-OCRv5 server CTC classifier: its neck output is nearly flat, 30x opens the top-2 gaps
+            std *= 30.0
         return rng.normal(0.0, std, shape).astype(np.float32)
     return rng.normal(0.0, 0.05, shape).astype(np.float32)
 
