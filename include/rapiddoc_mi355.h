@@ -184,6 +184,12 @@ int rd_ctc_collapse(int device_id, const int32_t* idx_bt_dev, const float* prob_
 int rd_ctc_collapse_lines(int device_id, const int32_t* idx_dev, const float* prob_dev, int n_lines, const int32_t* seg_dev, int max_tokens,
                           const uint8_t* char_table_dev, int max_len, int n_classes, uint8_t* out_dev, int row_bytes, uint16_t* kept_cols_dev,
                           float* kept_conf_dev, void* stream);
+/* Host: n rows of rd_ctc_collapse / rd_ctc_collapse_lines (HOST memory, row_bytes apart) -> text_out = the lines' UTF-8 texts back to
+ * back (line b = bytes byte_off_out[b] .. byte_off_out[b + 1], byte_off_out has n + 1 entries), n_chars_out[b] = its number of code
+ * points, conf_out[b] = the confidence as double, conf3_out[b] = float(f"{conf:.3f}") of it (analyze_utils.py:280).  text_cap =
+ * capacity of text_out in bytes (n * (row_bytes - 16) always suffices).  Returns 0, 1 = bad arguments / a corrupt row, 2 = capacity. */
+int rd_ctc_rows_text(const uint8_t* rows_host, int n, int row_bytes, uint8_t* text_out, int64_t text_cap, int64_t* byte_off_out,
+                     int32_t* n_chars_out, double* conf_out, double* conf3_out);
 
 /* DB post-process (HOST pointers, runs on the host like the reference's): probability maps [B][H][W] -> text boxes.
  * Replaces rapidocr DBPostProcess.__call__ as patched in rapid_doc/model/ocr/ocr_patch.py:223-241 (box_type "quad",
@@ -208,6 +214,15 @@ size_t rd_db_boxes_workspace(int B, int H, int W, int max_runs, int max_candidat
 int rd_db_boxes_device(int device_id, const float* prob_dev, int B, int H, int W, const int32_t* src_hw_dev, float thresh, float box_thresh,
                        float unclip_ratio, int use_dilation, int max_candidates, int max_runs, void* ws_dev, size_t ws_bytes,
                        rd_text_box* out_dev, int max_out, int32_t* n_out_dev, void* stream);
+
+/* Host: what follows the DB post-process for a whole page batch (rapid_doc/utils/ocr_utils.py:105-127 sorted_boxes, then
+ * merge_det_boxes :16-67,130-317).  boxes: [B][max_in] records as rd_db_postprocess / rd_db_boxes_device leave them (HOST memory; the
+ * first counts[b] of page b are read, the scores are not).  Coordinates are truncated toward zero to integers; reading order = stable
+ * sort by (y, x) of the first corner + adjacent swaps inside a row (top-left y closer than 10); merge = axis-aligned boxes sorted by
+ * top y, grouped into lines by y-overlap > 0.6 with the box before, lines wider than 4 x their height fused where their x intervals
+ * touch, tilted boxes (diagonal extent outside 0.8 .. 1.2 of the mean side height) appended unchanged.  float32 arithmetic, bit for bit
+ * what rapiddoc_amd.ocr_host.merge_det_boxes(sorted_boxes(.)) returns.  quads_out: float32 [B][max_in][4][2], n_out: int32 [B]. */
+int rd_text_boxes_order_merge(const rd_text_box* boxes, const int32_t* counts, int B, int max_in, float* quads_out, int32_t* n_out);
 
 /* PP-DocLayout post-process, rectangle mode (HOST pointers).  Replaces PPPostProcess.__call__ with
  * layout_shape_mode="rect": rapid_doc/model/layout/rapid_layout_self/model_handler/pp_doclayout/post_process.py:20-243.
@@ -285,6 +300,15 @@ int rd_fill_poly(uint8_t* img, int h, int w, const int32_t* pts, int n, int valu
 double rd_rec_chunk_cost(int n_lines, int wpad, int n_cu);
 int rd_rec_plan_chunks(const int32_t* wpad_sorted, int n, int n_min, int n_max, int n_step, int n_cu, int32_t* sizes_out, int max_out,
                        int32_t* n_out);
+/* Host, strict mode: all of the line bookkeeping between the crop sizes and the launches in one call.  ratios[n] = w/h of the pooled
+ * lines, order[n] = their sort order (the caller's np.argsort, the reference's own call: rapid_ocr.py:414).  Chunks of rec_batch_num
+ * lines of that order give line i of the SORTED list its reference width line_w_out[i] = int(img_h * max(img_w / img_h, chunk max ratio))
+ * (double arithmetic) and line_ratio_out[i] = that maximum (CTCLabelDecode's max_wh_ratio); the widths rounded up to launch_multiple go
+ * through rd_rec_plan_chunks: sizes_out / launch_w_out [*n_out <= max_out] = lines and tensor width of every launch.  Returns 0 on
+ * success, 1 on bad arguments (an index of `order` outside [0, n), a ratio that is not finite). */
+int rd_rec_plan_lines(const double* ratios, const int64_t* order, int n, int rec_batch_num, int img_h, int img_w, int launch_multiple,
+                      int n_min, int n_max, int n_step, int n_cu, int64_t* line_w_out, double* line_ratio_out, int32_t* sizes_out,
+                      int32_t* launch_w_out, int max_out, int32_t* n_out);
 
 /* Arithmetic of the dense layers of a network handle; every mode returns fp32 tensors with fp32-level error
  * (the reference runs the same layers through onnxruntime / torch fp32: rapid_doc/model/ocr/.../torch.py:58-76).

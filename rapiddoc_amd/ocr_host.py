@@ -10,12 +10,20 @@ sites in the reference and from the public PaddleOCR definitions of the same ste
 from __future__ import annotations
 
 import math
+import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
 REC_IMG_H = 48
 REC_IMG_W = 320
+
+
+def host_native_default() -> bool:
+    """The host stages between the GPU stages (box ordering + merging, the strict mode's line widths, CTC rows -> strings) run in the
+    library (csrc/host_stages.cpp, csrc/rec_chunks.cpp) unless RD_HOST_NATIVE=0 asks for the Python restatements below, which stay the
+    definition of the result (tests/test_host_native_*.py hold the two equal bit for bit)."""
+    return os.environ.get("RD_HOST_NATIVE", "1") != "0"
 
 
 def rec_seq_len(W: int) -> int:
@@ -126,6 +134,28 @@ def parse_ctc_rows(rows: np.ndarray) -> List[Tuple[str, float]]:
     nbytes = head[:, :4].view("<i4")[:, 0]
     conf = head[:, 4:8].view("<f4")[:, 0]
     return [(rows[b, 16:16 + int(nbytes[b])].tobytes().decode("utf-8"), float(conf[b])) for b in range(rows.shape[0])]
+
+
+def parse_ctc_rows_native(rows: np.ndarray) -> Tuple[List[str], List[float], List[float]]:
+    """`parse_ctc_rows` + `format_score` for all rows in one library call (`rd_ctc_rows_text`): (texts, confidences, confidences as
+    `format_score` rounds them).  The texts arrive as one UTF-8 buffer, decoded once and sliced by character counts."""
+    from . import _lib
+    lib = _lib.load()
+    rows = np.ascontiguousarray(rows)
+    n, row_bytes = rows.shape
+    cap = n * max(0, row_bytes - 16)
+    text = np.empty(max(cap, 1), np.uint8)
+    off = np.empty(n + 1, np.int64)
+    n_chars = np.empty(n, np.int32)
+    conf, conf3 = np.empty(n, np.float64), np.empty(n, np.float64)
+    rc = lib.rd_ctc_rows_text(rows.ctypes.data, n, row_bytes, text.ctypes.data, cap, off.ctypes.data, n_chars.ctypes.data,
+                              conf.ctypes.data, conf3.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("rd_ctc_rows_text failed")
+    s = text[: int(off[n])].tobytes().decode("utf-8")
+    ends = np.cumsum(n_chars, dtype=np.int64).tolist()
+    texts = [s[a:e] for a, e in zip([0] + ends[:-1], ends)]
+    return texts, conf.tolist(), conf3.tolist()
 
 
 def format_score(score: float) -> float:
@@ -251,7 +281,8 @@ def rec_reference_widths(wh_ratios: Sequence[float], rec_batch_num: int = 6, img
 
 def rec_batches_lines(wh_ratios: Sequence[float], rec_batch_num: int = 6, img_h: int = REC_IMG_H, img_w: int = REC_IMG_W,
                       launch_multiple: int = 32, n_min: int = 16, n_max: int = 160, n_step: int = 2,
-                      n_cu: int = 256, with_ratio: bool = False, given: Optional[Tuple[np.ndarray, np.ndarray]] = None):
+                      n_cu: int = 256, with_ratio: bool = False, given: Optional[Tuple[np.ndarray, np.ndarray]] = None,
+                      native: Optional[bool] = None):
     """The reference's batching RESULT at GPU launch sizes.  Every line keeps the padded width the reference gives it - the imgW of
     its own chunk of `rec_batch_num` lines of the one global `np.argsort` (`rec_batches(strict=True)`, rapid_ocr.py:411-440) - and
     the launches are runs of that sorted list whose sizes `rd_rec_plan_chunks` picks for the chip, each launch tensor as wide as
@@ -261,7 +292,13 @@ def rec_batches_lines(wh_ratios: Sequence[float], rec_batch_num: int = 6, img_h:
     by when word boxes are asked for).
     `given` = (reference width, max_wh_ratio) per INPUT line, decided elsewhere: a rank of a page-sharded run holds only some of the
     lines the reference would have pooled, sorted and chunked together, and gets every line's width from the global list
-    (dist.GlobalLineWidths); the launches are then runs of the local lines sorted by that width."""
+    (dist.GlobalLineWidths); the launches are then runs of the local lines sorted by that width.
+    `native` (default: `host_native_default()`): chunk maxima, widths and launches come from one library call (`rd_rec_plan_lines`)
+    instead of the Python loops below; the sort stays `np.argsort` here, the reference's own call."""
+    if native is None:
+        native = host_native_default()
+    if native and given is None:
+        return _rec_batches_lines_native(wh_ratios, rec_batch_num, img_h, img_w, launch_multiple, n_min, n_max, n_step, n_cu, with_ratio)
     if given is not None:
         gw, gr = np.asarray(given[0], dtype=np.int64), np.asarray(given[1], dtype=np.float64)
         assert len(gw) == len(gr) == len(wh_ratios)
@@ -300,6 +337,32 @@ def rec_batches_lines(wh_ratios: Sequence[float], rec_batch_num: int = 6, img_h:
     return out, line_w
 
 
+def _rec_batches_lines_native(wh_ratios, rec_batch_num, img_h, img_w, launch_multiple, n_min, n_max, n_step, n_cu, with_ratio):
+    import ctypes as C
+
+    from . import _lib
+    ratios = np.ascontiguousarray(wh_ratios, dtype=np.float64).reshape(-1)
+    total = len(ratios)
+    if total == 0:
+        return ([], np.zeros(0, np.int64), np.zeros(0)) if with_ratio else ([], np.zeros(0, np.int64))
+    order = np.ascontiguousarray(np.argsort(ratios), dtype=np.int64)      # numpy's DEFAULT kind: rec_batches(strict=True)
+    lib = _lib.load()
+    line_w, line_ratio = np.empty(total, np.int64), np.empty(total, np.float64)
+    sizes, launch_w = np.empty(total, np.int32), np.empty(total, np.int32)
+    n_out = C.c_int32(0)
+    rc = lib.rd_rec_plan_lines(ratios.ctypes.data, order.ctypes.data, total, int(rec_batch_num), int(img_h), int(img_w), int(launch_multiple),
+                               n_min, n_max, n_step, n_cu, line_w.ctypes.data, line_ratio.ctypes.data, sizes.ctypes.data,
+                               launch_w.ctypes.data, total, C.byref(n_out))
+    if rc != 0:
+        raise RuntimeError("rd_rec_plan_lines failed")
+    out, i = [], 0
+    for n, w in zip(sizes[: n_out.value].tolist(), launch_w[: n_out.value].tolist()):
+        out.append((order[i: i + n], w))
+        i += n
+    assert i == total
+    return (out, line_w, line_ratio) if with_ratio else (out, line_w)
+
+
 def rec_batches_equal_width(order: np.ndarray, line_w: np.ndarray, max_columns: int = 64 * 1088, n_max: int = 160) -> List[Tuple[np.ndarray, int]]:
     """Launches of ONE padded width each from `rec_batches_lines`' sorted list (`order` = its concatenated indices, `line_w` = the
     reference width per line in that order): runs of equal width, cut into launches of at most `n_max` lines and `max_columns` pixel
@@ -332,9 +395,10 @@ TEXT_BOX_DTYPE = np.dtype([("pts", "<f4", (8,)), ("score", "<f4")])
 
 def db_postprocess(prob: np.ndarray, src_hw: Sequence[Tuple[int, int]], thresh: float = 0.3, box_thresh: float = 0.5,
                    unclip_ratio: float = 1.6, use_dilation: bool = True, max_candidates: int = 1000, max_out: int = 2048,
-                   n_threads: int = 0) -> List[Tuple[np.ndarray, List[float]]]:
+                   n_threads: int = 0, raw: bool = False):
     """prob: [B,H,W] or [B,1,H,W] float32 DB probability maps (host).  Returns per image (boxes [n,4,2] int32 in
-    source pixels ordered tl,tr,br,bl, scores) - the (boxes, scores) pair rapidocr's DBPostProcess returns."""
+    source pixels ordered tl,tr,br,bl, scores) - the (boxes, scores) pair rapidocr's DBPostProcess returns.
+    `raw`: the library's own output instead, (TEXT_BOX_DTYPE records [B, max_out], counts int32 [B]) - what `order_merge_boxes_native` reads."""
     import ctypes as C
 
     from . import _lib
@@ -351,6 +415,8 @@ def db_postprocess(prob: np.ndarray, src_hw: Sequence[Tuple[int, int]], thresh: 
                                max_candidates, out.ctypes.data, max_out, n.ctypes.data, n_threads)
     if rc != 0:
         raise RuntimeError("rd_db_postprocess failed")
+    if raw:
+        return out, n
     res = []
     for b in range(B):
         k = int(n[b])
@@ -360,7 +426,7 @@ def db_postprocess(prob: np.ndarray, src_hw: Sequence[Tuple[int, int]], thresh: 
 
 def db_postprocess_device(prob_dev, src_hw: Sequence[Tuple[int, int]], thresh: float = 0.3, box_thresh: float = 0.5,
                           unclip_ratio: float = 1.6, use_dilation: bool = True, max_candidates: int = 1000, max_out: int = 2048,
-                          max_runs: int = 65536, stats: dict = None, cache: dict = None) -> List[Tuple[np.ndarray, List[float]]]:
+                          max_runs: int = 65536, stats: dict = None, cache: dict = None, raw: bool = False):
     """`db_postprocess` with NOTHING on the host (`rd_db_boxes_device`): `prob_dev` is the CUDA tensor [B,1,H,W] /
     [B,H,W] the det forward wrote; bitmap runs, region labelling, min-area rectangles, scores, unclip and the final filter run
     as six kernels on the current stream, and ONE device-to-host copy brings the finished boxes (a few KB).  Same boxes in the
@@ -369,7 +435,8 @@ def db_postprocess_device(prob_dev, src_hw: Sequence[Tuple[int, int]], thresh: f
 
     `cache` is the CALLER's dict of device workspaces / result buffers keyed by shape: one per PagePipeline / RegionOcr, i.e.
     one per host thread and HIP stream (PagePipelinePool runs one pipeline per thread; a process-wide cache would hand two
-    streams the same union-find arrays).  None = allocate for this call only."""
+    streams the same union-find arrays).  None = allocate for this call only.
+    `raw`: as in `db_postprocess`; the records are then a VIEW of the pinned result buffer, valid until the next call with this `cache`."""
     import time
 
     import torch
@@ -411,11 +478,16 @@ def db_postprocess_device(prob_dev, src_hw: Sequence[Tuple[int, int]], thresh: f
     bufs["res_h"].copy_(res, non_blocking=True)
     torch.cuda.current_stream().synchronize()          # the one wait: det forward + post-process + copy
     t1 = time.perf_counter()
-    raw = bufs["res_h"].numpy()
-    counts = raw[: 4 * (B + 1)].view("<i4")
+    raw_h = bufs["res_h"].numpy()
+    counts = raw_h[: 4 * (B + 1)].view("<i4")
     if int(counts[B]) != 0:
-        return db_postprocess(p.cpu().numpy(), src_hw, thresh, box_thresh, unclip_ratio, use_dilation, max_candidates, max_out)
-    boxes = raw[head:].view(TEXT_BOX_DTYPE).reshape(B, mo)
+        return db_postprocess(p.cpu().numpy(), src_hw, thresh, box_thresh, unclip_ratio, use_dilation, max_candidates, max_out, raw=raw)
+    boxes = raw_h[head:].view(TEXT_BOX_DTYPE).reshape(B, mo)
+    if raw:
+        if stats is not None:
+            stats["t_wait_maps_ms"] = (t1 - t0) * 1e3
+            stats["t_db_post_ms"] = (time.perf_counter() - t1) * 1e3
+        return boxes, counts[:B]
     out = []
     for b in range(B):
         k = int(counts[b])
@@ -424,6 +496,25 @@ def db_postprocess_device(prob_dev, src_hw: Sequence[Tuple[int, int]], thresh: f
         stats["t_wait_maps_ms"] = (t1 - t0) * 1e3
         stats["t_db_post_ms"] = (time.perf_counter() - t1) * 1e3
     return out
+
+
+def order_merge_boxes_native(records: np.ndarray, counts: np.ndarray) -> List[np.ndarray]:
+    """`merge_det_boxes(sorted_boxes(boxes.astype(float32)))` of every page of a batch in one library call
+    (`rd_text_boxes_order_merge`): `records` [B, max_in] TEXT_BOX_DTYPE and `counts` [B] as the DB post-process leaves them
+    (`db_postprocess(raw=True)`) -> per page float32 [k', 4, 2]."""
+    from . import _lib
+    lib = _lib.load()
+    assert records.dtype == TEXT_BOX_DTYPE and records.ndim == 2
+    records = np.ascontiguousarray(records)
+    B, max_in = records.shape
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    assert counts.shape == (B,)
+    quads = np.empty((B, max_in, 4, 2), np.float32)
+    n = np.zeros(B, np.int32)
+    rc = lib.rd_text_boxes_order_merge(records.ctypes.data, counts.ctypes.data, B, max_in, quads.ctypes.data, n.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("rd_text_boxes_order_merge failed")
+    return [quads[b, :k].copy() for b, k in enumerate(n.tolist())]
 
 
 def sorted_boxes(dt_boxes: Sequence[np.ndarray]) -> List[np.ndarray]:

@@ -197,6 +197,9 @@ class PagePipeline:
         self._ctc_table = torch.from_numpy(tab).to(self.tdev)
         self.device_ctc = True
         self.device_db = True            # DB post-process with the maps staying in HBM (ocr_host.db_postprocess_device)
+        # the host stages between the GPU stages - box ordering + merging, the strict mode's line widths, CTC rows -> strings - as one
+        # library call each; False (RD_HOST_NATIVE=0): the Python restatements of ocr_host, which define the result
+        self.host_native = ocr_host.host_native_default()
         self.db_ws: dict = {}            # its device workspaces / pinned result buffers: per pipeline = per host thread and stream
         # recogniser in two stages: the batches run only the backbone (each into its slice of one token buffer) on their
         # streams, then the LightSVTR neck + CTC head run ONCE over all lines (rd_rec_tail_forward); RD_REC_TWO_STAGE=0: whole
@@ -394,7 +397,7 @@ class PagePipeline:
             if sync is not None:        # the widths come from the pooled lines of every rank; key = the image key (global page index)
                 line_keys = key[keep] if image_keys is not None else page_of[keep].astype(np.int64)
                 given = self._synced_widths(sync, line_keys, np.asarray(ratios, dtype=np.float64))
-            batches, line_w, line_ratio = ocr_host.rec_batches_lines(ratios, n_cu=self.n_cu, with_ratio=True, given=given)
+            batches, line_w, line_ratio = ocr_host.rec_batches_lines(ratios, n_cu=self.n_cu, with_ratio=True, given=given, native=self.host_native)
             if not self.rec_lines_in_launch:
                 # same lines, same order, same reference width per line - but a launch holds lines of ONE width (a line's result depends
                 # on its pixels and its padded width only, so the launch boundaries do not enter the result)
@@ -594,7 +597,13 @@ class PagePipeline:
                 t1 = time.perf_counter()
                 lo = int(starts[grp[0]])
                 rows_np = rows.numpy()
-                dec = ocr_host.parse_ctc_rows(rows_np)
+                if self.host_native and not want_words:
+                    txt, _conf, conf3 = ocr_host.parse_ctc_rows_native(rows_np)
+                    for i, t, sc in zip(keep[order_all[lo: lo + len(txt)]].tolist(), txt, conf3):
+                        texts[i] = (t, sc)
+                    dec = ()
+                else:
+                    dec = ocr_host.parse_ctc_rows(rows_np)
                 if want_words:
                     n_kept = rows_np[:, 8:12].copy().view("<i4")[:, 0]
                     cols_np, confs_np = cols_h[0].numpy(), cols_h[1].numpy()
@@ -621,6 +630,13 @@ class PagePipeline:
                 self.last_rec_batches = [(keep[np.asarray(chunk)], x, idx, prob) for (chunk, _w), (idx, prob, _d, x, _r) in zip(batches, outs)]
             for (chunk, wpad), (idx, prob, done, _x, rows) in zip(batches, outs):
                 done.synchronize()
+                if rows is not None and self.host_native:
+                    t1 = time.perf_counter()
+                    txt, _conf, conf3 = ocr_host.parse_ctc_rows_native(rows.numpy())
+                    for i, t, s in zip(keep[np.asarray(chunk)].tolist(), txt, conf3):
+                        texts[i] = (t, s)
+                    t_dec += time.perf_counter() - t1
+                    continue
                 if rows is not None:
                     t1 = time.perf_counter()
                     dec = ocr_host.parse_ctc_rows(rows.numpy())
@@ -658,7 +674,13 @@ class PagePipeline:
         """DB post-process + reading-order sort + same-line merge (rapid_ocr.py:537-538; analyze_utils.py:196-204).
         box_thresh 0.3 / unclip 1.8 are the page-OCR settings (backend/pipeline/model_init.py:73)."""
         P = maps_host.shape[0]
-        res = ocr_host.db_postprocess(maps_host, [page_hw] * P, thresh=0.3, box_thresh=box_thresh, unclip_ratio=unclip_ratio)
+        res = ocr_host.db_postprocess(maps_host, [page_hw] * P, thresh=0.3, box_thresh=box_thresh, unclip_ratio=unclip_ratio,
+                                      raw=self.host_native)
+        t0 = time.perf_counter()
+        if self.host_native:
+            out = ocr_host.order_merge_boxes_native(*res)
+            self.stats["t_boxes_ms"] = (time.perf_counter() - t0) * 1e3
+            return out
         out = []
         for boxes, _scores in res:
             if len(boxes) == 0:
@@ -667,6 +689,7 @@ class PagePipeline:
             b = ocr_host.sorted_boxes(boxes.astype(np.float32))
             b = ocr_host.merge_det_boxes(b)
             out.append(np.asarray(b, dtype=np.float32).reshape(-1, 4, 2))
+        self.stats["t_boxes_ms"] = (time.perf_counter() - t0) * 1e3
         return out
 
     def boxes_from_maps_device(self, maps_dev: torch.Tensor, page_hw: Tuple[int, int], box_thresh: float = 0.3,
@@ -674,7 +697,12 @@ class PagePipeline:
         """`boxes_from_maps` with the maps staying in HBM (ocr_host.db_postprocess_device)."""
         P = maps_dev.shape[0]
         res = ocr_host.db_postprocess_device(maps_dev, [page_hw] * P, thresh=0.3, box_thresh=box_thresh, unclip_ratio=unclip_ratio,
-                                             stats=self.stats, cache=self.db_ws)
+                                             stats=self.stats, cache=self.db_ws, raw=self.host_native)
+        t0 = time.perf_counter()
+        if self.host_native:
+            out = ocr_host.order_merge_boxes_native(*res)
+            self.stats["t_boxes_ms"] = (time.perf_counter() - t0) * 1e3
+            return out
         out = []
         for boxes, _scores in res:
             if len(boxes) == 0:
@@ -682,6 +710,7 @@ class PagePipeline:
                 continue
             b = ocr_host.merge_det_boxes(ocr_host.sorted_boxes(boxes.astype(np.float32)))
             out.append(np.asarray(b, dtype=np.float32).reshape(-1, 4, 2))
+        self.stats["t_boxes_ms"] = (time.perf_counter() - t0) * 1e3
         return out
 
     def _boxes_via_host_maps(self, src: torch.Tensor, page_hw: Tuple[int, int]) -> List[np.ndarray]:
@@ -694,7 +723,7 @@ class PagePipeline:
         t1 = time.perf_counter()
         quads = self.boxes_from_maps(self._maps_host.numpy(), page_hw)
         self.stats["t_wait_maps_ms"] = (t1 - t0) * 1e3
-        self.stats["t_db_post_ms"] = (time.perf_counter() - t1) * 1e3
+        self.stats["t_db_post_ms"] = (time.perf_counter() - t1) * 1e3 - self.stats["t_boxes_ms"]
         return quads
 
     # ---------------------------------------------------------------- whole batch
