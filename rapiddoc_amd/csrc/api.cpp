@@ -690,7 +690,73 @@ float rd_debug_time_ctc(int M, int K, int Ccls, int iters, float* x, float* wp, 
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return ms / iters;
+    return iters > 0 ? ms / iters : 0.f;
+}
+
+// A range-flag word for the developer entries below: pinned, device-mapped host memory, as the engine's own (engine.cpp load_weights).
+static unsigned* debug_flag_new() {
+    unsigned* flag = nullptr;
+    if (hipHostMalloc((void**)&flag, sizeof(unsigned), hipHostMallocMapped) != hipSuccess || !flag) return nullptr;
+    *flag = 0;
+    return flag;
+}
+static int debug_finish(unsigned* flag, int* range_out) {
+    const bool ok = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
+    if (range_out) *range_out = flag ? (int)*flag : 0;
+    if (flag) (void)hipHostFree(flag);
+    return ok ? 0 : -1;
+}
+
+// developer entry: the self-attention alone on packed qkv [tokens][3 heads hd] fp32 -> o [tokens][heads hd].  seg = int32 [B][2] (first token,
+// tokens) on the device, or null: B dense lines of T tokens.  route 0 = launch_attention exactly as the engine calls it (kernel per line),
+// 1 = the VALU kernel for every line, 2 = the matrix-core kernel only (lines beyond its limit are left untouched).  One launch, synchronised.
+// *range_out (optional) receives 1 when the matrix-core kernel raised its range flag.  Returns 0, or -1 for a head size or route the
+// library does not have.
+int rd_debug_attention(int B, int T, int heads, int hd, float scale, float* qkv, float* o, const int32_t* seg, int route, int* range_out) {
+    if (range_out) *range_out = 0;
+    if (B <= 0 || T <= 0 || heads <= 0 || !(hd == 15 || hd == 16 || hd == 32) || route < 0 || route > 2) return -1;
+    if (route == 2 && !rd::attention_h3_applies(1, hd)) return -1;
+    unsigned* flag = debug_flag_new();
+    if (!flag) return -1;
+    if (route == 0) rd::launch_attention(qkv, o, B, T, heads, hd, scale, nullptr, seg, flag);
+    else if (route == 1) rd::launch_attention_valu(qkv, o, B, T, heads, hd, scale, nullptr, seg);
+    else rd::launch_attention_h3(qkv, o, B, T, heads, hd, scale, nullptr, seg, flag);
+    return debug_finish(flag, range_out);
+}
+// *h3_max_t = the longest line the matrix-core kernel serves at this head size (0: it has none), *valu_lds_keys = the keys the VALU kernel
+// holds in LDS at once (longer lines run over key tiles).  Returns -1 for a head size the library does not have.
+int rd_debug_attention_limits(int hd, int* h3_max_t, int* valu_lds_keys) {
+    if (!(hd == 15 || hd == 16 || hd == 32)) return -1;
+    if (h3_max_t) *h3_max_t = rd::attention_h3_applies(1, hd) ? rd::attention_h3_max_t() : 0;
+    if (valu_lds_keys) *valu_lds_keys = rd::attention_lds_keys(hd);
+    return 0;
+}
+
+// developer entry: LayerNorm over the last dimension, y[M][yld] = (x[M][xld] - mean) * rstd * g + b on the first C columns.  -1 for C > 512.
+int rd_debug_layernorm(int M, int C, float* x, int xld, float* y, int yld, float* g, float* b, float eps) {
+    if (M <= 0 || C <= 0 || C > 512 || xld < C || yld < C) return -1;
+    rd::launch_layernorm(x, xld, y, yld, g, b, M, C, eps, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
+
+// developer entry: ONE launch of the fused CTC head on prepared weights (as rd_debug_time_ctc), synchronised, with a free row stride of x
+// (xld >= K, a multiple of 4: rows are read as float4).  part = workspace of M * 64 * 4 floats.  *nsplit_out = the split count used,
+// *range_out = 1 when the split kernel raised its range flag.  Returns 0, or -1 for a shape the kernels do not take.
+int rd_debug_ctc_head(int M, int K, int Ccls, float* x, int xld, float* wp, void* wh, void* wl, float* part, int32_t* idx, float* prob,
+                      int nsplit_override, int* nsplit_out, int* range_out) {
+    if (range_out) *range_out = 0;
+    if (M <= 0 || Ccls <= 0 || K <= 0 || K >= 128 || K % 4 || xld < K || xld % 4 || nsplit_override > 64 || (wh == nullptr) != (wl == nullptr)) return -1;
+    rd::CtcParams p{};
+    p.x = x; p.xld = xld; p.w = wp; p.M = M; p.K = K; p.C = Ccls; p.part = part;
+    p.nsplit = nsplit_override > 0 ? nsplit_override : rd::ctc_head_nsplit(M, Ccls, wh != nullptr);
+    p.idx = idx; p.prob = prob;
+    p.wh = (const uint16_t*)wh; p.wl = (const uint16_t*)wl;
+    if (nsplit_out) *nsplit_out = p.nsplit;
+    unsigned* flag = debug_flag_new();
+    if (!flag) return -1;
+    p.range_flag = flag;
+    rd::launch_ctc_head(p, nullptr);
+    return debug_finish(flag, range_out);
 }
 
 int rd_set_precision(rd_handle* h, const char* mode) {

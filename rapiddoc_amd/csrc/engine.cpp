@@ -1215,9 +1215,14 @@ TView Builder::attention(const TView& qkv, int B, int T, int heads, int hd, cons
     const TView qv = qkv, ov = o;
     const bool ragged = seg != nullptr;
     const TView sv = ragged ? *seg : TView{};
-    r.run = [qv, ov, B, T, heads, hd, sc, ragged, sv](const Plan& pl, const RunCtx& c) {
-        launch_attention(pl.vptr(qv, c), pl.vptr(ov, c), B, T, heads, hd, sc, c.stream,
-                         ragged ? reinterpret_cast<const int32_t*>(pl.vptr(sv, c)) : nullptr);
+    // precision "fp32" means native fp32 arithmetic only: every line takes the VALU kernel, so the forward that the range guard repeats
+    // does not run the fp16 conversion again.  The other precisions pick the kernel per line and guard the matrix-core one's operands.
+    const bool split = h3_ || mixer_h3_;
+    unsigned* const flag = range_flag_;
+    r.run = [qv, ov, B, T, heads, hd, sc, ragged, sv, split, flag](const Plan& pl, const RunCtx& c) {
+        const int32_t* sg = ragged ? reinterpret_cast<const int32_t*>(pl.vptr(sv, c)) : nullptr;
+        if (split) launch_attention(pl.vptr(qv, c), pl.vptr(ov, c), B, T, heads, hd, sc, c.stream, sg, flag);
+        else launch_attention_valu(pl.vptr(qv, c), pl.vptr(ov, c), B, T, heads, hd, sc, c.stream, sg);
     };
     emit(std::move(r));
     return o;

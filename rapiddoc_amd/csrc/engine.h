@@ -273,7 +273,7 @@ class Engine {
     //              (hi, lo) operand splitting (3 MFMAs per product, fp32 accumulate; measured error vs fp64 is BELOW the
     //              fp32 MFMA path's).  Split operands must stay inside the fp16 range (|v| < 65504): the kernels raise
     //              the range flag otherwise and the caller re-runs in PREC_FP32 (take_range_flag()).
-    //   PREC_FP32  native fp32 MFMA only.      PREC_H3  every dense layer split (experimental; needs RD_PRECISION=h3 at load)
+    //   PREC_FP32  native fp32 MFMA only (the self-attention: the fp32 VALU kernel for every line).      PREC_H3  every dense layer split (experimental; needs RD_PRECISION=h3 at load)
     enum Precision : int { PREC_AUTO = 0, PREC_FP32 = 1, PREC_H3 = 2 };
     void set_precision(int p);
     int precision() const { return precision_; }

@@ -34,7 +34,7 @@ __host__ __device__ static inline int att_vrow_halfs(int tpad) {
 
 template <int HD>
 __global__ void __launch_bounds__(256) attention_h3_kernel(const float* __restrict__ qkv, float* __restrict__ o, int T, int heads, float scale,
-                                                           const int32_t* __restrict__ seg, int tpad_max) {
+                                                           const int32_t* __restrict__ seg, int tpad_max, unsigned* range_flag) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int b = blockIdx.x, head = blockIdx.y;
     const int C = heads * HD;
@@ -54,12 +54,17 @@ __global__ void __launch_bounds__(256) attention_h3_kernel(const float* __restri
     _Float16* Vl = Vh + (size_t)16 * vrow;
     const float* base = qkv + tok0 * 3 * C + head * HD;
 
+    // Largest |value| this thread converts to fp16 (K, V, scaled Q), as the bits of its absolute value: for non-negative floats the
+    // unsigned order is the numeric order, and a NaN sorts above infinity, so one v_and + v_max_u32 per value covers both.
+    unsigned amax = 0u;
     // ---- stage K and V^T (zero for dims >= HD and keys >= T: a zero key scores 0 and is masked below; a zero V row adds nothing)
     for (int i = threadIdx.x; i < tpad * 16; i += 256) {
         const int j = i >> 4, d = i & 15;
         const bool ok = j < T && d < HD;
         const float* src = base + (size_t)min(j, T - 1) * 3 * C + min(d, HD - 1);
         const float kv = src[C], vv = src[2 * C];
+        // (a clamped duplicate is some valid element of this (line, head): tracking it as well is harmless)
+        amax = max(amax, max(__float_as_uint(kv), __float_as_uint(vv)) & 0x7fffffffu);
         _Float16 h, l;
         rd_split(ok ? kv : 0.f, h, l);
         Kh[j * ATT_KROW + d] = h;
@@ -82,9 +87,10 @@ __global__ void __launch_bounds__(256) attention_h3_kernel(const float* __restri
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             const int d = 8 * lhi + t;
-            const float v = qrow[min(d, HD - 1)];
+            const float v = qrow[min(d, HD - 1)] * scale;
+            amax = max(amax, __float_as_uint(v) & 0x7fffffffu);
             _Float16 h, l;
-            rd_split(d < HD ? v * scale : 0.f, h, l);
+            rd_split(d < HD ? v : 0.f, h, l);
             qh[t] = h;
             ql[t] = l;
         }
@@ -151,6 +157,8 @@ __global__ void __launch_bounds__(256) attention_h3_kernel(const float* __restri
             }
         }
     }
+    // an operand of 65504 or more (or a NaN) does not survive the fp16 split: the caller repeats the forward in fp32 (ctc_head_h3_kernel)
+    if (amax >= 0x477fe000u /* 65504.f */ && range_flag) rd_raise_flag(range_flag);
 }
 
 bool attention_h3_applies(int T, int hd) {
@@ -159,16 +167,17 @@ bool attention_h3_applies(int T, int hd) {
 }
 int attention_h3_max_t() { return ATT_MAX_T; }
 
-void launch_attention_h3(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg) {
+void launch_attention_h3(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg,
+                         unsigned* range_flag) {
     const int tpad = std::min((T + 31) & ~31, ATT_MAX_T);       // (ragged launches: longer lines are skipped by the kernel)
     const size_t sh = (size_t)2 * tpad * ATT_KROW * 2 + (size_t)2 * 16 * att_vrow_halfs(tpad) * 2;
     static unsigned long long ok15 = 0, ok16 = 0;
     if (hd == 15) {
         rd_allow_dynamic_lds((const void*)attention_h3_kernel<15>, sh, ok15);
-        hipLaunchKernelGGL(attention_h3_kernel<15>, dim3(B, heads), dim3(256), sh, s, qkv, o, T, heads, scale, seg, tpad);
+        hipLaunchKernelGGL(attention_h3_kernel<15>, dim3(B, heads), dim3(256), sh, s, qkv, o, T, heads, scale, seg, tpad, range_flag);
     } else {
         rd_allow_dynamic_lds((const void*)attention_h3_kernel<16>, sh, ok16);
-        hipLaunchKernelGGL(attention_h3_kernel<16>, dim3(B, heads), dim3(256), sh, s, qkv, o, T, heads, scale, seg, tpad);
+        hipLaunchKernelGGL(attention_h3_kernel<16>, dim3(B, heads), dim3(256), sh, s, qkv, o, T, heads, scale, seg, tpad, range_flag);
     }
 }
 

@@ -230,6 +230,8 @@ __global__ void __launch_bounds__(512) ctc_head_h3_kernel(CtcParams p, int cls_p
     }
 
     float m_run = -INFINITY, s_run = 0.f;
+    float c_run = 0.f;                               // compensation term of s_run (see stats)
+    float nm_run = INFINITY;                         // minus the exponent s_run is relative to (+inf: nothing summed yet, the first factor is 0)
     int i_run = 0;                                   // class code: class - c_begin - 4 lhi
     const int wrow = l31 * CT_K, wkey = l31 & 15;
     constexpr float LOG2E = 1.4426950408889634f;
@@ -287,7 +289,19 @@ __global__ void __launch_bounds__(512) ctc_head_h3_kernel(CtcParams p, int cls_p
             float sum = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) sum += __builtin_amdgcn_exp2f(fmaf(v[j], LOG2E, nm));
-            s_run = fmaf(s_run, __builtin_amdgcn_exp2f(fmaf(m_run, LOG2E, nm)), sum);
+            // s_run is the sum of 2^(v LOG2E + nm_run): relative to the ROUNDED exponent -nm_run of the running maximum.  Moving it to this
+            // slice's reference is the factor 2^(nm - nm_run), exactly 1 while the maximum stands.  (2^(m_run LOG2E + nm) is not: the
+            // fma keeps the rounding residual of m_run LOG2E, up to half an ulp of it, with the same sign in each of a split's ~80
+            // slices - a relative error of the probability of up to 1e-4 at |logit| = 40.)  The residual is taken out once, after the loop.
+            // The sum is carried as s_run + c_run (Fast2Sum: c_run collects what each addition rounds away).  Behind a clear winner
+            // s_run is 1 and a slice of 8 far classes adds less than half an ulp of it: rounded away slice after slice, a lane's whole
+            // share of the other classes went missing - 1.3e-6 of the probability at 1108 classes per split, beyond fp32 summation noise.
+            // (Exact while the sum so far is the larger addend; otherwise the slice is of the sum's own size and one rounding is harmless.)
+            const float fr = __builtin_amdgcn_exp2f(nm - nm_run);
+            const float sa = s_run * fr;
+            s_run = sa + sum;
+            c_run = fmaf(c_run, fr, sum - (s_run - sa));
+            nm_run = nm;
             m_run = m_new;
         }
     };
@@ -307,9 +321,11 @@ __global__ void __launch_bounds__(512) ctc_head_h3_kernel(CtcParams p, int cls_p
             else stats(T{}, s);
         }
     }
-    if (late) stats(T{}, nit - 1);
+    if (late && nit > 0) stats(T{}, nit - 1);      // (an empty class split has no tile: its statistics stay (-inf, 0))
 
     if (!(amax < 65504.f) && p.range_flag) rd_raise_flag(p.range_flag);
+    // sum of 2^(v LOG2E + nm_run) -> sum of exp(v - m_run): the rounding residual of m_run LOG2E, once
+    if (m_run > -INFINITY) s_run = (s_run + c_run) * __builtin_amdgcn_exp2f(-fmaf(m_run, LOG2E, nm_run));
     i_run += c_begin + 4 * lhi;        // class code -> class
     const float om = __shfl_xor(m_run, 32, 64), os = __shfl_xor(s_run, 32, 64);
     const int oi = __shfl_xor(i_run, 32, 64);

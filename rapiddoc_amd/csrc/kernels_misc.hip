@@ -812,16 +812,29 @@ __global__ void __launch_bounds__(256) attention_kernel(const float* qkv, float*
         f32x4 acc[NV];
 #pragma unroll
         for (int v = 0; v < NV; ++v) acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // Sums over runs of 64 keys, then over the runs: one running fp32 sum over all T keys rounds every term to the grid of the FULL sum
+        // (error ~ sqrt(T) ulps of it: 4 - 8 x that of a blocked fp32 evaluation at T = 1152 - 2305).  A key tile (tk_cap keys) is a whole
+        // number of runs, so a line's runs - and with them its bits - do not depend on the launch it rides in.
         auto accumulate = [&](int kn) {
-            for (int j = 0; j < kn; ++j) {
-                const float e = __expf(dot(j) - mx);
-                l += e;
+            for (int j0 = 0; j0 < kn; j0 += 64) {
+                const int je = min(kn, j0 + 64);
+                float lr = 0.f;
+                f32x4 ar[NV];
 #pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    const f32x4 vv = Vs[(size_t)j * NV + v];
+                for (int v = 0; v < NV; ++v) ar[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int j = j0; j < je; ++j) {
+                    const float e = __expf(dot(j) - mx);
+                    lr += e;
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) acc[v][c] = fmaf(e, vv[c], acc[v][c]);
+                    for (int v = 0; v < NV; ++v) {
+                        const f32x4 vv = Vs[(size_t)j * NV + v];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) ar[v][c] = fmaf(e, vv[c], ar[v][c]);
+                    }
                 }
+                l += lr;
+#pragma unroll
+                for (int v = 0; v < NV; ++v) acc[v] += ar[v];
             }
         };
         if (!tiled) {
@@ -849,6 +862,7 @@ __global__ void __launch_bounds__(256) attention_kernel(const float* qkv, float*
 // keys whose padded K and V rows fit the dynamic LDS of one workgroup (144 KB of the CU's 160: the rest is left to the
 // kernels of other streams that share the CU)
 int attention_lds_keys(int hd) { return (144 * 1024) / (2 * ((hd + 3) / 4 * 4) * (int)sizeof(float)); }
+static_assert((144 * 1024) / (2 * 16 * 4) % 64 == 0 && (144 * 1024) / (2 * 32 * 4) % 64 == 0, "a key tile is a whole number of 64-key runs");
 template <int HD>
 static void launch_attention_t(const float* qkv, float* o, int B, int T, int heads, float scale, hipStream_t s, const int32_t* seg, int skip_upto) {
     const int cap = attention_lds_keys(HD);
@@ -857,19 +871,25 @@ static void launch_attention_t(const float* qkv, float* o, int B, int T, int hea
     if (sh > 64 * 1024) rd_allow_dynamic_lds((const void*)attention_kernel<HD>, (size_t)144 * 1024, lds_ok);
     hipLaunchKernelGGL(attention_kernel<HD>, dim3(B, heads), dim3(256), sh, s, qkv, o, T, heads, scale, seg, cap, skip_upto);
 }
-void launch_attention(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg) {
+void launch_attention(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg,
+                      unsigned* range_flag) {
     // The kernel that serves a line follows from the LINE's length (matrix cores up to attention_h3_max_t() tokens, the VALU kernel beyond),
     // not from the longest line of its launch: a ragged launch (seg) that holds lines of both kinds runs both kernels over the same line
     // table, each skipping the other's lines, so a line's bits do not depend on its neighbours in the launch.
     int skip_upto = 0;
     if (attention_h3_applies(1, hd)) {
-        if (attention_h3_applies(T, hd) || seg) launch_attention_h3(qkv, o, B, T, heads, hd, scale, s, seg);
+        if (attention_h3_applies(T, hd) || seg) launch_attention_h3(qkv, o, B, T, heads, hd, scale, s, seg, range_flag);
         if (attention_h3_applies(T, hd)) return;
         if (seg) skip_upto = attention_h3_max_t();
     }
     if (hd == 15) launch_attention_t<15>(qkv, o, B, T, heads, scale, s, seg, skip_upto);
     else if (hd == 16) launch_attention_t<16>(qkv, o, B, T, heads, scale, s, seg, skip_upto);
     else if (hd == 32) launch_attention_t<32>(qkv, o, B, T, heads, scale, s, seg, skip_upto);
+}
+void launch_attention_valu(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg) {
+    if (hd == 15) launch_attention_t<15>(qkv, o, B, T, heads, scale, s, seg, 0);
+    else if (hd == 16) launch_attention_t<16>(qkv, o, B, T, heads, scale, s, seg, 0);
+    else if (hd == 32) launch_attention_t<32>(qkv, o, B, T, heads, scale, s, seg, 0);
 }
 
 // --------------------------------------------------------------------------------------------------

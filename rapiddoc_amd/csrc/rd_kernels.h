@@ -230,8 +230,14 @@ void launch_layernorm(const float* x, int xld, float* y, int yld, const float* g
 // seg != nullptr: ragged batch - sequence b is seg[2b+1] tokens starting at token seg[2b]; T is then the longest one
 int attention_h3_max_t();                     // lines up to this many tokens run on the matrix-core kernel, longer ones on the VALU kernel
 bool attention_h3_applies(int T, int hd);     // kernels_attention_h3.hip: the same attention on the split-fp16 matrix cores
-void launch_attention_h3(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg);
-void launch_attention(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg = nullptr);
+int attention_lds_keys(int hd);               // keys whose K and V rows the VALU kernel holds in LDS at once; longer lines run over key tiles
+// range_flag (optional): raised when the matrix-core kernel converts a K, V or scaled Q value outside the fp16 range (as ConvParams::range_flag)
+void launch_attention_h3(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg,
+                         unsigned* range_flag = nullptr);
+void launch_attention(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg = nullptr,
+                      unsigned* range_flag = nullptr);
+// the VALU kernel (native fp32) for EVERY line, whatever its length: precision "fp32", developer entries
+void launch_attention_valu(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg = nullptr);
 
 // y = a + b (same geometry, views)
 void launch_add(const float* a, int ald, const float* b, int bld, float* y, int yld, int M, int C, hipStream_t s);

@@ -241,3 +241,63 @@ def test_range_guard_on_rec_forward_lines_path(golden_dir, monkeypatch):
     assert any(e.range_fallbacks for e in pipe.rec_engines)
     again = pipe.rec_forward_lines(pages, quads)      # now in fp32: stable, no further fallbacks
     assert again == out
+
+
+def _first_block_attention_magnitudes(st, x):
+    """(max |v|, max |softmax(q k^T) v|) of the recogniser's first tail block on the CPU oracle (oracle/nets.py lightsvtr, up to the first
+    attention)."""
+    import torch.nn.functional as F
+    e = "head.encoder"
+    f = F.avg_pool2d(O.lcnetv4_features(st, x, O.LCNETV4_REC_SMALL)[-1], [3, 2])
+    h = O._svtr_conv(st, e + ".conv_block.1", f)
+    wk = st[e + ".conv_block.2.convolution.weight"]
+    h = h + O._svtr_conv(st, e + ".conv_block.2", h, padding=(0, wk.shape[-1] // 2), groups=wk.shape[0])
+    b, c = h.shape[:2]
+    t = h.flatten(2).permute(0, 2, 1)
+    p = e + ".svtr_block.0"
+    y = F.layer_norm(t, (c,), st[p + ".layer_norm1.weight"], st[p + ".layer_norm1.bias"], O.LN_EPS)
+    qkv = F.linear(y, st[p + ".self_attn.qkv.weight"], st[p + ".self_attn.qkv.bias"])
+    q, k, v = qkv.reshape(b, -1, 3, 8, c // 8).permute(2, 0, 3, 1, 4)
+    o = torch.softmax(q @ k.transpose(-1, -2) * (c // 8) ** -0.5, dim=-1) @ v
+    return float(v.abs().max()), float(o.abs().max())
+
+
+def test_range_guard_on_an_attention_operand(golden_dir, monkeypatch):
+    """The V rows of the first tail block's qkv projection (weight and bias) times g, the projection behind the attention divided by g: the
+    network computes the same function and ONLY the attention meets an operand outside the fp16 range.  The qkv GEMM merely writes the
+    large values; the projection reads the attention's output, a convex combination of V that the near-flat softmax of synthetic
+    weights averages down - g is the geometric mean of the two limits, 65504 / sqrt(max|v| max|o|), so that max|v| g is beyond the
+    range and max|o| g inside it (both checked on the CPU oracle below).  The flag is raised in `auto` (by the attention itself - which
+    tests/test_gpu_attention.py pins - and, were it silent, by the projection GEMM on the NaN it would be handed); the guarded engine
+    repeats the forward in fp32, where every line takes the fp32 VALU kernel: no flag, finite results, and equal to a pure-fp32 engine
+    bit for bit.  (With the matrix-core kernel chosen in fp32 as well, the repeated forward converted V to fp16 again and returned NaN.)"""
+    from rapiddoc_amd.engine import RdEngine
+    monkeypatch.setenv("RD_PRECISION", "auto")
+    st = W.synth_state_dict(W.load_manifest(golden_dir / "manifest_ppocrv6_rec.json"), 0)
+    x = torch.from_numpy(np.random.default_rng(21).uniform(-1, 1, (2, 3, 48, 160)).astype(np.float32))
+    vmax, omax = _first_block_attention_magnitudes(O.as_torch_state(st), x)
+    g = 65504.0 / (vmax * omax) ** 0.5
+    assert vmax * g > 1.05 * 65504.0 and omax * g < 65504.0 / 1.05, (vmax, omax)
+    p = "head.encoder.svtr_block.0.self_attn."
+    big = dict(st)
+    c = big[p + "qkv.weight"].shape[0] // 3
+    scale = np.ones((3 * c,), dtype=np.float32)
+    scale[2 * c:] = g
+    big[p + "qkv.weight"] = big[p + "qkv.weight"] * scale[:, None]
+    big[p + "qkv.bias"] = big[p + "qkv.bias"] * scale
+    big[p + "projection.weight"] = big[p + "projection.weight"] * np.float32(1.0 / g)
+    xg = x.cuda()
+    plain = RdEngine("ppocrv6_rec", guard="off").load_weights(st)
+    plain.rec_forward(xg)
+    assert not plain.range_overflow()                              # the unscaled network trips nothing
+    ref_eng = RdEngine("ppocrv6_rec", guard="off").load_weights(big).set_precision("fp32")
+    ridx, rprob, _ = ref_eng.rec_forward(xg)
+    assert not ref_eng.range_overflow()                            # fp32: no fp16 conversion anywhere, the attention included
+    raw = RdEngine("ppocrv6_rec", guard="off").load_weights(big)   # guard off: look at the raw flag
+    raw.rec_forward(xg)
+    assert raw.range_overflow() and not raw.range_overflow()       # raised once, cleared by the read
+    eng = RdEngine("ppocrv6_rec").load_weights(big)                # default guard="sync": the forward itself falls back
+    idx, prob, _ = eng.rec_forward(xg)
+    assert eng.precision == "fp32" and eng.range_fallbacks == 1
+    assert torch.equal(idx, ridx) and torch.equal(prob, rprob)
+    assert bool(torch.isfinite(prob).all())
