@@ -97,11 +97,27 @@ int rd_query_workspace(rd_handle* h, int B, int H, int W, int flags, size_t* ws_
     });
 }
 
+static bool is_det_kind(const std::string& k) { return k == "ppocrv6_det" || k == "ppocrv5_det_server"; }
+
 int rd_det_forward(rd_handle* h, const float* x, int B, int H, int W, float* prob, void* ws, size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && h->eng->kind() == "ppocrv6_det", "handle is not a ppocrv6_det model");
+        RD_CHECK(h->eng && is_det_kind(h->eng->kind()), "handle is not a detector (ppocrv6_det / ppocrv5_det_server) model");
         RD_CHECK(x && prob && B > 0, "null input/output");
         h->eng->run(B, H, W, 0, {(void*)x, (void*)prob}, ws, ws_bytes, (hipStream_t)stream);
+    });
+}
+
+int rd_det_forward_ex(rd_handle* h, const float* x, int B, int H, int W, float* prob, int flags, float* aux, void* ws, size_t ws_bytes,
+                      void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->eng && is_det_kind(h->eng->kind()), "handle is not a detector (ppocrv6_det / ppocrv5_det_server) model");
+        RD_CHECK(x && prob && B > 0, "null input/output");
+        RD_CHECK((flags & ~RD_DET_WANT_NECK) == 0, "rd_det_forward_ex: unknown flag");
+        if (flags & RD_DET_WANT_NECK) {
+            RD_CHECK(h->eng->kind() == "ppocrv5_det_server", "RD_DET_WANT_NECK is offered by ppocrv5_det_server only");
+            RD_CHECK(aux, "aux_dev is NULL");
+        }
+        h->eng->run(B, H, W, flags, {(void*)x, (void*)prob, (void*)aux}, ws, ws_bytes, (hipStream_t)stream);
     });
 }
 
@@ -552,10 +568,53 @@ float rd_debug_seqconv(int M, int C0, int C1, int N, int T, int act, int split, 
     return ms;
 }
 
+// developer entry: the fused local tail of PFHeadLocal alone (kernels_det_local.hip).  Device pointers: f NHWC [N][H/2][W/2][64], shrink
+// [N][H][W], w3 = last_3's folded weights [64][65][3][3] (input channel 0 = shrink), b3 [64], w1 [64], y [N][H][W]; split != 0: the
+// split-fp16 route, else native fp32.  Returns ms per launch (iters timed launches after one untimed), or -1 for a geometry it does not take.
+float rd_debug_det_local(int N, int H, int W, int split, int iters, float* f, float* shrink, float* w3, float* b3, float* w1, float b1, float* y,
+                         int* range_out) {
+    if (N <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return -1.f;
+    std::vector<float> hw((size_t)64 * 65 * 9);
+    if (hipMemcpy(hw.data(), w3, hw.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    std::vector<float> img32;
+    std::vector<uint16_t> img16;
+    const float inv = rd::prepare_det_local_weights(hw.data(), img32, img16);
+    void *d32 = nullptr, *d16 = nullptr;
+    if (hipMalloc(&d32, img32.size() * 4) != hipSuccess || hipMalloc(&d16, img16.size() * 2) != hipSuccess) return -1.f;
+    (void)hipMemcpy(d32, img32.data(), img32.size() * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(d16, img16.data(), img16.size() * 2, hipMemcpyHostToDevice);
+    unsigned* flag = nullptr;
+    (void)hipHostMalloc((void**)&flag, sizeof(unsigned), hipHostMallocMapped);
+    *flag = 0;
+    rd::DetLocalParams p{};
+    p.f = f; p.fld = 64; p.shrink = shrink; p.y = y; p.N = N; p.H = H; p.W = W;
+    p.wimg32 = (const float*)d32; p.b3 = b3; p.w1 = w1; p.b1 = b1;
+    if (split) { p.wimg16 = (const uint16_t*)d16; p.w_inv = inv; p.range_flag = flag; }
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    rd::launch_det_local(p, nullptr);
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) rd::launch_det_local(p, nullptr);
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    ms = iters > 0 ? ms / iters : 0.f;
+    (void)hipDeviceSynchronize();
+    if (hipGetLastError() != hipSuccess) ms = -1.f;
+    if (range_out) *range_out = (int)*flag;
+    (void)hipHostFree(flag);
+    (void)hipFree(d32);
+    (void)hipFree(d16);
+    return ms;
+}
+
 // developer entry: one dense convolution on prepared operands (x NHWC fp32 [N][H][W][Cin]; w folded [Cout][K], k = (kh*KW+kw)*Cin+ci;
 // wh / wl its fp16 split with rows padded to Kp = ceil32(K), or null for the fp32 MFMA kernels; y NHWC [N][OH][OW][Cout]).
 // Returns ms per launch (iters timed launches after one untimed).  *used_direct: in = 1 forces the direct k x k kernel when it
-// supports the geometry, in = 2 the small-K streaming kernel; out = 1 / 2 when the direct / streaming kernel ran.
+// supports the geometry, in = 2 the small-K streaming kernel, in = 4 the direct 9x9 kernel (kernels_conv9x9_h1.hip; in = 0 leaves a 9x9 layer
+// on the generic k x k implicit GEMM it displaces); out = 1 / 2 / 4 when the direct / streaming / 9x9 kernel ran (3: the one-accumulator 3x3).
 float rd_debug_conv(int N, int H, int W, int Cin, int Cout, int KH, int KW, int S, int PT, int PL, int PB, int PR, int act, int iters,
                     float* x, float* w, void* wh, void* wl, float* bias, float* res, float* y, int* used_direct) {
     rd::ConvParams p{};
@@ -580,10 +639,24 @@ float rd_debug_conv(int N, int H, int W, int Cin, int Cout, int KH, int KW, int 
             }
         }
     }
+    void* img9 = nullptr;
+    if (wh && used_direct && *used_direct == 4 && rd::conv9x9_h1_shape_ok(KH, KW, Cin, Cout)) {
+        std::vector<float> hw((size_t)Cout * p.K);
+        if (hipMemcpy(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
+            std::vector<uint16_t> img;
+            const float inv = rd::prepare_conv9x9_h1_weights(hw.data(), Cout, Cin, img);
+            if (hipMalloc(&img9, img.size() * 2) == hipSuccess) {
+                (void)hipMemcpy(img9, img.data(), img.size() * 2, hipMemcpyHostToDevice);
+                p.w9 = (const uint16_t*)img9;
+                p.w9_inv = inv;
+            }
+        }
+    }
+    const bool c9 = wh && rd::conv9x9_h1_applies(p);
     const bool c3 = wh && rd::conv3x3_h1_applies(p);
     const bool force = used_direct && *used_direct == 1 && wh && rd::conv_direct_h3_supported(p);
     const bool force_stream = used_direct && *used_direct == 2 && wh && rd::conv_stream_h3_supported(p);
-    if (used_direct) *used_direct = c3 ? 3 : force_stream ? 2 : (force || (wh && !rd::conv_stream_h3_applies(p) && rd::conv_direct_h3_applies(p))) ? 1
+    if (used_direct) *used_direct = c9 ? 4 : c3 ? 3 : force_stream ? 2 : (force || (wh && !rd::conv_stream_h3_applies(p) && rd::conv_direct_h3_applies(p))) ? 1
                                     : (wh && rd::conv_stream_h3_applies(p)) ? 2 : 0;
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -602,6 +675,7 @@ float rd_debug_conv(int N, int H, int W, int Cin, int Cout, int KH, int KW, int 
     (void)hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (img3) (void)hipFree(img3);
+    if (img9) (void)hipFree(img9);
     return iters > 0 ? ms / iters : 0.f;
 }
 

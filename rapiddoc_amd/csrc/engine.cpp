@@ -141,6 +141,17 @@ void WeightStore::load_safetensors(const void* blob, size_t nbytes) {
     RD_CHECK(!map_.empty(), "weights: no tensors in image");
 }
 
+void WeightStore::add_derived(const std::string& name, const std::vector<int64_t>& shape, std::vector<float>&& data) {
+    derived_.push_back(std::make_unique<std::vector<float>>(std::move(data)));
+    HostTensor t;
+    t.shape = shape;
+    t.dtype = "F32";
+    t.data = reinterpret_cast<const uint8_t*>(derived_.back()->data());
+    t.nbytes = derived_.back()->size() * sizeof(float);
+    RD_CHECK(t.numel() * sizeof(float) == t.nbytes, "derived tensor size mismatch: " + name);
+    map_[name] = std::move(t);
+}
+
 const HostTensor& WeightStore::get(const std::string& name) const {
     auto it = map_.find(name);
     if (it == map_.end()) throw Error("weights: missing tensor '" + name + "'");
@@ -375,8 +386,12 @@ TView Builder::conv(const std::string& wname, const std::string& bname, const st
             p.w3 = reinterpret_cast<const uint16_t*>(pb_->ptr(key + "#w3"));
             p.w3_inv = *pb_->host_ptr(key + "#w3s");
         }
+        if (pb_->has(key + "#w9")) {
+            p.w9 = reinterpret_cast<const uint16_t*>(pb_->ptr(key + "#w9"));
+            p.w9_inv = *pb_->host_ptr(key + "#w9s");
+        }
         p.range_flag = range_flag_;
-        r.cfg = std::string(conv_stream_h3_applies(p) ? "stream" : conv3x3_h1_applies(p) ? "c3h1" : conv_direct_h3_applies(p) ? "direct" : gemm_h1_applies(p) ? "h1w256x128" : gemm_h3_dma_applies(p) ? (gemm_h3_dma_uses16(p) ? "dma16w256x128" : "dma256x128") : cout > 96 ? "256x128" : cout > 64 ? "128x96"
+        r.cfg = std::string(conv_stream_h3_applies(p) ? "stream" : conv3x3_h1_applies(p) ? "c3h1" : conv9x9_h1_applies(p) ? "c9h1" : conv_direct_h3_applies(p) ? "direct" : gemm_h1_applies(p) ? "h1w256x128" : gemm_h3_dma_applies(p) ? (gemm_h3_dma_uses16(p) ? "dma16w256x128" : "dma256x128") : cout > 96 ? "256x128" : cout > 64 ? "128x96"
                             : (cout > 32 && p.M >= 65536) ? "256x64" : K <= 256 || cout <= 32 ? "128x32" : "128x64") + "/h3";
     }
     r.run = [p, xv, yv, rv, av, has_res, has_as, h3](const Plan& pl, const RunCtx& c) mutable {
@@ -428,6 +443,12 @@ void Builder::fold_conv(const std::string& wname, const std::string& bname, cons
             const float inv = prepare_conv3x3_h1_weights(wf.data(), cout, cin, img);
             pb_->add_u16(key + "#w3", img);
             pb_->add(key + "#w3s", std::vector<float>{inv});
+        }
+        if (conv9x9_h1_shape_ok(kh, kw, cin, cout)) {               // one-accumulator direct 9x9 (LKPAN): slab-ordered fragment image
+            std::vector<uint16_t> img;
+            const float inv = prepare_conv9x9_h1_weights(wf.data(), cout, cin, img);
+            pb_->add_u16(key + "#w9", img);
+            pb_->add(key + "#w9s", std::vector<float>{inv});
         }
         if (kh == 1 && kw == 1 && gemm_h1_shape_ok(K, cout)) {      // single-accumulator GEMM: fragment-ordered, per-channel pre-scaled image
             std::vector<uint16_t> img;
@@ -1045,6 +1066,68 @@ TView Builder::dwconv(const std::string& wname, const std::string& bname, const 
     return y;
 }
 
+void Builder::det_local_tail(const std::string& w3n, const std::string& bn3, const std::string& w1n, const std::string& b1n, const TView& f,
+                             const TView& shrink, const TView& out) {
+    const HostTensor& w3 = ws_->get(w3n);
+    const HostTensor& w1 = ws_->get(w1n);
+    RD_CHECK(w3.shape.size() == 4 && w3.shape[0] == 64 && w3.shape[1] == 65 && w3.shape[2] == 3 && w3.shape[3] == 3, "det local tail: last_3 must be [64,65,3,3]");
+    RD_CHECK(w1.numel() == 64 && w1.shape[0] == 1, "det local tail: last_1 must be [1,64,1,1]");
+    RD_CHECK(f.c == 64 && shrink.c == 1 && out.c == 1 && shrink.h == 2 * f.h && shrink.w == 2 * f.w && out.h == shrink.h && out.w == shrink.w &&
+                 f.n == out.n && shrink.n == out.n, "det local tail: view mismatch");
+    RD_CHECK(plan_->ld(shrink) == 1 && plan_->ld(out) == 1 && plan_->ld(f) % 4 == 0, "det local tail: shrink / maps are dense one-channel maps");
+    const std::string key = w3n + "|" + bn3 + "|" + w1n + "|local";
+    if (!planning()) {
+        if (pb_->has(key + "#w32")) return;
+        std::vector<float> shift;
+        std::vector<float> scale = bn_scale_shift(bn3, 64, shift);
+        std::vector<float> wf(w3.numel());
+        for (size_t i = 0; i < wf.size(); ++i) wf[i] = w3.f32()[i] * scale[i / (65 * 9)];
+        std::vector<float> img32;
+        std::vector<uint16_t> img16;
+        const float inv = prepare_det_local_weights(wf.data(), img32, img16);
+        pb_->add(key + "#w32", img32);
+        pb_->add(key + "#b3", shift);
+        pb_->add(key + "#w1", std::vector<float>(w1.f32(), w1.f32() + 64));
+        pb_->add(key + "#b1", std::vector<float>{b1n.empty() ? 0.f : ws_->get(b1n).f32()[0]});
+        if (fits_fp16_range(wf)) {
+            pb_->add_u16(key + "#w16", img16);
+            pb_->add(key + "#inv", std::vector<float>{inv});
+        }
+        return;
+    }
+    DetLocalParams p{};
+    p.fld = plan_->ld(f);
+    p.N = out.n; p.H = out.h; p.W = out.w;
+    p.wimg32 = pb_->ptr(key + "#w32");
+    p.b3 = pb_->ptr(key + "#b3");
+    p.w1 = pb_->ptr(key + "#w1");
+    p.b1 = *pb_->host_ptr(key + "#b1");
+    // split in "auto" and "h3" (a fifth of the detector's arithmetic), native fp32 in "fp32"
+    const bool split = (h3_ || mixer_h3_) && pb_->has(key + "#w16");
+    if (split) {
+        p.wimg16 = reinterpret_cast<const uint16_t*>(pb_->ptr(key + "#w16"));
+        p.w_inv = *pb_->host_ptr(key + "#inv");
+        p.range_flag = range_flag_;
+    }
+    OpRecord r;
+    r.name = w3n + "+" + w1n;
+    r.kind = "det_local_tail";
+    r.cfg = split ? "fused/h1" : "fused/fp32";
+    const double m = (double)out.pixels();
+    r.shape = "M" + std::to_string(out.pixels()) + "_K272_N64";
+    r.flops = 2.0 * m * (272.0 * 64 + 64);
+    r.bytes = 4.0 * ((double)f.pixels() * 64 + 2.0 * m);
+    const TView fv = f, sv = shrink, yv = out;
+    r.run = [p, fv, sv, yv](const Plan& pl, const RunCtx& c) {
+        DetLocalParams q = p;
+        q.f = pl.vptr(fv, c);
+        q.shrink = pl.vptr(sv, c);
+        q.y = pl.vptr(yv, c);
+        launch_det_local(q, c.stream);
+    };
+    emit(std::move(r));
+}
+
 void Builder::maxpool2x2s1(const TView& x, const TView& out) {
     RD_CHECK(out.h == x.h && out.w == x.w && out.c == x.c && x.c % 4 == 0, "maxpool view mismatch");
     if (!planning()) return;
@@ -1382,7 +1465,8 @@ Engine::Engine(int device, const std::string& kind) : device_(device), kind_(kin
         RD_CHECK(v == "auto" || v == "fp32" || v == "h3", "RD_PRECISION must be auto, fp32 or h3");
         precision_ = v == "h3" ? PREC_H3 : v == "fp32" ? PREC_FP32 : PREC_AUTO;
     }
-    RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "pphgnetv2_b4" || kind == "pphgnetv2_b6_formula",
+    RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "ppocrv5_det_server" ||
+                 kind == "pphgnetv2_b4" || kind == "pphgnetv2_b6_formula",
              "unknown model kind '" + kind + "'");
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
@@ -1429,6 +1513,7 @@ void Engine::build(Builder& b, int B, int H, int W, int flags) {
     if (kind_ == "ppocrv6_det") build_ppocrv6_det(b, B, H, W);
     else if (kind_ == "ppocrv6_rec") build_ppocrv6_rec(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_rec_server") build_ppocrv5_rec_server(b, B, H, W, flags);
+    else if (kind_ == "ppocrv5_det_server") build_ppocrv5_det_server(b, B, H, W, flags);
     else if (kind_ == "pphgnetv2_b6_formula") build_pphgnetv2_b6_formula(b, B, H, W, flags);
     else build_pphgnetv2_b4(b, B, H, W);
 }
@@ -1443,6 +1528,8 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
     } else if (kind_ == "ppocrv5_rec_server") {
         n_classes_ = (int)store_.get("head.ctc_head.fc.weight").shape[0];
         rec_token_dim_ = (int)store_.get("head.ctc_encoder.encoder.conv1.conv.weight").shape[1];
+    } else if (kind_ == "ppocrv5_det_server") {
+        derive_ppocrv5_det_server_weights(store_);
     }
     Plan dummy;
     h3_prepared_ = precision_ == PREC_H3;

@@ -50,11 +50,14 @@ class WeightStore {
     bool has(const std::string& name) const { return map_.count(name) != 0; }
     const HostTensor& get(const std::string& name) const;
     size_t size() const { return map_.size(); }
-    void clear() { map_.clear(); blob_.clear(); blob_.shrink_to_fit(); }
+    void clear() { map_.clear(); blob_.clear(); blob_.shrink_to_fit(); derived_.clear(); }
+    // a tensor computed from loaded ones at load time (a folded multi-branch convolution): served by get() like a tensor of the file
+    void add_derived(const std::string& name, const std::vector<int64_t>& shape, std::vector<float>&& data);
 
    private:
     std::vector<uint8_t> blob_;
     std::unordered_map<std::string, HostTensor> map_;
+    std::vector<std::unique_ptr<std::vector<float>>> derived_;
 };
 
 // Folded, re-laid-out parameters in one device allocation.
@@ -203,6 +206,10 @@ class Builder {
     TView dwconv(const std::string& wname, const std::string& bname, const std::string& bn, const TView& x,
                  const ConvGeom& g, int act, const TView* out = nullptr, const TView* res = nullptr, GapOut* gap = nullptr,
                  const TView* tokinfo = nullptr);   // tokinfo: ragged rows (DwParams::tokinfo), an int32 external of x.pixels() entries
+    // PFHeadLocal's local tail in one kernel (kernels_det_local.hip): out = 0.5 (shrink + sigmoid(last_1(relu(bn(last_3(cat[shrink, up2(f)]))))));
+    // f [N][H/2][W/2][64], shrink [N][H][W][1], out [N][H][W][1].  No full-resolution 64- or 65-channel tensor is written
+    void det_local_tail(const std::string& w3n, const std::string& bn3, const std::string& w1n, const std::string& b1n, const TView& f,
+                        const TView& shrink, const TView& out);
     void maxpool2x2s1(const TView& x, const TView& out);
     TView avgpool3x2(const TView& x, const TView* out = nullptr);
     // squeeze-excite gate s[n][c]; `w1/b1/w2/b2` full tensor names
@@ -326,6 +333,12 @@ enum RecFlags : int { REC_UNFUSED_CTC = 1, REC_WANT_SOFTMAX = 2, REC_WANT_LOGITS
 void build_ppocrv6_rec(Builder& b, int B, int H, int W, int flags);
 // PP-OCRv5 server recogniser (PPHGNetV2-B4 text_rec + SVTR neck + CTC): same externals, flags and stages; REC_LINE_WIDTHS is refused
 void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags);
+// PP-OCRv5 server detector (PPHGNetV2-B4 + LKPAN with IntraCL + PFHeadLocal): ext[0] = x NCHW, ext[1] = maps [B,1,H,W];
+// DET_WANT_NECK: ext[2] = the neck output `fuse` NCHW [B,256,H/4,W/4]
+enum DetFlags : int { DET_WANT_NECK = 1 };
+void build_ppocrv5_det_server(Builder& b, int B, int H, int W, int flags);
+// tensors build_ppocrv5_det_server reads that are not in the file: the three branches of every IntraCL level folded into one k x k convolution
+void derive_ppocrv5_det_server_weights(WeightStore& ws);
 void build_pphgnetv2_b4(Builder& b, int B, int H, int W);
 // PP-FormulaNet_plus encoder; flags bit 0: the caller's image has 1 channel (replicated to 3 like the reference)
 void build_pphgnetv2_b6_formula(Builder& b, int B, int H, int W, int flags);

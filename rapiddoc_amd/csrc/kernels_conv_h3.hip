@@ -421,6 +421,10 @@ void launch_conv_igemm_h3(const ConvParams& p, hipStream_t s) {
         launch_conv3x3_h1(p, s);
         return;
     }
+    if (conv9x9_h1_applies(p)) {       // 9x9 stride 1 pad 4 to 33 .. 64 output channels (LKPAN): the same scheme with a 16 x 40 patch
+        launch_conv9x9_h1(p, s);
+        return;
+    }
     if (conv_direct_h3_applies(p)) {   // 2x2 / 3x3 stride 1, <= 96 output channels: patch in LDS, taps as address offsets
         launch_conv_direct_h3(p, s);
         return;

@@ -5,6 +5,8 @@
 //   DBHead (ppocrv6) ..... .../heads/det_db_head.py:52-149
 //   LightSVTR ............ .../necks/rnn.py:225-379
 //   MultiHead CTC branch . .../heads/rec_multi_head.py:43-75
+//   LKPAN ................ .../necks/db_fpn.py:418-525, IntraCLBlock .../necks/intracl.py
+//   PFHeadLocal .......... .../heads/det_db_head.py:8-49, 152-180
 //   PPHGNetV2-B4 (det) ... rapid_doc/model/formula/rapid_formula_self/networks/backbones/rec_pphgnetv2.py:860-1477
 #include "engine.h"
 
@@ -397,6 +399,110 @@ static void build_pphgnetv2(Builder& b, const TView& x, const HgStageCfg (&cfg)[
         emit(si, cur);
     }
     b.release(cur_cat);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// PP-OCRv5 server det (arch_config.yaml ch_PP-OCRv5_det_server): PPHGNetV2_B4(det=True) -> LKPAN(256, mode large, intracl) -> PFHeadLocal
+// (mode large).  ext[0] = x NCHW [B,3,H,W]; ext[1] = maps [B,1,H,W]; DET_WANT_NECK: ext[2] = fuse NCHW [B,256,H/4,W/4].
+// head.thresh.* is in the file and unused in eval mode: never asked for.
+// Two linear identities: (1) the three branches of an IntraCL level (k x k + k x 1 + 1 x k, biases included) are ONE k x k convolution
+// (derive_ppocrv5_det_server_weights); (2) last_3 over cat[shrink, up2(f)] = a 64-channel part over up2(f) + a 1-channel part over shrink,
+// both inside the fused tail kernel (Builder::det_local_tail), which also folds the 3 x 3 over the 2x upsample into a 2 x 2 per parity.
+// ---------------------------------------------------------------------------------------------------
+static const int kIntraK[3] = {7, 5, 3};
+static std::string intra_fold_name(const std::string& p, int k) { return p + ".fold_" + std::to_string(k) + "x" + std::to_string(k); }
+
+void derive_ppocrv5_det_server_weights(WeightStore& ws) {
+    for (int lvl = 1; lvl <= 4; ++lvl) {
+        const std::string p = "neck.incl" + std::to_string(lvl);
+        for (int k : kIntraK) {
+            const std::string ks = std::to_string(k);
+            const HostTensor& wc = ws.get(p + ".c_layer_" + ks + "x" + ks + ".weight");
+            const HostTensor& wv = ws.get(p + ".v_layer_" + ks + "x1.weight");
+            const HostTensor& wq = ws.get(p + ".q_layer_1x" + ks + ".weight");
+            RD_CHECK(wc.shape.size() == 4 && wc.shape[2] == k && wc.shape[3] == k, "IntraCL: c_layer shape");
+            const int co = (int)wc.shape[0], ci = (int)wc.shape[1];
+            RD_CHECK(wv.numel() == (size_t)co * ci * k && wq.numel() == (size_t)co * ci * k, "IntraCL: v / q layer shape");
+            std::vector<float> w(wc.f32(), wc.f32() + wc.numel());
+            for (int o = 0; o < co; ++o)
+                for (int i = 0; i < ci; ++i)
+                    for (int t = 0; t < k; ++t) {
+                        const size_t base = ((size_t)o * ci + i) * k * k;
+                        w[base + (size_t)t * k + k / 2] += wv.f32()[((size_t)o * ci + i) * k + t];      // k x 1: the middle column
+                        w[base + (size_t)(k / 2) * k + t] += wq.f32()[((size_t)o * ci + i) * k + t];    // 1 x k: the middle row
+                    }
+            std::vector<float> bias(co);
+            const float* bc = ws.get(p + ".c_layer_" + ks + "x" + ks + ".bias").f32();
+            const float* bv = ws.get(p + ".v_layer_" + ks + "x1.bias").f32();
+            const float* bq = ws.get(p + ".q_layer_1x" + ks + ".bias").f32();
+            for (int o = 0; o < co; ++o) bias[o] = bc[o] + bv[o] + bq[o];
+            ws.add_derived(intra_fold_name(p, k) + ".weight", {co, ci, k, k}, std::move(w));
+            ws.add_derived(intra_fold_name(p, k) + ".bias", {co}, std::move(bias));
+        }
+    }
+}
+
+void build_ppocrv5_det_server(Builder& b, int B, int H, int W, int flags) {
+    RD_CHECK(H % 32 == 0 && W % 32 == 0 && H >= 64 && W >= 64, "det server input H, W must be multiples of 32 (>= 64)");
+    RD_CHECK((flags & ~DET_WANT_NECK) == 0, "det server: unknown flag");
+    TView x = b.external(0, B, H, W, 3);
+    TView out = b.external(1, B, H, W, 1);
+    auto idx = [](const char* p, int i) { return std::string(p) + "." + std::to_string(i) + ".weight"; };
+
+    // backbone; ins_conv[i] (1x1 to 256) runs while stage i's buffer is live
+    TView in[4];
+    build_pphgnetv2(b, x, kB4Det, "backbone.", [&](int si, const TView& v) { in[si] = b.conv(idx("neck.ins_conv", si), "", "", v, geom(1), ACT_NONE); });
+    for (int i = 2; i >= 0; --i) b.upsample(in[i + 1], in[i], 2, true);          // out4, out3, out2 in place
+    TView f[4];
+    for (int i = 3; i >= 0; --i) {
+        f[i] = b.conv(idx("neck.inp_conv", i), "", "", in[i], geom(9), ACT_NONE);
+        b.release(in[i]);
+    }
+    // bottom-up path: pan_{i+1} = f_{i+1} + pan_head_conv[i](pan_i), the add as the convolution's residual
+    TView pan[4];
+    pan[0] = f[0];
+    for (int i = 0; i < 3; ++i) {
+        pan[i + 1] = b.conv(idx("neck.pan_head_conv", i), "", "", pan[i], geom(3, 2), ACT_NONE, nullptr, &f[i + 1]);
+        b.release(f[i + 1]);
+    }
+    TView cat = b.alloc(B, H / 4, W / 4, 256);
+    for (int i = 0; i < 4; ++i) {
+        TView pl = b.conv(idx("neck.pan_lat_conv", i), "", "", pan[i], geom(9), ACT_NONE);
+        // IntraCLBlock (reduce_factor 2): 1x1 down, three folded k x k levels, 1x1 back + BN + ReLU, + the block's input
+        const std::string p = "neck.incl" + std::to_string(i + 1);
+        TView t = b.conv(p + ".conv1x1_reduce_channel.weight", p + ".conv1x1_reduce_channel.bias", "", pl, geom(1), ACT_NONE);
+        for (int k : kIntraK) {
+            TView u = b.conv(intra_fold_name(p, k) + ".weight", intra_fold_name(p, k) + ".bias", "", t, geom(k), ACT_NONE);
+            b.release(t);
+            t = u;
+        }
+        TView slot = b.slice(cat, 64 * (3 - i), 64);                            // cat([p5, p4, p3, p2])
+        const std::string rw = p + ".conv1x1_return_channel.weight", rb = p + ".conv1x1_return_channel.bias";
+        if (i == 0) {
+            b.conv(rw, rb, p + ".bn", t, geom(1), ACT_RELU, &slot, &pl);
+        } else {
+            TView o = b.conv(rw, rb, p + ".bn", t, geom(1), ACT_RELU, nullptr, &pl);
+            b.upsample(o, slot, 1 << i, false);
+            b.release(o);
+        }
+        b.release(t);
+        b.release(pl);
+    }
+    for (int i = 0; i < 4; ++i) b.release(pan[i]);
+    if (flags & DET_WANT_NECK) {
+        TView o = b.external(2, B, cat.h, cat.w, cat.c);
+        b.to_nchw(cat, o);
+    }
+    // PFHeadLocal: binarize = conv1 + BN + ReLU -> transposed 2x2 + BN + ReLU (= f) -> transposed 2x2 + sigmoid (= shrink); then the local tail
+    TView c = b.conv("head.binarize.conv1.weight", "", "head.binarize.conv_bn1", cat, geom(3), ACT_RELU);
+    b.release(cat);
+    TView ff = b.deconv2x2("head.binarize.conv2.weight", "head.binarize.conv2.bias", "head.binarize.conv_bn2", c, ACT_RELU);
+    b.release(c);
+    TView shrink = b.deconv2x2("head.binarize.conv3.weight", "head.binarize.conv3.bias", "", ff, ACT_SIGMOID);
+    b.det_local_tail("head.cbn_layer.last_3.conv.weight", "head.cbn_layer.last_3.bn", "head.cbn_layer.last_1.weight", "head.cbn_layer.last_1.bias", ff,
+                     shrink, out);
+    b.release(shrink);
+    b.release(ff);
 }
 
 void build_pphgnetv2_b4(Builder& b, int B, int H, int W) {

@@ -62,6 +62,9 @@ struct ConvParams {
     // one-accumulator direct 3x3 (kernels_conv3x3_h1.hip): slab-ordered fragment image of the pre-scaled weights + the inverse scale
     const uint16_t* w3 = nullptr;
     float w3_inv = 0.f;
+    // one-accumulator direct 9x9 (kernels_conv9x9_h1.hip): slab-ordered fragment image of the pre-scaled weights + the inverse scale
+    const uint16_t* w9 = nullptr;
+    float w9_inv = 0.f;
     int fast_epi = 1;               // interior tiles of the split implicit-GEMM kernels store through buffer accesses (round 5; RD_CONV_FAST_EPI=0: A/B)
 };
 void launch_conv_igemm(const ConvParams& p, hipStream_t s);
@@ -103,6 +106,11 @@ bool conv3x3_h1_shape_ok(int kh, int kw, int cin, int cout);   // host-side: whi
 bool conv3x3_h1_applies(const ConvParams& p);
 void launch_conv3x3_h1(const ConvParams& p, hipStream_t s);
 float prepare_conv3x3_h1_weights(const float* w, int N, int Cin, std::vector<uint16_t>& img);   // returns the inverse scale
+// direct 9x9 / stride 1 / pad 4 to 33 .. 64 output channels, one accumulator set, two workgroups per CU (kernels_conv9x9_h1.hip): LKPAN
+bool conv9x9_h1_shape_ok(int kh, int kw, int cin, int cout);   // host-side: which layers get a weight image
+bool conv9x9_h1_applies(const ConvParams& p);
+void launch_conv9x9_h1(const ConvParams& p, hipStream_t s);
+float prepare_conv9x9_h1_weights(const float* w, int N, int Cin, std::vector<uint16_t>& img);   // returns the inverse scale
 // direct 2x2 / 3x3 stride-1 convolution for narrow outputs (kernels_conv_direct_h3.hip); launch_conv_igemm_h3 dispatches to it
 bool conv_direct_h3_supported(const ConvParams& p);   // geometry
 bool conv_direct_h3_applies(const ConvParams& p);     // geometry + routing policy
@@ -217,6 +225,22 @@ void launch_se_fc(const SeFcParams& p, hipStream_t s);
 bool det_head_tail_supported(int cin, int cmid, int cout);
 void launch_det_head_tail(const float* x, int xld, int N, int H, int W, const float* w1, const float* b1, const float* w2, const float* b2,
                           float* y, hipStream_t s);
+// Fused local tail of PFHeadLocal (kernels_det_local.hip): maps = 0.5 (shrink + sigmoid(last_1(relu(bn(last_3(cat[shrink, up2(f)])))))),
+// f NHWC [N][H/2][W/2][fld >= 64], shrink / y [N][H][W]; H and W even.  wimg16 set: the split-fp16 route, else native fp32 (wimg32).
+struct DetLocalParams {
+    const float* f; int fld;
+    const float* shrink;
+    float* y;
+    int N, H, W;
+    const float* wimg32;            // prepare_det_local_weights' fp32 fragment image
+    const uint16_t* wimg16;         // ... and its (hi, lo) fp16 image of the pre-scaled weights, or nullptr
+    float w_inv;                    // inverse of that scale
+    const float* b3;                // [64] last_3's folded BatchNorm shift
+    const float* w1; float b1;      // last_1: [64], bias
+    unsigned* range_flag;           // split route: raised when an operand leaves the fp16 range
+};
+void launch_det_local(const DetLocalParams& p, hipStream_t s);
+float prepare_det_local_weights(const float* w3_folded, std::vector<float>& img32, std::vector<uint16_t>& img16);   // returns the inverse scale
 void launch_scale_channels(const float* x, int xld, float* y, int yld, const float* scale, float alpha,
                            int N, int HW, int C, hipStream_t s);
 

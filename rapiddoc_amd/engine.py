@@ -14,7 +14,8 @@ from . import _lib, weights as W
 
 REC_UNFUSED_CTC, REC_WANT_SOFTMAX, REC_WANT_LOGITS = 1, 2, 4
 REC_WANT_NECK = 64          # ppocrv5_rec_server: `full` receives the neck's output [B, T, 120] instead
-KINDS = ("ppocrv6_det", "ppocrv6_rec", "ppocrv5_rec_server", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
+DET_WANT_NECK = 1           # ppocrv5_det_server: also hand out the neck's output `fuse` [B, 256, H/4, W/4]
+KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv6_rec", "ppocrv5_rec_server", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
 
 
 def rec_line_table(widths, first_tokens) -> np.ndarray:
@@ -154,8 +155,9 @@ class RdEngine:
             x = x.contiguous().float()
         return x
 
-    def det_forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, after_launch=None) -> torch.Tensor:
-        """`out` / `after_launch`: as in `rec_forward` (a caller-owned [B,1,H,W] float32 result tensor; work enqueued behind the launch)."""
+    def det_forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, after_launch=None, want_neck: bool = False):
+        """Either detector kind.  `out` / `after_launch`: as in `rec_forward` (a caller-owned [B,1,H,W] float32 result tensor; work
+        enqueued behind the launch).  `want_neck` (ppocrv5_det_server): returns (maps, fuse [B,256,H/4,W/4]) through rd_det_forward_ex."""
         x = self._prep(x)
         B, Cc, H, W_ = x.shape
         if out is None:
@@ -163,13 +165,19 @@ class RdEngine:
         elif out.shape != (B, 1, H, W_) or out.dtype != torch.float32 or not out.is_contiguous():
             raise EngineError("det_forward: `out` does not match the forward's shape")
 
+        neck = torch.empty((B, 256, H // 4, W_ // 4), dtype=torch.float32, device=x.device) if want_neck else None
+
         def launch():
-            self._chk(self._l.rd_det_forward(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), None, 0, _stream_ptr()))
+            if want_neck:
+                self._chk(self._l.rd_det_forward_ex(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), DET_WANT_NECK, neck.data_ptr(), None, 0,
+                                                    _stream_ptr()))
+            else:
+                self._chk(self._l.rd_det_forward(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), None, 0, _stream_ptr()))
             self._log()
             if after_launch is not None:
                 after_launch()
         self._guarded(launch)
-        return out
+        return (out, neck) if want_neck else out
 
     def rec_forward(self, x: torch.Tensor, flags: int = 0, out: Optional[tuple] = None,
                     after_launch=None) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:

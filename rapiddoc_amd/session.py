@@ -104,9 +104,51 @@ class _BaseSession:
 # The split-fp16 range guard (fp32 re-run) is part of every RdEngine forward (engine.RdEngine._guarded, guard="sync").
 
 
+# Detector architectures this engine serves, by weight-file stem (the reference: the stem through arch_config.yaml, torch.py:69-76).
+DET_ARCH_BY_STEM = {
+    "ch_PP-OCRv6_det_small": "ppocrv6_det",
+    "ch_PP-OCRv5_det_server": "ppocrv5_det_server",
+}
+
+
+def _state_keys(weights) -> set:
+    """Tensor names of a state dict or of a safetensors byte image, a leading `model.` dropped."""
+    if isinstance(weights, (bytes, bytearray, memoryview)):
+        import json
+        import struct
+        (hlen,) = struct.unpack("<Q", bytes(weights[:8]))
+        keys = set(json.loads(bytes(weights[8:8 + hlen])))
+    else:
+        keys = set(weights)
+    return {k[len("model."):] if k.startswith("model.") else k for k in keys}
+
+
+def resolve_det_kind(weights: WeightSrc) -> str:
+    """Engine kind of a detector's weights, built like `resolve_rec_kind`: a file goes by its stem (an unknown one is an error), a state
+    dict or a nameless safetensors image by the head it carries (`head.cbn_layer.last_1.weight`: PFHeadLocal of the v5 server detector;
+    `head.conv_down.convolution.weight`: the v6 DB head)."""
+    if isinstance(weights, (str, Path)):
+        stem = Path(str(weights)).stem
+        if stem not in DET_ARCH_BY_STEM:
+            raise ValueError(f"architecture {stem} is not in the detectors this engine serves {sorted(DET_ARCH_BY_STEM)}")
+        return DET_ARCH_BY_STEM[stem]
+    keys = _state_keys(weights)
+    if "head.cbn_layer.last_1.weight" in keys:
+        return "ppocrv5_det_server"
+    if "head.conv_down.convolution.weight" in keys:
+        return "ppocrv6_det"
+    raise ValueError("architecture of the detector weights is not in the detectors this engine serves "
+                     "(neither head.cbn_layer.last_1.weight nor head.conv_down.convolution.weight among the tensors)")
+
+
 class Mi355DetSession(_BaseSession):
-    """PP-OCRv6 det: [B,3,H,W] -> DB probability map [B,1,H,W] (`maps`, ocr/torch.py:183-184)."""
+    """PP-OCRv6 small / PP-OCRv5 server det: [B,3,H,W] -> DB probability map [B,1,H,W] (`maps`, ocr/torch.py:183-184).  The kind
+    follows from the weights (`resolve_det_kind`) unless `kind` names it."""
     kind = "ppocrv6_det"
+
+    def __init__(self, weights: WeightSrc, device: int = 0, kind: Optional[str] = None):
+        self.kind = kind or resolve_det_kind(weights)
+        super().__init__(weights, device)
 
     def __call__(self, img: np.ndarray) -> np.ndarray:
         with torch.cuda.stream(self.stream):

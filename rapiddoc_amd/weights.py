@@ -69,6 +69,12 @@ def synth_tensor(name: str, shape: Tuple[int, ...], dtype: str, seed: int) -> np
             std *= 6.0
         if name == "head.ctc_head.fc.weight":  # PP-OCRv5 server CTC classifier: its neck output is nearly flat, 30x opens the top-2 gaps
             std *= 30.0
+        # PP-OCRv5 server detector: with the plain rule both logits of PFHeadLocal stay near 0 and `maps` is flat (0.44-0.67); these two
+        # gains spread the shrink and the cbn logits so that the map fills (0, 1)
+        if name == "head.binarize.conv3.weight":
+            std *= 10.0
+        if name == "head.cbn_layer.last_1.weight":
+            std *= 100.0
         return rng.normal(0.0, std, shape).astype(np.float32)
     return rng.normal(0.0, 0.05, shape).astype(np.float32)
 
