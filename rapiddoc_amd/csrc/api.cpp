@@ -39,7 +39,7 @@ static int guarded(rd_handle* h, F&& f) {
 }
 
 // the recogniser kinds share one C surface (rd_rec_*)
-static bool is_rec_kind(const std::string& k) { return k == "ppocrv6_rec" || k == "ppocrv5_rec_server"; }
+static bool is_rec_kind(const std::string& k) { return k == "ppocrv6_rec" || k == "ppocrv5_rec_server" || k == "ppocrv5_rec_mobile"; }
 
 extern "C" {
 
@@ -124,7 +124,7 @@ int rd_det_forward_ex(rd_handle* h, const float* x, int B, int H, int W, float* 
 int rd_rec_forward(rd_handle* h, const float* x, int B, int W, int32_t* idx, float* prob, float* full, int flags, void* ws,
                    size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server) model");
+        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server / ppocrv5_rec_mobile) model");
         RD_CHECK(x && idx && prob && B > 0, "null input/output");
         if (flags & (RD_REC_WANT_SOFTMAX | RD_REC_WANT_LOGITS | RD_REC_WANT_NECK)) RD_CHECK(full, "full_btc_dev is NULL");
         RD_CHECK(!((flags & RD_REC_WANT_SOFTMAX) && (flags & RD_REC_WANT_LOGITS)), "choose softmax OR logits");
@@ -135,7 +135,7 @@ int rd_rec_forward(rd_handle* h, const float* x, int B, int W, int32_t* idx, flo
 int rd_rec_token_dim(rd_handle* h) { return (h && h->eng && is_rec_kind(h->eng->kind())) ? h->eng->rec_token_dim() : -1; }
 int rd_rec_backbone_forward(rd_handle* h, const float* x, int B, int W, float* tokens, void* ws, size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server) model");
+        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server / ppocrv5_rec_mobile) model");
         RD_CHECK(x && tokens && B > 0, "null input/output");
         h->eng->run(B, 48, W, rd::REC_STAGE_BACKBONE, {(void*)x, (void*)tokens}, ws, ws_bytes, (hipStream_t)stream);
     });
@@ -146,7 +146,8 @@ int rd_rec_backbone_forward_lines(rd_handle* h, const float* x, int B, int W, co
         RD_CHECK(!(h->eng && h->eng->kind() == "ppocrv5_rec_server"),
                  "rd_rec_backbone_forward_lines: per-line widths inside one backbone launch are out of scope for ppocrv5_rec_server "
                  "(run the backbone stage once per padded width)");
-        RD_CHECK(h->eng && h->eng->kind() == "ppocrv6_rec", "handle is not a ppocrv6_rec model");
+        RD_CHECK(h->eng && (h->eng->kind() == "ppocrv6_rec" || h->eng->kind() == "ppocrv5_rec_mobile"),
+                 "handle is not a ppocrv6_rec / ppocrv5_rec_mobile model");
         RD_CHECK(x && tokens && line_tab && B > 0, "null input/output");
         h->eng->run(B, 48, W, rd::REC_STAGE_BACKBONE | rd::REC_LINE_WIDTHS, {(void*)x, (void*)tokens, (void*)line_tab}, ws, ws_bytes,
                     (hipStream_t)stream);
@@ -155,7 +156,7 @@ int rd_rec_backbone_forward_lines(rd_handle* h, const float* x, int B, int W, co
 int rd_rec_tail_forward(rd_handle* h, const float* tokens, int n_tokens, int n_lines, int max_tokens, const int32_t* seg,
                         const int32_t* tokinfo, int32_t* idx, float* prob, void* ws, size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server) model");
+        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server / ppocrv5_rec_mobile) model");
         RD_CHECK(tokens && seg && tokinfo && idx && prob && n_tokens > 0 && n_lines > 0 && max_tokens > 0, "null input/output");
         h->eng->run(n_lines, max_tokens, n_tokens, rd::REC_STAGE_TAIL,
                     {(void*)tokens, (void*)idx, (void*)prob, nullptr, (void*)seg, (void*)tokinfo}, ws, ws_bytes, (hipStream_t)stream);
@@ -736,6 +737,59 @@ float rd_debug_dwconv(int N, int H, int W, int C, int K, int SH, int act, int it
     rd::launch_dwconv(p, nullptr);
     (void)hipEventRecord(e0, nullptr);
     for (int i = 0; i < iters; ++i) rd::launch_dwconv(p, nullptr);
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return iters > 0 ? ms / iters : 0.f;
+}
+
+// developer entry: one PPLCNetV3 depthwise layer through launch_lcv3_dw (kernels_lcv3.hip; x NHWC fp32 [N][H][W][C], w [K*K][C], bias [C],
+// y [N][OH][OW][C]; aff = {pre_s, pre_b, post_s, post_b}, pre_act: hardswish + (pre_s, pre_b) on load; line_in / line_out int32 [N] valid
+// widths or null; gap: [N][OH][C] row sums of y over the output width, or null).  Returns ms per launch, < 0: geometry not served.
+float rd_debug_lcv3_dw(int N, int H, int W, int C, int K, int SH, int SW, int pre_act, int iters, const float* aff, float* x, float* w, float* bias,
+                       float* y, const int32_t* line_in, const int32_t* line_out, float* gap) {
+    if (!rd::lcv3_dw_shape_ok(K, SH, SW, C) || !aff || (gap && !rd::lcv3_gap_shape_ok(C))) return -1.f;
+    rd::Lcv3DwParams p{};
+    p.x = x; p.xld = C; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = C;
+    p.K = K; p.SH = SH; p.SW = SW;
+    p.OH = (H + 2 * (K / 2) - K) / SH + 1; p.OW = (W + 2 * (K / 2) - K) / SW + 1;
+    p.pre_act = pre_act; p.pre_s = aff[0]; p.pre_b = aff[1]; p.post_s = aff[2]; p.post_b = aff[3];
+    p.line_in = line_in; p.line_out = line_out; p.line_stride = 1;
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    rd::launch_lcv3_dw(p, nullptr);
+    if (gap) rd::launch_lcv3_gap_rows(y, C, N, p.OH, p.OW, C, gap, line_out, 1, nullptr);
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) rd::launch_lcv3_dw(p, nullptr);
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return iters > 0 ? ms / iters : 0.f;
+}
+
+// developer entry: one PPLCNetV3 block (depthwise 3x3 stride 1 -> pointwise) through launch_lcv3_block (kernels_lcv3_block.hip; x NHWC fp32
+// [N][H][W][cin], dw_w [9][cin], dw_b [cin], pw_w [cout][cin], pw_b [cout], y [N][H][W][cout]; aff = {pre_s, pre_b, mid_s, mid_b, out_s,
+// out_b}; pre_act / out_act: hardswish + affine on load / in the epilogue; split: 1 = split-fp16 product raising *range_flag (a device-
+// visible word) on an operand beyond the fp16 range, 0 = fp32 product; line_w int32 [N] valid widths or null).  Returns ms per launch,
+// < 0: geometry not served.
+float rd_debug_lcv3_block(int N, int H, int W, int cin, int cout, int pre_act, int out_act, int split, int iters, const float* aff, float* x,
+                          float* dw_w, float* dw_b, float* pw_w, float* pw_b, float* y, const int32_t* line_w, unsigned* range_flag) {
+    if (!rd::lcv3_block_shape_ok(cin, cout) || !aff || N < 1 || H < 1 || W < 1) return -1.f;
+    rd::Lcv3BlockParams p{};
+    p.x = x; p.xld = cin; p.N = N; p.H = H; p.W = W; p.cin = cin; p.cout = cout;
+    p.dw_w = dw_w; p.dw_b = dw_b; p.pw_w = pw_w; p.pw_b = pw_b; p.y = y; p.yld = cout;
+    p.pre_act = pre_act; p.pre_s = aff[0]; p.pre_b = aff[1]; p.mid_s = aff[2]; p.mid_b = aff[3];
+    p.out_act = out_act; p.out_s = aff[4]; p.out_b = aff[5];
+    p.line_w = line_w; p.line_stride = 1; p.split = split; p.range_flag = range_flag;
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    rd::launch_lcv3_block(p, nullptr);
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) rd::launch_lcv3_block(p, nullptr);
     (void)hipEventRecord(e1, nullptr);
     (void)hipEventSynchronize(e1);
     float ms = 0.f;

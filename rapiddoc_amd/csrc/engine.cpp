@@ -908,18 +908,22 @@ TView Builder::seqconv(const std::string& wname, const std::string& bn, const TV
     const int cout = (int)w.shape[0], cin = (int)w.shape[1], kh = (int)w.shape[2];
     const int c0 = x0.c, c1 = x1 ? x1->c : 0;
     RD_CHECK(cin == c0 + c1, "seqconv Cin mismatch: " + wname);
-    RD_CHECK(seqconv_shape_ok(c0, c1, cout), "seqconv: channel counts (segments % 16, Cout % 64): " + wname);
+    // a layer narrower than the kernel's 64-channel tile (the mobile neck's 60) is prepared with zero rows up to 64; consumers read `cout`
+    const int coutp = (cout + 63) / 64 * 64;
+    RD_CHECK(seqconv_shape_ok(c0, c1, coutp), "seqconv: channel counts (segments % 16): " + wname);
     RD_CHECK(x0.h == 1 && (!x1 || (x1->h == 1 && x1->n == x0.n && x1->w == x0.w)), "seqconv: one row of tokens per line: " + wname);
     const bool ragged = tokinfo != nullptr;
     RD_CHECK(!ragged || x0.n == 1, "ragged seqconv: one token row");
-    TView y = alloc(x0.n, 1, x0.w, cout);
+    TView yp = alloc(x0.n, 1, x0.w, coutp);
+    TView y = coutp == cout ? yp : slice(yp, 0, cout);
     const int K = 3 * cin;
     const std::string key = wname + "|" + bn + "|seq";
     if (!planning()) {
         if (!pb_->has(key + "#w")) {
             std::vector<float> shift;
             std::vector<float> scale = bn_scale_shift(bn, cout, shift);
-            std::vector<float> wf((size_t)cout * K);
+            std::vector<float> wf((size_t)coutp * K, 0.f);
+            shift.resize(coutp, 0.f);
             const float* src = w.f32();
             const int mid = kh / 2;
             for (int co = 0; co < cout; ++co)
@@ -929,7 +933,7 @@ TView Builder::seqconv(const std::string& wname, const std::string& bn, const TV
             pb_->add(key + "#b", shift);
             if (fits_fp16_range(wf)) {      // (both split precision modes take the split route: the layer is the tail's widest)
                 std::vector<uint16_t> hi, lo;
-                split_weights_h3(wf.data(), cout, K, hi, lo);
+                split_weights_h3(wf.data(), coutp, K, hi, lo);
                 pb_->add_u16(key + "#wh", hi);
                 pb_->add_u16(key + "#wl", lo);
             }
@@ -948,8 +952,8 @@ TView Builder::seqconv(const std::string& wname, const std::string& bn, const TV
         p.wl = reinterpret_cast<const uint16_t*>(pb_->ptr(key + "#wl"));
         p.range_flag = range_flag_;
     }
-    p.yld = plan_->ld(y);
-    p.M = (int)x0.pixels(); p.N = cout;
+    p.yld = plan_->ld(yp);
+    p.M = (int)x0.pixels(); p.N = coutp;
     p.T = x0.w;
     p.act = act;
     OpRecord r;
@@ -959,7 +963,7 @@ TView Builder::seqconv(const std::string& wname, const std::string& bn, const TV
     r.shape = "M" + std::to_string(p.M) + "_K" + std::to_string(K) + "_N" + std::to_string(cout);
     r.flops = 2.0 * p.M * (double)K * cout;
     r.bytes = 4.0 * ((double)p.M * cin + (double)p.M * cout) + 4.0 * (double)cout * K;
-    const TView x0v = x0, x1v = x1 ? *x1 : TView{}, yv = y, tiv = ragged ? *tokinfo : TView{};
+    const TView x0v = x0, x1v = x1 ? *x1 : TView{}, yv = yp, tiv = ragged ? *tokinfo : TView{};
     const bool has1 = x1 != nullptr;
     r.run = [p, x0v, x1v, yv, tiv, has1, ragged](const Plan& pl, const RunCtx& c) {
         SeqConvParams q = p;
@@ -1126,6 +1130,166 @@ void Builder::det_local_tail(const std::string& w3n, const std::string& bn3, con
         launch_det_local(q, c.stream);
     };
     emit(std::move(r));
+}
+
+Builder::Affine Builder::affine(const std::string& prefix) const {
+    const HostTensor& sc = ws_->get(prefix + ".scale");
+    const HostTensor& bi = ws_->get(prefix + ".bias");
+    RD_CHECK(sc.numel() == 1 && bi.numel() == 1, "scalar affine expected: " + prefix);
+    return Affine{sc.f32()[0], bi.f32()[0]};
+}
+
+TView Builder::lcv3_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre, Affine post,
+                       int lt_in, int lt_out) {
+    const HostTensor& w = ws_->get(wname);
+    RD_CHECK(w.shape.size() == 4 && w.shape[1] == 1 && w.shape[2] == k && w.shape[3] == k, "lcv3 depthwise weight shape: " + wname);
+    const int c = (int)w.shape[0];
+    RD_CHECK(c == x.c && lcv3_dw_shape_ok(k, sh, sw, c), "lcv3 depthwise geometry: " + wname);
+    const int oh = out_dim(x.h, k, sh, k / 2, k / 2), ow = out_dim(x.w, k, sw, k / 2, k / 2);
+    TView y = alloc(x.n, oh, ow, c);
+    const std::string key = wname + "|lcv3dw";
+    if (!planning()) {
+        if (!pb_->has(key + "#w")) {
+            std::vector<float> wf((size_t)k * k * c);
+            for (int ch = 0; ch < c; ++ch)
+                for (int t = 0; t < k * k; ++t) wf[(size_t)t * c + ch] = w.f32()[(size_t)ch * k * k + t];
+            pb_->add(key + "#w", wf);
+            pb_->add(key + "#b", std::vector<float>(ws_->get(bname).f32(), ws_->get(bname).f32() + c));
+        }
+        return y;
+    }
+    Lcv3DwParams p{};
+    p.xld = plan_->ld(x);
+    p.N = x.n; p.H = x.h; p.W = x.w; p.C = c;
+    p.w = pb_->ptr(key + "#w");
+    p.bias = pb_->ptr(key + "#b");
+    p.yld = plan_->ld(y);
+    p.OH = oh; p.OW = ow; p.K = k; p.SH = sh; p.SW = sw;
+    p.pre_act = pre != nullptr;
+    p.pre_s = pre ? pre->s : 1.f; p.pre_b = pre ? pre->b : 0.f; p.post_s = post.s; p.post_b = post.b;
+    RD_CHECK(p.xld % 4 == 0 && x.coff % 4 == 0, "lcv3 depthwise: 16-byte aligned pixels");
+    OpRecord r;
+    r.name = wname;
+    r.kind = "lcv3_dw" + std::to_string(k) + "x" + std::to_string(k);
+    r.cfg = "s" + std::to_string(sh) + std::to_string(sw) + (has_lt_ ? "/lines" : "");
+    r.shape = "N" + std::to_string(x.n) + "_" + std::to_string(x.h) + "x" + std::to_string(x.w) + "_C" + std::to_string(c);
+    r.flops = 2.0 * x.n * oh * ow * (double)c * k * k;
+    r.bytes = 4.0 * ((double)x.pixels() * c + (double)y.pixels() * c);
+    const TView xv = x, yv = y, ltv = lt_;
+    const bool has_lt = has_lt_;
+    r.run = [p, xv, yv, ltv, has_lt, lt_in, lt_out](const Plan& pl, const RunCtx& cx) {
+        Lcv3DwParams q = p;
+        q.x = pl.vptr(xv, cx);
+        q.y = pl.vptr(yv, cx);
+        if (has_lt) {
+            const int32_t* lt = reinterpret_cast<const int32_t*>(pl.vptr(ltv, cx));
+            q.line_in = lt + lt_in;
+            q.line_out = lt + lt_out;
+            q.line_stride = kLineTabStride;
+        }
+        launch_lcv3_dw(q, cx.stream);
+    };
+    emit(std::move(r));
+    return y;
+}
+
+// the fused block's own parameters: the pointwise weights [cout][cin] as fp32 (the kernel splits them once per workgroup) + bias, for layers
+// whose weights fit the fp16 range.  Prepared for every handle (28 KB over the three blocks): plans pick the route later, per plan
+void Builder::prepare_lcv3_block(const std::string& key, const HostTensor& w, const std::string& pw_b) {
+    if (pb_->has(key + "#w")) return;
+    const int cout = (int)w.shape[0], cin = (int)w.shape[1];
+    std::vector<float> wf(w.f32(), w.f32() + (size_t)cout * cin);
+    if (!fits_fp16_range(wf)) return;
+    pb_->add(key + "#w", wf);
+    pb_->add(key + "#b", std::vector<float>(ws_->get(pw_b).f32(), ws_->get(pw_b).f32() + cout));
+}
+
+bool Builder::lcv3_block(const std::string& dw_w, const std::string& pw_w, const std::string& pw_b, const TView& x, const Affine* pre, Affine mid,
+                         int lt_col, TView* y_out) {
+    const HostTensor& w = ws_->get(pw_w);
+    const int cout = (int)w.shape[0], cin = (int)w.shape[1];
+    if (cin != x.c || !lcv3_block_shape_ok(cin, cout)) return false;
+    const std::string key = pw_w + "|lcv3blk", dkey = dw_w + "|lcv3dw";
+    if (!planning()) {          // PREPARE: the parameters only; the caller goes on to prepare the separate operators, whose depthwise
+        prepare_lcv3_block(key, w, pw_b);   // parameters this kernel shares
+        return false;
+    }
+    const bool on = std::getenv("RD_LCV3_FUSED") && std::getenv("RD_LCV3_FUSED")[0] == '1';   // A/B switch, read per plan
+    if (!on || !(h3_ || mixer_h3_) || !pb_->has(key + "#w") || !pb_->has(dkey + "#w") || plan_->ld(x) % 4 != 0 || x.coff % 4 != 0) return false;
+    TView y = alloc(x.n, x.h, x.w, cout);
+    Lcv3BlockParams p{};
+    p.xld = plan_->ld(x);
+    p.N = x.n; p.H = x.h; p.W = x.w; p.cin = cin; p.cout = cout;
+    p.dw_w = pb_->ptr(dkey + "#w"); p.dw_b = pb_->ptr(dkey + "#b");
+    p.pw_w = pb_->ptr(key + "#w"); p.pw_b = pb_->ptr(key + "#b");
+    p.yld = plan_->ld(y);
+    p.pre_act = pre != nullptr;
+    p.pre_s = pre ? pre->s : 1.f; p.pre_b = pre ? pre->b : 0.f; p.mid_s = mid.s; p.mid_b = mid.b;
+    p.out_act = 0; p.out_s = 1.f; p.out_b = 0.f;
+    p.split = 1; p.range_flag = range_flag_;
+    OpRecord r;
+    r.name = pw_w;
+    r.kind = "lcv3_block";
+    r.cfg = has_lt_ ? "h3/lines" : "h3";
+    r.shape = "N" + std::to_string(x.n) + "_" + std::to_string(x.h) + "x" + std::to_string(x.w) + "_C" + std::to_string(cin) + "_" + std::to_string(cout);
+    r.flops = 2.0 * x.pixels() * (double)cin * (9 + cout);
+    r.bytes = 4.0 * (double)x.pixels() * (cin + cout);
+    const TView xv = x, yv = y, ltv = lt_;
+    const bool has_lt = has_lt_;
+    r.run = [p, xv, yv, ltv, has_lt, lt_col](const Plan& pl, const RunCtx& cx) {
+        Lcv3BlockParams q = p;
+        q.x = pl.vptr(xv, cx);
+        q.y = pl.vptr(yv, cx);
+        if (has_lt) {
+            q.line_w = reinterpret_cast<const int32_t*>(pl.vptr(ltv, cx)) + lt_col;
+            q.line_stride = kLineTabStride;
+        }
+        launch_lcv3_block(q, cx.stream);
+    };
+    emit(std::move(r));
+    *y_out = y;
+    return true;
+}
+
+Builder::GapOut Builder::lcv3_gap(const TView& x, int lt_col) {
+    RD_CHECK(lcv3_gap_shape_ok(x.c), "lcv3 gap: channels % 4, at most 4096");
+    GapOut g;
+    g.chunks = x.h;
+    g.partial = alloc_raw((size_t)x.n * x.h * x.c);
+    if (!planning()) return g;
+    OpRecord r;
+    r.name = "lcv3_gap";
+    r.kind = "gap";
+    r.cfg = has_lt_ ? "rows/lines" : "rows";
+    r.bytes = 4.0 * x.pixels() * x.c;
+    const TView xv = x, pv = g.partial, ltv = lt_;
+    const bool has_lt = has_lt_;
+    r.run = [xv, pv, ltv, has_lt, lt_col](const Plan& pl, const RunCtx& cx) {
+        launch_lcv3_gap_rows(pl.vptr(xv, cx), pl.ld(xv), xv.n, xv.h, xv.w, xv.c, pl.vptr(pv, cx),
+                             has_lt ? reinterpret_cast<const int32_t*>(pl.vptr(ltv, cx)) + lt_col : nullptr, kLineTabStride, cx.stream);
+    };
+    emit(std::move(r));
+    return g;
+}
+
+TView Builder::lcv3_pool(const TView& x, Affine post, const TView* out) {
+    RD_CHECK(x.h == 3 && x.w >= 2 && x.c % 4 == 0, "lcv3 pool: a 3-row map");
+    const int ow = (x.w - 2) / 2 + 1;
+    TView y = out ? *out : alloc(x.n, 1, ow, x.c);
+    RD_CHECK(y.n == x.n && y.h == 1 && y.w == ow && y.c == x.c, "lcv3 pool: output view mismatch");
+    if (!planning()) return y;
+    OpRecord r;
+    r.name = "hswish+avgpool3x2+affine";
+    r.kind = "pool";
+    r.bytes = 4.0 * (x.pixels() * x.c + y.pixels() * y.c);
+    const TView xv = x, yv = y, ltv = lt_;
+    const bool has_lt = has_lt_;
+    r.run = [xv, yv, ltv, has_lt, post](const Plan& pl, const RunCtx& c) {
+        launch_lcv3_pool(pl.vptr(xv, c), pl.ld(xv), pl.vptr(yv, c), pl.ld(yv), xv.n, xv.h, xv.w, xv.c, post.s, post.b, c.stream,
+                         has_lt ? reinterpret_cast<const int32_t*>(pl.vptr(ltv, c)) : nullptr);
+    };
+    emit(std::move(r));
+    return y;
 }
 
 void Builder::maxpool2x2s1(const TView& x, const TView& out) {
@@ -1465,7 +1629,7 @@ Engine::Engine(int device, const std::string& kind) : device_(device), kind_(kin
         RD_CHECK(v == "auto" || v == "fp32" || v == "h3", "RD_PRECISION must be auto, fp32 or h3");
         precision_ = v == "h3" ? PREC_H3 : v == "fp32" ? PREC_FP32 : PREC_AUTO;
     }
-    RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "ppocrv5_det_server" ||
+    RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "ppocrv5_rec_mobile" || kind == "ppocrv5_det_server" ||
                  kind == "pphgnetv2_b4" || kind == "pphgnetv2_b6_formula",
              "unknown model kind '" + kind + "'");
     int count = 0;
@@ -1513,6 +1677,7 @@ void Engine::build(Builder& b, int B, int H, int W, int flags) {
     if (kind_ == "ppocrv6_det") build_ppocrv6_det(b, B, H, W);
     else if (kind_ == "ppocrv6_rec") build_ppocrv6_rec(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_rec_server") build_ppocrv5_rec_server(b, B, H, W, flags);
+    else if (kind_ == "ppocrv5_rec_mobile") build_ppocrv5_rec_mobile(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_det_server") build_ppocrv5_det_server(b, B, H, W, flags);
     else if (kind_ == "pphgnetv2_b6_formula") build_pphgnetv2_b6_formula(b, B, H, W, flags);
     else build_pphgnetv2_b4(b, B, H, W);
@@ -1525,9 +1690,10 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
     if (kind_ == "ppocrv6_rec") {
         n_classes_ = (int)store_.get("head.head.weight").shape[0];  // torch.py:112-116
         rec_token_dim_ = (int)store_.get("head.encoder.conv_block.0.convolution.weight").shape[1];
-    } else if (kind_ == "ppocrv5_rec_server") {
+    } else if (kind_ == "ppocrv5_rec_server" || kind_ == "ppocrv5_rec_mobile") {
         n_classes_ = (int)store_.get("head.ctc_head.fc.weight").shape[0];
         rec_token_dim_ = (int)store_.get("head.ctc_encoder.encoder.conv1.conv.weight").shape[1];
+        if (kind_ == "ppocrv5_rec_mobile") derive_ppocrv5_rec_mobile_weights(store_);
     } else if (kind_ == "ppocrv5_det_server") {
         derive_ppocrv5_det_server_weights(store_);
     }
@@ -1540,7 +1706,7 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
     RD_HIP(hipHostGetDevicePointer((void**)&range_flag_, (void*)range_flag_host_, 0));
     Builder b(Mode::PREPARE, &store_, &params_, &dummy, h3_prepared_, true);
     // smallest legal geometry; only weight names/shapes matter in PREPARE mode
-    if (kind_ == "ppocrv6_rec" || kind_ == "ppocrv5_rec_server") build(b, 1, 48, 64, 0), build(b, 1, 48, 64, REC_UNFUSED_CTC);
+    if (kind_ == "ppocrv6_rec" || kind_ == "ppocrv5_rec_server" || kind_ == "ppocrv5_rec_mobile") build(b, 1, 48, 64, 0), build(b, 1, 48, 64, REC_UNFUSED_CTC);
     else build(b, 1, 64, 64, 0);
     params_.upload();
     loaded_ = true;

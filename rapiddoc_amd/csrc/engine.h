@@ -210,6 +210,21 @@ class Builder {
     // f [N][H/2][W/2][64], shrink [N][H][W][1], out [N][H][W][1].  No full-resolution 64- or 65-channel tensor is written
     void det_local_tail(const std::string& w3n, const std::string& bn3, const std::string& w1n, const std::string& b1n, const TView& f,
                         const TView& shrink, const TView& out);
+    // PPLCNetV3 (kernels_lcv3.hip).  A scalar affine y = s x + b (LearnableAffineBlock); `pre` (when given) = the act.lab of the pointwise
+    // layer that produced x: that layer wrote conv + bias only and its consumer applies hardswish + act.lab on load; `post` = the layer's own.  lt_in / lt_out: LineTab columns of the valid
+    // input / output width under a line table
+    struct Affine { float s = 1.f, b = 0.f; };
+    Affine affine(const std::string& prefix) const;      // prefix.scale / prefix.bias
+    TView lcv3_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre, Affine post, int lt_in,
+                  int lt_out);
+    // one block without SE (3x3, stride 1) in one launch (kernels_lcv3_block.hip), writing the pointwise layer's convolution + bias as the separate
+    // route does.  Taken under RD_LCV3_FUSED=1 in the split precisions; false: not taken (and always in PREPARE mode, where it only adds its
+    // parameters), the caller emits the separate operators
+    void prepare_lcv3_block(const std::string& key, const HostTensor& w, const std::string& pw_b);
+    bool lcv3_block(const std::string& dw_w, const std::string& pw_w, const std::string& pw_b, const TView& x, const Affine* pre, Affine mid, int lt_col,
+                    TView* y);
+    GapOut lcv3_gap(const TView& x, int lt_col);          // SE pooling partial sums of x, one chunk per row
+    TView lcv3_pool(const TView& x, Affine post, const TView* out = nullptr);   // the deferred hardswish, avg_pool2d([3, 2]), the deferred affine
     void maxpool2x2s1(const TView& x, const TView& out);
     TView avgpool3x2(const TView& x, const TView* out = nullptr);
     // squeeze-excite gate s[n][c]; `w1/b1/w2/b2` full tensor names
@@ -333,6 +348,10 @@ enum RecFlags : int { REC_UNFUSED_CTC = 1, REC_WANT_SOFTMAX = 2, REC_WANT_LOGITS
 void build_ppocrv6_rec(Builder& b, int B, int H, int W, int flags);
 // PP-OCRv5 server recogniser (PPHGNetV2-B4 text_rec + SVTR neck + CTC): same externals, flags and stages; REC_LINE_WIDTHS is refused
 void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags);
+// PP-OCRv5 mobile recogniser (PPLCNetV3 scale 0.95 + the same SVTR neck + CTC): same externals, flags and stages; REC_LINE_WIDTHS is served
+void build_ppocrv5_rec_mobile(Builder& b, int B, int H, int W, int flags);
+// tensors build_ppocrv5_rec_mobile reads that are not in the file: every LearnableRepLayer folded into one convolution + bias
+void derive_ppocrv5_rec_mobile_weights(WeightStore& ws);
 // PP-OCRv5 server detector (PPHGNetV2-B4 + LKPAN with IntraCL + PFHeadLocal): ext[0] = x NCHW, ext[1] = maps [B,1,H,W];
 // DET_WANT_NECK: ext[2] = the neck output `fuse` NCHW [B,256,H/4,W/4]
 enum DetFlags : int { DET_WANT_NECK = 1 };

@@ -7,8 +7,11 @@
 //   MultiHead CTC branch . .../heads/rec_multi_head.py:43-75
 //   LKPAN ................ .../necks/db_fpn.py:418-525, IntraCLBlock .../necks/intracl.py
 //   PFHeadLocal .......... .../heads/det_db_head.py:8-49, 152-180
+//   PPLCNetV3 (rec) ...... .../backbones/rec_lcnetv3.py:45-64, 76-351, 493-517
 //   PPHGNetV2-B4 (det) ... rapid_doc/model/formula/rapid_formula_self/networks/backbones/rec_pphgnetv2.py:860-1477
 #include "engine.h"
+
+#include <cmath>
 
 namespace rd {
 
@@ -196,7 +199,7 @@ void build_ppocrv6_det(Builder& b, int B, int H, int W) {
 void build_ppocrv6_rec(Builder& b, int B, int H, int W, int flags) {
     const bool tail_only = (flags & REC_STAGE_TAIL) != 0, backbone_only = (flags & REC_STAGE_BACKBONE) != 0;
     RD_CHECK(!(tail_only && backbone_only), "rec: choose one stage");
-    RD_CHECK(!(flags & REC_WANT_NECK), "RD_REC_WANT_NECK is offered by ppocrv5_rec_server only");
+    RD_CHECK(!(flags & REC_WANT_NECK), "RD_REC_WANT_NECK is offered by the ppocrv5 recognisers only");
     const std::string e = "head.encoder";
     auto cw = [&](int i) { return e + ".conv_block." + std::to_string(i) + ".convolution.weight"; };
     auto cbn = [&](int i) { return e + ".conv_block." + std::to_string(i) + ".normalization"; };
@@ -529,15 +532,52 @@ void build_pphgnetv2_b6_formula(Builder& b, int B, int H, int W, int flags) {
     });
 }
 
+// the PPLCNetV3 backbone of the mobile recogniser (below): image -> pooled tokens
+static TView lcnetv3_rec(Builder& b, const TView& x, const TView* tokens_out);
+static int rec_tokens_of_width(int W) {      // rd_rec_seq_len
+    const int w2 = (W - 1) / 2 + 1, w4 = (w2 - 1) / 2 + 1;
+    return w4 / 2;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // PP-OCRv5 server rec (arch_config.yaml ch_PP-OCRv5_rec_server): PPHGNetV2_B4(text_rec=True) -> EncoderWithSVTR (necks/rnn.py:90-200,
 // dims 120, depth 2, kernel [1, 3], use_guide) -> CTCHead Linear(120, classes).  Externals and the two-stage form as build_ppocrv6_rec
 // (tokens are [.][2048]); per-line widths inside one backbone launch (REC_LINE_WIDTHS) are not offered for this kind.
+// `mobile`: the same neck and head behind the PPLCNetV3 backbone (build_ppocrv5_rec_mobile below), REC_LINE_WIDTHS served.
 // ---------------------------------------------------------------------------------------------------
-void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags) {
+// the server kind's backbone: image -> pooled tokens [B][1][w4 / 2][2048] (external 1 in the backbone stage)
+static TView pphgnetv2_rec_tokens(Builder& b, const TView& x, int B, int Cb, bool backbone_only) {
+    TView h;
+    // the height collapse avg_pool2d([3, 2]) runs while the last stage's buffer is live
+    build_pphgnetv2(b, x, kB4Rec, "backbone.", [&](int si, const TView& v) {
+        if (si != 3) return;
+        RD_CHECK(v.c == Cb, "rec server: backbone width");
+        if (backbone_only) {
+            TView out = b.external(1, B, 1, (v.w - 2) / 2 + 1, v.c);
+            b.avgpool3x2(v, &out);
+        } else {
+            h = b.avgpool3x2(v);
+        }
+    }, 1);
+    return h;
+}
+
+// the mobile kind's: the line table (REC_LINE_WIDTHS, backbone stage only) is external 2
+static TView lcnetv3_rec_tokens(Builder& b, const TView& x, int B, int W, int Cb, int flags) {
+    const bool backbone_only = (flags & REC_STAGE_BACKBONE) != 0;
+    if (flags & REC_LINE_WIDTHS) {
+        RD_CHECK(backbone_only, "rec: per-line widths belong to the backbone stage");
+        b.set_line_table(b.external(2, B, 1, 1, kLineTabStride));
+    }
+    if (!backbone_only) return lcnetv3_rec(b, x, nullptr);
+    TView out = b.external(1, B, 1, rec_tokens_of_width(W), Cb);
+    return lcnetv3_rec(b, x, &out);
+}
+
+static void build_ppocrv5_rec(Builder& b, int B, int H, int W, int flags, bool mobile) {
     const bool tail_only = (flags & REC_STAGE_TAIL) != 0, backbone_only = (flags & REC_STAGE_BACKBONE) != 0;
     RD_CHECK(!(tail_only && backbone_only), "rec: choose one stage");
-    RD_CHECK(!(flags & REC_LINE_WIDTHS), "ppocrv5_rec_server: per-line widths inside one backbone launch are out of scope for this kind");
+    RD_CHECK(mobile || !(flags & REC_LINE_WIDTHS), "ppocrv5_rec_server: per-line widths inside one backbone launch are out of scope for this kind");
     const std::string e = "head.ctc_encoder.encoder";
     auto cw = [&](const char* n) { return e + "." + n + ".conv.weight"; };
     auto cbn = [&](const char* n) { return e + "." + n + ".norm"; };
@@ -555,18 +595,8 @@ void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags) {
         RD_CHECK(H == 48, "rec input height must be 48");
         RD_CHECK(W >= 16, "rec input width must be >= 16");
         TView x = b.external(0, B, H, W, 3);
-        if (backbone_only) RD_CHECK((flags & ~REC_STAGE_BACKBONE) == 0, "rec backbone stage takes no other flag");
-        // the height collapse avg_pool2d([3, 2]) runs while the last stage's buffer is live
-        build_pphgnetv2(b, x, kB4Rec, "backbone.", [&](int si, const TView& v) {
-            if (si != 3) return;
-            RD_CHECK(v.c == Cb, "rec server: backbone width");
-            if (backbone_only) {
-                TView out = b.external(1, B, 1, (v.w - 2) / 2 + 1, v.c);
-                b.avgpool3x2(v, &out);
-            } else {
-                h = b.avgpool3x2(v);
-            }
-        }, 1);
+        if (backbone_only) RD_CHECK((flags & ~(REC_STAGE_BACKBONE | REC_LINE_WIDTHS)) == 0, "rec backbone stage takes no other flag");
+        h = mobile ? lcnetv3_rec_tokens(b, x, B, W, Cb, flags) : pphgnetv2_rec_tokens(b, x, B, Cb, backbone_only);
         if (backbone_only) return;
         T = h.w;
         RD_CHECK(h.h == 1, "rec: pooled height");
@@ -637,5 +667,132 @@ void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags) {
     }
     b.release(seq);
 }
+
+void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags) { build_ppocrv5_rec(b, B, H, W, flags, false); }
+
+// ---------------------------------------------------------------------------------------------------
+// PP-OCRv5 mobile rec (arch_config.yaml ch_PP-OCRv5_rec_mobile): PPLCNetV3(scale 0.95, rec geometry) -> the server kind's neck and
+// head (dims 120; the neck's two sequence convolutions are 60 wide here).  Externals, flags and stages as build_ppocrv6_rec, per-line
+// widths (REC_LINE_WIDTHS) included; tokens are [.][480].
+// A block is dw_conv -> (SE) -> pw_conv, each a LearnableRepLayer = lab(sum of branches) -> hardswish -> act.lab.  At load time every
+// layer becomes one convolution + bias (derive_ppocrv5_rec_mobile_weights).  `act.lab` stays a scalar affine after the activation: the
+// depthwise kernel applies hardswish and its own affine in its epilogue; a pointwise layer writes convolution + bias, and its hardswish
+// and affine are applied by its consumer - the next depthwise kernel on load (inside the map only: the padding stays zero, as in the
+// reference) or the final pooling kernel - so the matrix kernels' shared epilogue does not change (kernels_lcv3.hip says why).
+// Every layer here is activated: the rec geometry's strides are 1 or tuples and the reference skips the activation for `stride == 2` only.
+// ---------------------------------------------------------------------------------------------------
+struct Lcv3Cfg { const char* name; int k, cin, cout, sh, sw; bool se; };
+static const Lcv3Cfg kLcv3Rec[] = {
+    {"blocks2.0", 3, 16, 32, 1, 1, false},
+    {"blocks3.0", 3, 32, 64, 1, 1, false},   {"blocks3.1", 3, 64, 64, 1, 1, false},
+    {"blocks4.0", 3, 64, 128, 2, 1, false},  {"blocks4.1", 3, 128, 128, 1, 1, false},
+    {"blocks5.0", 3, 128, 240, 1, 2, false}, {"blocks5.1", 5, 240, 240, 1, 1, false}, {"blocks5.2", 5, 240, 240, 1, 1, false},
+    {"blocks5.3", 5, 240, 240, 1, 1, false}, {"blocks5.4", 5, 240, 240, 1, 1, false},
+    {"blocks6.0", 5, 240, 480, 2, 1, true},  {"blocks6.1", 5, 480, 480, 1, 1, true},  {"blocks6.2", 5, 480, 480, 2, 1, false},
+    {"blocks6.3", 5, 480, 480, 1, 1, false},
+};
+
+// lab(sum_i BN_i(conv_i) + BN_1x1(conv_1x1) + BN_id(x)) as ONE k x k convolution + bias: the BN-folded branch sum in double, the 1 x 1
+// and the identity on the centre tap, `lab` multiplied in, rounded once
+static void fold_rep_layer(WeightStore& ws, const std::string& p, bool depthwise) {
+    const HostTensor& w0 = ws.get(p + ".conv_kxk.0.conv.weight");
+    const int co = (int)w0.shape[0], ci = (int)w0.shape[1], k = (int)w0.shape[2];
+    RD_CHECK(w0.shape.size() == 4 && w0.shape[3] == k && (depthwise ? ci == 1 : k == 1), "LearnableRepLayer: branch shape: " + p);
+    const size_t per = (size_t)ci * k * k;
+    std::vector<double> w((size_t)co * per, 0.0), bias(co, 0.0);
+    auto bn = [&](const std::string& q, int o, double& scale, double& shift) {
+        const double g = ws.get(q + ".weight").f32()[o], be = ws.get(q + ".bias").f32()[o], m = ws.get(q + ".running_mean").f32()[o],
+                     v = ws.get(q + ".running_var").f32()[o];
+        scale = g / std::sqrt(v + 1e-5);
+        shift = be - m * scale;
+    };
+    for (int i = 0; ws.has(p + ".conv_kxk." + std::to_string(i) + ".conv.weight"); ++i) {
+        const std::string q = p + ".conv_kxk." + std::to_string(i);
+        const HostTensor& wi = ws.get(q + ".conv.weight");
+        RD_CHECK(wi.numel() == (size_t)co * per, "LearnableRepLayer: branch shape: " + q);
+        for (int o = 0; o < co; ++o) {
+            double sc, sh;
+            bn(q + ".bn", o, sc, sh);
+            for (size_t t = 0; t < per; ++t) w[o * per + t] += sc * wi.f32()[o * per + t];
+            bias[o] += sh;
+        }
+    }
+    const size_t centre = (size_t)(k / 2) * k + k / 2;
+    if (ws.has(p + ".conv_1x1.conv.weight")) {
+        const HostTensor& w1 = ws.get(p + ".conv_1x1.conv.weight");
+        RD_CHECK(w1.numel() == (size_t)co * ci, "LearnableRepLayer: 1x1 branch shape: " + p);
+        for (int o = 0; o < co; ++o) {
+            double sc, sh;
+            bn(p + ".conv_1x1.bn", o, sc, sh);
+            for (int c = 0; c < ci; ++c) w[o * per + (size_t)c * k * k + centre] += sc * w1.f32()[(size_t)o * ci + c];
+            bias[o] += sh;
+        }
+    }
+    if (ws.has(p + ".identity.weight")) {
+        for (int o = 0; o < co; ++o) {
+            double sc, sh;
+            bn(p + ".identity", o, sc, sh);
+            w[o * per + (size_t)(depthwise ? 0 : o) * k * k + centre] += sc;
+            bias[o] += sh;
+        }
+    }
+    const double ls = ws.get(p + ".lab.scale").f32()[0], lb = ws.get(p + ".lab.bias").f32()[0];
+    std::vector<float> wf(w.size()), bf(co);
+    for (size_t i = 0; i < w.size(); ++i) wf[i] = (float)(w[i] * ls);
+    for (int o = 0; o < co; ++o) bf[o] = (float)(bias[o] * ls + lb);
+    ws.add_derived(p + ".fold.weight", {co, ci, k, k}, std::move(wf));
+    ws.add_derived(p + ".fold.bias", {co}, std::move(bf));
+}
+
+void derive_ppocrv5_rec_mobile_weights(WeightStore& ws) {
+    for (const Lcv3Cfg& c : kLcv3Rec) {
+        const std::string p = std::string("backbone.") + c.name;
+        fold_rep_layer(ws, p + ".dw_conv", true);
+        fold_rep_layer(ws, p + ".pw_conv", false);
+    }
+}
+
+// x NCHW image -> pooled tokens [B][1][w4 / 2][480] (into *tokens_out when given)
+static TView lcnetv3_rec(Builder& b, const TView& x, const TView* tokens_out) {
+    TView h = b.stem3x3s2("backbone.conv1.conv.weight", "backbone.conv1.bn", x, ACT_NONE);   // columns >= a line's w2 are ignored by every reader
+    Builder::Affine pre;
+    bool has_pre = false;     // conv1 has neither activation nor affine
+    int lt_col = 1;           // LineTab column of the current map's valid width: w2 up to blocks5.0's input, w4 after it
+    for (const Lcv3Cfg& c : kLcv3Rec) {
+        const std::string p = std::string("backbone.") + c.name;
+        RD_CHECK(h.c == c.cin, "PPLCNetV3: channel chain: " + p);
+        const int lt_out = c.sw == 2 ? 2 : lt_col;
+        TView fused;
+        if (c.k == 3 && c.sh == 1 && c.sw == 1 && !c.se &&
+            b.lcv3_block(p + ".dw_conv.fold.weight", p + ".pw_conv.fold.weight", p + ".pw_conv.fold.bias", h, has_pre ? &pre : nullptr,
+                         b.affine(p + ".dw_conv.act.lab"), lt_col, &fused)) {     // RD_LCV3_FUSED=1: the block in one launch
+            b.release(h);
+            h = fused;
+            pre = b.affine(p + ".pw_conv.act.lab");
+            has_pre = true;
+            continue;
+        }
+        TView t = b.lcv3_dw(p + ".dw_conv.fold.weight", p + ".dw_conv.fold.bias", h, c.k, c.sh, c.sw, has_pre ? &pre : nullptr,
+                            b.affine(p + ".dw_conv.act.lab"), lt_col, lt_out);
+        b.release(h);
+        lt_col = lt_out;
+        if (c.se) {
+            Builder::GapOut gap = b.lcv3_gap(t, lt_col);
+            TView gate = b.se_gate(p + ".se.conv1.weight", p + ".se.conv1.bias", p + ".se.conv2.weight", p + ".se.conv2.bias", t, ACT_HSIG, &gap);
+            b.scale(t, gate, 0.f, t);
+            b.release(gate);
+        }
+        h = b.conv(p + ".pw_conv.fold.weight", p + ".pw_conv.fold.bias", "", t, geom(1), ACT_NONE);    // hardswish + act.lab: the consumer's
+        b.release(t);
+        pre = b.affine(p + ".pw_conv.act.lab");
+        has_pre = true;
+        RD_CHECK(h.c == c.cout, "PPLCNetV3: channel chain: " + p);
+    }
+    TView tok = b.lcv3_pool(h, pre, tokens_out);
+    b.release(h);
+    return tok;
+}
+
+void build_ppocrv5_rec_mobile(Builder& b, int B, int H, int W, int flags) { build_ppocrv5_rec(b, B, H, W, flags, true); }
 
 }  // namespace rd

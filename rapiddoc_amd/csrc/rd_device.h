@@ -92,6 +92,15 @@ __device__ __forceinline__ float rd_act(float v, int act) {
     }
 }
 
+// s * nn.Hardswish(v) + b,  Hardswish(v) = v relu6(v + 3) / 6: a PPLCNetV3 layer's activation and its scalar affine `act.lab`
+// (kernels_lcv3.hip, kernels_lcv3_block.hip)
+__device__ __forceinline__ f32x4 lcv3_hswish_aff(f32x4 v, float s, float b) {
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = fmaf(v[e] * fminf(fmaxf(v[e] + 3.f, 0.f), 6.f) * (1.f / 6.f), s, b);
+    return r;
+}
+
 // x = hi + lo * 2^-11 with hi = fp16(x), lo = fp16((x - hi) * 2^11).  The second line is ONE fused op on the f16 source
 // (exact: the difference is representable and the scale is a power of two); it compiles to v_fma_mix{lo,hi}_f16, so the
 // split costs 2 VALU ops per element (v_cvt_pk_f16_f32 + v_fma_mix) instead of 4.

@@ -203,6 +203,47 @@ void launch_dwconv_lds(const DwParams& p, hipStream_t s);
 bool dwconv_kxk_lds_applies(const DwParams& p);
 void launch_dwconv_kxk_lds(const DwParams& p, hipStream_t s);
 
+// PPLCNetV3 depthwise layer (kernels_lcv3.hip): y = post_s hardswish(dw(x') + bias) + post_b, x' = pre_act ? pre_s hardswish(x) + pre_b : x, k = 3 / 5, strides (1,1), (2,1),
+// (1,2; k = 3), 'same' padding of ZEROS around the pre-affined map; per-image valid widths of the input / output (LineTab columns) or nullptr
+struct Lcv3DwParams {
+    const float* x; int xld;
+    int N, H, W, C;
+    const float* w;      // [K*K][C]
+    const float* bias;   // [C]
+    float* y; int yld;
+    int OH, OW, K, SH, SW;
+    int pre_act; float pre_s, pre_b;     // the producing pointwise layer's hardswish + act.lab, applied on load inside the map
+    float post_s, post_b;   // this layer's act.lab
+    const int32_t* line_in; const int32_t* line_out; int line_stride;
+};
+bool lcv3_dw_shape_ok(int k, int sh, int sw, int c);
+void launch_lcv3_dw(const Lcv3DwParams& p, hipStream_t s);
+// One PPLCNetV3 block without SE, 3x3 / stride 1, in one launch (kernels_lcv3_block.hip): the depthwise layer as above into an LDS tile, the
+// pointwise layer on the matrix cores from it.  y = out_act ? out_s hardswish(a W^T + pw_b) + out_b : a W^T + pw_b with
+// a = mid_s hardswish(dw(x') + dw_b) + mid_b; split = 1: split-fp16 product guarded by range_flag, 0: fp32 MFMA.
+struct Lcv3BlockParams {
+    const float* x; int xld;
+    int N, H, W, cin, cout;
+    const float* dw_w;   // [9][cin]
+    const float* dw_b;   // [cin]
+    const float* pw_w;   // [cout][cin]
+    const float* pw_b;   // [cout]
+    float* y; int yld;
+    int pre_act; float pre_s, pre_b;
+    float mid_s, mid_b;
+    int out_act; float out_s, out_b;
+    const int32_t* line_w; int line_stride;
+    int split; unsigned* range_flag;
+};
+bool lcv3_block_shape_ok(int cin, int cout);      // (16, 32), (32, 64), (64, 64)
+void launch_lcv3_block(const Lcv3BlockParams& p, hipStream_t s);
+// partial[n][h][c] = sum over w < line_w[n * stride] (or W) of x[n][h][w][c]: the SE pooling partial sums, one chunk per map row
+bool lcv3_gap_shape_ok(int c);      // c % 4 == 0, c <= 4096
+void launch_lcv3_gap_rows(const float* x, int xld, int N, int H, int W, int C, float* partial, const int32_t* line_w, int stride, hipStream_t s);
+// y = post_s avg_pool2d([3, 2])(hardswish(x)) + post_b of a 3-row map; line_tab as launch_avgpool3x2
+void launch_lcv3_pool(const float* x, int xld, float* y, int yld, int N, int H, int W, int C, float post_s, float post_b, hipStream_t s,
+                      const int32_t* line_tab = nullptr);
+
 // 2x2 stride-1 max-pool over an input zero-padded by one pixel on the right/bottom (stem branch b)
 void launch_maxpool2x2s1(const float* x, int xld, float* y, int yld, int N, int H, int W, int C, hipStream_t s);
 // avg_pool2d(kernel (3,2), stride (3,2)) - rec height collapse

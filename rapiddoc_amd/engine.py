@@ -13,9 +13,9 @@ import torch
 from . import _lib, weights as W
 
 REC_UNFUSED_CTC, REC_WANT_SOFTMAX, REC_WANT_LOGITS = 1, 2, 4
-REC_WANT_NECK = 64          # ppocrv5_rec_server: `full` receives the neck's output [B, T, 120] instead
+REC_WANT_NECK = 64          # ppocrv5_rec_server / ppocrv5_rec_mobile: `full` receives the neck's output [B, T, 120] instead
 DET_WANT_NECK = 1           # ppocrv5_det_server: also hand out the neck's output `fuse` [B, 256, H/4, W/4]
-KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv6_rec", "ppocrv5_rec_server", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
+KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
 
 
 def rec_line_table(widths, first_tokens) -> np.ndarray:

@@ -272,13 +272,15 @@ REC_ARCH_BY_STEM = {
     "ch_PP-OCRv6_rec_small": "ppocrv6_rec",
     "ch_PP-OCRv6_small_rec_infer": "ppocrv6_rec",
     "ch_PP-OCRv5_rec_server": "ppocrv5_rec_server",
+    "ch_PP-OCRv5_rec_mobile": "ppocrv5_rec_mobile",
 }
 
 
 def resolve_rec_kind(weights: WeightSrc) -> str:
     """Engine kind of a recogniser's weights: a file goes by its stem (an unknown one is an error, as in the reference - never a guess at
     the graph), a state dict or a safetensors byte image without a name by the CTC classifier it carries (`head.ctc_head.fc.weight`:
-    the v5 server MultiHead; `head.head.weight`: the v6 LightSVTR head)."""
+    the v5 MultiHead - the mobile recogniser where the backbone is PPLCNetV3, `backbone.conv1.conv.weight` / `backbone.blocks2.*`, the server
+    one otherwise; `head.head.weight`: the v6 LightSVTR head)."""
     if isinstance(weights, (str, Path)):
         stem = Path(str(weights)).stem
         if stem not in REC_ARCH_BY_STEM:
@@ -294,6 +296,8 @@ def resolve_rec_kind(weights: WeightSrc) -> str:
         keys = set(weights)
     keys = {k[len("model."):] if k.startswith("model.") else k for k in keys}
     if "head.ctc_head.fc.weight" in keys:
+        if "backbone.conv1.conv.weight" in keys or any(k.startswith("backbone.blocks2.") for k in keys):
+            return "ppocrv5_rec_mobile"
         return "ppocrv5_rec_server"
     if "head.head.weight" in keys:
         return "ppocrv6_rec"
@@ -302,7 +306,7 @@ def resolve_rec_kind(weights: WeightSrc) -> str:
 
 
 class Mi355RecSession(_BaseSession):
-    """PP-OCRv6 small / PP-OCRv5 server rec: [B,3,48,W] -> softmax(ctc_logits) [B,T,C] (ocr/torch.py:185-187; the v5 CTCHead applies
+    """PP-OCRv6 small / PP-OCRv5 server / PP-OCRv5 mobile rec: [B,3,48,W] -> softmax(ctc_logits) [B,T,C] (ocr/torch.py:185-187; the v5 CTCHead applies
     the softmax itself, rec_ctc_head.py:51-53 - the session's result is the same tensor for both).  The kind follows from the weights
     (`resolve_rec_kind`) unless `kind` names it.
 

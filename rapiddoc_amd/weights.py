@@ -23,6 +23,7 @@ import numpy as np
 
 Manifest = List[Tuple[str, Tuple[int, ...], str]]
 
+_LCNETV3_BRANCH_GAIN = (("blocks2", 0.65), ("blocks3", 0.65), ("blocks4", 0.6), ("blocks5", 0.6), ("blocks6", 0.7))
 _NORM_TOKENS = (".normalization.", ".norm.", ".bn.", "layer_norm", ".norm1.", ".norm2.")
 
 
@@ -75,6 +76,13 @@ def synth_tensor(name: str, shape: Tuple[int, ...], dtype: str, seed: int) -> np
             std *= 10.0
         if name == "head.cbn_layer.last_1.weight":
             std *= 100.0
+        # PP-OCRv5 mobile recogniser (PPLCNetV3): every layer is a sum of 4-6 branches under a hardswish, which is quadratic below 3, so
+        # the plain rule explodes (1e7 by blocks6) and one global damping collapses the net onto its biases; a factor per block group
+        # on the branch convolutions keeps every group's activations O(10)
+        if name.endswith(".conv.weight") and (".conv_kxk." in name or ".conv_1x1." in name):
+            for group, f in _LCNETV3_BRANCH_GAIN:
+                if name.startswith("backbone." + group + "."):
+                    std *= f
         return rng.normal(0.0, std, shape).astype(np.float32)
     return rng.normal(0.0, 0.05, shape).astype(np.float32)
 
