@@ -10,7 +10,15 @@ namespace rd {
 class FormulaDecoder;
 FormulaDecoder* formula_decoder_create(int device, const void* blob, size_t nbytes);
 void formula_decoder_destroy(FormulaDecoder* d);
-int formula_decoder_decode(FormulaDecoder* d, const float* enc, int B, int S, int max_new, long long* ids, hipStream_t s);
+int formula_decoder_decode(FormulaDecoder* d, const float* enc, int B, int S, int max_new, long long* ids, hipStream_t s, float* trace_logits,
+                           float* trace_hidden);
+int debug_dec_gemv(int M, int K, int N, int act, const float* x, const float* w, const float* bias, const float* ln_g, const float* ln_b,
+                   const float* res, float* y);
+int debug_dec_attention(int route, int self, int B, int T, float* kc, float* vc, int ldkv, long long seq_stride, const float* x, const float* ln_g,
+                        const float* ln_b, const float* w, const float* bias, const float* q, int ldq, const float* kcur, const float* vcur,
+                        int ldcur, float* out, int ldo);
+int debug_dec_select(int mode, const float* logits, int V, int B, int step, long long* ids, int ids_ld, int* unfinished, int n_unfinished, int max_new,
+                     const float* emb, const float* pos, const float* g, const float* b, float* x, int* state_out);
 int formula_decoder_max_new(FormulaDecoder* d);
 }  // namespace rd
 
@@ -192,7 +200,20 @@ int rd_formula_decode(rd_handle* h, const float* enc, int B, int S, int max_new_
     return guarded(h, [&] {
         RD_CHECK(h->kind == "ppformulanet_head" && h->dec, "handle is not a loaded ppformulanet_head model");
         RD_CHECK(enc && ids && n_cols, "null input/output");
-        *n_cols = rd::formula_decoder_decode(h->dec, enc, B, S, max_new_tokens, reinterpret_cast<long long*>(ids), (hipStream_t)stream);
+        *n_cols = rd::formula_decoder_decode(h->dec, enc, B, S, max_new_tokens, reinterpret_cast<long long*>(ids), (hipStream_t)stream, nullptr,
+                                             nullptr);
+    });
+}
+// developer entry: rd_formula_decode plus two optional traces written inside every step (graph replay included): the step's logits
+// trace_logits [max_new_tokens][B][V] and the hidden row in front of the final LayerNorm trace_hidden [max_new_tokens][B][512].  With both
+// null it enqueues exactly what rd_formula_decode enqueues.
+int rd_debug_formula_decode(rd_handle* h, const float* enc, int B, int S, int max_new_tokens, int64_t* ids, int32_t* n_cols, void* stream,
+                            float* trace_logits, float* trace_hidden) {
+    return guarded(h, [&] {
+        RD_CHECK(h->kind == "ppformulanet_head" && h->dec, "handle is not a loaded ppformulanet_head model");
+        RD_CHECK(enc && ids && n_cols, "null input/output");
+        *n_cols = rd::formula_decoder_decode(h->dec, enc, B, S, max_new_tokens, reinterpret_cast<long long*>(ids), (hipStream_t)stream,
+                                             trace_logits, trace_hidden);
     });
 }
 int rd_formula_max_new_tokens(rd_handle* h) { return (h && h->dec) ? rd::formula_decoder_max_new(h->dec) : -1; }
@@ -885,6 +906,25 @@ int rd_debug_ctc_head(int M, int K, int Ccls, float* x, int xld, float* wp, void
     p.range_flag = flag;
     rd::launch_ctc_head(p, nullptr);
     return debug_finish(flag, range_out);
+}
+
+// developer entries for the formula decoder's kernels (csrc/formula_decoder.hip): one synchronised launch each through the decode step's own
+// routing on caller-provided device buffers.  rd_debug_dec_gemv returns the dec_gemv_kernel instantiation that ran as
+// MT * 10000 + CW * 1000 + KPL * 100 + DB * 10 + DX, 0 where the routing declines the shape (nothing launched); the others return 0.
+// All return -1 for arguments the launch cannot take.
+int rd_debug_dec_gemv(int M, int K, int N, int act, const float* x, const float* w, const float* bias, const float* ln_g, const float* ln_b,
+                      const float* res, float* y) {
+    return rd::debug_dec_gemv(M, K, N, act, x, w, bias, ln_g, ln_b, res, y);
+}
+int rd_debug_dec_attention(int route, int self, int B, int T, float* kc, float* vc, int ldkv, long long seq_stride, const float* x,
+                           const float* ln_g, const float* ln_b, const float* w, const float* bias, const float* q, int ldq, const float* kcur,
+                           const float* vcur, int ldcur, float* out, int ldo) {
+    return rd::debug_dec_attention(route, self, B, T, kc, vc, ldkv, seq_stride, x, ln_g, ln_b, w, bias, q, ldq, kcur, vcur, ldcur, out, ldo);
+}
+int rd_debug_dec_select(int mode, const float* logits, int V, int B, int step, int64_t* ids, int ids_ld, int32_t* unfinished, int n_unfinished,
+                        int max_new, const float* emb, const float* pos, const float* g, const float* b, float* x, int32_t* state_out) {
+    return rd::debug_dec_select(mode, logits, V, B, step, reinterpret_cast<long long*>(ids), ids_ld, unfinished, n_unfinished, max_new, emb, pos, g,
+                                b, x, state_out);
 }
 
 int rd_set_precision(rd_handle* h, const char* mode) {

@@ -598,7 +598,10 @@ __global__ void __launch_bounds__(256) dec_gemv_kernel(GemvParams p, int n_group
         }
     } else {
         for (int g = gw; g < n_groups; g += GW) {
-            if (g != gw) load_w(wa, g);
+            if (g != gw) {
+                load_w(wa, g);
+                if constexpr (DX && XR < MT) load_x(0);      // finish() left the LAST row batch in xd: the next group starts at row 0 again
+            }
             finish(wa, g);
         }
     }
@@ -613,8 +616,11 @@ __global__ void __launch_bounds__(1024) dec_select_kernel(const float* logits, i
                                                           DecState* st, int B, NextEmbed ne) {
     const int b = blockIdx.x, tid = threadIdx.x, t = st->step;
     const float* z = logits + (size_t)b * V;
+    // numpy / torch argmax: a NaN counts as the greatest value, the lowest index among equals wins.  Every thread that owns an element starts
+    // on its FIRST one's index, so a row of nothing but -inf (nothing ever compares greater) still names a real column: the token is in [0, V).
+    auto above = [](float c, float a) { return c > a || (c != c && a == a); };
     float mx = -INFINITY;
-    int mi = 0x7fffffff;
+    int mi = 0x7fffffff;            // (a thread without elements: loses every tie)
     if ((V & 3) == 0 && V <= 65536) {
         // 16-byte loads, every load of the thread requested before the first compare (the scalar loop below ran its 49 loads per
         // thread through a compare-and-select chain: 18 us for 200 KB); indices still visited in increasing order per thread
@@ -628,21 +634,24 @@ __global__ void __launch_bounds__(1024) dec_select_kernel(const float* logits, i
         for (int it = 0; it < MAXQ; ++it) {
             const int c0 = 4 * (tid + 1024 * it);
             if (tid + 1024 * it < nq) {
+                if (it == 0) mi = c0;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (q[it][e] > mx) { mx = q[it][e]; mi = c0 + e; }
+                    if (above(q[it][e], mx)) { mx = q[it][e]; mi = c0 + e; }
             }
         }
-    } else
-    for (int c = tid; c < V; c += 1024) {
-        const float v = z[c];
-        if (v > mx) { mx = v; mi = c; }
+    } else {
+        if (tid < V) mi = tid;
+        for (int c = tid; c < V; c += 1024) {
+            const float v = z[c];
+            if (above(v, mx)) { mx = v; mi = c; }
+        }
     }
     // (value, index) pairs are totally ordered - larger value first, then smaller index - so any reduction tree gives the pair the ten-level
     // LDS tree of rounds 1-5 gave: butterfly inside the wavefront, one exchange between the sixteen (round 6: two barriers instead of eleven)
     __shared__ float smx[16];
     __shared__ int smi[16];
-    auto better = [](float c, int ic, float a, int ia) { return c > a || (c == a && ic < ia); };
+    auto better = [&](float c, int ic, float a, int ia) { return above(c, a) || ((c == a || (c != c && a != a)) && ic < ia); };
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float c = __shfl_xor(mx, o, 64);
@@ -716,7 +725,9 @@ class FormulaDecoder {
     }
     void load(const WeightStore& ws);
     // enc [B,S,2048] (device) -> ids [B][max_new+1] (device, int64); returns the number of columns the reference returns
-    int decode(const float* enc, int B, int S, int max_new, long long* ids_out, hipStream_t s);
+    // trace_logits [max_new][B][V] / trace_hidden [max_new][B][512] (the row in front of ln_out), or null: developer traces of every step
+    int decode(const float* enc, int B, int S, int max_new, long long* ids_out, hipStream_t s, float* trace_logits = nullptr,
+               float* trace_hidden = nullptr);
     int max_positions() const { return n_pos_ - 2; }
 
    private:
@@ -848,12 +859,43 @@ static void launch_gemv(const GemvParams& p, int max_wgs, hipStream_t s) {
     hipLaunchKernelGGL((dec_gemv_kernel<MT, CW, KPL, DB, DX>), dim3(grid), dim3(256), lds, s, p, n_groups);
 }
 
-bool FormulaDecoder::gemv(const float* x, int M, int K, const std::string& key, int N, float* y, int act, const float* res, hipStream_t s,
-                          const std::string& ln_key) {
+// The routing of the decode step's linears: which dec_gemv_kernel instantiation serves (M, K, N, LayerNorm in front), or none.  Returns 0 when
+// the shape is not covered (nothing launched), otherwise the instantiation's code MT * 10000 + CW * 1000 + KPL * 100 + DB * 10 + DX
+// (FormulaDecoder::gemv and the developer entry rd_debug_dec_gemv both launch through here).
+template <int MT, int CW, int KPL, bool DB, bool DX = false>
+static int route_gemv(const GemvParams& p, int max_wgs, hipStream_t s) {
+    launch_gemv<MT, CW, KPL, DB, DX>(p, max_wgs, s);
+    return MT * 10000 + CW * 1000 + KPL * 100 + (DB ? 10 : 0) + (DX ? 1 : 0);
+}
+int dec_gemv_route(const GemvParams& p, hipStream_t s) {
     static const bool on = [] { const char* e = getenv("RD_DEC_GEMV"); return !(e && e[0] == '0'); }();
     // developer knobs (tools/bench_formula.py sweeps): workgroups of a wide layer's loop, columns per wavefront of a wide layer
     static const int wide_wgs = [] { const char* e = getenv("RD_DEC_GEMV_WGS"); return e ? atoi(e) : 512; }();
-    if (!on || M > 32 || (K != 512 && K != 2048) || (K == 2048 && (M > 16 || !ln_key.empty()))) return false;
+    static const bool dx = [] { const char* e = getenv("RD_DEC_GEMV_DX"); return !(e && e[0] == '0'); }();     // A/B
+    const int M = p.M, K = p.K;
+    const bool has_ln = p.ln_g != nullptr;
+    if (!on || M < 1 || p.N < 1 || M > 32 || (K != 512 && K != 2048) || (K == 2048 && (M > 16 || has_ln))) return 0;
+    const bool wide = p.N > 4096;          // loops over column groups with the next group's weights in flight
+    if (K == 2048) {
+        if (M <= 8 && dx) return route_gemv<8, 1, 8, false, true>(p, 1024, s);
+        if (M <= 8) return route_gemv<8, 1, 8, false>(p, 1024, s);
+        return route_gemv<16, 1, 8, false>(p, 1024, s);
+    }
+    if (M <= 8) {
+        if (wide) return route_gemv<8, 4, 2, true>(p, wide_wgs, s);
+        if (dx && !has_ln) return route_gemv<8, 1, 2, false, true>(p, 1024, s);
+        return route_gemv<8, 1, 2, false>(p, 1024, s);
+    }
+    if (M <= 16) {
+        if (wide) return route_gemv<16, 2, 2, true>(p, wide_wgs, s);
+        return route_gemv<16, 1, 2, false>(p, 1024, s);
+    }
+    if (wide) return route_gemv<32, 1, 2, true>(p, wide_wgs, s);
+    return route_gemv<32, 1, 2, false>(p, 1024, s);
+}
+
+bool FormulaDecoder::gemv(const float* x, int M, int K, const std::string& key, int N, float* y, int act, const float* res, hipStream_t s,
+                          const std::string& ln_key) {
     GemvParams p{};
     p.x = x; p.M = M; p.K = K; p.N = N;
     p.w = params_.ptr(key + "#w");
@@ -863,28 +905,35 @@ bool FormulaDecoder::gemv(const float* x, int M, int K, const std::string& key, 
         p.ln_b = params_.ptr(ln_key + ".bias");
     }
     p.res = res; p.y = y; p.act = act;
-    const bool wide = N > 4096;          // loops over column groups with the next group's weights in flight
-    if (K == 2048) {
-        static const bool dx8 = [] { const char* e = getenv("RD_DEC_GEMV_DX"); return !(e && e[0] == '0'); }();     // A/B
-        if (M <= 8 && dx8) launch_gemv<8, 1, 8, false, true>(p, 1024, s);
-        else if (M <= 8) launch_gemv<8, 1, 8, false>(p, 1024, s);
-        else launch_gemv<16, 1, 8, false>(p, 1024, s);
-    } else if (M <= 8) {
-        static const bool dx = [] { const char* e = getenv("RD_DEC_GEMV_DX"); return !(e && e[0] == '0'); }();     // A/B
-        if (wide) launch_gemv<8, 4, 2, true>(p, wide_wgs, s);
-        else if (dx && ln_key.empty()) launch_gemv<8, 1, 2, false, true>(p, 1024, s);
-        else launch_gemv<8, 1, 2, false>(p, 1024, s);
-    } else if (M <= 16) {
-        if (wide) launch_gemv<16, 2, 2, true>(p, wide_wgs, s);
-        else launch_gemv<16, 1, 2, false>(p, 1024, s);
-    } else {
-        if (wide) launch_gemv<32, 1, 2, true>(p, wide_wgs, s);
-        else launch_gemv<32, 1, 2, false>(p, 1024, s);
-    }
-    return true;
+    return dec_gemv_route(p, s) != 0;
 }
 
-int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long long* ids_out, hipStream_t s) {
+// The attention launches of a decode step (decode() and the developer entry rd_debug_dec_attention).  `keys` sizes the score array in LDS:
+// the longest sequence the launch may see (self: max_new + 1, cross: S).
+void launch_dec_attention(const AttnDecParams& p, int B, int keys, hipStream_t s) {
+    const size_t sh = (size_t)(((keys + 3) & ~3) + 128) * sizeof(float);
+    hipLaunchKernelGGL(dec_attention_kernel, dim3(B, HEADS), dim3(128), sh, s, p);
+}
+// `two` = the round-6 kernel (dec_attn_fused2_kernel), otherwise the round-4 one
+void launch_dec_attn_fused(const AttnFusedParams& p, bool self, bool two, int B, int keys, hipStream_t s) {
+    const size_t sh = (size_t)(D + 3 * HD + 256 + ((keys + 3) & ~3)) * sizeof(float);
+    if (self) {
+        if (two) hipLaunchKernelGGL((dec_attn_fused2_kernel<true>), dim3(B, HEADS), dim3(768), sh, s, p);
+        else hipLaunchKernelGGL((dec_attn_fused_kernel<true>), dim3(B, HEADS), dim3(256), sh, s, p);
+    } else {
+        if (two) hipLaunchKernelGGL((dec_attn_fused2_kernel<false>), dim3(B, HEADS), dim3(256), sh, s, p);
+        else hipLaunchKernelGGL((dec_attn_fused_kernel<false>), dim3(B, HEADS), dim3(256), sh, s, p);
+    }
+}
+
+// developer trace (rd_debug_formula_decode): row block `st->step` of dst [steps][n] = src [n], inside the step (graph replay included)
+__global__ void __launch_bounds__(256) dec_trace_kernel(const float* src, float* dst, long long n, const DecState* st) {
+    float* d = dst + (size_t)st->step * n;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) d[i] = src[i];
+}
+
+int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long long* ids_out, hipStream_t s, float* trace_logits,
+                           float* trace_hidden) {
     RD_HIP(hipSetDevice(device_));
     RD_CHECK(B > 0 && S > 0 && max_new > 0, "formula decode: empty batch");
     RD_CHECK(max_new + 2 <= n_pos_, "formula decode: max_new_tokens exceeds the positional table of these weights");
@@ -931,12 +980,10 @@ int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long lon
     for (int l = 0; l < n_layers_; ++l)
         gemm(enc_d, B * S, D, "l" + std::to_string(l) + ".ckv", 2 * D, ckv + (size_t)l * B * S * 2 * D, ACT_NONE, nullptr, s);
 
-    const size_t attn_sh_self = (size_t)(((Tmax + 3) & ~3) + 128) * f, attn_sh_cross = (size_t)(((S + 3) & ~3) + 128) * f;
     // fused projection + attention launches (dec_attn_fused_kernel): RD_DEC_FUSED=0 keeps the round-3 form (A/B, parity tests)
     static const bool fused_env = [] { const char* e = getenv("RD_DEC_FUSED"); return !(e && e[0] == '0'); }();
     const bool fused = fused_env && B <= 32;
     static const bool attn2 = [] { const char* e = getenv("RD_DEC_ATTN2"); return !(e && e[0] == '0'); }();
-    const size_t fsh_self = (size_t)(D + 3 * HD + 256 + ((Tmax + 3) & ~3)) * f, fsh_cross = (size_t)(D + 3 * HD + 256 + ((S + 3) & ~3)) * f;
     // One decode step = ~70 dependent launches whose arguments never change (the step index lives in device memory), so
     // the step is captured once into a hipGraph and replayed: the host cost per step drops from ~70 launches to one.
     // a linear of the step: the weight-streaming GEMV where it covers the shape, the round-3 skinny GEMM otherwise
@@ -964,8 +1011,7 @@ int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long lon
                 sp.kc = kc + (size_t)l * B * Tmax * D; sp.vc = vc + (size_t)l * B * Tmax * D; sp.ldkv = D; sp.seq_stride = (long long)Tmax * D;
                 sp.kw = kc + (size_t)l * B * Tmax * D; sp.vw = vc + (size_t)l * B * Tmax * D;
                 sp.st = st; sp.fixed_T = 0; sp.out = a; sp.ldo = D;
-                if (attn2) hipLaunchKernelGGL((dec_attn_fused2_kernel<true>), dim3(B, HEADS), dim3(768), fsh_self, s, sp);
-                else hipLaunchKernelGGL((dec_attn_fused_kernel<true>), dim3(B, HEADS), dim3(256), fsh_self, s, sp);
+                launch_dec_attn_fused(sp, true, attn2, B, Tmax, s);
                 lin(a, D, K + "so", D, nxt, ACT_NONE, cur);
                 std::swap(cur, nxt);
                 AttnFusedParams xp{};
@@ -973,8 +1019,7 @@ int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long lon
                 xp.w = params_.ptr(K + "cq#w"); xp.bias = params_.ptr(K + "cq#b");
                 xp.kc = ckv + (size_t)l * B * S * 2 * D; xp.vc = xp.kc + D; xp.ldkv = 2 * D; xp.seq_stride = (long long)S * 2 * D;
                 xp.st = st; xp.fixed_T = S; xp.out = a; xp.ldo = D;
-                if (attn2) hipLaunchKernelGGL((dec_attn_fused2_kernel<false>), dim3(B, HEADS), dim3(256), fsh_cross, s, xp);
-                else hipLaunchKernelGGL((dec_attn_fused_kernel<false>), dim3(B, HEADS), dim3(256), fsh_cross, s, xp);
+                launch_dec_attn_fused(xp, false, attn2, B, S, s);
                 lin(a, D, K + "co", D, nxt, ACT_NONE, cur);
                 std::swap(cur, nxt);
                 lin(cur, D, K + "fc1", FFN, ff, ACT_GELU, nullptr, K + "ln3", h);
@@ -990,7 +1035,7 @@ int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long lon
             ap.kcur = qkv + D; ap.vcur = qkv + 2 * D; ap.ldcur = 3 * D;
             ap.kw = kc + (size_t)l * B * Tmax * D; ap.vw = vc + (size_t)l * B * Tmax * D;
             ap.st = st; ap.fixed_T = 0; ap.out = a; ap.ldo = D;
-            hipLaunchKernelGGL(dec_attention_kernel, dim3(B, HEADS), dim3(128), attn_sh_self, s, ap);
+            launch_dec_attention(ap, B, Tmax, s);
             gemm(a, B, D, K + "so", D, nxt, ACT_NONE, cur, s);
             std::swap(cur, nxt);
             // cross-attention over the (projected) encoder tokens
@@ -999,7 +1044,7 @@ int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long lon
             cp.q = qkv; cp.ldq = D;
             cp.kc = ckv + (size_t)l * B * S * 2 * D; cp.vc = cp.kc + D; cp.ldkv = 2 * D; cp.seq_stride = (long long)S * 2 * D;
             cp.st = st; cp.fixed_T = S; cp.out = a; cp.ldo = D;
-            hipLaunchKernelGGL(dec_attention_kernel, dim3(B, HEADS), dim3(128), attn_sh_cross, s, cp);
+            launch_dec_attention(cp, B, S, s);
             gemm(a, B, D, K + "co", D, nxt, ACT_NONE, cur, s);
             std::swap(cur, nxt);
             // feed-forward
@@ -1007,7 +1052,10 @@ int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long lon
             gemm(ff, B, FFN, K + "fc2", D, nxt, ACT_NONE, cur, s);
             std::swap(cur, nxt);
         }
+        if (trace_hidden) hipLaunchKernelGGL(dec_trace_kernel, dim3(std::min(B * 2, 256)), dim3(256), 0, s, cur, trace_hidden, (long long)B * D, st);
         lin(cur, D, "lm", vocab_, lg, ACT_NONE, nullptr, "ln_out", h);
+        if (trace_logits)
+            hipLaunchKernelGGL(dec_trace_kernel, dim3(256), dim3(256), 0, s, lg, trace_logits, (long long)B * vocab_, st);
         RD_CHECK(cur == x, "formula decode: the layer stack must end in the buffer the next embedding is written to");
         NextEmbed ne{};
         if (embed_in_select) ne = NextEmbed{params_.ptr("emb"), params_.ptr("pos"), params_.ptr("ln_emb.weight"), params_.ptr("ln_emb.bias"), x, max_new};
@@ -1078,9 +1126,89 @@ FormulaDecoder* formula_decoder_create(int device, const void* blob, size_t nbyt
     return d;
 }
 void formula_decoder_destroy(FormulaDecoder* d) { delete d; }
-int formula_decoder_decode(FormulaDecoder* d, const float* enc, int B, int S, int max_new, long long* ids, hipStream_t s) {
-    return d->decode(enc, B, S, max_new, ids, s);
+int formula_decoder_decode(FormulaDecoder* d, const float* enc, int B, int S, int max_new, long long* ids, hipStream_t s, float* trace_logits,
+                           float* trace_hidden) {
+    return d->decode(enc, B, S, max_new, ids, s, trace_logits, trace_hidden);
 }
 int formula_decoder_max_new(FormulaDecoder* d) { return d->max_positions(); }
+
+// ---- developer entries (api.cpp rd_debug_dec_*): ONE synchronised launch of the decode step's own code - the routing above, the product's
+// instantiations - on caller-provided device buffers; no weight file.  -1 = arguments the launch cannot take (nothing launched) or a HIP error.
+static bool debug_sync() { return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess; }
+struct DebugState {      // a DecState of the entry's own
+    DecState* d = nullptr;
+    explicit DebugState(const DecState& v) {
+        if (hipMalloc((void**)&d, sizeof(DecState)) != hipSuccess) d = nullptr;
+        else if (hipMemcpy(d, &v, sizeof(DecState), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); d = nullptr; }
+    }
+    ~DebugState() { if (d) (void)hipFree(d); }
+    bool read(int* out3) {
+        DecState h{};
+        if (hipMemcpy(&h, d, sizeof(DecState), hipMemcpyDeviceToHost) != hipSuccess) return false;
+        if (out3) { out3[0] = h.step; out3[1] = h.n_unfinished; out3[2] = h.arrived; }
+        return true;
+    }
+};
+
+// y [M][N] = act(LN?(x [M][K]) w [N][K]^T + bias) + res through dec_gemv_route: the instantiation's code, 0 = declined (nothing launched)
+int debug_dec_gemv(int M, int K, int N, int act, const float* x, const float* w, const float* bias, const float* ln_g, const float* ln_b,
+                   const float* res, float* y) {
+    if (!x || !w || !y || (ln_g == nullptr) != (ln_b == nullptr) || act < ACT_NONE || act > ACT_HSIG_PADDLE) return -1;
+    GemvParams p{};
+    p.x = x; p.M = M; p.K = K; p.N = N; p.w = w; p.bias = bias; p.ln_g = ln_g; p.ln_b = ln_b; p.res = res; p.y = y; p.act = act;
+    const int code = dec_gemv_route(p, nullptr);
+    return debug_sync() ? code : -1;
+}
+
+// route 0 = dec_attention_kernel (q / kcur / vcur given), 1 = dec_attn_fused_kernel, 2 = dec_attn_fused2_kernel (x, LayerNorm and projection
+// weights given); self != 0: T = the step (keys 0 .. T - 1 come from the cache, this step's k, v are appended as row T), otherwise T = S
+// cached keys.  Cache rows: kc / vc + b * seq_stride + j * ldkv; seq_stride must cover rows 0 .. T (self) / T - 1 (cross), else -1.
+int debug_dec_attention(int route, int self, int B, int T, float* kc, float* vc, int ldkv, long long seq_stride, const float* x, const float* ln_g,
+                        const float* ln_b, const float* w, const float* bias, const float* q, int ldq, const float* kcur, const float* vcur,
+                        int ldcur, float* out, int ldo) {
+    if (route < 0 || route > 2 || B < 1 || T < (self ? 0 : 1) || T > 8192 || !kc || !vc || !out || ldkv < D || (ldkv & 3) || (seq_stride & 3) ||
+        ldo < D || seq_stride < (long long)(T + (self ? 1 : 0)) * ldkv)      // a sequence's cache must hold the rows the launch reads and appends
+        return -1;
+    if (route == 0 ? (!q || ldq < D || (ldq & 3) || (self && (!kcur || !vcur || ldcur < D || (ldcur & 3)))) : (!x || !ln_g || !ln_b || !w || !bias))
+        return -1;
+    DebugState st(DecState{self ? T : 0, B, 0});
+    if (!st.d) return -1;
+    const int keys = T + (self ? 1 : 0);
+    if (route == 0) {
+        AttnDecParams p{};
+        p.q = q; p.ldq = ldq; p.kc = kc; p.vc = vc; p.ldkv = ldkv; p.seq_stride = seq_stride;
+        if (self) { p.kcur = kcur; p.vcur = vcur; p.ldcur = ldcur; p.kw = kc; p.vw = vc; }
+        p.st = st.d; p.fixed_T = self ? 0 : T; p.out = out; p.ldo = ldo;
+        launch_dec_attention(p, B, keys, nullptr);
+    } else {
+        AttnFusedParams p{};
+        p.x = x; p.ln_g = ln_g; p.ln_b = ln_b; p.w = w; p.bias = bias; p.kc = kc; p.vc = vc; p.ldkv = ldkv; p.seq_stride = seq_stride;
+        if (self) { p.kw = kc; p.vw = vc; }
+        p.st = st.d; p.fixed_T = self ? 0 : T; p.out = out; p.ldo = ldo;
+        launch_dec_attn_fused(p, self != 0, route == 2, B, keys, nullptr);
+    }
+    return debug_sync() ? 0 : -1;
+}
+
+// mode 0: dec_select_kernel at `step` (with the next step's embedding when emb is given), mode 1: dec_embed_ln_kernel at `step` on the same
+// ids.  state_out [3] = DecState (step, n_unfinished, arrived) after the launch.
+int debug_dec_select(int mode, const float* logits, int V, int B, int step, long long* ids, int ids_ld, int* unfinished, int n_unfinished, int max_new,
+                     const float* emb, const float* pos, const float* g, const float* b, float* x, int* state_out) {
+    if (mode < 0 || mode > 1 || B < 1 || step < 0 || !ids || ids_ld < 1) return -1;
+    if (mode == 0 ? (!logits || V < 1 || !unfinished || step + 1 >= ids_ld || (emb && (!pos || !g || !b || !x)))
+                  : (!emb || !pos || !g || !b || !x || step >= ids_ld))
+        return -1;
+    DebugState st(DecState{step, n_unfinished, 0});
+    if (!st.d) return -1;
+    if (mode == 0) {
+        NextEmbed ne{};
+        if (emb) ne = NextEmbed{emb, pos, g, b, x, max_new};
+        hipLaunchKernelGGL(dec_select_kernel, dim3(B), dim3(1024), 0, nullptr, logits, V, ids, ids_ld, unfinished, st.d, B, ne);
+    } else {
+        hipLaunchKernelGGL(dec_embed_ln_kernel, dim3(B), dim3(64), 0, nullptr, emb, pos, ids, ids_ld, st.d, g, b, x);
+    }
+    if (!debug_sync()) return -1;
+    return st.read(state_out) ? 0 : -1;
+}
 
 }  // namespace rd
