@@ -42,7 +42,8 @@ typedef struct rd_handle rd_handle;
                                * [B,T,120] (the CTC classifier's input); idx / prob come from the fused head as with flags 0 */
 
 const char* rd_version(void);
-/* model_kind: "ppocrv6_det" | "ppocrv5_det_server" (PPHGNetV2-B4 + LKPAN + PFHeadLocal; rd_det_forward / rd_det_forward_ex) | "ppocrv6_rec" | "ppocrv5_rec_server" (PPHGNetV2-B4 + SVTR neck + CTC; every rd_rec_* call except
+/* model_kind: "ppocrv6_det" | "ppocrv5_det_server" (PPHGNetV2-B4 + LKPAN + PFHeadLocal; rd_det_forward / rd_det_forward_ex) |
+ * "ppocrv5_det_mobile" (PPLCNetV3 scale 0.75 + RSEFPN + DBHead; the same two calls) | "ppocrv6_rec" | "ppocrv5_rec_server" (PPHGNetV2-B4 + SVTR neck + CTC; every rd_rec_* call except
  * rd_rec_backbone_forward_lines) | "ppocrv5_rec_mobile" (PPLCNetV3 scale 0.95 + the same SVTR neck + CTC; every rd_rec_* call) | "pphgnetv2_b4" | "pphgnetv2_b6_formula" | "ppformulanet_head".  NULL on failure -> rd_create_error(). */
 rd_handle* rd_create(int device_id, const char* model_kind);
 const char* rd_create_error(void);
@@ -55,12 +56,12 @@ int rd_load_weights(rd_handle* h, const void* safetensors_image, size_t nbytes);
 /* bytes of device workspace one call with this geometry needs (H is ignored for rec: always 48) */
 int rd_query_workspace(rd_handle* h, int B, int H, int W, int flags, size_t* ws_bytes);
 
-/* Text detector ("ppocrv6_det" or "ppocrv5_det_server"): x [B,3,H,W] (H, W multiples of 32; the server detector: >= 64) -> DB probability
+/* Text detector ("ppocrv6_det", "ppocrv5_det_server" or "ppocrv5_det_mobile"): x [B,3,H,W] (H, W multiples of 32; the server detector: >= 64) -> DB probability
  * map [B,1,H,W] (the reference session's `maps`) */
 int rd_det_forward(rd_handle* h, const float* x_nchw_dev, int B, int H, int W, float* prob_b1hw_dev, void* ws_dev,
                    size_t ws_bytes, void* stream);
-/* The same forward with debug outputs.  flags 0: exactly rd_det_forward (aux_dev may be NULL).  RD_DET_WANT_NECK ("ppocrv5_det_server" only):
- * aux_dev also receives the neck's output `fuse` as NCHW [B,256,H/4,W/4].  rd_query_workspace takes the same flags. */
+/* The same forward with debug outputs.  flags 0: exactly rd_det_forward (aux_dev may be NULL).  RD_DET_WANT_NECK ("ppocrv5_det_server" and
+ * "ppocrv5_det_mobile"): aux_dev also receives the neck's output `fuse` as NCHW [B,256,H/4,W/4] (server) or [B,96,H/4,W/4] (mobile).  rd_query_workspace takes the same flags. */
 #define RD_DET_WANT_NECK 1
 int rd_det_forward_ex(rd_handle* h, const float* x_nchw_dev, int B, int H, int W, float* prob_b1hw_dev, int flags, float* aux_dev,
                       void* ws_dev, size_t ws_bytes, void* stream);

@@ -105,11 +105,11 @@ int rd_query_workspace(rd_handle* h, int B, int H, int W, int flags, size_t* ws_
     });
 }
 
-static bool is_det_kind(const std::string& k) { return k == "ppocrv6_det" || k == "ppocrv5_det_server"; }
+static bool is_det_kind(const std::string& k) { return k == "ppocrv6_det" || k == "ppocrv5_det_server" || k == "ppocrv5_det_mobile"; }
 
 int rd_det_forward(rd_handle* h, const float* x, int B, int H, int W, float* prob, void* ws, size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && is_det_kind(h->eng->kind()), "handle is not a detector (ppocrv6_det / ppocrv5_det_server) model");
+        RD_CHECK(h->eng && is_det_kind(h->eng->kind()), "handle is not a detector (ppocrv6_det / ppocrv5_det_server / ppocrv5_det_mobile) model");
         RD_CHECK(x && prob && B > 0, "null input/output");
         h->eng->run(B, H, W, 0, {(void*)x, (void*)prob}, ws, ws_bytes, (hipStream_t)stream);
     });
@@ -118,11 +118,12 @@ int rd_det_forward(rd_handle* h, const float* x, int B, int H, int W, float* pro
 int rd_det_forward_ex(rd_handle* h, const float* x, int B, int H, int W, float* prob, int flags, float* aux, void* ws, size_t ws_bytes,
                       void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && is_det_kind(h->eng->kind()), "handle is not a detector (ppocrv6_det / ppocrv5_det_server) model");
+        RD_CHECK(h->eng && is_det_kind(h->eng->kind()), "handle is not a detector (ppocrv6_det / ppocrv5_det_server / ppocrv5_det_mobile) model");
         RD_CHECK(x && prob && B > 0, "null input/output");
         RD_CHECK((flags & ~RD_DET_WANT_NECK) == 0, "rd_det_forward_ex: unknown flag");
         if (flags & RD_DET_WANT_NECK) {
-            RD_CHECK(h->eng->kind() == "ppocrv5_det_server", "RD_DET_WANT_NECK is offered by ppocrv5_det_server only");
+            RD_CHECK(h->eng->kind() == "ppocrv5_det_server" || h->eng->kind() == "ppocrv5_det_mobile",
+                     "RD_DET_WANT_NECK is offered by ppocrv5_det_server and ppocrv5_det_mobile only");
             RD_CHECK(aux, "aux_dev is NULL");
         }
         h->eng->run(B, H, W, flags, {(void*)x, (void*)prob, (void*)aux}, ws, ws_bytes, (hipStream_t)stream);
@@ -776,7 +777,7 @@ float rd_debug_lcv3_dw(int N, int H, int W, int C, int K, int SH, int SW, int pr
     p.x = x; p.xld = C; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = C;
     p.K = K; p.SH = SH; p.SW = SW;
     p.OH = (H + 2 * (K / 2) - K) / SH + 1; p.OW = (W + 2 * (K / 2) - K) / SW + 1;
-    p.pre_act = pre_act; p.pre_s = aff[0]; p.pre_b = aff[1]; p.post_s = aff[2]; p.post_b = aff[3];
+    p.pre_act = pre_act; p.pre_s = aff[0]; p.pre_b = aff[1]; p.post_s = aff[2]; p.post_b = aff[3]; p.post_act = 1;
     p.line_in = line_in; p.line_out = line_out; p.line_stride = 1;
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -784,6 +785,54 @@ float rd_debug_lcv3_dw(int N, int H, int W, int C, int K, int SH, int SW, int pr
     if (gap) rd::launch_lcv3_gap_rows(y, C, N, p.OH, p.OW, C, gap, line_out, 1, nullptr);
     (void)hipEventRecord(e0, nullptr);
     for (int i = 0; i < iters; ++i) rd::launch_lcv3_dw(p, nullptr);
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return iters > 0 ? ms / iters : 0.f;
+}
+
+// developer entry, host only (no device is touched): the load-time derived tensor `name` of "ppocrv5_det_mobile" - a folded
+// LearnableRepLayer (`<layer>.fold.weight / .bias`) or `neck.ins_conv.<i>.fold.*` - from a safetensors image.  Copies at most
+// `capacity` floats to `out` and returns the tensor's element count; -1: unknown kind, name or a malformed image.
+long rd_debug_derived_tensor(const char* kind, const void* img, size_t nbytes, const char* name, float* out, long capacity) {
+    try {
+        if (!kind || !img || !name) return -1;
+        const std::string k(kind);
+        rd::WeightStore ws;
+        ws.load_safetensors(img, nbytes);
+        if (k != "ppocrv5_det_mobile") return -1;
+        rd::derive_ppocrv5_det_mobile_weights(ws);
+        if (!ws.has(name)) return -1;
+        const rd::HostTensor& t = ws.get(name);
+        const long n = (long)t.numel();
+        if (out) std::copy(t.f32(), t.f32() + std::min(n, capacity), out);
+        return n;
+    } catch (const std::exception&) {
+        return -1;
+    }
+}
+
+// developer entry: one PPLCNetV3 depthwise layer in the detector geometry (x NHWC fp32 [N][H][W][C], w [K*K][C], bias [C], y [N][OH][OW][C] with
+// OH = (H + 2 (K / 2) - K) / S + 1; aff as above; post_act 0: convolution + bias only).  route 0: launch_lcv3_dw (kernels_lcv3.hip), 1: the
+// LDS-staged launch_lcv3_dw2d (kernels_lcv3_det.hip).  Returns ms per launch, < 0: geometry not served by that route.
+float rd_debug_lcv3_dw_det(int N, int H, int W, int C, int K, int S, int pre_act, int post_act, int route, int iters, const float* aff, float* x,
+                           float* w, float* bias, float* y) {
+    if (!aff || N < 1 || H < 1 || W < 1 || (S != 1 && S != 2) || (route != 0 && route != 1)) return -1.f;
+    if (route == 0 && !rd::lcv3_dw_shape_ok(K, S, S, C)) return -1.f;
+    rd::Lcv3DwParams p{};
+    p.x = x; p.xld = C; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = C;
+    p.K = K; p.SH = p.SW = S;
+    p.OH = (H + 2 * (K / 2) - K) / S + 1; p.OW = (W + 2 * (K / 2) - K) / S + 1;
+    p.pre_act = pre_act; p.pre_s = aff[0]; p.pre_b = aff[1]; p.post_s = aff[2]; p.post_b = aff[3]; p.post_act = post_act;
+    if (route == 1 && !rd::lcv3_dw2d_launch_ok(p)) return -1.f;         // shape, or a grid beyond 2^31 workgroups
+    auto launch = [&] { if (route) (void)rd::launch_lcv3_dw2d(p, nullptr); else rd::launch_lcv3_dw(p, nullptr); };
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    launch();
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) launch();
     (void)hipEventRecord(e1, nullptr);
     (void)hipEventSynchronize(e1);
     float ms = 0.f;

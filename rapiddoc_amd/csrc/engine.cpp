@@ -1139,14 +1139,17 @@ Builder::Affine Builder::affine(const std::string& prefix) const {
     return Affine{sc.f32()[0], bi.f32()[0]};
 }
 
-TView Builder::lcv3_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre, Affine post,
-                       int lt_in, int lt_out) {
+// Shared by both PPLCNetV3 depthwise builders: checks, the output view, in PREPARE mode the [k*k][C] weight image + bias, in PLAN mode
+// the kernel parameters (pointers of x / y are filled in at run time) and the op's record without its `run`
+bool Builder::lcv3_dw_common(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre,
+                             const Affine* post, TView* y_out, Lcv3DwParams* p_out, OpRecord* r_out) {
     const HostTensor& w = ws_->get(wname);
     RD_CHECK(w.shape.size() == 4 && w.shape[1] == 1 && w.shape[2] == k && w.shape[3] == k, "lcv3 depthwise weight shape: " + wname);
     const int c = (int)w.shape[0];
     RD_CHECK(c == x.c && lcv3_dw_shape_ok(k, sh, sw, c), "lcv3 depthwise geometry: " + wname);
     const int oh = out_dim(x.h, k, sh, k / 2, k / 2), ow = out_dim(x.w, k, sw, k / 2, k / 2);
     TView y = alloc(x.n, oh, ow, c);
+    *y_out = y;
     const std::string key = wname + "|lcv3dw";
     if (!planning()) {
         if (!pb_->has(key + "#w")) {
@@ -1156,7 +1159,7 @@ TView Builder::lcv3_dw(const std::string& wname, const std::string& bname, const
             pb_->add(key + "#w", wf);
             pb_->add(key + "#b", std::vector<float>(ws_->get(bname).f32(), ws_->get(bname).f32() + c));
         }
-        return y;
+        return false;
     }
     Lcv3DwParams p{};
     p.xld = plan_->ld(x);
@@ -1166,15 +1169,26 @@ TView Builder::lcv3_dw(const std::string& wname, const std::string& bname, const
     p.yld = plan_->ld(y);
     p.OH = oh; p.OW = ow; p.K = k; p.SH = sh; p.SW = sw;
     p.pre_act = pre != nullptr;
-    p.pre_s = pre ? pre->s : 1.f; p.pre_b = pre ? pre->b : 0.f; p.post_s = post.s; p.post_b = post.b;
+    p.pre_s = pre ? pre->s : 1.f; p.pre_b = pre ? pre->b : 0.f;
+    p.post_act = post != nullptr;
+    p.post_s = post ? post->s : 1.f; p.post_b = post ? post->b : 0.f;
     RD_CHECK(p.xld % 4 == 0 && x.coff % 4 == 0, "lcv3 depthwise: 16-byte aligned pixels");
+    *p_out = p;
+    r_out->name = wname;
+    r_out->kind = "lcv3_dw" + std::to_string(k) + "x" + std::to_string(k);
+    r_out->shape = "N" + std::to_string(x.n) + "_" + std::to_string(x.h) + "x" + std::to_string(x.w) + "_C" + std::to_string(c);
+    r_out->flops = 2.0 * x.n * oh * ow * (double)c * k * k;
+    r_out->bytes = 4.0 * ((double)x.pixels() * c + (double)y.pixels() * c);
+    return true;
+}
+
+TView Builder::lcv3_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre, Affine post,
+                       int lt_in, int lt_out) {
+    TView y{};
+    Lcv3DwParams p{};
     OpRecord r;
-    r.name = wname;
-    r.kind = "lcv3_dw" + std::to_string(k) + "x" + std::to_string(k);
+    if (!lcv3_dw_common(wname, bname, x, k, sh, sw, pre, &post, &y, &p, &r)) return y;
     r.cfg = "s" + std::to_string(sh) + std::to_string(sw) + (has_lt_ ? "/lines" : "");
-    r.shape = "N" + std::to_string(x.n) + "_" + std::to_string(x.h) + "x" + std::to_string(x.w) + "_C" + std::to_string(c);
-    r.flops = 2.0 * x.n * oh * ow * (double)c * k * k;
-    r.bytes = 4.0 * ((double)x.pixels() * c + (double)y.pixels() * c);
     const TView xv = x, yv = y, ltv = lt_;
     const bool has_lt = has_lt_;
     r.run = [p, xv, yv, ltv, has_lt, lt_in, lt_out](const Plan& pl, const RunCtx& cx) {
@@ -1188,6 +1202,62 @@ TView Builder::lcv3_dw(const std::string& wname, const std::string& bname, const
             q.line_stride = kLineTabStride;
         }
         launch_lcv3_dw(q, cx.stream);
+    };
+    emit(std::move(r));
+    return y;
+}
+
+// Per-layer default of the detector's depthwise route, from the same-run alternating A/B of tools/mb_det_mobile.py at [32, 3, 960, 704]
+// (profiles/mb_det_mobile.txt): the LDS-staged kernel where its median was below the direct kernel's by more than either route's own
+// repeat spread, the direct kernel everywhere else (it is the simpler one).  Direct / staged ms of the measured layers:
+//   k 3 s 1  C 16 @ 1/2   0.229 / 0.154    k 3 s 2  C 32 @ 1/2   0.208 / 0.259 (direct stays)    k 5 s 1  C 192 @ 1/16  0.083 / 0.050
+//   k 3 s 1  C 48 @ 1/4   0.183 / 0.146    k 3 s 2  C 48 @ 1/4   0.087 / 0.103 (direct stays)    k 5 s 2  C 192 @ 1/16  0.051 / 0.044
+//   k 3 s 1  C 96 @ 1/8   0.087 / 0.074    k 3 s 2  C 96 @ 1/8   0.037 / 0.056 (direct stays)    k 5 s 1  C 384 @ 1/32  0.046 / 0.026
+// A (k, stride, C, level) that was not measured stays on the direct kernel.
+bool lcv3_dw2d_default(int k, int stride, int c, int level) {
+    if (k == 3 && stride == 1) return (c == 16 && level == 1) || (c == 48 && level == 2) || (c == 96 && level == 3);
+    if (k == 5 && stride == 1) return (c == 192 && level == 4) || (c == 384 && level == 5);
+    if (k == 5 && stride == 2) return c == 192 && level == 4;
+    return false;
+}
+
+TView Builder::lcv3_dw_det(const std::string& wname, const std::string& bname, const TView& x, int k, int stride, const Affine* pre, const Affine* post,
+                           int level) {
+    RD_CHECK(stride == 1 || stride == 2, "lcv3 depthwise (detector geometry): stride 1 or 2: " + wname);
+    RD_CHECK(!has_lt_, "lcv3 depthwise (detector geometry): no line table");
+    TView y{};
+    Lcv3DwParams p{};
+    OpRecord r;
+    if (!lcv3_dw_common(wname, bname, x, k, stride, stride, pre, post, &y, &p, &r)) return y;
+    // the route is a property of the layer (k, stride, C, pyramid level), never of the batch or the page size; A/B switch read per plan
+    const char* sw = std::getenv("RD_LCV3_DW2D");
+    const bool staged = lcv3_dw2d_shape_ok(k, stride, stride, p.C) && (sw && (sw[0] == '0' || sw[0] == '1') ? sw[0] == '1' : lcv3_dw2d_default(k, stride, p.C, level));
+    RD_CHECK(!staged || lcv3_dw2d_launch_ok(p), "lcv3 depthwise: the staged kernel's grid does not fit: " + wname);
+    r.cfg = "s" + std::to_string(stride) + std::to_string(stride) + (staged ? "/lds2d" : "/direct") + (post ? "" : "/noact");
+    const TView xv = x, yv = y;
+    r.run = [p, xv, yv, staged](const Plan& pl, const RunCtx& cx) {
+        Lcv3DwParams q = p;
+        q.x = pl.vptr(xv, cx);
+        q.y = pl.vptr(yv, cx);
+        if (staged) (void)launch_lcv3_dw2d(q, cx.stream);      // (servable: checked above)
+        else launch_lcv3_dw(q, cx.stream);
+    };
+    emit(std::move(r));
+    return y;
+}
+
+TView Builder::lcv3_act(const TView& x, Affine a) {
+    RD_CHECK(x.c % 4 == 0, "lcv3 act: channels % 4");
+    TView y = alloc(x.n, x.h, x.w, x.c);
+    if (!planning()) return y;
+    RD_CHECK(plan_->ld(x) % 4 == 0 && x.coff % 4 == 0, "lcv3 act: 16-byte aligned pixels");
+    OpRecord r;
+    r.name = "hswish+affine";
+    r.kind = "lcv3_act";
+    r.bytes = 8.0 * x.pixels() * x.c;
+    const TView xv = x, yv = y;
+    r.run = [xv, yv, a](const Plan& pl, const RunCtx& cx) {
+        launch_lcv3_act(pl.vptr(xv, cx), pl.ld(xv), pl.vptr(yv, cx), pl.ld(yv), (long)xv.pixels(), xv.c, a.s, a.b, cx.stream);
     };
     emit(std::move(r));
     return y;
@@ -1630,6 +1700,7 @@ Engine::Engine(int device, const std::string& kind) : device_(device), kind_(kin
         precision_ = v == "h3" ? PREC_H3 : v == "fp32" ? PREC_FP32 : PREC_AUTO;
     }
     RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "ppocrv5_rec_mobile" || kind == "ppocrv5_det_server" ||
+                 kind == "ppocrv5_det_mobile" ||
                  kind == "pphgnetv2_b4" || kind == "pphgnetv2_b6_formula",
              "unknown model kind '" + kind + "'");
     int count = 0;
@@ -1679,6 +1750,7 @@ void Engine::build(Builder& b, int B, int H, int W, int flags) {
     else if (kind_ == "ppocrv5_rec_server") build_ppocrv5_rec_server(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_rec_mobile") build_ppocrv5_rec_mobile(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_det_server") build_ppocrv5_det_server(b, B, H, W, flags);
+    else if (kind_ == "ppocrv5_det_mobile") build_ppocrv5_det_mobile(b, B, H, W, flags);
     else if (kind_ == "pphgnetv2_b6_formula") build_pphgnetv2_b6_formula(b, B, H, W, flags);
     else build_pphgnetv2_b4(b, B, H, W);
 }
@@ -1696,6 +1768,8 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
         if (kind_ == "ppocrv5_rec_mobile") derive_ppocrv5_rec_mobile_weights(store_);
     } else if (kind_ == "ppocrv5_det_server") {
         derive_ppocrv5_det_server_weights(store_);
+    } else if (kind_ == "ppocrv5_det_mobile") {
+        derive_ppocrv5_det_mobile_weights(store_);
     }
     Plan dummy;
     h3_prepared_ = precision_ == PREC_H3;

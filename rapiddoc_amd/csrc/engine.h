@@ -217,6 +217,14 @@ class Builder {
     Affine affine(const std::string& prefix) const;      // prefix.scale / prefix.bias
     TView lcv3_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre, Affine post, int lt_in,
                   int lt_out);
+    // the detector geometry: `post` null = convolution + bias only (a stride-2 layer); `level` = log2 of the input map's reduction of the
+    // page (1 = H/2 ... 5 = H/32), which with (k, stride, C) picks the direct or the LDS-staged kernel (lcv3_dw2d_default; RD_LCV3_DW2D=0|1
+    // forces one route for every layer the staged kernel serves)
+    TView lcv3_dw_det(const std::string& wname, const std::string& bname, const TView& x, int k, int stride, const Affine* pre, const Affine* post,
+                      int level);
+    bool lcv3_dw_common(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre, const Affine* post,
+                        TView* y, Lcv3DwParams* p, OpRecord* r);   // shared by the two builders above; false in PREPARE mode
+    TView lcv3_act(const TView& x, Affine a);             // a hardswish(x) + b, elementwise (kernels_lcv3_det.hip)
     // one block without SE (3x3, stride 1) in one launch (kernels_lcv3_block.hip), writing the pointwise layer's convolution + bias as the separate
     // route does.  Taken under RD_LCV3_FUSED=1 in the split precisions; false: not taken (and always in PREPARE mode, where it only adds its
     // parameters), the caller emits the separate operators
@@ -358,6 +366,14 @@ enum DetFlags : int { DET_WANT_NECK = 1 };
 void build_ppocrv5_det_server(Builder& b, int B, int H, int W, int flags);
 // tensors build_ppocrv5_det_server reads that are not in the file: the three branches of every IntraCL level folded into one k x k convolution
 void derive_ppocrv5_det_server_weights(WeightStore& ws);
+// PP-OCRv5 mobile detector (PPLCNetV3 scale 0.75 det + RSEFPN 96 + DBHead): externals as the server detector; DET_WANT_NECK: ext[2] = `fuse`
+// NCHW [B,96,H/4,W/4]
+void build_ppocrv5_det_mobile(Builder& b, int B, int H, int W, int flags);
+// tensors build_ppocrv5_det_mobile reads that are not in the file: every LearnableRepLayer folded into one convolution + bias, and
+// layer_list[i] followed by ins_conv[i].in_conv as one 1x1 convolution + bias
+void derive_ppocrv5_det_mobile_weights(WeightStore& ws);
+// default route of one depthwise layer of that backbone: true = the LDS-staged kernel (set from the per-layer A/B table of tools/mb_det_mobile.py)
+bool lcv3_dw2d_default(int k, int stride, int c, int level);
 void build_pphgnetv2_b4(Builder& b, int B, int H, int W);
 // PP-FormulaNet_plus encoder; flags bit 0: the caller's image has 1 channel (replicated to 3 like the reference)
 void build_pphgnetv2_b6_formula(Builder& b, int B, int H, int W, int flags);

@@ -7,6 +7,9 @@
 // convolution's padding stays zero, as in the reference, where activation and affine precede the padding.
 // Per-line widths (rd_kernels.h LineTab): input columns >= line_in[n] are that padding too (whatever the shared tensor holds there),
 // output columns >= line_out[n] are written as zeros.  Strides (1,1), (2,1) and (1,2); 3x3 and 5x5.
+// The mobile DETECTOR (build_ppocrv5_det_mobile) adds stride (2,2) for both kernel sizes and post_act = 0: the reference skips the
+// activation of a layer whose stride is the integer 2, so such a layer writes dw_kxk(x') + bias and nothing else.  The detector's
+// LDS-staged alternative to this kernel is kernels_lcv3_det.hip.
 // One thread = 4 channels x TW adjacent output columns of one row: the (TW - 1) SW + K input columns of a kernel row are loaded once
 // and feed all TW outputs.  Channel quads are the fastest thread index: every load is a coalesced 16-byte access.
 #include "rd_device.h"
@@ -63,7 +66,7 @@ __global__ void __launch_bounds__(256) lcv3_dw_kernel(Lcv3DwParams p) {
         for (int j = 0; j < TW; ++j) {
             const int ow = ow0 + j;
             if (ow >= p.OW) break;
-            const f32x4 o = ow < lw_out ? lcv3_hswish_aff(acc[j], p.post_s, p.post_b) : f32x4{0.f, 0.f, 0.f, 0.f};
+            const f32x4 o = ow >= lw_out ? f32x4{0.f, 0.f, 0.f, 0.f} : p.post_act ? lcv3_hswish_aff(acc[j], p.post_s, p.post_b) : acc[j];
             *reinterpret_cast<f32x4*>(yrow + (size_t)ow * p.yld) = o;
         }
     }
@@ -75,7 +78,7 @@ static inline int lcv3_grid(long total) {
 }
 
 bool lcv3_dw_shape_ok(int k, int sh, int sw, int c) {
-    return (k == 3 || k == 5) && c % 4 == 0 && ((sh == 1 && sw == 1) || (sh == 2 && sw == 1) || (sh == 1 && sw == 2 && k == 3));
+    return (k == 3 || k == 5) && c % 4 == 0 && ((sh == 1 && sw == 1) || (sh == 2 && sw == 1) || (sh == 1 && sw == 2 && k == 3) || (sh == 2 && sw == 2));
 }
 
 void launch_lcv3_dw(const Lcv3DwParams& p, hipStream_t s) {
@@ -85,6 +88,7 @@ void launch_lcv3_dw(const Lcv3DwParams& p, hipStream_t s) {
     if (p.K == 3 && p.SW == 1) hipLaunchKernelGGL((lcv3_dw_kernel<3, 1, TW>), g, b, 0, s, p);
     else if (p.K == 3 && p.SW == 2) hipLaunchKernelGGL((lcv3_dw_kernel<3, 2, TW>), g, b, 0, s, p);
     else if (p.K == 5 && p.SW == 1) hipLaunchKernelGGL((lcv3_dw_kernel<5, 1, TW>), g, b, 0, s, p);
+    else if (p.K == 5 && p.SW == 2) hipLaunchKernelGGL((lcv3_dw_kernel<5, 2, TW>), g, b, 0, s, p);
 }
 
 // SE pooling partial sums of a depthwise output under per-line widths: partial[n][h][c] = sum over w < line_w[n] of x[n][h][w][c], one

@@ -8,6 +8,8 @@
 //   LKPAN ................ .../necks/db_fpn.py:418-525, IntraCLBlock .../necks/intracl.py
 //   PFHeadLocal .......... .../heads/det_db_head.py:8-49, 152-180
 //   PPLCNetV3 (rec) ...... .../backbones/rec_lcnetv3.py:45-64, 76-351, 493-517
+//   PPLCNetV3 (det) ...... .../backbones/rec_lcnetv3.py:24-43, 469-511; RSEFPN .../necks/db_fpn.py:210-285; SEModule
+//                          .../backbones/det_mobilenet_v3.py:55-85; DBHead (non-v6 branch) .../heads/det_db_head.py:8-49, 148-149
 //   PPHGNetV2-B4 (det) ... rapid_doc/model/formula/rapid_formula_self/networks/backbones/rec_pphgnetv2.py:860-1477
 #include "engine.h"
 
@@ -744,13 +746,18 @@ static void fold_rep_layer(WeightStore& ws, const std::string& p, bool depthwise
     ws.add_derived(p + ".fold.bias", {co}, std::move(bf));
 }
 
-void derive_ppocrv5_rec_mobile_weights(WeightStore& ws) {
-    for (const Lcv3Cfg& c : kLcv3Rec) {
+// both layers of every block of a PPLCNetV3 configuration; the fold goes by the tensors the file has (an identity BatchNorm exists only
+// where cin == cout and the stride is 1)
+template <size_t N>
+static void fold_lcv3_blocks(WeightStore& ws, const Lcv3Cfg (&cfg)[N]) {
+    for (const Lcv3Cfg& c : cfg) {
         const std::string p = std::string("backbone.") + c.name;
         fold_rep_layer(ws, p + ".dw_conv", true);
         fold_rep_layer(ws, p + ".pw_conv", false);
     }
 }
+
+void derive_ppocrv5_rec_mobile_weights(WeightStore& ws) { fold_lcv3_blocks(ws, kLcv3Rec); }
 
 // x NCHW image -> pooled tokens [B][1][w4 / 2][480] (into *tokens_out when given)
 static TView lcnetv3_rec(Builder& b, const TView& x, const TView* tokens_out) {
@@ -794,5 +801,136 @@ static TView lcnetv3_rec(Builder& b, const TView& x, const TView* tokens_out) {
 }
 
 void build_ppocrv5_rec_mobile(Builder& b, int B, int H, int W, int flags) { build_ppocrv5_rec(b, B, H, W, flags, true); }
+
+// ---------------------------------------------------------------------------------------------------
+// PP-OCRv5 mobile det (arch_config.yaml ch_PP-OCRv5_det_mobile): PPLCNetV3(scale 0.75, det=True) -> RSEFPN(96, shortcut) -> DBHead(k 50).
+// ext[0] = x NCHW [B,3,H,W]; ext[1] = maps [B,1,H,W]; DET_WANT_NECK: ext[2] = fuse NCHW [B,96,H/4,W/4].
+// The backbone is the mobile recogniser's with integer strides.  The reference activates a LearnableRepLayer `if self.stride != 2`, and
+// here the stride IS the integer 2: a stride-2 depthwise layer is lab(branches) and nothing else - `lab` is in the folded weights, and
+// the `act.lab` tensors the file carries for those layers are never asked for.  Everything else follows the recogniser: a pointwise layer
+// writes convolution + bias, its hardswish + act.lab run in its consumer.  The four stage outputs feed matrix kernels, which cannot
+// activate on load: their activated form is written once by lcv3_act.
+// layer_list[i] (1x1, bias) -> ins_conv[i].in_conv (1x1, no bias) has nothing nonlinear in between: ONE 1x1 convolution + bias, derived
+// in double at load time; the widths 12 / 18 / 42 / 360 never exist.  head.thresh.* is in the file and unused in eval mode.
+// ---------------------------------------------------------------------------------------------------
+static const Lcv3Cfg kLcv3Det[] = {
+    {"blocks2.0", 3, 16, 32, 1, 1, false},
+    {"blocks3.0", 3, 32, 48, 2, 2, false},   {"blocks3.1", 3, 48, 48, 1, 1, false},
+    {"blocks4.0", 3, 48, 96, 2, 2, false},   {"blocks4.1", 3, 96, 96, 1, 1, false},
+    {"blocks5.0", 3, 96, 192, 2, 2, false},  {"blocks5.1", 5, 192, 192, 1, 1, false}, {"blocks5.2", 5, 192, 192, 1, 1, false},
+    {"blocks5.3", 5, 192, 192, 1, 1, false}, {"blocks5.4", 5, 192, 192, 1, 1, false},
+    {"blocks6.0", 5, 192, 384, 2, 2, true},  {"blocks6.1", 5, 384, 384, 1, 1, true},  {"blocks6.2", 5, 384, 384, 1, 1, false},
+    {"blocks6.3", 5, 384, 384, 1, 1, false},
+};
+static const char* const kLcv3DetTaps[4] = {"blocks3.1", "blocks4.1", "blocks5.4", "blocks6.3"};
+static std::string ins_fold_name(int i) { return "neck.ins_conv." + std::to_string(i) + ".fold"; }
+
+void derive_ppocrv5_det_mobile_weights(WeightStore& ws) {
+    fold_lcv3_blocks(ws, kLcv3Det);
+    for (int i = 0; i < 4; ++i) {
+        const HostTensor& wl = ws.get("backbone.layer_list." + std::to_string(i) + ".weight");     // [m][k][1][1]
+        const HostTensor& bl = ws.get("backbone.layer_list." + std::to_string(i) + ".bias");
+        const HostTensor& wi = ws.get("neck.ins_conv." + std::to_string(i) + ".in_conv.weight");    // [co][m][1][1]
+        const int m = (int)wl.shape[0], k = (int)wl.shape[1], co = (int)wi.shape[0];
+        RD_CHECK(wl.numel() == (size_t)m * k && wi.numel() == (size_t)co * m && (int)wi.shape[1] == m && bl.numel() == (size_t)m,
+                 "layer_list / ins_conv shapes of level " + std::to_string(i));
+        std::vector<float> w((size_t)co * k), bias(co);
+        for (int o = 0; o < co; ++o) {
+            for (int c = 0; c < k; ++c) {
+                double a = 0.0;
+                for (int j = 0; j < m; ++j) a += (double)wi.f32()[(size_t)o * m + j] * wl.f32()[(size_t)j * k + c];
+                w[(size_t)o * k + c] = (float)a;
+            }
+            double a = 0.0;
+            for (int j = 0; j < m; ++j) a += (double)wi.f32()[(size_t)o * m + j] * bl.f32()[j];
+            bias[o] = (float)a;
+        }
+        ws.add_derived(ins_fold_name(i) + ".weight", {co, k, 1, 1}, std::move(w));
+        ws.add_derived(ins_fold_name(i) + ".bias", {co}, std::move(bias));
+    }
+}
+
+void build_ppocrv5_det_mobile(Builder& b, int B, int H, int W, int flags) {
+    RD_CHECK(H % 32 == 0 && W % 32 == 0 && H >= 32 && W >= 32, "det mobile input H, W must be multiples of 32");
+    RD_CHECK((flags & ~DET_WANT_NECK) == 0, "det mobile: unknown flag");
+    TView x = b.external(0, B, H, W, 3);
+    TView out = b.external(1, B, H, W, 1);
+
+    // backbone; the folded layer_list + ins_conv 1x1 and its RSE gate run while the stage's buffers are live
+    TView h = b.stem3x3s2("backbone.conv1.conv.weight", "backbone.conv1.bn", x, ACT_NONE);
+    Builder::Affine pre;
+    bool has_pre = false;     // conv1 has neither activation nor affine
+    int level = 1, tap = 0;   // level: log2 of the current map's reduction of the page
+    TView in[4];
+    for (const Lcv3Cfg& c : kLcv3Det) {
+        const std::string p = std::string("backbone.") + c.name;
+        RD_CHECK(h.c == c.cin, "PPLCNetV3: channel chain: " + p);
+        Builder::Affine post;
+        if (c.sh != 2) post = b.affine(p + ".dw_conv.act.lab");             // a stride-2 layer's act.lab is never asked for: a file without it loads
+        TView t = b.lcv3_dw_det(p + ".dw_conv.fold.weight", p + ".dw_conv.fold.bias", h, c.k, c.sh, has_pre ? &pre : nullptr, c.sh == 2 ? nullptr : &post,
+                                level);
+        b.release(h);
+        if (c.sh == 2) ++level;
+        if (c.se) {
+            Builder::GapOut gap = b.lcv3_gap(t, 0);
+            TView gate = b.se_gate(p + ".se.conv1.weight", p + ".se.conv1.bias", p + ".se.conv2.weight", p + ".se.conv2.bias", t, ACT_HSIG, &gap);
+            b.scale(t, gate, 0.f, t);
+            b.release(gate);
+        }
+        h = b.conv(p + ".pw_conv.fold.weight", p + ".pw_conv.fold.bias", "", t, geom(1), ACT_NONE);    // hardswish + act.lab: the consumer's
+        b.release(t);
+        pre = b.affine(p + ".pw_conv.act.lab");
+        has_pre = true;
+        RD_CHECK(h.c == c.cout, "PPLCNetV3: channel chain: " + p);
+        if (tap < 4 && std::string(c.name) == kLcv3DetTaps[tap]) {
+            TView a = b.lcv3_act(h, pre);
+            TView y = b.conv(ins_fold_name(tap) + ".weight", ins_fold_name(tap) + ".bias", "", a, geom(1), ACT_NONE);
+            b.release(a);
+            const std::string s = "neck.ins_conv." + std::to_string(tap) + ".se_block.";
+            TView gate = b.se_gate(s + "conv1.weight", s + "conv1.bias", s + "conv2.weight", s + "conv2.bias", y, ACT_HSIG_PADDLE);
+            b.scale(y, gate, 1.f, y);  // y + y*s (shortcut)
+            b.release(gate);
+            in[tap++] = y;
+        }
+    }
+    b.release(h);
+    RD_CHECK(tap == 4 && level == 5, "PPLCNetV3 det: four taps down to 1/32");
+
+    // RSEFPN
+    for (int i = 2; i >= 0; --i) b.upsample(in[i + 1], in[i], 2, true);          // out4, out3, out2 in place
+    TView cat = b.alloc(B, H / 4, W / 4, 96);
+    for (int i = 0; i < 4; ++i) {
+        const std::string p = "neck.inp_conv." + std::to_string(i);
+        TView z = b.conv(p + ".in_conv.weight", "", "", in[i], geom(3), ACT_NONE);
+        b.release(in[i]);
+        const std::string s = p + ".se_block.";
+        TView gate = b.se_gate(s + "conv1.weight", s + "conv1.bias", s + "conv2.weight", s + "conv2.bias", z, ACT_HSIG_PADDLE);
+        TView slot = b.slice(cat, 24 * (3 - i), 24);                             // cat([p5, p4, p3, p2])
+        if (i == 0) {
+            b.scale(z, gate, 1.f, slot);
+        } else {
+            b.scale(z, gate, 1.f, z);
+            b.upsample(z, slot, 1 << i, false);
+        }
+        b.release(gate);
+        b.release(z);
+    }
+    if (flags & DET_WANT_NECK) {
+        TView o = b.external(2, B, cat.h, cat.w, cat.c);
+        b.to_nchw(cat, o);
+    }
+    // DBHead: binarize = 3x3 + BN + ReLU -> transposed 2x2 + BN + ReLU -> transposed 2x2 to one channel -> sigmoid
+    TView c = b.conv("head.binarize.conv1.weight", "", "head.binarize.conv_bn1", cat, geom(3), ACT_RELU);
+    b.release(cat);
+    if (b.deconv_pair_to_prob("head.binarize.conv2.weight", "head.binarize.conv2.bias", "head.binarize.conv_bn2", "head.binarize.conv3.weight",
+                              "head.binarize.conv3.bias", c, out)) {
+        b.release(c);
+    } else {
+        TView u = b.deconv2x2("head.binarize.conv2.weight", "head.binarize.conv2.bias", "head.binarize.conv_bn2", c, ACT_RELU);
+        b.release(c);
+        b.deconv2x2("head.binarize.conv3.weight", "head.binarize.conv3.bias", "", u, ACT_SIGMOID, &out);
+        b.release(u);
+    }
+}
 
 }  // namespace rd

@@ -203,8 +203,8 @@ void launch_dwconv_lds(const DwParams& p, hipStream_t s);
 bool dwconv_kxk_lds_applies(const DwParams& p);
 void launch_dwconv_kxk_lds(const DwParams& p, hipStream_t s);
 
-// PPLCNetV3 depthwise layer (kernels_lcv3.hip): y = post_s hardswish(dw(x') + bias) + post_b, x' = pre_act ? pre_s hardswish(x) + pre_b : x, k = 3 / 5, strides (1,1), (2,1),
-// (1,2; k = 3), 'same' padding of ZEROS around the pre-affined map; per-image valid widths of the input / output (LineTab columns) or nullptr
+// PPLCNetV3 depthwise layer (kernels_lcv3.hip): y = post_act ? post_s hardswish(dw(x') + bias) + post_b : dw(x') + bias, x' = pre_act ? pre_s hardswish(x) + pre_b : x,
+// k = 3 / 5, strides (1,1), (2,1), (1,2; k = 3), (2,2), 'same' padding of ZEROS around the pre-affined map; per-image valid widths of the input / output (LineTab columns) or nullptr
 struct Lcv3DwParams {
     const float* x; int xld;
     int N, H, W, C;
@@ -215,9 +215,18 @@ struct Lcv3DwParams {
     int pre_act; float pre_s, pre_b;     // the producing pointwise layer's hardswish + act.lab, applied on load inside the map
     float post_s, post_b;   // this layer's act.lab
     const int32_t* line_in; const int32_t* line_out; int line_stride;
+    int post_act;           // 0: convolution + bias only (a stride-2 layer of the detector geometry)
 };
 bool lcv3_dw_shape_ok(int k, int sh, int sw, int c);
 void launch_lcv3_dw(const Lcv3DwParams& p, hipStream_t s);
+// The same layer for the mobile detector's rectangular maps (kernels_lcv3_det.hip): a workgroup stages a 2-D input patch with its halo in
+// LDS - contiguous row segments of 16 channels, the producer's hardswish + affine applied once per element, inside the map only - and
+// computes its output tile from there.  k = 3 / 5, stride (1,1) or (2,2), C % 16 == 0, no line table.
+bool lcv3_dw2d_shape_ok(int k, int sh, int sw, int c);
+bool lcv3_dw2d_launch_ok(const Lcv3DwParams& p);   // shape_ok, no line table, a non-empty output and a grid below 2^31 workgroups
+bool launch_lcv3_dw2d(const Lcv3DwParams& p, hipStream_t s);   // false: not launched (launch_ok says no)
+// y = s hardswish(x) + b, elementwise: the four stage outputs of the detector's backbone, whose consumers are matrix kernels
+void launch_lcv3_act(const float* x, int xld, float* y, int yld, long pixels, int C, float s, float b, hipStream_t st);
 // One PPLCNetV3 block without SE, 3x3 / stride 1, in one launch (kernels_lcv3_block.hip): the depthwise layer as above into an LDS tile, the
 // pointwise layer on the matrix cores from it.  y = out_act ? out_s hardswish(a W^T + pw_b) + out_b : a W^T + pw_b with
 // a = mid_s hardswish(dw(x') + dw_b) + mid_b; split = 1: split-fp16 product guarded by range_flag, 0: fp32 MFMA.

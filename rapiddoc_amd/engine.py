@@ -14,8 +14,9 @@ from . import _lib, weights as W
 
 REC_UNFUSED_CTC, REC_WANT_SOFTMAX, REC_WANT_LOGITS = 1, 2, 4
 REC_WANT_NECK = 64          # ppocrv5_rec_server / ppocrv5_rec_mobile: `full` receives the neck's output [B, T, 120] instead
-DET_WANT_NECK = 1           # ppocrv5_det_server: also hand out the neck's output `fuse` [B, 256, H/4, W/4]
-KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
+DET_WANT_NECK = 1           # ppocrv5_det_server / ppocrv5_det_mobile: also hand out the neck's output `fuse` [B, 256 / 96, H/4, W/4]
+DET_NECK_CHANNELS = {"ppocrv5_det_server": 256, "ppocrv5_det_mobile": 96}
+KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
 
 
 def rec_line_table(widths, first_tokens) -> np.ndarray:
@@ -157,7 +158,8 @@ class RdEngine:
 
     def det_forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, after_launch=None, want_neck: bool = False):
         """Either detector kind.  `out` / `after_launch`: as in `rec_forward` (a caller-owned [B,1,H,W] float32 result tensor; work
-        enqueued behind the launch).  `want_neck` (ppocrv5_det_server): returns (maps, fuse [B,256,H/4,W/4]) through rd_det_forward_ex."""
+        enqueued behind the launch).  `want_neck` (ppocrv5_det_server / ppocrv5_det_mobile): returns (maps, fuse [B,256 / 96,H/4,W/4])
+        through rd_det_forward_ex."""
         x = self._prep(x)
         B, Cc, H, W_ = x.shape
         if out is None:
@@ -165,7 +167,9 @@ class RdEngine:
         elif out.shape != (B, 1, H, W_) or out.dtype != torch.float32 or not out.is_contiguous():
             raise EngineError("det_forward: `out` does not match the forward's shape")
 
-        neck = torch.empty((B, 256, H // 4, W_ // 4), dtype=torch.float32, device=x.device) if want_neck else None
+        if want_neck and self.kind not in DET_NECK_CHANNELS:
+            raise EngineError(f"det_forward: want_neck is offered by {sorted(DET_NECK_CHANNELS)} only")
+        neck = torch.empty((B, DET_NECK_CHANNELS[self.kind], H // 4, W_ // 4), dtype=torch.float32, device=x.device) if want_neck else None
 
         def launch():
             if want_neck:

@@ -109,6 +109,10 @@ DET_ARCH_BY_STEM = {
     "ch_PP-OCRv6_det_small": "ppocrv6_det",
     "ch_PP-OCRv5_det_server": "ppocrv5_det_server",
 }
+# ... and the PP-OCRv5 mobile detector (PPLCNetV3 + RSEFPN + DBHead), the detector the mobile recogniser is shipped with
+DET_ARCH_BY_STEM_V5_MOBILE = {
+    "ch_PP-OCRv5_det_mobile": "ppocrv5_det_mobile",
+}
 
 
 def _state_keys(weights) -> set:
@@ -126,23 +130,27 @@ def _state_keys(weights) -> set:
 def resolve_det_kind(weights: WeightSrc) -> str:
     """Engine kind of a detector's weights, built like `resolve_rec_kind`: a file goes by its stem (an unknown one is an error), a state
     dict or a nameless safetensors image by the head it carries (`head.cbn_layer.last_1.weight`: PFHeadLocal of the v5 server detector;
-    `head.conv_down.convolution.weight`: the v6 DB head)."""
+    `head.conv_down.convolution.weight`: the v6 DB head; `backbone.layer_list.0.weight` with `head.binarize.conv1.weight`: PPLCNetV3's
+    det taps in front of the plain DB head of the v5 mobile detector)."""
     if isinstance(weights, (str, Path)):
         stem = Path(str(weights)).stem
-        if stem not in DET_ARCH_BY_STEM:
-            raise ValueError(f"architecture {stem} is not in the detectors this engine serves {sorted(DET_ARCH_BY_STEM)}")
-        return DET_ARCH_BY_STEM[stem]
+        served = {**DET_ARCH_BY_STEM, **DET_ARCH_BY_STEM_V5_MOBILE}
+        if stem not in served:
+            raise ValueError(f"architecture {stem} is not in the detectors this engine serves {sorted(served)}")
+        return served[stem]
     keys = _state_keys(weights)
     if "head.cbn_layer.last_1.weight" in keys:
         return "ppocrv5_det_server"
     if "head.conv_down.convolution.weight" in keys:
         return "ppocrv6_det"
-    raise ValueError("architecture of the detector weights is not in the detectors this engine serves "
-                     "(neither head.cbn_layer.last_1.weight nor head.conv_down.convolution.weight among the tensors)")
+    if "backbone.layer_list.0.weight" in keys and "head.binarize.conv1.weight" in keys:
+        return "ppocrv5_det_mobile"
+    raise ValueError("architecture of the detector weights is not in the detectors this engine serves (none of head.cbn_layer.last_1.weight, "
+                     "head.conv_down.convolution.weight, backbone.layer_list.0.weight + head.binarize.conv1.weight among the tensors)")
 
 
 class Mi355DetSession(_BaseSession):
-    """PP-OCRv6 small / PP-OCRv5 server det: [B,3,H,W] -> DB probability map [B,1,H,W] (`maps`, ocr/torch.py:183-184).  The kind
+    """PP-OCRv6 small / PP-OCRv5 server / PP-OCRv5 mobile det: [B,3,H,W] -> DB probability map [B,1,H,W] (`maps`, ocr/torch.py:183-184).  The kind
     follows from the weights (`resolve_det_kind`) unless `kind` names it."""
     kind = "ppocrv6_det"
 

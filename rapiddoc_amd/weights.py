@@ -24,6 +24,17 @@ import numpy as np
 Manifest = List[Tuple[str, Tuple[int, ...], str]]
 
 _LCNETV3_BRANCH_GAIN = (("blocks2", 0.65), ("blocks3", 0.65), ("blocks4", 0.6), ("blocks5", 0.6), ("blocks6", 0.7))
+# opt-in extra factors per model kind (synth_state_dict(..., kind=...)), on top of the rules of synth_tensor; (name test, factor)
+_KIND_GAINS = {
+    # PP-OCRv5 mobile detector: the PPLCNetV3 damping above was set for the recogniser's 48-row maps; at page size the reference
+    # saturates (features 1700, fuse 7900, `maps` nearly binary).  These keep the stage features O(2-25) and spread the shrink logit
+    "ppocrv5_det_mobile": (
+        (lambda n: n.startswith("backbone.blocks5.") and n.endswith(".conv.weight"), 0.85),
+        (lambda n: n.startswith("backbone.blocks6.") and n.endswith(".conv.weight"), 0.8),
+        (lambda n: n.startswith("backbone.layer_list.") and n.endswith(".weight"), 0.5),
+        (lambda n: n == "head.binarize.conv3.weight", 3.0),
+    ),
+}
 _NORM_TOKENS = (".normalization.", ".norm.", ".bn.", "layer_norm", ".norm1.", ".norm2.")
 
 
@@ -87,8 +98,19 @@ def synth_tensor(name: str, shape: Tuple[int, ...], dtype: str, seed: int) -> np
     return rng.normal(0.0, 0.05, shape).astype(np.float32)
 
 
-def synth_state_dict(manifest: Manifest, seed: int = 0) -> Dict[str, np.ndarray]:
-    return {name: synth_tensor(name, shape, dtype, seed) for name, shape, dtype in manifest}
+def synth_state_dict(manifest: Manifest, seed: int = 0, kind: str = None) -> Dict[str, np.ndarray]:
+    """`kind`: opt-in gains of one model kind (_KIND_GAINS); without it every tensor is synth_tensor's, whatever the manifest."""
+    state = {name: synth_tensor(name, shape, dtype, seed) for name, shape, dtype in manifest}
+    if kind is not None:
+        if kind not in _KIND_GAINS:
+            raise ValueError(f"no synthetic-weight gains are defined for kind {kind!r}")
+        for name, arr in state.items():
+            if arr.dtype != np.float32 or arr.ndim < 2:
+                continue
+            for applies, f in _KIND_GAINS[kind]:
+                if applies(name):
+                    state[name] = (arr * np.float32(f)).astype(np.float32)
+    return state
 
 
 def checksum(state: Dict[str, np.ndarray]) -> float:
