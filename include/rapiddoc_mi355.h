@@ -38,13 +38,15 @@ typedef struct rd_handle rd_handle;
 #define RD_REC_UNFUSED_CTC 1  /* materialise logits, then row statistics (validation path)              */
 #define RD_REC_WANT_SOFTMAX 2 /* also write softmax probabilities [B,T,C] (the reference session output) */
 #define RD_REC_WANT_LOGITS 4  /* also write raw logits [B,T,C]                                          */
-#define RD_REC_WANT_NECK 64   /* "ppocrv5_rec_server" / "ppocrv5_rec_mobile" only, instead of the two above: full_btc_dev receives the neck's output
-                               * [B,T,120] (the CTC classifier's input); idx / prob come from the fused head as with flags 0 */
+#define RD_REC_WANT_NECK 64   /* "ppocrv5_rec_server" / "ppocrv5_rec_mobile" / "ppocr_rec_mv1e" only, instead of the two above: full_btc_dev receives the neck's output
+                               * [B,T,120] ("ppocr_rec_mv1e": [B,T,64]) (the CTC classifier's input); idx / prob come from the fused head as with flags 0 */
 
 const char* rd_version(void);
 /* model_kind: "ppocrv6_det" | "ppocrv5_det_server" (PPHGNetV2-B4 + LKPAN + PFHeadLocal; rd_det_forward / rd_det_forward_ex) |
  * "ppocrv5_det_mobile" (PPLCNetV3 scale 0.75 + RSEFPN + DBHead; the same two calls) | "ppocrv6_rec" | "ppocrv5_rec_server" (PPHGNetV2-B4 + SVTR neck + CTC; every rd_rec_* call except
- * rd_rec_backbone_forward_lines) | "ppocrv5_rec_mobile" (PPLCNetV3 scale 0.95 + the same SVTR neck + CTC; every rd_rec_* call) | "pphgnetv2_b4" | "pphgnetv2_b6_formula" | "ppformulanet_head".  NULL on failure -> rd_create_error(). */
+ * rd_rec_backbone_forward_lines) | "ppocrv5_rec_mobile" (PPLCNetV3 scale 0.95 + the same SVTR neck + CTC; every rd_rec_* call) | "ppocr_rec_mv1e" (MobileNetV1Enhance scale 0.5 + SVTR neck dims 64 + CTC:
+ * the ten multilingual PP-OCRv3 / v4 mobile files latin_ / cyrillic_ / chinese_cht_PP-OCRv3_rec_mobile, arabic_ / korean_ / japan_ / ta_ / te_ / ka_ /
+ * devanagari_PP-OCRv4_rec_mobile, which differ in their class count only; every rd_rec_* call) | "pphgnetv2_b4" | "pphgnetv2_b6_formula" | "ppformulanet_head".  NULL on failure -> rd_create_error(). */
 rd_handle* rd_create(int device_id, const char* model_kind);
 const char* rd_create_error(void);
 void rd_destroy(rd_handle* h);
@@ -94,7 +96,7 @@ int rd_rec_tail_forward(rd_handle* h, const float* tokens_dev, int n_tokens, int
  * beyond), line_tab_dev = int32 [B][4] = (w_b, (w_b - 1) / 2 + 1, ((w_b - 1) / 2) / 2 + 1, first token of the line in tokens_dev);
  * line b writes rd_rec_seq_len(w_b) tokens there.  Results per line == rd_rec_backbone_forward on [1,3,48,w_b].
  * rd_query_workspace(h, B, 0, W, RD_REC_STAGE_BACKBONE | RD_REC_LINE_WIDTHS) sizes the workspace.
- * Served by "ppocrv6_rec" and "ppocrv5_rec_mobile"; "ppocrv5_rec_server" returns an error that says so. */
+ * Served by "ppocrv6_rec", "ppocrv5_rec_mobile" and "ppocr_rec_mv1e"; "ppocrv5_rec_server" returns an error that says so. */
 #define RD_REC_LINE_WIDTHS 32
 int rd_rec_backbone_forward_lines(rd_handle* h, const float* x_nchw_dev, int B, int W, const int32_t* line_tab_dev, float* tokens_dev,
                                   void* ws_dev, size_t ws_bytes, void* stream);

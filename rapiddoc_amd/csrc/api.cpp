@@ -47,7 +47,7 @@ static int guarded(rd_handle* h, F&& f) {
 }
 
 // the recogniser kinds share one C surface (rd_rec_*)
-static bool is_rec_kind(const std::string& k) { return k == "ppocrv6_rec" || k == "ppocrv5_rec_server" || k == "ppocrv5_rec_mobile"; }
+static bool is_rec_kind(const std::string& k) { return k == "ppocrv6_rec" || k == "ppocrv5_rec_server" || k == "ppocrv5_rec_mobile" || k == "ppocr_rec_mv1e"; }
 
 extern "C" {
 
@@ -133,7 +133,7 @@ int rd_det_forward_ex(rd_handle* h, const float* x, int B, int H, int W, float* 
 int rd_rec_forward(rd_handle* h, const float* x, int B, int W, int32_t* idx, float* prob, float* full, int flags, void* ws,
                    size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server / ppocrv5_rec_mobile) model");
+        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server / ppocrv5_rec_mobile / ppocr_rec_mv1e) model");
         RD_CHECK(x && idx && prob && B > 0, "null input/output");
         if (flags & (RD_REC_WANT_SOFTMAX | RD_REC_WANT_LOGITS | RD_REC_WANT_NECK)) RD_CHECK(full, "full_btc_dev is NULL");
         RD_CHECK(!((flags & RD_REC_WANT_SOFTMAX) && (flags & RD_REC_WANT_LOGITS)), "choose softmax OR logits");
@@ -144,7 +144,7 @@ int rd_rec_forward(rd_handle* h, const float* x, int B, int W, int32_t* idx, flo
 int rd_rec_token_dim(rd_handle* h) { return (h && h->eng && is_rec_kind(h->eng->kind())) ? h->eng->rec_token_dim() : -1; }
 int rd_rec_backbone_forward(rd_handle* h, const float* x, int B, int W, float* tokens, void* ws, size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server / ppocrv5_rec_mobile) model");
+        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server / ppocrv5_rec_mobile / ppocr_rec_mv1e) model");
         RD_CHECK(x && tokens && B > 0, "null input/output");
         h->eng->run(B, 48, W, rd::REC_STAGE_BACKBONE, {(void*)x, (void*)tokens}, ws, ws_bytes, (hipStream_t)stream);
     });
@@ -155,8 +155,8 @@ int rd_rec_backbone_forward_lines(rd_handle* h, const float* x, int B, int W, co
         RD_CHECK(!(h->eng && h->eng->kind() == "ppocrv5_rec_server"),
                  "rd_rec_backbone_forward_lines: per-line widths inside one backbone launch are out of scope for ppocrv5_rec_server "
                  "(run the backbone stage once per padded width)");
-        RD_CHECK(h->eng && (h->eng->kind() == "ppocrv6_rec" || h->eng->kind() == "ppocrv5_rec_mobile"),
-                 "handle is not a ppocrv6_rec / ppocrv5_rec_mobile model");
+        RD_CHECK(h->eng && (h->eng->kind() == "ppocrv6_rec" || h->eng->kind() == "ppocrv5_rec_mobile" || h->eng->kind() == "ppocr_rec_mv1e"),
+                 "handle is not a ppocrv6_rec / ppocrv5_rec_mobile / ppocr_rec_mv1e model");
         RD_CHECK(x && tokens && line_tab && B > 0, "null input/output");
         h->eng->run(B, 48, W, rd::REC_STAGE_BACKBONE | rd::REC_LINE_WIDTHS, {(void*)x, (void*)tokens, (void*)line_tab}, ws, ws_bytes,
                     (hipStream_t)stream);
@@ -165,7 +165,7 @@ int rd_rec_backbone_forward_lines(rd_handle* h, const float* x, int B, int W, co
 int rd_rec_tail_forward(rd_handle* h, const float* tokens, int n_tokens, int n_lines, int max_tokens, const int32_t* seg,
                         const int32_t* tokinfo, int32_t* idx, float* prob, void* ws, size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server / ppocrv5_rec_mobile) model");
+        RD_CHECK(h->eng && is_rec_kind(h->eng->kind()), "handle is not a recogniser (ppocrv6_rec / ppocrv5_rec_server / ppocrv5_rec_mobile / ppocr_rec_mv1e) model");
         RD_CHECK(tokens && seg && tokinfo && idx && prob && n_tokens > 0 && n_lines > 0 && max_tokens > 0, "null input/output");
         h->eng->run(n_lines, max_tokens, n_tokens, rd::REC_STAGE_TAIL,
                     {(void*)tokens, (void*)idx, (void*)prob, nullptr, (void*)seg, (void*)tokinfo}, ws, ws_bytes, (hipStream_t)stream);
@@ -791,6 +791,41 @@ float rd_debug_lcv3_dw(int N, int H, int W, int C, int K, int SH, int SW, int pr
     (void)hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return iters > 0 ? ms / iters : 0.f;
+}
+
+// developer entry: one 5x5 depthwise layer of the recogniser geometry through launch_dw5_strip (kernels_mv1e.hip; x NHWC fp32 [N][H][W][xld],
+// w [25][C], bias [C], y [N][OH][OW][yld], OH = (H - 1) / SH + 1, OW = (W - 1) / SW + 1; aff = {pre_s, pre_b, post_s, post_b}; pre_act:
+// hardswish + (pre_s, pre_b) on load; post_act 0: convolution + bias only; line_in / line_out int32 [N] valid widths or null).  Returns ms
+// per launch, < 0: geometry not served (dw5_strip_launch_ok).
+float rd_debug_dw5_strip(int N, int H, int W, int C, int SH, int SW, int pre_act, int post_act, int xld, int yld, int iters, const float* aff, float* x,
+                         float* w, float* bias, float* y, const int32_t* line_in, const int32_t* line_out) {
+    if (!aff || SH < 1 || SW < 1) return -1.f;
+    rd::Lcv3DwParams p{};
+    p.x = x; p.xld = xld; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = yld;
+    p.K = 5; p.SH = SH; p.SW = SW;
+    p.OH = (H - 1) / SH + 1; p.OW = (W - 1) / SW + 1;
+    p.pre_act = pre_act; p.pre_s = aff[0]; p.pre_b = aff[1]; p.post_s = aff[2]; p.post_b = aff[3]; p.post_act = post_act;
+    p.line_in = line_in; p.line_out = line_out; p.line_stride = 1;
+    if (!rd::dw5_strip_launch_ok(p)) return -1.f;
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    (void)rd::launch_dw5_strip(p, nullptr);
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) (void)rd::launch_dw5_strip(p, nullptr);
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return iters > 0 ? ms / iters : 0.f;
+}
+
+// developer entry: MobileNetV1Enhance's final pooling through launch_mv1e_pool (x NHWC [N][H][W][C], H >= 2; y [N][W / 2][C], or with
+// line_tab int32 [N][4] the compact token rows it names).  Returns 0, < 0: geometry not served.
+int rd_debug_mv1e_pool(int N, int H, int W, int C, float* x, float* y, const int32_t* line_tab) {
+    if (N < 1 || H < 2 || W < 2 || C < 4 || C % 4 != 0) return -1;
+    rd::launch_mv1e_pool(x, C, y, C, N, H, W, C, nullptr, line_tab);
+    return hipStreamSynchronize(nullptr) == hipSuccess ? 0 : -2;
 }
 
 // developer entry, host only (no device is touched): the load-time derived tensor `name` of "ppocrv5_det_mobile" - a folded

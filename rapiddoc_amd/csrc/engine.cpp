@@ -1182,16 +1182,31 @@ bool Builder::lcv3_dw_common(const std::string& wname, const std::string& bname,
     return true;
 }
 
+// Per-geometry default of MobileNetV1Enhance's 5x5 depthwise route, from the same-run alternating A/B of tools/mb_rec_mv1e.py on the same
+// operands, 64 lines at w2 = 544 (profiles/mb_rec_mv1e.txt; docs/notebook/rec_mv1e.md).  Direct / strip ms (median of 7 rounds of 20 launches;
+// every round of the strip kernel below every round of the direct one):
+//   C 256, 6 rows, s (1,1)   0.236 / 0.148      C 256, 6 rows, s (2,1)   0.133 / 0.113      C 512, 3 rows, s (1,2)   0.160 / 0.131
+// A (stride, C) that was not measured stays on the direct kernel.
+bool mv1e_dw_strip_default(int sh, int sw, int c) {
+    return (sh == 1 && sw == 1 && c == 256) || (sh == 2 && sw == 1 && c == 256) || (sh == 1 && sw == 2 && c == 512);
+}
+
 TView Builder::lcv3_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre, Affine post,
-                       int lt_in, int lt_out) {
+                       int lt_in, int lt_out, int strip) {
     TView y{};
     Lcv3DwParams p{};
     OpRecord r;
     if (!lcv3_dw_common(wname, bname, x, k, sh, sw, pre, &post, &y, &p, &r)) return y;
-    r.cfg = "s" + std::to_string(sh) + std::to_string(sw) + (has_lt_ ? "/lines" : "");
+    bool staged = false;      // the route is a property of the layer's geometry, never of the batch or the line widths
+    if (strip && dw5_strip_launch_ok(p)) {
+        const char* sv = std::getenv(strip == 1 ? "RD_LCV3_DW_STRIP" : "RD_MV1E_DW_STRIP");
+        const bool forced = sv && (sv[0] == '0' || sv[0] == '1');
+        staged = forced ? sv[0] == '1' : strip == 2 && mv1e_dw_strip_default(sh, sw, p.C);
+    }
+    r.cfg = "s" + std::to_string(sh) + std::to_string(sw) + (staged ? "/strip" : "") + (has_lt_ ? "/lines" : "");
     const TView xv = x, yv = y, ltv = lt_;
     const bool has_lt = has_lt_;
-    r.run = [p, xv, yv, ltv, has_lt, lt_in, lt_out](const Plan& pl, const RunCtx& cx) {
+    r.run = [p, xv, yv, ltv, has_lt, lt_in, lt_out, staged](const Plan& pl, const RunCtx& cx) {
         Lcv3DwParams q = p;
         q.x = pl.vptr(xv, cx);
         q.y = pl.vptr(yv, cx);
@@ -1201,7 +1216,29 @@ TView Builder::lcv3_dw(const std::string& wname, const std::string& bname, const
             q.line_out = lt + lt_out;
             q.line_stride = kLineTabStride;
         }
-        launch_lcv3_dw(q, cx.stream);
+        if (staged) (void)launch_dw5_strip(q, cx.stream);      // (servable: checked above)
+        else launch_lcv3_dw(q, cx.stream);
+    };
+    emit(std::move(r));
+    return y;
+}
+
+TView Builder::mv1e_pool(const TView& x, const TView* out) {
+    RD_CHECK(x.h == 3 && x.w >= 2 && x.c % 4 == 0, "mv1e pool: a 3-row map");
+    const int ow = x.w / 2;
+    TView y = out ? *out : alloc(x.n, 1, ow, x.c);
+    RD_CHECK(y.n == x.n && y.h == 1 && y.w == ow && y.c == x.c, "mv1e pool: output view mismatch");
+    if (!planning()) return y;
+    RD_CHECK(plan_->ld(x) % 4 == 0 && x.coff % 4 == 0 && plan_->ld(y) % 4 == 0 && y.coff % 4 == 0, "mv1e pool: 16-byte aligned pixels");
+    OpRecord r;
+    r.name = "hswish+avgpool2x2";
+    r.kind = "pool";
+    r.bytes = 4.0 * (2.0 * x.n * x.w * x.c + y.pixels() * y.c);
+    const TView xv = x, yv = y, ltv = lt_;
+    const bool has_lt = has_lt_;
+    r.run = [xv, yv, ltv, has_lt](const Plan& pl, const RunCtx& c) {
+        launch_mv1e_pool(pl.vptr(xv, c), pl.ld(xv), pl.vptr(yv, c), pl.ld(yv), xv.n, xv.h, xv.w, xv.c, c.stream,
+                         has_lt ? reinterpret_cast<const int32_t*>(pl.vptr(ltv, c)) : nullptr);
     };
     emit(std::move(r));
     return y;
@@ -1399,7 +1436,7 @@ TView Builder::avgpool3x2(const TView& x, const TView* out) {
 }
 
 TView Builder::se_gate(const std::string& w1n, const std::string& b1n, const std::string& w2n, const std::string& b2n,
-                       const TView& x, int gate_act, const GapOut* pre) {
+                       const TView& x, int gate_act, const GapOut* pre, int lt_col) {
     const HostTensor& w1 = ws_->get(w1n);
     const int cr = (int)w1.shape[0], c = (int)w1.shape[1];
     RD_CHECK(c == x.c && c % 4 == 0, "SE channel mismatch: " + w1n);
@@ -1445,12 +1482,12 @@ TView Builder::se_gate(const std::string& w1n, const std::string& b1n, const std
         const bool has_lt = has_lt_;
         const TView ltv = lt_;
         p.H = x.h;
-        r.run = [p, pv, gv, has_lt, ltv](const Plan& pl, const RunCtx& cx) {
+        r.run = [p, pv, gv, has_lt, ltv, lt_col](const Plan& pl, const RunCtx& cx) {
             SeFcParams q = p;
             q.partial = pl.vptr(pv, cx);
             q.scale = pl.vptr(gv, cx);
             if (has_lt) {
-                q.line_w = reinterpret_cast<const int32_t*>(pl.vptr(ltv, cx)) + 2;
+                q.line_w = reinterpret_cast<const int32_t*>(pl.vptr(ltv, cx)) + lt_col;
                 q.line_w_stride = kLineTabStride;
             }
             launch_se_fc(q, cx.stream);
@@ -1699,7 +1736,7 @@ Engine::Engine(int device, const std::string& kind) : device_(device), kind_(kin
         RD_CHECK(v == "auto" || v == "fp32" || v == "h3", "RD_PRECISION must be auto, fp32 or h3");
         precision_ = v == "h3" ? PREC_H3 : v == "fp32" ? PREC_FP32 : PREC_AUTO;
     }
-    RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "ppocrv5_rec_mobile" || kind == "ppocrv5_det_server" ||
+    RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "ppocrv5_rec_mobile" || kind == "ppocr_rec_mv1e" || kind == "ppocrv5_det_server" ||
                  kind == "ppocrv5_det_mobile" ||
                  kind == "pphgnetv2_b4" || kind == "pphgnetv2_b6_formula",
              "unknown model kind '" + kind + "'");
@@ -1749,6 +1786,7 @@ void Engine::build(Builder& b, int B, int H, int W, int flags) {
     else if (kind_ == "ppocrv6_rec") build_ppocrv6_rec(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_rec_server") build_ppocrv5_rec_server(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_rec_mobile") build_ppocrv5_rec_mobile(b, B, H, W, flags);
+    else if (kind_ == "ppocr_rec_mv1e") build_ppocr_rec_mv1e(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_det_server") build_ppocrv5_det_server(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_det_mobile") build_ppocrv5_det_mobile(b, B, H, W, flags);
     else if (kind_ == "pphgnetv2_b6_formula") build_pphgnetv2_b6_formula(b, B, H, W, flags);
@@ -1766,6 +1804,10 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
         n_classes_ = (int)store_.get("head.ctc_head.fc.weight").shape[0];
         rec_token_dim_ = (int)store_.get("head.ctc_encoder.encoder.conv1.conv.weight").shape[1];
         if (kind_ == "ppocrv5_rec_mobile") derive_ppocrv5_rec_mobile_weights(store_);
+    } else if (kind_ == "ppocr_rec_mv1e") {
+        n_classes_ = (int)store_.get("head.fc.weight").shape[0];
+        rec_token_dim_ = (int)store_.get("neck.encoder.conv1.conv.weight").shape[1];
+        derive_ppocr_rec_mv1e_weights(store_);
     } else if (kind_ == "ppocrv5_det_server") {
         derive_ppocrv5_det_server_weights(store_);
     } else if (kind_ == "ppocrv5_det_mobile") {
@@ -1780,7 +1822,7 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
     RD_HIP(hipHostGetDevicePointer((void**)&range_flag_, (void*)range_flag_host_, 0));
     Builder b(Mode::PREPARE, &store_, &params_, &dummy, h3_prepared_, true);
     // smallest legal geometry; only weight names/shapes matter in PREPARE mode
-    if (kind_ == "ppocrv6_rec" || kind_ == "ppocrv5_rec_server" || kind_ == "ppocrv5_rec_mobile") build(b, 1, 48, 64, 0), build(b, 1, 48, 64, REC_UNFUSED_CTC);
+    if (kind_ == "ppocrv6_rec" || kind_ == "ppocrv5_rec_server" || kind_ == "ppocrv5_rec_mobile" || kind_ == "ppocr_rec_mv1e") build(b, 1, 48, 64, 0), build(b, 1, 48, 64, REC_UNFUSED_CTC);
     else build(b, 1, 64, 64, 0);
     params_.upload();
     loaded_ = true;

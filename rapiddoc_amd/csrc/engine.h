@@ -215,8 +215,13 @@ class Builder {
     // input / output width under a line table
     struct Affine { float s = 1.f, b = 0.f; };
     Affine affine(const std::string& prefix) const;      // prefix.scale / prefix.bias
+    // `strip`: route of a 5x5 layer that the LDS-staged strip kernel serves (kernels_mv1e.hip, dw5_strip_launch_ok).  0: the direct kernel;
+    // 1: the strip kernel under RD_LCV3_DW_STRIP=1 only (opt-in, ppocrv5_rec_mobile); 2: the per-geometry default mv1e_dw_strip_default,
+    // RD_MV1E_DW_STRIP=0|1 forcing one route for every layer the strip kernel serves (ppocr_rec_mv1e).  Read per plan
     TView lcv3_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre, Affine post, int lt_in,
-                  int lt_out);
+                  int lt_out, int strip = 0);
+    // MobileNetV1Enhance's end (kernels_mv1e.hip): the deferred hardswish, AvgPool2d(2, 2) over rows 0-1 of the 3-row map
+    TView mv1e_pool(const TView& x, const TView* out = nullptr);
     // the detector geometry: `post` null = convolution + bias only (a stride-2 layer); `level` = log2 of the input map's reduction of the
     // page (1 = H/2 ... 5 = H/32), which with (k, stride, C) picks the direct or the LDS-staged kernel (lcv3_dw2d_default; RD_LCV3_DW2D=0|1
     // forces one route for every layer the staged kernel serves)
@@ -237,7 +242,7 @@ class Builder {
     TView avgpool3x2(const TView& x, const TView* out = nullptr);
     // squeeze-excite gate s[n][c]; `w1/b1/w2/b2` full tensor names
     TView se_gate(const std::string& w1, const std::string& b1, const std::string& w2, const std::string& b2,
-                  const TView& x, int gate_act, const GapOut* pre = nullptr);
+                  const TView& x, int gate_act, const GapOut* pre = nullptr, int lt_col = 2);   // lt_col: LineTab column of x's valid width
     void scale(const TView& x, const TView& gate, float alpha, const TView& out);
     void upsample(const TView& x, const TView& out, int f, bool accumulate);
     TView layernorm(const std::string& prefix, const TView& x, float eps);
@@ -360,6 +365,13 @@ void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags);
 void build_ppocrv5_rec_mobile(Builder& b, int B, int H, int W, int flags);
 // tensors build_ppocrv5_rec_mobile reads that are not in the file: every LearnableRepLayer folded into one convolution + bias
 void derive_ppocrv5_rec_mobile_weights(WeightStore& ws);
+// Multilingual PP-OCRv3 / v4 mobile recognisers (MobileNetV1Enhance scale 0.5 + SVTR neck dims 64 + CTC; ten weight files, one graph):
+// same externals, flags and stages; REC_LINE_WIDTHS is served
+void build_ppocr_rec_mv1e(Builder& b, int B, int H, int W, int flags);
+// tensors build_ppocr_rec_mv1e reads that are not in the file: every Conv + BatchNorm of the backbone's blocks folded into weight + bias
+void derive_ppocr_rec_mv1e_weights(WeightStore& ws);
+// default route of one 5x5 depthwise layer of that backbone: true = the LDS-staged strip kernel (from the per-geometry A/B of tools/mb_rec_mv1e.py)
+bool mv1e_dw_strip_default(int sh, int sw, int c);
 // PP-OCRv5 server detector (PPHGNetV2-B4 + LKPAN with IntraCL + PFHeadLocal): ext[0] = x NCHW, ext[1] = maps [B,1,H,W];
 // DET_WANT_NECK: ext[2] = the neck output `fuse` NCHW [B,256,H/4,W/4]
 enum DetFlags : int { DET_WANT_NECK = 1 };

@@ -6,7 +6,8 @@
 // hardswish and `act.lab` are applied here, on load, to the elements INSIDE the map - x' = pre_s hardswish(x) + pre_b (pre_act) - while the
 // convolution's padding stays zero, as in the reference, where activation and affine precede the padding.
 // Per-line widths (rd_kernels.h LineTab): input columns >= line_in[n] are that padding too (whatever the shared tensor holds there),
-// output columns >= line_out[n] are written as zeros.  Strides (1,1), (2,1) and (1,2); 3x3 and 5x5.
+// output columns >= line_out[n] are written as zeros.  Strides (1,1), (2,1) and (1,2); 3x3 and 5x5 (5x5 at (1,2): MobileNetV1Enhance's last
+// block, build_ppocr_rec_mv1e, whose LDS-staged alternative to this kernel is kernels_mv1e.hip).
 // The mobile DETECTOR (build_ppocrv5_det_mobile) adds stride (2,2) for both kernel sizes and post_act = 0: the reference skips the
 // activation of a layer whose stride is the integer 2, so such a layer writes dw_kxk(x') + bias and nothing else.  The detector's
 // LDS-staged alternative to this kernel is kernels_lcv3_det.hip.
@@ -78,7 +79,7 @@ static inline int lcv3_grid(long total) {
 }
 
 bool lcv3_dw_shape_ok(int k, int sh, int sw, int c) {
-    return (k == 3 || k == 5) && c % 4 == 0 && ((sh == 1 && sw == 1) || (sh == 2 && sw == 1) || (sh == 1 && sw == 2 && k == 3) || (sh == 2 && sw == 2));
+    return (k == 3 || k == 5) && c % 4 == 0 && ((sh == 1 && sw == 1) || (sh == 2 && sw == 1) || (sh == 1 && sw == 2) || (sh == 2 && sw == 2));
 }
 
 void launch_lcv3_dw(const Lcv3DwParams& p, hipStream_t s) {

@@ -534,8 +534,9 @@ void build_pphgnetv2_b6_formula(Builder& b, int B, int H, int W, int flags) {
     });
 }
 
-// the PPLCNetV3 backbone of the mobile recogniser (below): image -> pooled tokens
+// the PPLCNetV3 backbone of the mobile recogniser and MobileNetV1Enhance of the multilingual ones (below): image -> pooled tokens
 static TView lcnetv3_rec(Builder& b, const TView& x, const TView* tokens_out);
+static TView mv1e_rec(Builder& b, const TView& x, const TView* tokens_out);
 static int rec_tokens_of_width(int W) {      // rd_rec_seq_len
     const int w2 = (W - 1) / 2 + 1, w4 = (w2 - 1) / 2 + 1;
     return w4 / 2;
@@ -545,7 +546,8 @@ static int rec_tokens_of_width(int W) {      // rd_rec_seq_len
 // PP-OCRv5 server rec (arch_config.yaml ch_PP-OCRv5_rec_server): PPHGNetV2_B4(text_rec=True) -> EncoderWithSVTR (necks/rnn.py:90-200,
 // dims 120, depth 2, kernel [1, 3], use_guide) -> CTCHead Linear(120, classes).  Externals and the two-stage form as build_ppocrv6_rec
 // (tokens are [.][2048]); per-line widths inside one backbone launch (REC_LINE_WIDTHS) are not offered for this kind.
-// `mobile`: the same neck and head behind the PPLCNetV3 backbone (build_ppocrv5_rec_mobile below), REC_LINE_WIDTHS served.
+// RecSvtrCfg: the same neck and head behind another backbone - PPLCNetV3 (build_ppocrv5_rec_mobile below) or MobileNetV1Enhance
+// (build_ppocr_rec_mv1e, whose neck lives under `neck.encoder` and whose classifier is `head.fc`) - both with REC_LINE_WIDTHS served.
 // ---------------------------------------------------------------------------------------------------
 // the server kind's backbone: image -> pooled tokens [B][1][w4 / 2][2048] (external 1 in the backbone stage)
 static TView pphgnetv2_rec_tokens(Builder& b, const TView& x, int B, int Cb, bool backbone_only) {
@@ -564,23 +566,27 @@ static TView pphgnetv2_rec_tokens(Builder& b, const TView& x, int B, int Cb, boo
     return h;
 }
 
-// the mobile kind's: the line table (REC_LINE_WIDTHS, backbone stage only) is external 2
-static TView lcnetv3_rec_tokens(Builder& b, const TView& x, int B, int W, int Cb, int flags) {
+enum RecBackbone { REC_BB_PPHGNETV2, REC_BB_LCNETV3, REC_BB_MV1E };
+struct RecSvtrCfg { const char* neck; const char* fc; RecBackbone backbone; };   // neck / classifier tensor prefixes
+
+// the mobile kinds': the line table (REC_LINE_WIDTHS, backbone stage only) is external 2
+static TView lcnetv3_rec_tokens(Builder& b, const TView& x, int B, int W, int Cb, int flags, bool mv1e) {
     const bool backbone_only = (flags & REC_STAGE_BACKBONE) != 0;
     if (flags & REC_LINE_WIDTHS) {
         RD_CHECK(backbone_only, "rec: per-line widths belong to the backbone stage");
         b.set_line_table(b.external(2, B, 1, 1, kLineTabStride));
     }
-    if (!backbone_only) return lcnetv3_rec(b, x, nullptr);
+    if (!backbone_only) return mv1e ? mv1e_rec(b, x, nullptr) : lcnetv3_rec(b, x, nullptr);
     TView out = b.external(1, B, 1, rec_tokens_of_width(W), Cb);
-    return lcnetv3_rec(b, x, &out);
+    return mv1e ? mv1e_rec(b, x, &out) : lcnetv3_rec(b, x, &out);
 }
 
-static void build_ppocrv5_rec(Builder& b, int B, int H, int W, int flags, bool mobile) {
+static void build_ppocrv5_rec(Builder& b, int B, int H, int W, int flags, const RecSvtrCfg& cfg) {
+    const bool mobile = cfg.backbone != REC_BB_PPHGNETV2;
     const bool tail_only = (flags & REC_STAGE_TAIL) != 0, backbone_only = (flags & REC_STAGE_BACKBONE) != 0;
     RD_CHECK(!(tail_only && backbone_only), "rec: choose one stage");
     RD_CHECK(mobile || !(flags & REC_LINE_WIDTHS), "ppocrv5_rec_server: per-line widths inside one backbone launch are out of scope for this kind");
-    const std::string e = "head.ctc_encoder.encoder";
+    const std::string e = cfg.neck;
     auto cw = [&](const char* n) { return e + "." + n + ".conv.weight"; };
     auto cbn = [&](const char* n) { return e + "." + n + ".norm"; };
     const int Cb = b.weight_dim(cw("conv1"), 1);
@@ -598,7 +604,7 @@ static void build_ppocrv5_rec(Builder& b, int B, int H, int W, int flags, bool m
         RD_CHECK(W >= 16, "rec input width must be >= 16");
         TView x = b.external(0, B, H, W, 3);
         if (backbone_only) RD_CHECK((flags & ~(REC_STAGE_BACKBONE | REC_LINE_WIDTHS)) == 0, "rec backbone stage takes no other flag");
-        h = mobile ? lcnetv3_rec_tokens(b, x, B, W, Cb, flags) : pphgnetv2_rec_tokens(b, x, B, Cb, backbone_only);
+        h = mobile ? lcnetv3_rec_tokens(b, x, B, W, Cb, flags, cfg.backbone == REC_BB_MV1E) : pphgnetv2_rec_tokens(b, x, B, Cb, backbone_only);
         if (backbone_only) return;
         T = h.w;
         RD_CHECK(h.h == 1, "rec: pooled height");
@@ -644,7 +650,7 @@ static void build_ppocrv5_rec(Builder& b, int B, int H, int W, int flags, bool m
         TView o = b.external(3, B, 1, T, seq.c);
         b.copy(seq, o);
     }
-    const std::string fc = "head.ctc_head.fc";
+    const std::string fc = cfg.fc;
     const int ncls = b.weight_dim(fc + ".weight", 0);
     TView idx = tail_only ? b.external(1, 1, 1, W, 1) : b.external(1, B, 1, T, 1);
     TView prob = tail_only ? b.external(2, 1, 1, W, 1) : b.external(2, B, 1, T, 1);
@@ -670,7 +676,10 @@ static void build_ppocrv5_rec(Builder& b, int B, int H, int W, int flags, bool m
     b.release(seq);
 }
 
-void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags) { build_ppocrv5_rec(b, B, H, W, flags, false); }
+static const RecSvtrCfg kRecV5Server = {"head.ctc_encoder.encoder", "head.ctc_head.fc", REC_BB_PPHGNETV2};
+static const RecSvtrCfg kRecV5Mobile = {"head.ctc_encoder.encoder", "head.ctc_head.fc", REC_BB_LCNETV3};
+static const RecSvtrCfg kRecMv1e = {"neck.encoder", "head.fc", REC_BB_MV1E};
+void build_ppocrv5_rec_server(Builder& b, int B, int H, int W, int flags) { build_ppocrv5_rec(b, B, H, W, flags, kRecV5Server); }
 
 // ---------------------------------------------------------------------------------------------------
 // PP-OCRv5 mobile rec (arch_config.yaml ch_PP-OCRv5_rec_mobile): PPLCNetV3(scale 0.95, rec geometry) -> the server kind's neck and
@@ -779,8 +788,10 @@ static TView lcnetv3_rec(Builder& b, const TView& x, const TView* tokens_out) {
             has_pre = true;
             continue;
         }
+        // (strip 1: a 5x5 layer may take the LDS-staged strip kernel of kernels_mv1e.hip under RD_LCV3_DW_STRIP=1 - opt-in, measured in
+        // docs/notebook/rec_mv1e.md; the default route and its bits are the direct kernel's)
         TView t = b.lcv3_dw(p + ".dw_conv.fold.weight", p + ".dw_conv.fold.bias", h, c.k, c.sh, c.sw, has_pre ? &pre : nullptr,
-                            b.affine(p + ".dw_conv.act.lab"), lt_col, lt_out);
+                            b.affine(p + ".dw_conv.act.lab"), lt_col, lt_out, c.k == 5 ? 1 : 0);
         b.release(h);
         lt_col = lt_out;
         if (c.se) {
@@ -800,7 +811,88 @@ static TView lcnetv3_rec(Builder& b, const TView& x, const TView* tokens_out) {
     return tok;
 }
 
-void build_ppocrv5_rec_mobile(Builder& b, int B, int H, int W, int flags) { build_ppocrv5_rec(b, B, H, W, flags, true); }
+void build_ppocrv5_rec_mobile(Builder& b, int B, int H, int W, int flags) { build_ppocrv5_rec(b, B, H, W, flags, kRecV5Mobile); }
+
+// ---------------------------------------------------------------------------------------------------
+// Multilingual PP-OCRv3 / v4 mobile rec (arch_config.yaml latin_ / cyrillic_ / chinese_cht_PP-OCRv3_rec_mobile, arabic_ / korean_ / japan_ /
+// ta_ / te_ / ka_ / devanagari_PP-OCRv4_rec_mobile - one graph, ten class counts): MobileNetV1Enhance(scale 0.5, last_conv_stride
+// [1, 2], avg pool; backbones/rec_mv1_enhance.py) -> SequenceEncoder(svtr, dims 64, depth 2, hidden_dims 120, use_guide; necks/rnn.py:90-200,
+// 382-422) -> CTCHead Linear(64, classes) (heads/rec_ctc_head.py).  Externals, flags and stages as build_ppocrv6_rec, per-line widths
+// (REC_LINE_WIDTHS) included; tokens are [.][512].
+// Every backbone layer is Conv -> BatchNorm -> hardswish, without branches.  At load time every layer of the blocks becomes weight + bias
+// (derive_ppocr_rec_mv1e_weights: in double, rounded once).  The activation is placed as in PPLCNetV3 with identity affines: a depthwise
+// layer applies its own hardswish in its epilogue; conv1 and every pointwise layer write convolution + bias, and their hardswish is applied
+// by the consumer on load - the next depthwise kernel (inside the map and inside the line's width only: the padding stays zero) or the
+// final pooling kernel - so the matrix kernels' shared epilogue does not change (kernels_lcv3.hip says why).
+// Rows go 48 -> 24 (conv1) -> 12 -> 6 -> 3; the width is w2 up to the last block, whose stride (1, 2) makes it w4.  AvgPool2d(2, 2) on the
+// 3-row map uses rows 0 and 1 only.  SE: relu between the two FCs, gate relu6(x + 3) / 6 (ACT_HSIG), the mean over all rows inside the
+// line's width.
+// ---------------------------------------------------------------------------------------------------
+struct Mv1eCfg { int k, cin, cout, sh, sw; bool se; };
+static const Mv1eCfg kMv1eRec[13] = {
+    {3, 16, 32, 1, 1, false},   {3, 32, 64, 1, 1, false},   {3, 64, 64, 1, 1, false},   {3, 64, 128, 2, 1, false},  {3, 128, 128, 1, 1, false},
+    {3, 128, 256, 2, 1, false}, {5, 256, 256, 1, 1, false}, {5, 256, 256, 1, 1, false}, {5, 256, 256, 1, 1, false}, {5, 256, 256, 1, 1, false},
+    {5, 256, 256, 1, 1, false}, {5, 256, 512, 2, 1, true},  {5, 512, 512, 1, 2, true},
+};
+
+// Conv (no bias) + BatchNorm (eps 1e-5) of `p` (p._conv.weight, p._batch_norm.*) as p.fold.weight / p.fold.bias
+static void fold_conv_bn(WeightStore& ws, const std::string& p) {
+    const HostTensor& w = ws.get(p + "._conv.weight");
+    RD_CHECK(w.shape.size() == 4, "MobileNetV1Enhance: convolution weight shape: " + p);
+    const int co = (int)w.shape[0];
+    const size_t per = w.numel() / co;
+    const std::string q = p + "._batch_norm";
+    std::vector<float> wf(w.numel()), bf(co);
+    for (int o = 0; o < co; ++o) {
+        const double g = ws.get(q + ".weight").f32()[o], be = ws.get(q + ".bias").f32()[o], m = ws.get(q + ".running_mean").f32()[o],
+                     v = ws.get(q + ".running_var").f32()[o];
+        const double sc = g / std::sqrt(v + 1e-5);
+        for (size_t t = 0; t < per; ++t) wf[o * per + t] = (float)(sc * w.f32()[o * per + t]);
+        bf[o] = (float)(be - m * sc);
+    }
+    ws.add_derived(p + ".fold.weight", std::vector<int64_t>(w.shape.begin(), w.shape.end()), std::move(wf));
+    ws.add_derived(p + ".fold.bias", {co}, std::move(bf));
+}
+
+void derive_ppocr_rec_mv1e_weights(WeightStore& ws) {
+    for (int i = 0; i < 13; ++i) {      // (conv1 is folded by Builder::stem3x3s2, as every stem here)
+        const std::string p = "backbone.block_list." + std::to_string(i);
+        fold_conv_bn(ws, p + "._depthwise_conv");
+        fold_conv_bn(ws, p + "._pointwise_conv");
+    }
+}
+
+// x NCHW image -> pooled tokens [B][1][w4 / 2][512] (into *tokens_out when given)
+static TView mv1e_rec(Builder& b, const TView& x, const TView* tokens_out) {
+    // conv1 writes convolution + BatchNorm; its hardswish is the first depthwise layer's.  Columns >= a line's w2 are ignored by every reader
+    TView h = b.stem3x3s2("backbone.conv1._conv.weight", "backbone.conv1._batch_norm", x, ACT_NONE);
+    const Builder::Affine one;    // hardswish without an affine
+    int lt_col = 1;               // LineTab column of the current map's valid width: w2 up to the last block's input, w4 after it
+    for (int i = 0; i < 13; ++i) {
+        const Mv1eCfg& c = kMv1eRec[i];
+        const std::string p = "backbone.block_list." + std::to_string(i);
+        RD_CHECK(h.c == c.cin, "MobileNetV1Enhance: channel chain: " + p);
+        const int lt_out = c.sw == 2 ? 2 : lt_col;
+        TView t = b.lcv3_dw(p + "._depthwise_conv.fold.weight", p + "._depthwise_conv.fold.bias", h, c.k, c.sh, c.sw, &one, one, lt_col, lt_out,
+                            c.k == 5 ? 2 : 0);
+        b.release(h);
+        lt_col = lt_out;
+        if (c.se) {
+            Builder::GapOut gap = b.lcv3_gap(t, lt_col);
+            TView gate = b.se_gate(p + "._se.conv1.weight", p + "._se.conv1.bias", p + "._se.conv2.weight", p + "._se.conv2.bias", t, ACT_HSIG, &gap, lt_col);
+            b.scale(t, gate, 0.f, t);
+            b.release(gate);
+        }
+        h = b.conv(p + "._pointwise_conv.fold.weight", p + "._pointwise_conv.fold.bias", "", t, geom(1), ACT_NONE);    // hardswish: the consumer's
+        b.release(t);
+        RD_CHECK(h.c == c.cout, "MobileNetV1Enhance: channel chain: " + p);
+    }
+    TView tok = b.mv1e_pool(h, tokens_out);
+    b.release(h);
+    return tok;
+}
+
+void build_ppocr_rec_mv1e(Builder& b, int B, int H, int W, int flags) { build_ppocrv5_rec(b, B, H, W, flags, kRecMv1e); }
 
 // ---------------------------------------------------------------------------------------------------
 // PP-OCRv5 mobile det (arch_config.yaml ch_PP-OCRv5_det_mobile): PPLCNetV3(scale 0.75, det=True) -> RSEFPN(96, shortcut) -> DBHead(k 50).

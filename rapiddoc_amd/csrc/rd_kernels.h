@@ -204,7 +204,7 @@ bool dwconv_kxk_lds_applies(const DwParams& p);
 void launch_dwconv_kxk_lds(const DwParams& p, hipStream_t s);
 
 // PPLCNetV3 depthwise layer (kernels_lcv3.hip): y = post_act ? post_s hardswish(dw(x') + bias) + post_b : dw(x') + bias, x' = pre_act ? pre_s hardswish(x) + pre_b : x,
-// k = 3 / 5, strides (1,1), (2,1), (1,2; k = 3), (2,2), 'same' padding of ZEROS around the pre-affined map; per-image valid widths of the input / output (LineTab columns) or nullptr
+// k = 3 / 5, strides (1,1), (2,1), (1,2), (2,2), 'same' padding of ZEROS around the pre-affined map; per-image valid widths of the input / output (LineTab columns) or nullptr
 struct Lcv3DwParams {
     const float* x; int xld;
     int N, H, W, C;
@@ -225,6 +225,14 @@ void launch_lcv3_dw(const Lcv3DwParams& p, hipStream_t s);
 bool lcv3_dw2d_shape_ok(int k, int sh, int sw, int c);
 bool lcv3_dw2d_launch_ok(const Lcv3DwParams& p);   // shape_ok, no line table, a non-empty output and a grid below 2^31 workgroups
 bool launch_lcv3_dw2d(const Lcv3DwParams& p, hipStream_t s);   // false: not launched (launch_ok says no)
+// The 5x5 layer of the recogniser geometry, LDS-staged, with the line table (kernels_mv1e.hip): one workgroup = one line x a strip of output
+// columns x 16 channels x all rows.  k = 5, strides (1,1), (2,1), (1,2), H <= 6, C % 16 == 0; launch_ok declines everything else (and a grid
+// beyond 2^31 workgroups) and the caller stays on launch_lcv3_dw
+bool dw5_strip_launch_ok(const Lcv3DwParams& p);
+bool launch_dw5_strip(const Lcv3DwParams& p, hipStream_t s);   // false: not launched (launch_ok says no)
+// MobileNetV1Enhance's end: y = AvgPool2d(2, 2)(hardswish(x)) over rows 0 and 1 of a map of H >= 2 rows, floor(W / 2) tokens; line_tab as
+// launch_avgpool3x2
+void launch_mv1e_pool(const float* x, int xld, float* y, int yld, int N, int H, int W, int C, hipStream_t s, const int32_t* line_tab = nullptr);
 // y = s hardswish(x) + b, elementwise: the four stage outputs of the detector's backbone, whose consumers are matrix kernels
 void launch_lcv3_act(const float* x, int xld, float* y, int yld, long pixels, int C, float s, float b, hipStream_t st);
 // One PPLCNetV3 block without SE, 3x3 / stride 1, in one launch (kernels_lcv3_block.hip): the depthwise layer as above into an LDS tile, the

@@ -13,10 +13,11 @@ import torch
 from . import _lib, weights as W
 
 REC_UNFUSED_CTC, REC_WANT_SOFTMAX, REC_WANT_LOGITS = 1, 2, 4
-REC_WANT_NECK = 64          # ppocrv5_rec_server / ppocrv5_rec_mobile: `full` receives the neck's output [B, T, 120] instead
+REC_WANT_NECK = 64          # ppocrv5_rec_server / ppocrv5_rec_mobile: `full` receives the neck's output [B, T, 120] instead (ppocr_rec_mv1e: [B, T, 64])
+REC_NECK_DIMS = {"ppocr_rec_mv1e": 64}      # the SVTR neck's `dims` where it is not 120
 DET_WANT_NECK = 1           # ppocrv5_det_server / ppocrv5_det_mobile: also hand out the neck's output `fuse` [B, 256 / 96, H/4, W/4]
 DET_NECK_CHANNELS = {"ppocrv5_det_server": 256, "ppocrv5_det_mobile": 96}
-KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
+KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "ppocr_rec_mv1e", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
 
 
 def rec_line_table(widths, first_tokens) -> np.ndarray:
@@ -195,7 +196,7 @@ class RdEngine:
             raise EngineError("rec input height must be 48")
         T = self._l.rd_rec_seq_len(W_)
         want_full = bool(flags & (REC_WANT_SOFTMAX | REC_WANT_LOGITS | REC_WANT_NECK))
-        n_full = 120 if flags & REC_WANT_NECK else None       # (the SVTR neck's `dims`; every other flag: the class count)
+        n_full = REC_NECK_DIMS.get(self.kind, 120) if flags & REC_WANT_NECK else None       # (the SVTR neck's `dims`; every other flag: the class count)
         if out is not None:
             idx, prob, full = out
             ok = (idx.shape == (B, T) and idx.dtype == torch.int32 and idx.is_contiguous() and prob.shape == (B, T)

@@ -123,7 +123,8 @@ class PagePipeline:
         SVTR neck + CTC): strict mode then runs the backbone stage once per distinct reference width (that kind has no per-line widths
         inside a launch), everything behind the token buffer - the ragged tail, the collapse, word boxes - is the same.  Or as
         'ppocrv5_rec_mobile' (PPLCNetV3 + the same neck): that kind computes per-line widths inside a launch, so strict mode plans its
-        launches as for v6.
+        launches as for v6.  Or as 'ppocr_rec_mv1e' (MobileNetV1Enhance + the SVTR neck at dims 64: the ten multilingual PP-OCRv3 / v4
+        mobile files), which computes per-line widths inside a launch too.
 
         `rec_mode`: how the text lines are batched for the recogniser.  A line's logits depend on its batch's padded width
         (LightSVTR attends over the zero-padded columns), so the batching is part of the result:
@@ -170,12 +171,12 @@ class PagePipeline:
         self.det = RdEngine(self.det_kind, device, guard="deferred", reuse_outputs=True).load_weights(states[self.det_kind])
         # rec batches are independent: they alternate between `n_rec_streams` HIP streams (one engine handle = one
         # workspace per stream) so that the launch gaps / tails of one batch are filled by kernels of the other
-        rec_kinds = [k for k in ("ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile") if k in states]
+        rec_kinds = [k for k in ("ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "ppocr_rec_mv1e") if k in states]
         if len(rec_kinds) != 1:
-            raise ValueError("states must carry exactly one recogniser: 'ppocrv6_rec' or 'ppocrv5_rec_server' or 'ppocrv5_rec_mobile'")
+            raise ValueError("states must carry exactly one recogniser: 'ppocrv6_rec' or 'ppocrv5_rec_server' or 'ppocrv5_rec_mobile' or 'ppocr_rec_mv1e'")
         self.rec_kind = rec_kinds[0]
         # strict mode: lines of different reference widths share a launch only where the kind computes per-line widths inside one
-        self.rec_lines_in_launch = self.rec_kind in ("ppocrv6_rec", "ppocrv5_rec_mobile")
+        self.rec_lines_in_launch = self.rec_kind in ("ppocrv6_rec", "ppocrv5_rec_mobile", "ppocr_rec_mv1e")
         self.rec_engines = [RdEngine(self.rec_kind, device, guard="deferred").load_weights(states[self.rec_kind]) for _ in range(max(1, n_rec_streams))]
         self.rec = self.rec_engines[0]
         self.rec_streams = [torch.cuda.Stream(device=self.tdev) for _ in self.rec_engines]

@@ -282,17 +282,28 @@ REC_ARCH_BY_STEM = {
     "ch_PP-OCRv5_rec_server": "ppocrv5_rec_server",
     "ch_PP-OCRv5_rec_mobile": "ppocrv5_rec_mobile",
 }
+# The multilingual PP-OCRv3 / v4 mobile recognisers: ten arch_config.yaml keys on ONE graph (MobileNetV1Enhance scale 0.5 -> SVTR neck
+# dims 64 -> CTCHead), which differ in their class count only (130 ... 8423)
+REC_MV1E_STEMS = (
+    "latin_PP-OCRv3_rec_mobile", "cyrillic_PP-OCRv3_rec_mobile", "chinese_cht_PP-OCRv3_rec_mobile",
+    "arabic_PP-OCRv4_rec_mobile", "korean_PP-OCRv4_rec_mobile", "japan_PP-OCRv4_rec_mobile", "ta_PP-OCRv4_rec_mobile",
+    "te_PP-OCRv4_rec_mobile", "ka_PP-OCRv4_rec_mobile", "devanagari_PP-OCRv4_rec_mobile",
+)
+REC_ARCH_BY_STEM_MV1E = {stem: "ppocr_rec_mv1e" for stem in REC_MV1E_STEMS}
 
 
 def resolve_rec_kind(weights: WeightSrc) -> str:
     """Engine kind of a recogniser's weights: a file goes by its stem (an unknown one is an error, as in the reference - never a guess at
     the graph), a state dict or a safetensors byte image without a name by the CTC classifier it carries (`head.ctc_head.fc.weight`:
     the v5 MultiHead - the mobile recogniser where the backbone is PPLCNetV3, `backbone.conv1.conv.weight` / `backbone.blocks2.*`, the server
-    one otherwise; `head.head.weight`: the v6 LightSVTR head)."""
+    one otherwise; `head.head.weight`: the v6 LightSVTR head; `head.fc.weight` together with
+    `backbone.block_list.0._depthwise_conv._conv.weight`: a bare CTCHead behind MobileNetV1Enhance, the multilingual v3 / v4 mobile kind)."""
     if isinstance(weights, (str, Path)):
         stem = Path(str(weights)).stem
+        if stem in REC_ARCH_BY_STEM_MV1E:
+            return REC_ARCH_BY_STEM_MV1E[stem]
         if stem not in REC_ARCH_BY_STEM:
-            raise ValueError(f"architecture {stem} is not in the recognisers this engine serves {sorted(REC_ARCH_BY_STEM)}")
+            raise ValueError(f"architecture {stem} is not in the recognisers this engine serves {sorted(REC_ARCH_BY_STEM) + sorted(REC_ARCH_BY_STEM_MV1E)}")
         return REC_ARCH_BY_STEM[stem]
     if isinstance(weights, (bytes, bytearray, memoryview)):
         import json
@@ -309,12 +320,14 @@ def resolve_rec_kind(weights: WeightSrc) -> str:
         return "ppocrv5_rec_server"
     if "head.head.weight" in keys:
         return "ppocrv6_rec"
+    if "head.fc.weight" in keys and "backbone.block_list.0._depthwise_conv._conv.weight" in keys:
+        return "ppocr_rec_mv1e"
     raise ValueError("architecture of the recogniser weights is not in the recognisers this engine serves "
-                     "(neither head.ctc_head.fc.weight nor head.head.weight among the tensors)")
+                     "(neither head.ctc_head.fc.weight nor head.head.weight, nor head.fc.weight behind MobileNetV1Enhance, among the tensors)")
 
 
 class Mi355RecSession(_BaseSession):
-    """PP-OCRv6 small / PP-OCRv5 server / PP-OCRv5 mobile rec: [B,3,48,W] -> softmax(ctc_logits) [B,T,C] (ocr/torch.py:185-187; the v5 CTCHead applies
+    """PP-OCRv6 small / PP-OCRv5 server / PP-OCRv5 mobile / multilingual PP-OCRv3-v4 mobile rec: [B,3,48,W] -> softmax(ctc_logits) [B,T,C] (ocr/torch.py:185-187; the v5 CTCHead applies
     the softmax itself, rec_ctc_head.py:51-53 - the session's result is the same tensor for both).  The kind follows from the weights
     (`resolve_rec_kind`) unless `kind` names it.
 

@@ -35,6 +35,22 @@ _KIND_GAINS = {
         (lambda n: n == "head.binarize.conv3.weight", 3.0),
     ),
 }
+# Multilingual PP-OCRv3 / v4 mobile recogniser (MobileNetV1Enhance): a plain chain of Conv + BN + hardswish.  Under the plain rule it
+# collapses onto its biases (std along the line 0.1-0.3 % of absmax) and a uniform gain explodes it; these per-layer factors on the
+# convolutions (depthwise, pointwise per block) were calibrated to a block-output absmax of about 8 on a 2 x 320 input
+_MV1E_BLOCK_GAINS = ((0.7, 1.3), (0.6, 1.3), (1.6, 1.2), (1.6, 1.4), (1.1, 1.4), (0.7, 2.2), (1.0, 2.2), (0.9, 1.2), (1.1, 2.0), (1.1, 1.6),
+                     (0.5, 2.5), (0.8, 2.8), (1.2, 4.0))
+
+
+def _mv1e_gains():
+    rules = [(lambda n: n == "backbone.conv1._conv.weight", 2.2), (lambda n: n == "head.fc.weight", 30.0)]
+    for i, (dw, pw) in enumerate(_MV1E_BLOCK_GAINS):
+        rules.append((lambda n, i=i: n == "backbone.block_list.%d._depthwise_conv._conv.weight" % i, dw))
+        rules.append((lambda n, i=i: n == "backbone.block_list.%d._pointwise_conv._conv.weight" % i, pw))
+    return tuple(rules)
+
+
+_KIND_GAINS["ppocr_rec_mv1e"] = _mv1e_gains()
 _NORM_TOKENS = (".normalization.", ".norm.", ".bn.", "layer_norm", ".norm1.", ".norm2.")
 
 
