@@ -43,7 +43,8 @@ typedef struct rd_handle rd_handle;
 
 const char* rd_version(void);
 /* model_kind: "ppocrv6_det" | "ppocrv5_det_server" (PPHGNetV2-B4 + LKPAN + PFHeadLocal; rd_det_forward / rd_det_forward_ex) |
- * "ppocrv5_det_mobile" (PPLCNetV3 scale 0.75 + RSEFPN + DBHead; the same two calls) | "ppocrv6_rec" | "ppocrv5_rec_server" (PPHGNetV2-B4 + SVTR neck + CTC; every rd_rec_* call except
+ * "ppocrv5_det_mobile" (PPLCNetV3 scale 0.75 + RSEFPN + DBHead; the same two calls) |
+ * "ppocrv3_det_mobile" (MobileNetV3 large scale 0.5 without SE + RSEFPN + DBHead - multi_ / en_PP-OCRv3_det_mobile; the same two calls) | "ppocrv6_rec" | "ppocrv5_rec_server" (PPHGNetV2-B4 + SVTR neck + CTC; every rd_rec_* call except
  * rd_rec_backbone_forward_lines) | "ppocrv5_rec_mobile" (PPLCNetV3 scale 0.95 + the same SVTR neck + CTC; every rd_rec_* call) | "ppocr_rec_mv1e" (MobileNetV1Enhance scale 0.5 + SVTR neck dims 64 + CTC:
  * the ten multilingual PP-OCRv3 / v4 mobile files latin_ / cyrillic_ / chinese_cht_PP-OCRv3_rec_mobile, arabic_ / korean_ / japan_ / ta_ / te_ / ka_ /
  * devanagari_PP-OCRv4_rec_mobile, which differ in their class count only; every rd_rec_* call) | "pphgnetv2_b4" | "pphgnetv2_b6_formula" | "ppformulanet_head".  NULL on failure -> rd_create_error(). */
@@ -58,12 +59,12 @@ int rd_load_weights(rd_handle* h, const void* safetensors_image, size_t nbytes);
 /* bytes of device workspace one call with this geometry needs (H is ignored for rec: always 48) */
 int rd_query_workspace(rd_handle* h, int B, int H, int W, int flags, size_t* ws_bytes);
 
-/* Text detector ("ppocrv6_det", "ppocrv5_det_server" or "ppocrv5_det_mobile"): x [B,3,H,W] (H, W multiples of 32; the server detector: >= 64) -> DB probability
+/* Text detector ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile" or "ppocrv3_det_mobile"): x [B,3,H,W] (H, W multiples of 32; the server detector: >= 64) -> DB probability
  * map [B,1,H,W] (the reference session's `maps`) */
 int rd_det_forward(rd_handle* h, const float* x_nchw_dev, int B, int H, int W, float* prob_b1hw_dev, void* ws_dev,
                    size_t ws_bytes, void* stream);
-/* The same forward with debug outputs.  flags 0: exactly rd_det_forward (aux_dev may be NULL).  RD_DET_WANT_NECK ("ppocrv5_det_server" and
- * "ppocrv5_det_mobile"): aux_dev also receives the neck's output `fuse` as NCHW [B,256,H/4,W/4] (server) or [B,96,H/4,W/4] (mobile).  rd_query_workspace takes the same flags. */
+/* The same forward with debug outputs.  flags 0: exactly rd_det_forward (aux_dev may be NULL).  RD_DET_WANT_NECK ("ppocrv5_det_server",
+ * "ppocrv5_det_mobile" and "ppocrv3_det_mobile"): aux_dev also receives the neck's output `fuse` as NCHW [B,256,H/4,W/4] (server) or [B,96,H/4,W/4] (both mobile kinds).  rd_query_workspace takes the same flags. */
 #define RD_DET_WANT_NECK 1
 int rd_det_forward_ex(rd_handle* h, const float* x_nchw_dev, int B, int H, int W, float* prob_b1hw_dev, int flags, float* aux_dev,
                       void* ws_dev, size_t ws_bytes, void* stream);

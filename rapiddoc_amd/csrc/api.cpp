@@ -105,11 +105,11 @@ int rd_query_workspace(rd_handle* h, int B, int H, int W, int flags, size_t* ws_
     });
 }
 
-static bool is_det_kind(const std::string& k) { return k == "ppocrv6_det" || k == "ppocrv5_det_server" || k == "ppocrv5_det_mobile"; }
+static bool is_det_kind(const std::string& k) { return k == "ppocrv6_det" || k == "ppocrv5_det_server" || k == "ppocrv5_det_mobile" || k == "ppocrv3_det_mobile"; }
 
 int rd_det_forward(rd_handle* h, const float* x, int B, int H, int W, float* prob, void* ws, size_t ws_bytes, void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && is_det_kind(h->eng->kind()), "handle is not a detector (ppocrv6_det / ppocrv5_det_server / ppocrv5_det_mobile) model");
+        RD_CHECK(h->eng && is_det_kind(h->eng->kind()), "handle is not a detector (ppocrv6_det / ppocrv5_det_server / ppocrv5_det_mobile / ppocrv3_det_mobile) model");
         RD_CHECK(x && prob && B > 0, "null input/output");
         h->eng->run(B, H, W, 0, {(void*)x, (void*)prob}, ws, ws_bytes, (hipStream_t)stream);
     });
@@ -118,15 +118,33 @@ int rd_det_forward(rd_handle* h, const float* x, int B, int H, int W, float* pro
 int rd_det_forward_ex(rd_handle* h, const float* x, int B, int H, int W, float* prob, int flags, float* aux, void* ws, size_t ws_bytes,
                       void* stream) {
     return guarded(h, [&] {
-        RD_CHECK(h->eng && is_det_kind(h->eng->kind()), "handle is not a detector (ppocrv6_det / ppocrv5_det_server / ppocrv5_det_mobile) model");
+        RD_CHECK(h->eng && is_det_kind(h->eng->kind()), "handle is not a detector (ppocrv6_det / ppocrv5_det_server / ppocrv5_det_mobile / ppocrv3_det_mobile) model");
         RD_CHECK(x && prob && B > 0, "null input/output");
         RD_CHECK((flags & ~RD_DET_WANT_NECK) == 0, "rd_det_forward_ex: unknown flag");
         if (flags & RD_DET_WANT_NECK) {
-            RD_CHECK(h->eng->kind() == "ppocrv5_det_server" || h->eng->kind() == "ppocrv5_det_mobile",
-                     "RD_DET_WANT_NECK is offered by ppocrv5_det_server and ppocrv5_det_mobile only");
+            RD_CHECK(h->eng->kind() == "ppocrv5_det_server" || h->eng->kind() == "ppocrv5_det_mobile" || h->eng->kind() == "ppocrv3_det_mobile",
+                     "RD_DET_WANT_NECK is offered by ppocrv5_det_server, ppocrv5_det_mobile and ppocrv3_det_mobile only");
             RD_CHECK(aux, "aux_dev is NULL");
         }
         h->eng->run(B, H, W, flags, {(void*)x, (void*)prob, (void*)aux}, ws, ws_bytes, (hipStream_t)stream);
+    });
+}
+
+// developer entry ("ppocrv3_det_mobile" only): rd_det_forward plus `fuse` and the backbone's four stage features, written as NCHW back to
+// back into aux_dev: [B,96,H/4,W/4], [B,16,H/4,W/4], [B,24,H/8,W/8], [B,56,H/16,W/16], [B,480,H/32,W/32].  The plan of the engine's
+// DET_WANT_NECK | DET_WANT_STAGES variant; the internal workspace.  Not part of the public header.
+int rd_debug_det_forward_stages(rd_handle* h, const float* x, int B, int H, int W, float* prob, float* aux, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->eng && h->eng->kind() == "ppocrv3_det_mobile", "handle is not a ppocrv3_det_mobile model");
+        RD_CHECK(x && prob && aux && B > 0 && H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0, "null input/output, or H / W no multiple of 32");
+        static const int kC[5] = {96, 16, 24, 56, 480}, kR[5] = {4, 4, 8, 16, 32};
+        std::vector<void*> ext = {(void*)x, (void*)prob};
+        float* q = aux;
+        for (int i = 0; i < 5; ++i) {
+            ext.push_back(q);
+            q += (size_t)B * kC[i] * (H / kR[i]) * (W / kR[i]);
+        }
+        h->eng->run(B, H, W, rd::DET_WANT_NECK | rd::DET_WANT_STAGES, ext, nullptr, 0, (hipStream_t)stream);
     });
 }
 
@@ -829,7 +847,8 @@ int rd_debug_mv1e_pool(int N, int H, int W, int C, float* x, float* y, const int
 }
 
 // developer entry, host only (no device is touched): the load-time derived tensor `name` of "ppocrv5_det_mobile" - a folded
-// LearnableRepLayer (`<layer>.fold.weight / .bias`) or `neck.ins_conv.<i>.fold.*` - from a safetensors image.  Copies at most
+// LearnableRepLayer (`<layer>.fold.weight / .bias`) or `neck.ins_conv.<i>.fold.*` - or of "ppocrv3_det_mobile" - a folded Conv + BatchNorm
+// (`backbone.stages.<s>.<i>.{expand,bottleneck,linear}_conv.fold.*`, `backbone.stages.3.3.fold.*`) - from a safetensors image.  Copies at most
 // `capacity` floats to `out` and returns the tensor's element count; -1: unknown kind, name or a malformed image.
 long rd_debug_derived_tensor(const char* kind, const void* img, size_t nbytes, const char* name, float* out, long capacity) {
     try {
@@ -837,8 +856,9 @@ long rd_debug_derived_tensor(const char* kind, const void* img, size_t nbytes, c
         const std::string k(kind);
         rd::WeightStore ws;
         ws.load_safetensors(img, nbytes);
-        if (k != "ppocrv5_det_mobile") return -1;
-        rd::derive_ppocrv5_det_mobile_weights(ws);
+        if (k == "ppocrv5_det_mobile") rd::derive_ppocrv5_det_mobile_weights(ws);
+        else if (k == "ppocrv3_det_mobile") rd::derive_ppocrv3_det_mobile_weights(ws);
+        else return -1;
         if (!ws.has(name)) return -1;
         const rd::HostTensor& t = ws.get(name);
         const long n = (long)t.numel();
@@ -847,6 +867,60 @@ long rd_debug_derived_tensor(const char* kind, const void* img, size_t nbytes, c
     } catch (const std::exception&) {
         return -1;
     }
+}
+
+// shared by the developer entries below: one untimed launch (so `iters` = 0 still runs the kernel once: the correctness tests rely on
+// that), then `iters` timed ones between two events; ms per timed launch.  A developer tool: HIP return codes are not looked at
+static float rd_debug_time(int iters, const std::function<void()>& launch) {
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    launch();
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) launch();
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return iters > 0 ? ms / iters : 0.f;
+}
+
+// developer entry: one MobileNetV3 depthwise layer through launch_mbv3_dw (kernels_mbv3.hip; x NHWC fp32 [N][H][W][xld >= C], w [K*K][C], bias
+// [C], y [N][OH][OW][yld >= C], OH = (H - 1) / S + 1; pre_act / post_act: 0 none, 1 ReLU, 2 hardswish - the producer's on load inside the map,
+// the layer's own in the epilogue; max_blocks > 0 caps the grid, so that a small map meets the grid-stride loop).  Returns ms per launch, < 0: not served (mbv3_dw_launch_ok).
+float rd_debug_mbv3_dw(int N, int H, int W, int C, int K, int S, int pre_act, int post_act, int xld, int yld, int iters, int max_blocks, float* x, float* w,
+                       float* bias, float* y) {
+    if (S < 1) return -1.f;
+    rd::Mbv3DwParams p{};
+    p.x = x; p.xld = xld; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = yld;
+    p.K = K; p.S = S; p.OH = (H - 1) / S + 1; p.OW = (W - 1) / S + 1;
+    p.pre_act = pre_act; p.post_act = post_act; p.max_blocks = max_blocks;
+    if (!x || !w || !bias || !y || !rd::mbv3_dw_launch_ok(p)) return -1.f;
+    return rd_debug_time(iters, [&] { (void)rd::launch_mbv3_dw(p, nullptr); });
+}
+
+// developer entry: one MobileNetV3 inverted-residual block through launch_mbv3_block (kernels_mbv3.hip; x NHWC fp32 [N][H][W][xld >= cin],
+// we [mid][cin], be [mid], wd [K*K][mid], bd [mid], wl [cout][mid], bl [cout], y [N][OH][OW][yld >= cout]; act 1 ReLU / 2 hardswish;
+// in_hswish: hardswish on load; shortcut: y += x').  Returns ms per launch, < 0: not served (mbv3_block_launch_ok).
+float rd_debug_mbv3_block(int N, int H, int W, int cin, int mid, int cout, int K, int S, int act, int in_hswish, int shortcut, int xld, int yld, int iters,
+                          float* x, float* we, float* be, float* wd, float* bd, float* wl, float* bl, float* y) {
+    if (S < 1) return -1.f;
+    rd::Mbv3BlockParams p{};
+    p.x = x; p.xld = xld; p.N = N; p.H = H; p.W = W; p.cin = cin; p.mid = mid; p.cout = cout;
+    p.we = we; p.be = be; p.wd = wd; p.bd = bd; p.wl = wl; p.bl = bl; p.y = y; p.yld = yld;
+    p.K = K; p.S = S; p.OH = (H - 1) / S + 1; p.OW = (W - 1) / S + 1;
+    p.act = act; p.in_hswish = in_hswish; p.shortcut = shortcut;
+    if (!x || !we || !be || !wd || !bd || !wl || !bl || !y || !rd::mbv3_block_launch_ok(p)) return -1.f;
+    return rd_debug_time(iters, [&] { (void)rd::launch_mbv3_block(p, nullptr); });
+}
+// host only: would mbv3_block_kernel serve this geometry (contiguous, aligned views assumed)?  1 yes, 0 no
+int rd_debug_mbv3_block_ok(int N, int H, int W, int cin, int mid, int cout, int K, int S, int act, int shortcut, int xld, int yld) {
+    if (S < 1) return 0;
+    rd::Mbv3BlockParams p{};
+    p.xld = xld; p.N = N; p.H = H; p.W = W; p.cin = cin; p.mid = mid; p.cout = cout; p.yld = yld;
+    p.K = K; p.S = S; p.OH = (H - 1) / S + 1; p.OW = (W - 1) / S + 1;
+    p.act = act; p.shortcut = shortcut;
+    return rd::mbv3_block_launch_ok(p) ? 1 : 0;
 }
 
 // developer entry: one PPLCNetV3 depthwise layer in the detector geometry (x NHWC fp32 [N][H][W][C], w [K*K][C], bias [C], y [N][OH][OW][C] with

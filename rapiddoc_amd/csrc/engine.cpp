@@ -1300,6 +1300,137 @@ TView Builder::lcv3_act(const TView& x, Affine a) {
     return y;
 }
 
+// ---- MobileNetV3 (kernels_mbv3.hip)
+// Per-layer default of the hardswish depthwise layers with C % 16 == 0: true = lcv3_dw2d_kernel (kernels_lcv3_det.hip), by the same rule, from
+// the per-layer A/B of tools/mb_det_v3_mobile.py --routes (docs/notebook/v3_mobile_det.md); a layer that was not measured stays direct.
+//   direct / staged ms at 32 pages (median of 7 repeats of 40 launches, alternating; spreads 0.5 - 9.5 %):
+//   k 3 s 1  C 96 @ 1/16   0.0290 / 0.0235      k 3 s 1  C 240 @ 1/16  0.0622 / 0.0501      k 3 s 1  C 336 @ 1/16  0.0865 / 0.0679
+//   k 5 s 1  C 480 @ 1/32  0.0759 / 0.0353      k 5 s 2  C 336 @ 1/16  0.0700 / 0.0739 (direct stays)
+bool mbv3_dw2d_default(int k, int stride, int c, int level) {
+    if (k == 3 && stride == 1) return (c == 96 || c == 240 || c == 336) && level == 4;
+    if (k == 5 && stride == 1) return c == 480 && level == 5;
+    return false;
+}
+
+TView Builder::mbv3_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int stride, int pre_act, int post_act, int level) {
+    const HostTensor& w = ws_->get(wname);
+    RD_CHECK(w.shape.size() == 4 && w.shape[1] == 1 && w.shape[2] == k && w.shape[3] == k, "mbv3 depthwise weight shape: " + wname);
+    const int c = (int)w.shape[0];
+    RD_CHECK(c == x.c && mbv3_dw_shape_ok(k, stride, c), "mbv3 depthwise geometry: " + wname);
+    RD_CHECK(!has_lt_, "mbv3 depthwise: no line table");
+    const int oh = (x.h - 1) / stride + 1, ow = (x.w - 1) / stride + 1;
+    TView y = alloc(x.n, oh, ow, c);
+    const std::string key = wname + "|mbv3dw";
+    if (!planning()) {
+        if (!pb_->has(key + "#w")) {
+            std::vector<float> wf((size_t)k * k * c);
+            for (int ch = 0; ch < c; ++ch)
+                for (int t = 0; t < k * k; ++t) wf[(size_t)t * c + ch] = w.f32()[(size_t)ch * k * k + t];
+            pb_->add(key + "#w", wf);
+            pb_->add(key + "#b", std::vector<float>(ws_->get(bname).f32(), ws_->get(bname).f32() + c));
+        }
+        return y;
+    }
+    Mbv3DwParams p{};
+    p.xld = plan_->ld(x);
+    p.N = x.n; p.H = x.h; p.W = x.w; p.C = c;
+    p.w = pb_->ptr(key + "#w");
+    p.bias = pb_->ptr(key + "#b");
+    p.yld = plan_->ld(y);
+    p.OH = oh; p.OW = ow; p.K = k; p.S = stride;
+    p.pre_act = pre_act; p.post_act = post_act;
+    RD_CHECK(mbv3_dw_launch_ok(p) && x.coff % 4 == 0 && y.coff % 4 == 0, "mbv3 depthwise: 16-byte aligned pixels: " + wname);
+    static const char* const kActName[3] = {"none", "relu", "hswish"};
+    OpRecord r;
+    r.name = wname;
+    r.kind = "mbv3_dw" + std::to_string(k) + "x" + std::to_string(k);
+    // hardswish on load AND in the epilogue, C % 16 == 0: the v5 mobile detector's LDS-staged kernel computes the same layer (identity affines)
+    Lcv3DwParams sp{};
+    sp.xld = p.xld; sp.N = p.N; sp.H = p.H; sp.W = p.W; sp.C = c; sp.w = p.w; sp.bias = p.bias; sp.yld = p.yld;
+    sp.OH = oh; sp.OW = ow; sp.K = k; sp.SH = sp.SW = stride;
+    sp.pre_act = 1; sp.pre_s = 1.f; sp.pre_b = 0.f; sp.post_act = 1; sp.post_s = 1.f; sp.post_b = 0.f;
+    const char* sw = std::getenv("RD_MBV3_DW2D");      // A/B switch, read per plan; the route goes by the layer, never by batch or page size
+    const bool staged = pre_act == MBV3_HSWISH && post_act == MBV3_HSWISH && lcv3_dw2d_launch_ok(sp) &&
+                        (sw && (sw[0] == '0' || sw[0] == '1') ? sw[0] == '1' : mbv3_dw2d_default(k, stride, c, level));
+    r.cfg = "s" + std::to_string(stride) + "/" + kActName[pre_act] + ">" + kActName[post_act] + (staged ? "/lds2d" : "");
+    r.shape = "N" + std::to_string(x.n) + "_" + std::to_string(x.h) + "x" + std::to_string(x.w) + "_C" + std::to_string(c);
+    r.flops = 2.0 * x.n * oh * ow * (double)c * k * k;
+    r.bytes = 4.0 * ((double)x.pixels() * c + (double)y.pixels() * c);
+    const TView xv = x, yv = y;
+    r.run = [p, sp, staged, xv, yv](const Plan& pl, const RunCtx& cx) {
+        if (staged) {
+            Lcv3DwParams q = sp;
+            q.x = pl.vptr(xv, cx);
+            q.y = pl.vptr(yv, cx);
+            (void)launch_lcv3_dw2d(q, cx.stream);    // (servable: checked above)
+            return;
+        }
+        Mbv3DwParams q = p;
+        q.x = pl.vptr(xv, cx);
+        q.y = pl.vptr(yv, cx);
+        (void)launch_mbv3_dw(q, cx.stream);      // (servable: checked above)
+    };
+    emit(std::move(r));
+    return y;
+}
+
+// Per-block default of the MobileNetV3 route.  A block becomes fused only by the rule of docs/notebook/v5_mobile_det.md: routes alternating
+// on the same operands at [32, 3, 960, 704] (tools/mb_det_v3_mobile.py --routes), the fused median below the unfused one by more than the
+// larger of the two spreads.  The table and what it decided are in docs/notebook/v3_mobile_det.md; a (k, stride, cin, mid, level) that was
+// not measured stays unfused.
+//   block (k / s, cin-mid-cout @ level)   unfused / fused ms (median of 7 alternating profiled launches; spreads 0.6 - 7.2 %)
+//   3 / 1   8-8-8   @ 1/2   0.787 / 0.313      3 / 2   8-32-16 @ 1/2   0.473 / 0.379      3 / 1  16-40-16 @ 1/4   0.451 / 0.248
+//   5 / 2  16-40-24 @ 1/4   0.377 / 0.261      5 / 1  24-64-24 @ 1/8   0.234 / 0.191 and 0.230 / 0.190
+// All five measured geometries win by more than either route's spread; the forward went from 6.11 to 5.20 ms.
+bool mbv3_fused_default(int k, int stride, int cin, int mid, int level) {
+    if (k == 3 && stride == 1) return (cin == 8 && mid == 8 && level == 1) || (cin == 16 && mid == 40 && level == 2);
+    if (k == 3 && stride == 2) return cin == 8 && mid == 32 && level == 1;
+    if (k == 5 && stride == 2) return cin == 16 && mid == 40 && level == 2;
+    if (k == 5 && stride == 1) return cin == 24 && mid == 64 && level == 3;
+    return false;
+}
+
+bool Builder::mbv3_block(const std::string& prefix, const TView& x, int k, int stride, int act, bool in_hswish, bool shortcut, int level, TView* y_out) {
+    if (!planning()) return false;
+    const std::string we = prefix + ".expand_conv.fold.weight", wd = prefix + ".bottleneck_conv.fold.weight", wl = prefix + ".linear_conv.fold.weight";
+    const std::string ke = we + "|", kd = wd + "|mbv3dw", kl = wl + "|";
+    if (!pb_->has(ke + "#w") || !pb_->has(ke + "#b") || !pb_->has(kd + "#w") || !pb_->has(kl + "#w") || !pb_->has(kl + "#b")) return false;
+    Mbv3BlockParams p{};
+    p.xld = plan_->ld(x);
+    p.N = x.n; p.H = x.h; p.W = x.w; p.cin = x.c;
+    p.mid = weight_dim(we, 0); p.cout = weight_dim(wl, 0);
+    p.we = pb_->ptr(ke + "#w"); p.be = pb_->ptr(ke + "#b");
+    p.wd = pb_->ptr(kd + "#w"); p.bd = pb_->ptr(kd + "#b");
+    p.wl = pb_->ptr(kl + "#w"); p.bl = pb_->ptr(kl + "#b");
+    p.OH = (x.h - 1) / stride + 1; p.OW = (x.w - 1) / stride + 1; p.K = k; p.S = stride;
+    p.act = act; p.in_hswish = in_hswish; p.shortcut = shortcut;
+    p.yld = p.cout;      // (the output is a fresh full-width buffer)
+    if (weight_dim(we, 1) != x.c || weight_dim(wl, 1) != p.mid || has_lt_ || x.coff % 4 != 0 || !mbv3_block_launch_ok(p)) return false;
+    // the route is a property of the layer (k, stride, cin, mid, pyramid level), never of the batch or the page size; A/B switch read per plan
+    const char* sw = std::getenv("RD_MBV3_FUSED");
+    if (!(sw && (sw[0] == '0' || sw[0] == '1') ? sw[0] == '1' : mbv3_fused_default(k, stride, p.cin, p.mid, level))) return false;
+    TView y = alloc(x.n, p.OH, p.OW, p.cout);
+    RD_CHECK(plan_->ld(y) == p.yld, "mbv3 block: output row stride");
+    OpRecord r;
+    r.name = prefix;
+    r.kind = "mbv3_block";
+    r.cfg = "k" + std::to_string(k) + "s" + std::to_string(stride) + (act == MBV3_RELU ? "/relu" : "/hswish") + (in_hswish ? "/inact" : "") + (shortcut ? "/res" : "");
+    r.shape = "N" + std::to_string(x.n) + "_" + std::to_string(x.h) + "x" + std::to_string(x.w) + "_C" + std::to_string(p.cin) + "_" + std::to_string(p.mid) + "_" +
+              std::to_string(p.cout);
+    r.flops = 2.0 * ((double)x.pixels() * p.cin * p.mid + (double)y.pixels() * p.mid * (k * k + p.cout));
+    r.bytes = 4.0 * ((double)x.pixels() * p.cin + (double)y.pixels() * p.cout);
+    const TView xv = x, yv = y;
+    r.run = [p, xv, yv](const Plan& pl, const RunCtx& cx) {
+        Mbv3BlockParams q = p;
+        q.x = pl.vptr(xv, cx);
+        q.y = pl.vptr(yv, cx);
+        (void)launch_mbv3_block(q, cx.stream);   // (servable: checked above)
+    };
+    emit(std::move(r));
+    *y_out = y;
+    return true;
+}
+
 // the fused block's own parameters: the pointwise weights [cout][cin] as fp32 (the kernel splits them once per workgroup) + bias, for layers
 // whose weights fit the fp16 range.  Prepared for every handle (28 KB over the three blocks): plans pick the route later, per plan
 void Builder::prepare_lcv3_block(const std::string& key, const HostTensor& w, const std::string& pw_b) {
@@ -1737,7 +1868,7 @@ Engine::Engine(int device, const std::string& kind) : device_(device), kind_(kin
         precision_ = v == "h3" ? PREC_H3 : v == "fp32" ? PREC_FP32 : PREC_AUTO;
     }
     RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "ppocrv5_rec_mobile" || kind == "ppocr_rec_mv1e" || kind == "ppocrv5_det_server" ||
-                 kind == "ppocrv5_det_mobile" ||
+                 kind == "ppocrv5_det_mobile" || kind == "ppocrv3_det_mobile" ||
                  kind == "pphgnetv2_b4" || kind == "pphgnetv2_b6_formula",
              "unknown model kind '" + kind + "'");
     int count = 0;
@@ -1789,6 +1920,7 @@ void Engine::build(Builder& b, int B, int H, int W, int flags) {
     else if (kind_ == "ppocr_rec_mv1e") build_ppocr_rec_mv1e(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_det_server") build_ppocrv5_det_server(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_det_mobile") build_ppocrv5_det_mobile(b, B, H, W, flags);
+    else if (kind_ == "ppocrv3_det_mobile") build_ppocrv3_det_mobile(b, B, H, W, flags);
     else if (kind_ == "pphgnetv2_b6_formula") build_pphgnetv2_b6_formula(b, B, H, W, flags);
     else build_pphgnetv2_b4(b, B, H, W);
 }
@@ -1812,6 +1944,8 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
         derive_ppocrv5_det_server_weights(store_);
     } else if (kind_ == "ppocrv5_det_mobile") {
         derive_ppocrv5_det_mobile_weights(store_);
+    } else if (kind_ == "ppocrv3_det_mobile") {
+        derive_ppocrv3_det_mobile_weights(store_);
     }
     Plan dummy;
     h3_prepared_ = precision_ == PREC_H3;

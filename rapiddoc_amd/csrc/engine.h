@@ -230,6 +230,16 @@ class Builder {
     bool lcv3_dw_common(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre, const Affine* post,
                         TView* y, Lcv3DwParams* p, OpRecord* r);   // shared by the two builders above; false in PREPARE mode
     TView lcv3_act(const TView& x, Affine a);             // a hardswish(x) + b, elementwise (kernels_lcv3_det.hip)
+    // MobileNetV3 in the detector geometry (kernels_mbv3.hip).  The depthwise layer alone: pre_act = the producer's activation, applied on
+    // load inside the map; post_act = the layer's own (Mbv3Act)
+    // `level` = log2 of the input map's reduction of the page: with (k, stride, C) it picks, for a hardswish layer of C % 16 == 0, the
+    // LDS-staged lcv3_dw2d_kernel (mbv3_dw2d_default; RD_MBV3_DW2D=0|1 forces one route for every layer that kernel serves)
+    TView mbv3_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int stride, int pre_act, int post_act, int level);
+    // One inverted-residual block `prefix`.{expand,bottleneck,linear}_conv.fold.* in one launch; in_hswish: x is conv1's convolution + bias,
+    // activated on load.  `level` = log2 of the input map's reduction of the page.  Taken where mbv3_block_launch_ok serves the geometry AND
+    // (RD_MBV3_FUSED=0|1, read per plan, forcing one route for every such block) mbv3_fused_default says so.  false: not taken (always in
+    // PREPARE mode: the parameters are those the separate operators fold), the caller emits expand -> depthwise -> linear
+    bool mbv3_block(const std::string& prefix, const TView& x, int k, int stride, int act, bool in_hswish, bool shortcut, int level, TView* y);
     // one block without SE (3x3, stride 1) in one launch (kernels_lcv3_block.hip), writing the pointwise layer's convolution + bias as the separate
     // route does.  Taken under RD_LCV3_FUSED=1 in the split precisions; false: not taken (and always in PREPARE mode, where it only adds its
     // parameters), the caller emits the separate operators
@@ -374,7 +384,7 @@ void derive_ppocr_rec_mv1e_weights(WeightStore& ws);
 bool mv1e_dw_strip_default(int sh, int sw, int c);
 // PP-OCRv5 server detector (PPHGNetV2-B4 + LKPAN with IntraCL + PFHeadLocal): ext[0] = x NCHW, ext[1] = maps [B,1,H,W];
 // DET_WANT_NECK: ext[2] = the neck output `fuse` NCHW [B,256,H/4,W/4]
-enum DetFlags : int { DET_WANT_NECK = 1 };
+enum DetFlags : int { DET_WANT_NECK = 1, DET_WANT_STAGES = 2 };   // DET_WANT_STAGES: ppocrv3_det_mobile only, developer (rd_debug_det_forward_stages): ext[3..6] = its four stage features NCHW
 void build_ppocrv5_det_server(Builder& b, int B, int H, int W, int flags);
 // tensors build_ppocrv5_det_server reads that are not in the file: the three branches of every IntraCL level folded into one k x k convolution
 void derive_ppocrv5_det_server_weights(WeightStore& ws);
@@ -386,6 +396,18 @@ void build_ppocrv5_det_mobile(Builder& b, int B, int H, int W, int flags);
 void derive_ppocrv5_det_mobile_weights(WeightStore& ws);
 // default route of one depthwise layer of that backbone: true = the LDS-staged kernel (set from the per-layer A/B table of tools/mb_det_mobile.py)
 bool lcv3_dw2d_default(int k, int stride, int c, int level);
+// PP-OCRv3 multilingual detector (multi_ / en_PP-OCRv3_det_mobile: MobileNetV3 large scale 0.5 without SE + RSEFPN 96 + DBHead): externals as
+// the v5 mobile detector, DET_WANT_NECK included.  Its DBHead has no fix_nan; the shared ACT_SIGMOID maps NaN to 0, which is the identity
+// on finite input, so the head tail is the v5 mobile detector's
+void build_ppocrv3_det_mobile(Builder& b, int B, int H, int W, int flags);
+// tensors build_ppocrv3_det_mobile reads that are not in the file: every Conv + BatchNorm of the backbone's blocks and conv_last folded into
+// weight + bias (in double, rounded once)
+void derive_ppocrv3_det_mobile_weights(WeightStore& ws);
+// default route of one inverted-residual block of that backbone: true = mbv3_block_kernel (set from the per-block A/B table of
+// tools/mb_det_v3_mobile.py --routes; a geometry that was not measured stays unfused)
+bool mbv3_fused_default(int k, int stride, int cin, int mid, int level);
+// default route of one hardswish depthwise layer (C % 16 == 0) of that backbone: true = the LDS-staged lcv3_dw2d_kernel (same table, same rule)
+bool mbv3_dw2d_default(int k, int stride, int c, int level);
 void build_pphgnetv2_b4(Builder& b, int B, int H, int W);
 // PP-FormulaNet_plus encoder; flags bit 0: the caller's image has 1 channel (replicated to 3 like the reference)
 void build_pphgnetv2_b6_formula(Builder& b, int B, int H, int W, int flags);

@@ -835,13 +835,14 @@ static const Mv1eCfg kMv1eRec[13] = {
     {5, 256, 256, 1, 1, false}, {5, 256, 512, 2, 1, true},  {5, 512, 512, 1, 2, true},
 };
 
-// Conv (no bias) + BatchNorm (eps 1e-5) of `p` (p._conv.weight, p._batch_norm.*) as p.fold.weight / p.fold.bias
-static void fold_conv_bn(WeightStore& ws, const std::string& p) {
-    const HostTensor& w = ws.get(p + "._conv.weight");
-    RD_CHECK(w.shape.size() == 4, "MobileNetV1Enhance: convolution weight shape: " + p);
+// Conv (no bias) `p`<conv>.weight + BatchNorm (eps 1e-5) `p`<bn>.* as p.fold.weight / p.fold.bias: scale and product in double, rounded once
+static void fold_conv_bn(WeightStore& ws, const std::string& p, const char* conv = "._conv", const char* bn = "._batch_norm") {
+    const HostTensor& w = ws.get(p + conv + ".weight");
+    RD_CHECK(w.shape.size() == 4, "Conv + BatchNorm fold: convolution weight shape: " + p);
     const int co = (int)w.shape[0];
     const size_t per = w.numel() / co;
-    const std::string q = p + "._batch_norm";
+    const std::string q = p + bn;
+    RD_CHECK(ws.get(q + ".weight").numel() == (size_t)co, "Conv + BatchNorm fold: channel count: " + p);
     std::vector<float> wf(w.numel()), bf(co);
     for (int o = 0; o < co; ++o) {
         const double g = ws.get(q + ".weight").f32()[o], be = ws.get(q + ".bias").f32()[o], m = ws.get(q + ".running_mean").f32()[o],
@@ -905,6 +906,55 @@ void build_ppocr_rec_mv1e(Builder& b, int B, int H, int W, int flags) { build_pp
 // layer_list[i] (1x1, bias) -> ins_conv[i].in_conv (1x1, no bias) has nothing nonlinear in between: ONE 1x1 convolution + bias, derived
 // in double at load time; the widths 12 / 18 / 42 / 360 never exist.  head.thresh.* is in the file and unused in eval mode.
 // ---------------------------------------------------------------------------------------------------
+// The part of RSEFPN + DBHead that the PP-OCRv5 mobile detector and the PP-OCRv3 multilingual detector share.
+// y <- y + y * gate(y): an RSELayer's squeeze-excite with the paddle hard-sigmoid slope and the shortcut, in place
+static void rse_gate_shortcut(Builder& b, const std::string& p, const TView& y) {
+    const std::string s = p + ".se_block.";
+    TView gate = b.se_gate(s + "conv1.weight", s + "conv1.bias", s + "conv2.weight", s + "conv2.bias", y, ACT_HSIG_PADDLE);
+    b.scale(y, gate, 1.f, y);  // y + y*s (shortcut)
+    b.release(gate);
+}
+// in[0..3]: the gated ins_conv outputs [B,96,H/4 .. H/32,.] (released here) -> top-down adds, inp_conv 3x3 + gate, concat (`fuse`; under
+// DET_WANT_NECK also ext[2]), DBHead -> out.  ACT_SIGMOID maps NaN to 0 (the v5 head's fix_nan); on finite input that is the identity, so a
+// head without fix_nan (PP-OCRv3) runs the same tail
+static void rsefpn_db_tail(Builder& b, TView (&in)[4], int B, int H, int W, int flags, const TView& out) {
+    // RSEFPN
+    for (int i = 2; i >= 0; --i) b.upsample(in[i + 1], in[i], 2, true);          // out4, out3, out2 in place
+    TView cat = b.alloc(B, H / 4, W / 4, 96);
+    for (int i = 0; i < 4; ++i) {
+        const std::string p = "neck.inp_conv." + std::to_string(i);
+        TView z = b.conv(p + ".in_conv.weight", "", "", in[i], geom(3), ACT_NONE);
+        b.release(in[i]);
+        const std::string s = p + ".se_block.";
+        TView gate = b.se_gate(s + "conv1.weight", s + "conv1.bias", s + "conv2.weight", s + "conv2.bias", z, ACT_HSIG_PADDLE);
+        TView slot = b.slice(cat, 24 * (3 - i), 24);                             // cat([p5, p4, p3, p2])
+        if (i == 0) {
+            b.scale(z, gate, 1.f, slot);
+        } else {
+            b.scale(z, gate, 1.f, z);
+            b.upsample(z, slot, 1 << i, false);
+        }
+        b.release(gate);
+        b.release(z);
+    }
+    if (flags & DET_WANT_NECK) {
+        TView o = b.external(2, B, cat.h, cat.w, cat.c);
+        b.to_nchw(cat, o);
+    }
+    // DBHead: binarize = 3x3 + BN + ReLU -> transposed 2x2 + BN + ReLU -> transposed 2x2 to one channel -> sigmoid
+    TView c = b.conv("head.binarize.conv1.weight", "", "head.binarize.conv_bn1", cat, geom(3), ACT_RELU);
+    b.release(cat);
+    if (b.deconv_pair_to_prob("head.binarize.conv2.weight", "head.binarize.conv2.bias", "head.binarize.conv_bn2", "head.binarize.conv3.weight",
+                              "head.binarize.conv3.bias", c, out)) {
+        b.release(c);
+    } else {
+        TView u = b.deconv2x2("head.binarize.conv2.weight", "head.binarize.conv2.bias", "head.binarize.conv_bn2", c, ACT_RELU);
+        b.release(c);
+        b.deconv2x2("head.binarize.conv3.weight", "head.binarize.conv3.bias", "", u, ACT_SIGMOID, &out);
+        b.release(u);
+    }
+}
+
 static const Lcv3Cfg kLcv3Det[] = {
     {"blocks2.0", 3, 16, 32, 1, 1, false},
     {"blocks3.0", 3, 32, 48, 2, 2, false},   {"blocks3.1", 3, 48, 48, 1, 1, false},
@@ -978,51 +1028,98 @@ void build_ppocrv5_det_mobile(Builder& b, int B, int H, int W, int flags) {
             TView a = b.lcv3_act(h, pre);
             TView y = b.conv(ins_fold_name(tap) + ".weight", ins_fold_name(tap) + ".bias", "", a, geom(1), ACT_NONE);
             b.release(a);
-            const std::string s = "neck.ins_conv." + std::to_string(tap) + ".se_block.";
-            TView gate = b.se_gate(s + "conv1.weight", s + "conv1.bias", s + "conv2.weight", s + "conv2.bias", y, ACT_HSIG_PADDLE);
-            b.scale(y, gate, 1.f, y);  // y + y*s (shortcut)
-            b.release(gate);
+            rse_gate_shortcut(b, "neck.ins_conv." + std::to_string(tap), y);
             in[tap++] = y;
         }
     }
     b.release(h);
     RD_CHECK(tap == 4 && level == 5, "PPLCNetV3 det: four taps down to 1/32");
 
-    // RSEFPN
-    for (int i = 2; i >= 0; --i) b.upsample(in[i + 1], in[i], 2, true);          // out4, out3, out2 in place
-    TView cat = b.alloc(B, H / 4, W / 4, 96);
-    for (int i = 0; i < 4; ++i) {
-        const std::string p = "neck.inp_conv." + std::to_string(i);
-        TView z = b.conv(p + ".in_conv.weight", "", "", in[i], geom(3), ACT_NONE);
-        b.release(in[i]);
-        const std::string s = p + ".se_block.";
-        TView gate = b.se_gate(s + "conv1.weight", s + "conv1.bias", s + "conv2.weight", s + "conv2.bias", z, ACT_HSIG_PADDLE);
-        TView slot = b.slice(cat, 24 * (3 - i), 24);                             // cat([p5, p4, p3, p2])
-        if (i == 0) {
-            b.scale(z, gate, 1.f, slot);
-        } else {
-            b.scale(z, gate, 1.f, z);
-            b.upsample(z, slot, 1 << i, false);
+    rsefpn_db_tail(b, in, B, H, W, flags, out);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// PP-OCRv3 multilingual det (arch_config.yaml multi_PP-OCRv3_det_mobile = en_PP-OCRv3_det_mobile): MobileNetV3(scale 0.5, large,
+// disable_se; backbones/det_mobilenet_v3.py) -> RSEFPN(96, shortcut) -> DBHead(k 50, no fix_nan).  Externals as build_ppocrv5_det_mobile;
+// DET_WANT_STAGES (developer): ext[3..6] = the four stage features NCHW [B,16,H/4,.], [B,24,H/8,.], [B,56,H/16,.], [B,480,H/32,.].
+// conv1 (3x3 / 2, 3 -> 8) is folded by the stem kernel's builder and writes convolution + bias; its hardswish runs in its consumer - on
+// load in mbv3_block_kernel, or once through lcv3_act where block 0 is unfused (its consumer is then a matrix kernel).
+// A block = expand 1x1 + act -> depthwise k x k / s + act -> linear 1x1 (+ input where s == 1 and cin == cout), every Conv + BatchNorm
+// folded at load time.  Unfused: a ReLU block's expand applies ReLU in the matrix kernel's epilogue (ACT_RELU exists there); a hardswish
+// block's expand writes convolution + bias and the depthwise kernel activates on load, inside the map only (hardswish is not in the
+// shared epilogue: kernels_lcv3.hip says why); the linear layer adds the shortcut in its epilogue.  Fused: mbv3_block_kernel
+// (kernels_mbv3.hip), per block by mbv3_fused_default / RD_MBV3_FUSED.  Every 1x1 route serves these channel counts (K % 4 == 0): no
+// weight is padded.  The four stage outputs are linear (or conv_last + hardswish through lcv3_act) and feed ins_conv[i].in_conv, a plain
+// 1x1 of K = 16 / 24 / 56 / 480 without bias.  head.thresh.* is in the file and unused in eval mode.
+// ---------------------------------------------------------------------------------------------------
+struct Mbv3Cfg { int stage, idx, k, cin, mid, cout, s, act; };
+static const Mbv3Cfg kMbv3Det[15] = {
+    {0, 0, 3, 8, 8, 8, 1, MBV3_RELU},       {0, 1, 3, 8, 32, 16, 2, MBV3_RELU},      {0, 2, 3, 16, 40, 16, 1, MBV3_RELU},
+    {1, 0, 5, 16, 40, 24, 2, MBV3_RELU},    {1, 1, 5, 24, 64, 24, 1, MBV3_RELU},     {1, 2, 5, 24, 64, 24, 1, MBV3_RELU},
+    {2, 0, 3, 24, 120, 40, 2, MBV3_HSWISH}, {2, 1, 3, 40, 104, 40, 1, MBV3_HSWISH},  {2, 2, 3, 40, 96, 40, 1, MBV3_HSWISH},
+    {2, 3, 3, 40, 96, 40, 1, MBV3_HSWISH},  {2, 4, 3, 40, 240, 56, 1, MBV3_HSWISH},  {2, 5, 3, 56, 336, 56, 1, MBV3_HSWISH},
+    {3, 0, 5, 56, 336, 80, 2, MBV3_HSWISH}, {3, 1, 5, 80, 480, 80, 1, MBV3_HSWISH},  {3, 2, 5, 80, 480, 80, 1, MBV3_HSWISH},
+};
+static const char* const kMbv3ConvLast = "backbone.stages.3.3";
+static std::string mbv3_name(const Mbv3Cfg& c) { return "backbone.stages." + std::to_string(c.stage) + "." + std::to_string(c.idx); }
+
+void derive_ppocrv3_det_mobile_weights(WeightStore& ws) {
+    for (const Mbv3Cfg& c : kMbv3Det)       // (conv1 is folded by Builder::stem3x3s2, as every stem here)
+        for (const char* layer : {".expand_conv", ".bottleneck_conv", ".linear_conv"}) fold_conv_bn(ws, mbv3_name(c) + layer, ".conv", ".bn");
+    fold_conv_bn(ws, kMbv3ConvLast, ".conv", ".bn");
+}
+
+void build_ppocrv3_det_mobile(Builder& b, int B, int H, int W, int flags) {
+    RD_CHECK(H % 32 == 0 && W % 32 == 0 && H >= 32 && W >= 32, "det v3 mobile input H, W must be multiples of 32");
+    RD_CHECK((flags & ~(DET_WANT_NECK | DET_WANT_STAGES)) == 0, "det v3 mobile: unknown flag");
+    TView x = b.external(0, B, H, W, 3);
+    TView out = b.external(1, B, H, W, 1);
+
+    TView h = b.stem3x3s2("backbone.conv.conv.weight", "backbone.conv.bn", x, ACT_NONE);
+    bool raw = true;          // h is conv1's convolution + bias: its hardswish is still to come
+    int level = 1, tap = 0;   // level: log2 of the current map's reduction of the page
+    TView in[4];
+    auto ins = [&](const TView& f) {        // a stage output -> ins_conv[tap] + RSE gate, while the stage's buffer is live
+        const std::string p = "neck.ins_conv." + std::to_string(tap);
+        if (flags & DET_WANT_STAGES) b.to_nchw(f, b.external(3 + tap, f.n, f.h, f.w, f.c));
+        TView y = b.conv(p + ".in_conv.weight", "", "", f, geom(1), ACT_NONE);
+        rse_gate_shortcut(b, p, y);
+        in[tap++] = y;
+    };
+    for (int i = 0; i < 15; ++i) {
+        const Mbv3Cfg& c = kMbv3Det[i];
+        const std::string p = mbv3_name(c);
+        RD_CHECK(h.c == c.cin, "MobileNetV3: channel chain: " + p);
+        if (c.s == 2 && i > 2) ins(h);      // (det_mobilenet_v3.py: a stage ends in front of every stride-2 block past the third)
+        const bool shortcut = c.s == 1 && c.cin == c.cout;
+        TView y;
+        if (!b.mbv3_block(p, h, c.k, c.s, c.act, raw, shortcut, level, &y)) {
+            if (raw) {
+                TView a = b.lcv3_act(h, Builder::Affine{});
+                b.release(h);
+                h = a;
+            }
+            const bool relu = c.act == MBV3_RELU;
+            TView e = b.conv(p + ".expand_conv.fold.weight", p + ".expand_conv.fold.bias", "", h, geom(1), relu ? ACT_RELU : ACT_NONE);
+            TView d = b.mbv3_dw(p + ".bottleneck_conv.fold.weight", p + ".bottleneck_conv.fold.bias", e, c.k, c.s, relu ? MBV3_NONE : MBV3_HSWISH, c.act, level);
+            b.release(e);
+            y = b.conv(p + ".linear_conv.fold.weight", p + ".linear_conv.fold.bias", "", d, geom(1), ACT_NONE, nullptr, shortcut ? &h : nullptr);
+            b.release(d);
         }
-        b.release(gate);
-        b.release(z);
+        raw = false;
+        b.release(h);
+        h = y;
+        if (c.s == 2) ++level;
+        RD_CHECK(h.c == c.cout, "MobileNetV3: channel chain: " + p);
     }
-    if (flags & DET_WANT_NECK) {
-        TView o = b.external(2, B, cat.h, cat.w, cat.c);
-        b.to_nchw(cat, o);
-    }
-    // DBHead: binarize = 3x3 + BN + ReLU -> transposed 2x2 + BN + ReLU -> transposed 2x2 to one channel -> sigmoid
-    TView c = b.conv("head.binarize.conv1.weight", "", "head.binarize.conv_bn1", cat, geom(3), ACT_RELU);
-    b.release(cat);
-    if (b.deconv_pair_to_prob("head.binarize.conv2.weight", "head.binarize.conv2.bias", "head.binarize.conv_bn2", "head.binarize.conv3.weight",
-                              "head.binarize.conv3.bias", c, out)) {
-        b.release(c);
-    } else {
-        TView u = b.deconv2x2("head.binarize.conv2.weight", "head.binarize.conv2.bias", "head.binarize.conv_bn2", c, ACT_RELU);
-        b.release(c);
-        b.deconv2x2("head.binarize.conv3.weight", "head.binarize.conv3.bias", "", u, ACT_SIGMOID, &out);
-        b.release(u);
-    }
+    TView t = b.conv(std::string(kMbv3ConvLast) + ".fold.weight", std::string(kMbv3ConvLast) + ".fold.bias", "", h, geom(1), ACT_NONE);
+    b.release(h);
+    TView last = b.lcv3_act(t, Builder::Affine{});
+    b.release(t);
+    ins(last);
+    b.release(last);
+    RD_CHECK(tap == 4 && level == 5, "MobileNetV3 det: four stages down to 1/32");
+    rsefpn_db_tail(b, in, B, H, W, flags, out);
 }
 
 }  // namespace rd

@@ -254,6 +254,41 @@ struct Lcv3BlockParams {
 };
 bool lcv3_block_shape_ok(int cin, int cout);      // (16, 32), (32, 64), (64, 64)
 void launch_lcv3_block(const Lcv3BlockParams& p, hipStream_t s);
+// MobileNetV3 in the detector geometry (kernels_mbv3.hip; PP-OCRv3 multilingual detector).  Activations of its layers:
+enum Mbv3Act : int { MBV3_NONE = 0, MBV3_RELU = 1, MBV3_HSWISH = 2 };
+// Depthwise layer: y = post(dw_kxk(pre(x)) + bias), zero padding around pre(x) (the producer's activation touches the elements INSIDE the
+// map only); k = 3 / 5, stride (1,1) / (2,2), C % 4 == 0, OH = (H - 1) / S + 1
+struct Mbv3DwParams {
+    const float* x; int xld;
+    int N, H, W, C;
+    const float* w;      // [K*K][C]
+    const float* bias;   // [C]
+    float* y; int yld;
+    int OH, OW, K, S;
+    int pre_act, post_act;   // Mbv3Act
+    int max_blocks = 0;      // > 0: cap of the grid (default 65536 workgroups; the kernel walks the rest in a grid-stride loop)
+};
+bool mbv3_dw_shape_ok(int k, int s, int c);
+bool mbv3_dw_launch_ok(const Mbv3DwParams& p);    // shape, strides and 16-byte alignment of every pointer that is set
+bool launch_mbv3_dw(const Mbv3DwParams& p, hipStream_t s);   // false: not launched (launch_ok says no, or a pointer is null)
+// One inverted-residual block without SE in one launch, all fp32: y = act(dw_kxk(pad0(act(x' We^T + be))) + bd) Wl^T + bl (+ x'),
+// x' = in_hswish ? hardswish(x) : x.  The expanded tensor never leaves the chip.
+struct Mbv3BlockParams {
+    const float* x; int xld;
+    int N, H, W, cin, mid, cout;
+    const float* we; const float* be;   // expand [mid][cin], [mid]
+    const float* wd; const float* bd;   // depthwise [K*K][mid], [mid]
+    const float* wl; const float* bl;   // linear [cout][mid], [cout]
+    float* y; int yld;
+    int OH, OW, K, S;
+    int act;         // MBV3_RELU / MBV3_HSWISH: the expand and the depthwise layer's activation
+    int in_hswish;   // x is convolution + bias of a hardswish layer (conv1): activated on load, for the expand and the shortcut alike
+    int shortcut;    // y += x' (stride 1 and cin == cout only)
+};
+// what the kernel serves: k 3 / 5, stride 1 / 2, cin % 4, mid % 8, cout % 8, at most 80 KB of LDS for the tile of (k, stride), 16-byte
+// aligned views, a non-empty map, OH / OW as above, a grid below 2^31 workgroups.  Null pointers pass (a planner fills them in later)
+bool mbv3_block_launch_ok(const Mbv3BlockParams& p);
+bool launch_mbv3_block(const Mbv3BlockParams& p, hipStream_t s);   // false: not launched (launch_ok says no, or a pointer is null)
 // partial[n][h][c] = sum over w < line_w[n * stride] (or W) of x[n][h][w][c]: the SE pooling partial sums, one chunk per map row
 bool lcv3_gap_shape_ok(int c);      // c % 4 == 0, c <= 4096
 void launch_lcv3_gap_rows(const float* x, int xld, int N, int H, int W, int C, float* partial, const int32_t* line_w, int stride, hipStream_t s);

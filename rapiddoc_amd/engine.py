@@ -15,9 +15,10 @@ from . import _lib, weights as W
 REC_UNFUSED_CTC, REC_WANT_SOFTMAX, REC_WANT_LOGITS = 1, 2, 4
 REC_WANT_NECK = 64          # ppocrv5_rec_server / ppocrv5_rec_mobile: `full` receives the neck's output [B, T, 120] instead (ppocr_rec_mv1e: [B, T, 64])
 REC_NECK_DIMS = {"ppocr_rec_mv1e": 64}      # the SVTR neck's `dims` where it is not 120
-DET_WANT_NECK = 1           # ppocrv5_det_server / ppocrv5_det_mobile: also hand out the neck's output `fuse` [B, 256 / 96, H/4, W/4]
+DET_WANT_NECK = 1           # ppocrv5_det_server / ppocrv5_det_mobile / ppocrv3_det_mobile: also hand out the neck's output `fuse` [B, 256 / 96, H/4, W/4]
 DET_NECK_CHANNELS = {"ppocrv5_det_server": 256, "ppocrv5_det_mobile": 96}
-KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "ppocr_rec_mv1e", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
+DET_NECK_CHANNELS_V3_MOBILE = {"ppocrv3_det_mobile": 96}    # the PP-OCRv3 multilingual detector: the same RSEFPN
+KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv3_det_mobile", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "ppocr_rec_mv1e", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
 
 
 def rec_line_table(widths, first_tokens) -> np.ndarray:
@@ -157,10 +158,10 @@ class RdEngine:
             x = x.contiguous().float()
         return x
 
-    def det_forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, after_launch=None, want_neck: bool = False):
+    def det_forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, after_launch=None, want_neck: bool = False, want_stages: bool = False):
         """Either detector kind.  `out` / `after_launch`: as in `rec_forward` (a caller-owned [B,1,H,W] float32 result tensor; work
-        enqueued behind the launch).  `want_neck` (ppocrv5_det_server / ppocrv5_det_mobile): returns (maps, fuse [B,256 / 96,H/4,W/4])
-        through rd_det_forward_ex."""
+        enqueued behind the launch).  `want_neck` (ppocrv5_det_server / ppocrv5_det_mobile / ppocrv3_det_mobile): returns (maps, fuse [B,256 / 96,H/4,W/4])
+        through rd_det_forward_ex.  `want_stages` (developer, ppocrv3_det_mobile; rd_debug_det_forward_stages): returns (maps, fuse, [the four stage features NCHW])."""
         x = self._prep(x)
         B, Cc, H, W_ = x.shape
         if out is None:
@@ -168,9 +169,27 @@ class RdEngine:
         elif out.shape != (B, 1, H, W_) or out.dtype != torch.float32 or not out.is_contiguous():
             raise EngineError("det_forward: `out` does not match the forward's shape")
 
-        if want_neck and self.kind not in DET_NECK_CHANNELS:
-            raise EngineError(f"det_forward: want_neck is offered by {sorted(DET_NECK_CHANNELS)} only")
-        neck = torch.empty((B, DET_NECK_CHANNELS[self.kind], H // 4, W_ // 4), dtype=torch.float32, device=x.device) if want_neck else None
+        if want_stages:
+            if self.kind != "ppocrv3_det_mobile":
+                raise EngineError("det_forward: want_stages is offered by ppocrv3_det_mobile only")
+            shapes = [(B, 96, H // 4, W_ // 4), (B, 16, H // 4, W_ // 4), (B, 24, H // 8, W_ // 8), (B, 56, H // 16, W_ // 16), (B, 480, H // 32, W_ // 32)]
+            sizes = [int(np.prod(s)) for s in shapes]
+            aux = torch.empty((sum(sizes),), dtype=torch.float32, device=x.device)
+
+            def launch_stages():
+                fn = self._l.rd_debug_det_forward_stages       # developer entry, not in the public header
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+                self._chk(fn(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), aux.data_ptr(), _stream_ptr()))
+                self._log()
+            self._guarded(launch_stages)
+            parts = [t.view(s) for t, s in zip(torch.split(aux, sizes), shapes)]
+            return out, parts[0], parts[1:]
+
+        neck_channels = {**DET_NECK_CHANNELS, **DET_NECK_CHANNELS_V3_MOBILE}
+        if want_neck and self.kind not in neck_channels:
+            raise EngineError(f"det_forward: want_neck is offered by {sorted(neck_channels)} only")
+        neck = torch.empty((B, neck_channels[self.kind], H // 4, W_ // 4), dtype=torch.float32, device=x.device) if want_neck else None
 
         def launch():
             if want_neck:

@@ -118,7 +118,8 @@ class PagePipeline:
                  rec_mode: Optional[str] = None, rec_chunking: Optional[str] = None):
         """`states`: {'ppocrv6_det': ..., 'ppocrv6_rec': ..., 'pphgnetv2_b4': ...}, each a .safetensors path,
         bytes, or name->ndarray dict.  The detector may be given as 'ppocrv5_det_server' instead of 'ppocrv6_det' (PPHGNetV2-B4 + LKPAN +
-        PFHeadLocal) or as 'ppocrv5_det_mobile' (PPLCNetV3 + RSEFPN + DBHead); exactly one of the three, exposed as `det_kind`: pre-process, DB post-process, prefetch and the range guard do not
+        PFHeadLocal) or as 'ppocrv5_det_mobile' (PPLCNetV3 + RSEFPN + DBHead) or as 'ppocrv3_det_mobile' (MobileNetV3 + RSEFPN + DBHead: the multilingual and the
+        English PP-OCRv3 files); exactly one of the four, exposed as `det_kind`: pre-process, DB post-process, prefetch and the range guard do not
         care which network drew the map.  The recogniser may be given as 'ppocrv5_rec_server' instead of 'ppocrv6_rec' (PPHGNetV2-B4 +
         SVTR neck + CTC): strict mode then runs the backbone stage once per distinct reference width (that kind has no per-line widths
         inside a launch), everything behind the token buffer - the ragged tail, the collapse, word boxes - is the same.  Or as
@@ -164,9 +165,9 @@ class PagePipeline:
         # (reuse_outputs: the engines hand out the same output tensors for the same shape - every result is consumed inside the
         #  step that produced it - so that buffer addresses repeat from step to step and the library replays a forward as ONE
         #  hipGraph launch; the buffers this class owns are kept per role for the same reason, `_buf`)
-        det_kinds = [k for k in ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile") if k in states]
+        det_kinds = [k for k in ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv3_det_mobile") if k in states]
         if len(det_kinds) != 1:
-            raise ValueError("states must carry exactly one detector: 'ppocrv6_det' or 'ppocrv5_det_server' or 'ppocrv5_det_mobile'")
+            raise ValueError("states must carry exactly one detector: 'ppocrv6_det' or 'ppocrv5_det_server' or 'ppocrv5_det_mobile' or 'ppocrv3_det_mobile'")
         self.det_kind = det_kinds[0]
         self.det = RdEngine(self.det_kind, device, guard="deferred", reuse_outputs=True).load_weights(states[self.det_kind])
         # rec batches are independent: they alternate between `n_rec_streams` HIP streams (one engine handle = one

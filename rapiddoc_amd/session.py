@@ -113,6 +113,12 @@ DET_ARCH_BY_STEM = {
 DET_ARCH_BY_STEM_V5_MOBILE = {
     "ch_PP-OCRv5_det_mobile": "ppocrv5_det_mobile",
 }
+# ... and the PP-OCRv3 multilingual detector (MobileNetV3 + RSEFPN + DBHead), the detector the ten multilingual recognisers are shipped
+# with; the English file is the same graph
+DET_ARCH_BY_STEM_V3_MOBILE = {
+    "multi_PP-OCRv3_det_mobile": "ppocrv3_det_mobile",
+    "en_PP-OCRv3_det_mobile": "ppocrv3_det_mobile",
+}
 
 
 def _state_keys(weights) -> set:
@@ -131,10 +137,12 @@ def resolve_det_kind(weights: WeightSrc) -> str:
     """Engine kind of a detector's weights, built like `resolve_rec_kind`: a file goes by its stem (an unknown one is an error), a state
     dict or a nameless safetensors image by the head it carries (`head.cbn_layer.last_1.weight`: PFHeadLocal of the v5 server detector;
     `head.conv_down.convolution.weight`: the v6 DB head; `backbone.layer_list.0.weight` with `head.binarize.conv1.weight`: PPLCNetV3's
-    det taps in front of the plain DB head of the v5 mobile detector)."""
+    det taps in front of the plain DB head of the v5 mobile detector; `backbone.stages.0.0.expand_conv.conv.weight` with
+    `head.binarize.conv1.weight`: MobileNetV3's first inverted-residual block in front of the same head, the PP-OCRv3 multilingual
+    detector).  The plain DB head alone names no backbone and is refused."""
     if isinstance(weights, (str, Path)):
         stem = Path(str(weights)).stem
-        served = {**DET_ARCH_BY_STEM, **DET_ARCH_BY_STEM_V5_MOBILE}
+        served = {**DET_ARCH_BY_STEM, **DET_ARCH_BY_STEM_V5_MOBILE, **DET_ARCH_BY_STEM_V3_MOBILE}
         if stem not in served:
             raise ValueError(f"architecture {stem} is not in the detectors this engine serves {sorted(served)}")
         return served[stem]
@@ -145,12 +153,15 @@ def resolve_det_kind(weights: WeightSrc) -> str:
         return "ppocrv6_det"
     if "backbone.layer_list.0.weight" in keys and "head.binarize.conv1.weight" in keys:
         return "ppocrv5_det_mobile"
+    if "backbone.stages.0.0.expand_conv.conv.weight" in keys and "head.binarize.conv1.weight" in keys:
+        return "ppocrv3_det_mobile"
     raise ValueError("architecture of the detector weights is not in the detectors this engine serves (none of head.cbn_layer.last_1.weight, "
-                     "head.conv_down.convolution.weight, backbone.layer_list.0.weight + head.binarize.conv1.weight among the tensors)")
+                     "head.conv_down.convolution.weight, backbone.layer_list.0.weight + head.binarize.conv1.weight, "
+                     "backbone.stages.0.0.expand_conv.conv.weight + head.binarize.conv1.weight among the tensors)")
 
 
 class Mi355DetSession(_BaseSession):
-    """PP-OCRv6 small / PP-OCRv5 server / PP-OCRv5 mobile det: [B,3,H,W] -> DB probability map [B,1,H,W] (`maps`, ocr/torch.py:183-184).  The kind
+    """PP-OCRv6 small / PP-OCRv5 server / PP-OCRv5 mobile / PP-OCRv3 multilingual det: [B,3,H,W] -> DB probability map [B,1,H,W] (`maps`, ocr/torch.py:183-184).  The kind
     follows from the weights (`resolve_det_kind`) unless `kind` names it."""
     kind = "ppocrv6_det"
 

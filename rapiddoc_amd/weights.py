@@ -51,6 +51,14 @@ def _mv1e_gains():
 
 
 _KIND_GAINS["ppocr_rec_mv1e"] = _mv1e_gains()
+# PP-OCRv3 multilingual detector (MobileNetV3 large scale 0.5 without SE): the residual blocks at 1/16 add up (stage features 50-100, `fuse`
+# 300 under the plain rule); damping their linear layers keeps the stage features O(5-30), and the last transposed convolution is spread so
+# that the shrink logit fills (0, 1) at page size
+_KIND_GAINS["ppocrv3_det_mobile"] = (
+    (lambda n: n.startswith("backbone.stages.2.") and n.endswith(".linear_conv.conv.weight"), 0.7),
+    (lambda n: n.startswith("backbone.stages.3.") and n.endswith(".linear_conv.conv.weight"), 0.7),
+    (lambda n: n == "head.binarize.conv3.weight", 3.0),
+)
 _NORM_TOKENS = (".normalization.", ".norm.", ".bn.", "layer_norm", ".norm1.", ".norm2.")
 
 
