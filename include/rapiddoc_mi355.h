@@ -44,7 +44,8 @@ typedef struct rd_handle rd_handle;
 const char* rd_version(void);
 /* model_kind: "ppocrv6_det" | "ppocrv5_det_server" (PPHGNetV2-B4 + LKPAN + PFHeadLocal; rd_det_forward / rd_det_forward_ex) |
  * "ppocrv5_det_mobile" (PPLCNetV3 scale 0.75 + RSEFPN + DBHead; the same two calls) |
- * "ppocrv3_det_mobile" (MobileNetV3 large scale 0.5 without SE + RSEFPN + DBHead - multi_ / en_PP-OCRv3_det_mobile; the same two calls) | "ppocrv6_rec" | "ppocrv5_rec_server" (PPHGNetV2-B4 + SVTR neck + CTC; every rd_rec_* call except
+ * "ppocrv3_det_mobile" (MobileNetV3 large scale 0.5 without SE + RSEFPN + DBHead - multi_ / en_PP-OCRv3_det_mobile; the same two calls) |
+ * "ppocr_cls_mobile" (MobileNetV3 small scale 0.35 with squeeze-excite + ClsHead - ch_ptocr_mobile_v2.0_cls_mobile, the 0 / 180 degree text-line classifier; rd_cls_forward) | "ppocrv6_rec" | "ppocrv5_rec_server" (PPHGNetV2-B4 + SVTR neck + CTC; every rd_rec_* call except
  * rd_rec_backbone_forward_lines) | "ppocrv5_rec_mobile" (PPLCNetV3 scale 0.95 + the same SVTR neck + CTC; every rd_rec_* call) | "ppocr_rec_mv1e" (MobileNetV1Enhance scale 0.5 + SVTR neck dims 64 + CTC:
  * the ten multilingual PP-OCRv3 / v4 mobile files latin_ / cyrillic_ / chinese_cht_PP-OCRv3_rec_mobile, arabic_ / korean_ / japan_ / ta_ / te_ / ka_ /
  * devanagari_PP-OCRv4_rec_mobile, which differ in their class count only; every rd_rec_* call) | "pphgnetv2_b4" | "pphgnetv2_b6_formula" | "ppformulanet_head".  NULL on failure -> rd_create_error(). */
@@ -179,6 +180,20 @@ int rd_line_warp_batch(int device_id, const uint8_t* pages_u8_dev, int P, int H,
                        int64_t max_crop_pixels, uint8_t* scratch_u8_dev, void* stream);
 int rd_line_resize_norm_batch(int device_id, const rd_line_crop_desc* descs_dev, int n, const uint8_t* scratch_u8_dev, int out_h,
                               int out_w_padded, int swap_rb, float* out_nchw_dev, void* stream);
+
+/* Text-line direction classifier ("ppocr_cls_mobile"): x [B,3,H,W] (rapidocr's classifier pre-process gives 48 x 192) -> the head's softmax
+ * [B,2] = (P(0 deg), P(180 deg)), the tensor the reference session returns for this graph.  flags 0, or RD_CLS_WANT_AUX: aux_dev also
+ * receives per line [2 logits | 200 pooled features] (B x 202 floats).  An H, W that leaves an empty map in front of the 2 x 2 max-pool
+ * (H < 33 or W < 3) fails, and rd_last_error says so.  rd_query_workspace takes the same B, H, W, flags. */
+#define RD_CLS_WANT_AUX 1
+int rd_cls_forward(rd_handle* h, const float* x_nchw_dev, int B, int H, int W, float* prob_b2_dev, int flags, float* aux_dev, void* ws_dev,
+                   size_t ws_bytes, void* stream);
+/* The classifier's verdict applied on the device, between rd_line_warp_batch and rd_line_resize_norm_batch: every line with
+ * prob[1] > prob[0] and prob[1] >= thresh has its packed uint8 crop in scratch_u8_dev turned by 180 degrees in place
+ * (cv2.rotate(ROTATE_180): the pixel order reversed); flipped_out_dev[i] = 1 for those lines, 0 for the others.  The scratch holds the
+ * crop BEFORE the optional rot90; two rotations commute, so this equals turning the crop the classifier saw. */
+int rd_line_flip180_batch(int device_id, const rd_line_crop_desc* descs_dev, int n, const float* cls_prob_n2_dev, float thresh,
+                          uint8_t* scratch_u8_dev, int32_t* flipped_out_dev, void* stream);
 
 /* CTC greedy decode on the device (replaces rapidocr CTCLabelDecode's per-line loop, called from
  * rapid_doc/model/ocr/rapid_ocr.py:444-449): idx / prob [B][T] as rd_rec_forward wrote them -> per line, at out + b * row_bytes:

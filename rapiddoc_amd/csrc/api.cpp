@@ -1,6 +1,7 @@
 // extern "C" surface of librapiddoc_mi355.so - see include/rapiddoc_mi355.h for the contract.
 #include "../../include/rapiddoc_mi355.h"
 
+#include <algorithm>
 #include <mutex>
 #include <string>
 
@@ -146,6 +147,44 @@ int rd_debug_det_forward_stages(rd_handle* h, const float* x, int B, int H, int 
         }
         h->eng->run(B, H, W, rd::DET_WANT_NECK | rd::DET_WANT_STAGES, ext, nullptr, 0, (hipStream_t)stream);
     });
+}
+
+int rd_cls_forward(rd_handle* h, const float* x, int B, int H, int W, float* prob, int flags, float* aux, void* ws, size_t ws_bytes, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->eng && h->eng->kind() == "ppocr_cls_mobile", "handle is not a text-line classifier (ppocr_cls_mobile) model");
+        RD_CHECK(x && prob && B > 0, "null input/output");
+        RD_CHECK((flags & ~RD_CLS_WANT_AUX) == 0, "rd_cls_forward: unknown flag");
+        RD_CHECK(!(flags & RD_CLS_WANT_AUX) || aux, "aux_dev is NULL");
+        h->eng->run(B, H, W, flags, {(void*)x, (void*)prob, (void*)aux}, ws, ws_bytes, (hipStream_t)stream);
+    });
+}
+
+// developer entry ("ppocr_cls_mobile" only): rd_cls_forward with RD_CLS_WANT_AUX plus the outputs of blocks 0, 3, 8, 10, written as NCHW back
+// to back into stages_dev ([B,8,r0,w], [B,16,r1,w], [B,32,r2,w], [B,32,r3,w]: rd::cls_mobile_geometry).  The internal workspace.  Not part
+// of the public header.
+int rd_debug_cls_forward_stages(rd_handle* h, const float* x, int B, int H, int W, float* prob, float* aux, float* stages, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->eng && h->eng->kind() == "ppocr_cls_mobile", "handle is not a ppocr_cls_mobile model");
+        RD_CHECK(x && prob && aux && stages && B > 0, "null input/output");
+        int rows[4], cols = 0;
+        RD_CHECK(rd::cls_mobile_geometry(H, W, rows, &cols), "text-line classifier: H x W leaves an empty map");
+        static const int kC[4] = {8, 16, 32, 32};
+        std::vector<void*> ext = {(void*)x, (void*)prob, (void*)aux};
+        float* q = stages;
+        for (int i = 0; i < 4; ++i) {
+            ext.push_back(q);
+            q += (size_t)B * kC[i] * rows[i] * cols;
+        }
+        h->eng->run(B, H, W, rd::CLS_WANT_AUX | rd::CLS_WANT_STAGES, ext, nullptr, 0, (hipStream_t)stream);
+    });
+}
+
+int rd_line_flip180_batch(int device_id, const rd_line_crop_desc* descs, int n, const float* cls_prob, float thresh, uint8_t* scratch,
+                          int32_t* flipped_out, void* stream) {
+    if (!descs || !cls_prob || !scratch || !flipped_out || n < 0) return 1;
+    if (hipSetDevice(device_id) != hipSuccess) return 1;
+    if (rd::launch_line_flip180(reinterpret_cast<const rd::LineCropDesc*>(descs), n, cls_prob, thresh, scratch, flipped_out, (hipStream_t)stream) != 0) return 1;
+    return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 int rd_rec_forward(rd_handle* h, const float* x, int B, int W, int32_t* idx, float* prob, float* full, int flags, void* ws,
@@ -921,6 +960,85 @@ int rd_debug_mbv3_block_ok(int N, int H, int W, int cin, int mid, int cout, int 
     p.K = K; p.S = S; p.OH = (H - 1) / S + 1; p.OW = (W - 1) / S + 1;
     p.act = act; p.shortcut = shortcut;
     return rd::mbv3_block_launch_ok(p) ? 1 : 0;
+}
+
+// developer entry: one MobileNetV3-small depthwise layer through launch_mbv3s_dw (kernels_mbv3s.hip; x NHWC fp32 [N][H][W][xld >= C], w [K*K][C],
+// bias [C], y [N][OH][OW][yld >= C], OH = (H - 1) / SH + 1, OW = (W - 1) / SW + 1; pre_act / post_act / max_blocks as rd_debug_mbv3_dw).
+// Returns ms per launch, < 0: not served (mbv3s_dw_launch_ok).
+float rd_debug_mbv3s_dw(int N, int H, int W, int C, int K, int SH, int SW, int pre_act, int post_act, int xld, int yld, int iters, int max_blocks, float* x,
+                        float* w, float* bias, float* y) {
+    if (SH < 1 || SW < 1) return -1.f;
+    rd::Mbv3sDwParams p{};
+    p.x = x; p.xld = xld; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = yld;
+    p.K = K; p.SH = SH; p.SW = SW; p.OH = (H - 1) / SH + 1; p.OW = (W - 1) / SW + 1;
+    p.pre_act = pre_act; p.post_act = post_act; p.max_blocks = max_blocks;
+    if (!x || !w || !bias || !y || !rd::mbv3s_dw_launch_ok(p)) return -1.f;
+    return rd_debug_time(iters, [&] { (void)rd::launch_mbv3s_dw(p, nullptr); });
+}
+
+// developer entry: one MobileNetV3-small inverted-residual block with optional squeeze-excite on caller-supplied FOLDED weights, through the
+// operators the engine's plan chains for it (route 0) or through cls_block_kernel, the block as the one-launch classifier runs it (route 1).
+// Route 0: fp32 1x1 (launch_conv_igemm; a ReLU block activates in its
+// epilogue, a hardswish block in the depthwise kernel's load) -> launch_mbv3s_dw -> [launch_gap_partial -> launch_se_fc with the paddle
+// hard-sigmoid -> launch_scale_channels] -> fp32 1x1 (+ x).  x NHWC [N][H][W][xld >= cin], we [mid][cin], be [mid], wd [K*K][mid], bd [mid],
+// w1 [mid/4][mid], b1 [mid/4], w2 [mid][mid/4], b2 [mid] (se != 0), wl [cout][mid], bl [cout], y [N][OH][W][yld >= cout]; act 1 ReLU / 2
+// hardswish.  Temporaries are allocated per call.  Returns ms per block, < 0: not served (another route, a geometry a kernel declines,
+// or no memory).
+float rd_debug_mbv3s_block(int route, int N, int H, int W, int cin, int mid, int cout, int K, int SH, int act, int se, int shortcut, int xld, int yld,
+                           int iters, float* x, float* we, float* be, float* wd, float* bd, float* w1, float* b1, float* w2, float* b2, float* wl,
+                           float* bl, float* y) {
+    if ((route != 0 && route != 1) || SH < 1 || N < 1 || H < 1 || W < 1 || cin % 4 != 0 || mid % 8 != 0 || cout % 4 != 0 || mid > 512) return -1.f;
+    if (act != rd::MBV3_RELU && act != rd::MBV3_HSWISH) return -1.f;
+    if (shortcut && (SH != 1 || cin != cout)) return -1.f;
+    if (!x || !we || !be || !wd || !bd || !wl || !bl || !y || (se && (!w1 || !b1 || !w2 || !b2))) return -1.f;
+    if (route == 1) {       // the block as cls_line_kernel runs it, one workgroup per image
+        rd::ClsBlockParams L{};
+        L.we = we; L.be = be; L.wd = wd; L.bd = bd; L.w1 = w1; L.b1 = b1; L.w2 = w2; L.b2 = b2; L.wl = wl; L.bl = bl;
+        L.k = K; L.cin = cin; L.mid = mid; L.cout = cout; L.sh = SH; L.se = se ? 1 : 0; L.act = act; L.shortcut = shortcut ? 1 : 0;
+        if (!rd::cls_block_plan(L, H, W) || !rd::cls_block_launch_ok(L, N, H, W, xld, yld)) return -1.f;
+        float* scratch = nullptr;
+        if (hipMalloc((void**)&scratch, (size_t)std::min(N, 512) * rd::cls_block_scratch_floats(L, H, W) * sizeof(float)) != hipSuccess) return -1.f;
+        const float t = rd_debug_time(iters, [&] { (void)rd::launch_cls_block(L, x, xld, y, yld, N, H, W, scratch, nullptr); });
+        (void)hipFree(scratch);
+        return t;
+    }
+    const int OH = (H - 1) / SH + 1, hw = OH * W;
+    const int chunks = std::max(1, std::min(64, hw / 256));
+    const size_t ne = (size_t)N * H * W * mid, nd = (size_t)N * OH * W * mid, np = (size_t)N * chunks * mid, ng = (size_t)N * mid;
+    float* tmp = nullptr;
+    if (hipMalloc((void**)&tmp, (ne + nd + np + ng) * sizeof(float)) != hipSuccess) return -1.f;
+    float *e = tmp, *d = e + ne, *partial = d + nd, *gate = partial + np;
+    rd::Mbv3sDwParams q{};
+    q.x = e; q.xld = mid; q.N = N; q.H = H; q.W = W; q.C = mid; q.w = wd; q.bias = bd; q.y = d; q.yld = mid;
+    q.K = K; q.SH = SH; q.SW = 1; q.OH = OH; q.OW = W;
+    q.pre_act = act == rd::MBV3_RELU ? rd::MBV3_NONE : rd::MBV3_HSWISH; q.post_act = act;
+    if (!rd::mbv3s_dw_launch_ok(q)) {
+        (void)hipFree(tmp);
+        return -1.f;
+    }
+    auto pointwise = [&](const float* in, int ild, int pixels_h, int ci, const float* w, const float* b, float* out, int old, int co, int a, const float* res) {
+        rd::ConvParams c{};
+        c.x = in; c.xld = ild; c.N = N; c.H = pixels_h; c.W = W; c.Cin = ci; c.w = w; c.bias = b; c.y = out; c.yld = old;
+        c.OH = pixels_h; c.OW = W; c.Cout = co; c.KH = c.KW = c.SH = c.SW = 1;
+        c.res = res; c.rld = res ? xld : 0; c.act = a; c.out_mode = rd::OUT_NHWC;
+        c.M = N * pixels_h * W; c.K = ci; c.Ng = co;
+        rd::launch_conv_igemm(c, nullptr);
+    };
+    const float ms = rd_debug_time(iters, [&] {
+        pointwise(x, xld, H, cin, we, be, e, mid, mid, act == rd::MBV3_RELU ? rd::ACT_RELU : rd::ACT_NONE, nullptr);
+        (void)rd::launch_mbv3s_dw(q, nullptr);
+        if (se) {
+            rd::launch_gap_partial(d, mid, N, hw, mid, partial, chunks, nullptr);
+            rd::SeFcParams f{};
+            f.partial = partial; f.chunks = chunks; f.N = N; f.C = mid; f.Cr = mid / 4; f.inv_hw = 1.f / (float)hw;
+            f.w1 = w1; f.b1 = b1; f.w2 = w2; f.b2 = b2; f.gate = rd::ACT_HSIG_PADDLE; f.scale = gate; f.H = OH;
+            rd::launch_se_fc(f, nullptr);
+            rd::launch_scale_channels(d, mid, d, mid, gate, 0.f, N, hw, mid, nullptr);
+        }
+        pointwise(d, mid, OH, mid, wl, bl, y, yld, cout, rd::ACT_NONE, shortcut ? x : nullptr);
+    });
+    (void)hipFree(tmp);
+    return ms;
 }
 
 // developer entry: one PPLCNetV3 depthwise layer in the detector geometry (x NHWC fp32 [N][H][W][C], w [K*K][C], bias [C], y [N][OH][OW][C] with

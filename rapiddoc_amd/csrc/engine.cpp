@@ -1431,6 +1431,157 @@ bool Builder::mbv3_block(const std::string& prefix, const TView& x, int k, int s
     return true;
 }
 
+// ---- MobileNetV3 small in the text-line geometry (kernels_mbv3s.hip)
+TView Builder::mbv3s_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, int pre_act, int post_act) {
+    const HostTensor& w = ws_->get(wname);
+    RD_CHECK(w.shape.size() == 4 && w.shape[1] == 1 && w.shape[2] == k && w.shape[3] == k, "mbv3s depthwise weight shape: " + wname);
+    const int c = (int)w.shape[0];
+    RD_CHECK(c == x.c && mbv3s_dw_shape_ok(k, sh, sw, c), "mbv3s depthwise geometry: " + wname);
+    RD_CHECK(!has_lt_, "mbv3s depthwise: no line table");
+    const int oh = (x.h - 1) / sh + 1, ow = (x.w - 1) / sw + 1;
+    TView y = alloc(x.n, oh, ow, c);
+    const std::string key = wname + "|mbv3sdw";
+    if (!planning()) {
+        if (!pb_->has(key + "#w")) {
+            std::vector<float> wf((size_t)k * k * c);
+            for (int ch = 0; ch < c; ++ch)
+                for (int t = 0; t < k * k; ++t) wf[(size_t)t * c + ch] = w.f32()[(size_t)ch * k * k + t];
+            pb_->add(key + "#w", wf);
+            pb_->add(key + "#b", std::vector<float>(ws_->get(bname).f32(), ws_->get(bname).f32() + c));
+        }
+        return y;
+    }
+    Mbv3sDwParams p{};
+    p.xld = plan_->ld(x);
+    p.N = x.n; p.H = x.h; p.W = x.w; p.C = c;
+    p.w = pb_->ptr(key + "#w");
+    p.bias = pb_->ptr(key + "#b");
+    p.yld = plan_->ld(y);
+    p.OH = oh; p.OW = ow; p.K = k; p.SH = sh; p.SW = sw;
+    p.pre_act = pre_act; p.post_act = post_act;
+    RD_CHECK(mbv3s_dw_launch_ok(p) && x.coff % 4 == 0 && y.coff % 4 == 0, "mbv3s depthwise: 16-byte aligned pixels: " + wname);
+    static const char* const kActName[3] = {"none", "relu", "hswish"};
+    OpRecord r;
+    r.name = wname;
+    r.kind = "mbv3s_dw" + std::to_string(k) + "x" + std::to_string(k);
+    r.cfg = "s" + std::to_string(sh) + std::to_string(sw) + "/" + kActName[pre_act] + ">" + kActName[post_act];
+    r.shape = "N" + std::to_string(x.n) + "_" + std::to_string(x.h) + "x" + std::to_string(x.w) + "_C" + std::to_string(c);
+    r.flops = 2.0 * x.n * oh * ow * (double)c * k * k;
+    r.bytes = 4.0 * ((double)x.pixels() * c + (double)y.pixels() * c);
+    const TView xv = x, yv = y;
+    r.run = [p, xv, yv](const Plan& pl, const RunCtx& cx) {
+        Mbv3sDwParams q = p;
+        q.x = pl.vptr(xv, cx);
+        q.y = pl.vptr(yv, cx);
+        (void)launch_mbv3s_dw(q, cx.stream);      // (servable: checked above)
+    };
+    emit(std::move(r));
+    return y;
+}
+
+void Builder::cls_tail(const std::string& prefix, const TView& x, const TView& prob_ext, const TView* aux_ext) {
+    const HostTensor& w = ws_->get(prefix + ".weight");
+    RD_CHECK(w.shape.size() == 2 && w.shape[0] == 2 && (int)w.shape[1] == x.c, "classifier head: Linear C -> 2: " + prefix);
+    RD_CHECK(prob_ext.pixels() * prob_ext.c == (long)x.n * 2, "classifier head: probability view");
+    if (aux_ext) RD_CHECK(aux_ext->pixels() * aux_ext->c == (long)x.n * (2 + x.c), "classifier head: aux view");
+    const std::string key = prefix + "|clstail";
+    if (!planning()) {
+        if (!pb_->has(key + "#w")) {
+            pb_->add(key + "#w", std::vector<float>(w.f32(), w.f32() + w.numel()));
+            pb_->add(key + "#b", std::vector<float>(ws_->get(prefix + ".bias").f32(), ws_->get(prefix + ".bias").f32() + 2));
+        }
+        return;
+    }
+    ClsTailParams p{};
+    p.xld = plan_->ld(x);
+    p.N = x.n; p.H = x.h; p.W = x.w; p.C = x.c;
+    p.w = pb_->ptr(key + "#w");
+    p.bias = pb_->ptr(key + "#b");
+    RD_CHECK(cls_tail_launch_ok(p), "classifier head: the map behind the backbone has no 2 x 2 window (or more than 1024 channels)");
+    OpRecord r;
+    r.name = prefix;
+    r.kind = "cls_tail";
+    r.cfg = "hswish>maxpool2>gap>fc2>softmax";
+    r.shape = "N" + std::to_string(x.n) + "_" + std::to_string(x.h) + "x" + std::to_string(x.w) + "_C" + std::to_string(x.c);
+    r.flops = (double)x.n * (4.0 * x.c + 5.0 * x.h * x.w * x.c);
+    r.bytes = 4.0 * (double)x.pixels() * x.c;
+    const TView xv = x, pv = prob_ext, av = aux_ext ? *aux_ext : TView{};
+    const bool has_aux = aux_ext != nullptr;
+    r.run = [p, xv, pv, av, has_aux](const Plan& pl, const RunCtx& cx) {
+        ClsTailParams q = p;
+        q.x = pl.vptr(xv, cx);
+        q.prob = pl.vptr(pv, cx);
+        q.aux = has_aux ? pl.vptr(av, cx) : nullptr;
+        (void)launch_cls_tail(q, cx.stream);      // (servable: checked above)
+    };
+    emit(std::move(r));
+}
+
+// Default route of the text-line classifier, by the project's rule (docs/notebook/v5_mobile_det.md): the fused kernel only where its median
+// lies below the unfused chain's by more than the larger of the two spreads, alternating in one run (tools/mb_cls_mobile.py,
+// profiles/mb_cls_mobile.txt).  Measured, unfused / fused ms per forward at [B, 3, 48, 192] (median of 7 alternating rounds, spreads 0.1 - 1.4 %):
+//   B = 6      0.584 / 1.527 (auto)   0.600 / 1.529 (fp32)        B = 1440   3.814 / 8.225 (auto)   3.766 / 8.228 (fp32)
+// cls_line_kernel loses at both sizes (one line is 1.5 ms of dependent phases on eight wavefronts, its weights read from global memory per
+// FMA quad; docs/notebook/cls_mobile.md), so the chain of separate operators - replayed as one hipGraph - is the default.
+bool cls_fused_default() { return false; }
+
+bool Builder::cls_line(const std::string& stem_w, const std::string& stem_bn, const std::vector<ClsBlockDesc>& blocks, const std::string& conv2,
+                       const std::string& head, const TView& x, const TView& prob_ext, const TView* aux_ext, const TView* stages, const int* stage_block) {
+    if (!planning() || has_lt_ || blocks.size() > 11) return false;
+    const char* sw = std::getenv("RD_CLS_FUSED");      // A/B switch, read per plan
+    if (!(sw && (sw[0] == '0' || sw[0] == '1') ? sw[0] == '1' : cls_fused_default())) return false;
+    const std::string ks = stem_w + "|" + stem_bn + "|stem", k2 = conv2 + ".weight|", kh = head + "|clstail";
+    if (!pb_->has(ks + "#w") || !pb_->has(k2 + "#w") || !pb_->has(k2 + "#b") || !pb_->has(kh + "#w")) return false;
+    ClsLineParams p{};
+    p.B = x.n; p.H = x.h; p.W = x.w;
+    p.w1c = pb_->ptr(ks + "#w"); p.b1c = pb_->ptr(ks + "#b"); p.c1 = weight_dim(stem_w, 0);
+    p.n_blocks = (int)blocks.size();
+    for (size_t i = 0; i < blocks.size(); ++i) {
+        const ClsBlockDesc& d = blocks[i];
+        const std::string ke = d.prefix + ".expand_conv.fold.weight|", kd = d.prefix + ".bottleneck_conv.fold.weight|mbv3sdw",
+                          kl = d.prefix + ".linear_conv.fold.weight|", se = d.prefix + ".mid_se.";
+        if (!pb_->has(ke + "#w") || !pb_->has(ke + "#b") || !pb_->has(kd + "#w") || !pb_->has(kl + "#w") || !pb_->has(kl + "#b")) return false;
+        if (d.se && !pb_->has(se + "conv1.weight")) return false;
+        ClsBlockParams& L = p.blk[i];
+        L.we = pb_->ptr(ke + "#w"); L.be = pb_->ptr(ke + "#b");
+        L.wd = pb_->ptr(kd + "#w"); L.bd = pb_->ptr(kd + "#b");
+        L.wl = pb_->ptr(kl + "#w"); L.bl = pb_->ptr(kl + "#b");
+        if (d.se) {
+            L.w1 = pb_->ptr(se + "conv1.weight"); L.b1 = pb_->ptr(se + "conv1.bias");
+            L.w2 = pb_->ptr(se + "conv2.weight"); L.b2 = pb_->ptr(se + "conv2.bias");
+        }
+        L.k = d.k; L.cin = d.cin; L.mid = d.mid; L.cout = d.cout; L.sh = d.sh;
+        L.se = d.se ? 1 : 0; L.act = d.act; L.shortcut = d.sh == 1 && d.cin == d.cout;
+    }
+    p.w2c = pb_->ptr(k2 + "#w"); p.b2c = pb_->ptr(k2 + "#b"); p.c2 = weight_dim(conv2 + ".weight", 0);
+    p.wf = pb_->ptr(kh + "#w"); p.bf = pb_->ptr(kh + "#b");
+    for (int i = 0; i < 4; ++i) p.stage_block[i] = stage_block[i];
+    if (weight_dim(conv2 + ".weight", 1) != 32 || !cls_line_plan(p)) return false;      // a shape the kernel cannot hold: the separate operators take it
+    TView scratch = alloc_raw(cls_line_scratch_floats(p));
+    OpRecord r;
+    r.name = "backbone+head";
+    r.kind = "cls_line";
+    r.cfg = "fused/" + std::to_string(p.n_blocks) + "blocks";
+    r.shape = "N" + std::to_string(x.n) + "_" + std::to_string(x.h) + "x" + std::to_string(x.w);
+    r.bytes = 4.0 * (double)x.n * 3 * x.h * x.w;
+    const TView xv = x, pv = prob_ext, av = aux_ext ? *aux_ext : TView{}, sv = scratch;
+    const bool has_aux = aux_ext != nullptr, has_st = stages != nullptr;
+    TView stv[4];
+    for (int i = 0; i < 4; ++i) stv[i] = has_st ? stages[i] : TView{};
+    r.run = [p, xv, pv, av, sv, has_aux, has_st, stv](const Plan& pl, const RunCtx& cx) {
+        ClsLineParams q = p;
+        q.x = pl.vptr(xv, cx);
+        q.prob = pl.vptr(pv, cx);
+        q.aux = has_aux ? pl.vptr(av, cx) : nullptr;
+        for (int i = 0; i < 4; ++i) q.stage_out[i] = has_st ? pl.vptr(stv[i], cx) : nullptr;
+        q.scratch = pl.vptr(sv, cx);
+        (void)launch_cls_line(q, cx.stream);      // (servable: planned above)
+    };
+    emit(std::move(r));
+    release(scratch);
+    return true;
+}
+
 // the fused block's own parameters: the pointwise weights [cout][cin] as fp32 (the kernel splits them once per workgroup) + bias, for layers
 // whose weights fit the fp16 range.  Prepared for every handle (28 KB over the three blocks): plans pick the route later, per plan
 void Builder::prepare_lcv3_block(const std::string& key, const HostTensor& w, const std::string& pw_b) {
@@ -1868,7 +2019,7 @@ Engine::Engine(int device, const std::string& kind) : device_(device), kind_(kin
         precision_ = v == "h3" ? PREC_H3 : v == "fp32" ? PREC_FP32 : PREC_AUTO;
     }
     RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "ppocrv5_rec_mobile" || kind == "ppocr_rec_mv1e" || kind == "ppocrv5_det_server" ||
-                 kind == "ppocrv5_det_mobile" || kind == "ppocrv3_det_mobile" ||
+                 kind == "ppocrv5_det_mobile" || kind == "ppocrv3_det_mobile" || kind == "ppocr_cls_mobile" ||
                  kind == "pphgnetv2_b4" || kind == "pphgnetv2_b6_formula",
              "unknown model kind '" + kind + "'");
     int count = 0;
@@ -1921,6 +2072,7 @@ void Engine::build(Builder& b, int B, int H, int W, int flags) {
     else if (kind_ == "ppocrv5_det_server") build_ppocrv5_det_server(b, B, H, W, flags);
     else if (kind_ == "ppocrv5_det_mobile") build_ppocrv5_det_mobile(b, B, H, W, flags);
     else if (kind_ == "ppocrv3_det_mobile") build_ppocrv3_det_mobile(b, B, H, W, flags);
+    else if (kind_ == "ppocr_cls_mobile") build_ppocr_cls_mobile(b, B, H, W, flags);
     else if (kind_ == "pphgnetv2_b6_formula") build_pphgnetv2_b6_formula(b, B, H, W, flags);
     else build_pphgnetv2_b4(b, B, H, W);
 }
@@ -1946,6 +2098,8 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
         derive_ppocrv5_det_mobile_weights(store_);
     } else if (kind_ == "ppocrv3_det_mobile") {
         derive_ppocrv3_det_mobile_weights(store_);
+    } else if (kind_ == "ppocr_cls_mobile") {
+        derive_ppocr_cls_mobile_weights(store_);
     }
     Plan dummy;
     h3_prepared_ = precision_ == PREC_H3;
@@ -1957,6 +2111,7 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
     Builder b(Mode::PREPARE, &store_, &params_, &dummy, h3_prepared_, true);
     // smallest legal geometry; only weight names/shapes matter in PREPARE mode
     if (kind_ == "ppocrv6_rec" || kind_ == "ppocrv5_rec_server" || kind_ == "ppocrv5_rec_mobile" || kind_ == "ppocr_rec_mv1e") build(b, 1, 48, 64, 0), build(b, 1, 48, 64, REC_UNFUSED_CTC);
+    else if (kind_ == "ppocr_cls_mobile") build(b, 1, 48, 192, 0);
     else build(b, 1, 64, 64, 0);
     params_.upload();
     loaded_ = true;

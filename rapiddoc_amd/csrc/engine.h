@@ -240,6 +240,19 @@ class Builder {
     // (RD_MBV3_FUSED=0|1, read per plan, forcing one route for every such block) mbv3_fused_default says so.  false: not taken (always in
     // PREPARE mode: the parameters are those the separate operators fold), the caller emits expand -> depthwise -> linear
     bool mbv3_block(const std::string& prefix, const TView& x, int k, int stride, int act, bool in_hswish, bool shortcut, int level, TView* y);
+    // MobileNetV3 small in the text-line geometry (kernels_mbv3s.hip): the depthwise layer with separate row / column strides, C % 8 == 0;
+    // pre_act / post_act as mbv3_dw
+    TView mbv3s_dw(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, int pre_act, int post_act);
+    // the classifier's end: x = conv2's convolution + bias -> hardswish -> MaxPool2d(2, 2) -> global average -> Linear `prefix` (C -> 2) ->
+    // softmax into prob_ext [B,2]; aux_ext (optional) [B, 2 + C] = logits | pooled features
+    void cls_tail(const std::string& prefix, const TView& x, const TView& prob_ext, const TView* aux_ext);
+    // The whole classifier in ONE launch (cls_line_kernel, kernels_mbv3s.hip): conv1 `stem_w` / `stem_bn`, the blocks, conv2 `conv2` (folded
+    // weight / bias names), the head `head`.  Reads the parameters the separate operators fold, so it is never taken in PREPARE mode.  Taken
+    // where cls_line_plan holds the shape AND RD_CLS_FUSED=0|1 (read per plan) or, without it, cls_fused_default says so.  false: not
+    // taken, the caller emits the separate operators.  stages: four externals for the outputs of blocks stage_block[0..3] (developer), or null
+    struct ClsBlockDesc { std::string prefix; int k, cin, mid, cout, sh; bool se; int act; };
+    bool cls_line(const std::string& stem_w, const std::string& stem_bn, const std::vector<ClsBlockDesc>& blocks, const std::string& conv2,
+                  const std::string& head, const TView& x, const TView& prob_ext, const TView* aux_ext, const TView* stages, const int* stage_block);
     // one block without SE (3x3, stride 1) in one launch (kernels_lcv3_block.hip), writing the pointwise layer's convolution + bias as the separate
     // route does.  Taken under RD_LCV3_FUSED=1 in the split precisions; false: not taken (and always in PREPARE mode, where it only adds its
     // parameters), the caller emits the separate operators
@@ -408,6 +421,19 @@ void derive_ppocrv3_det_mobile_weights(WeightStore& ws);
 bool mbv3_fused_default(int k, int stride, int cin, int mid, int level);
 // default route of one hardswish depthwise layer (C % 16 == 0) of that backbone: true = the LDS-staged lcv3_dw2d_kernel (same table, same rule)
 bool mbv3_dw2d_default(int k, int stride, int c, int level);
+// Text-line direction classifier (ch_ptocr_mobile_v2.0_cls_mobile: MobileNetV3 small scale 0.35 with SE + ClsHead): ext[0] = x NCHW
+// [B,3,H,W], ext[1] = softmax probabilities [B,2].  CLS_WANT_AUX: ext[2] = [B][2 logits | 200 pooled features].  CLS_WANT_STAGES
+// (developer, rd_debug_cls_forward_stages): ext[3..6] = the outputs of blocks 0, 3, 8, 10 as NCHW
+enum ClsFlags : int { CLS_WANT_AUX = 1, CLS_WANT_STAGES = 2 };
+void build_ppocr_cls_mobile(Builder& b, int B, int H, int W, int flags);
+// tensors build_ppocr_cls_mobile reads that are not in the file: every Conv + BatchNorm of the blocks and conv2 folded into weight + bias
+void derive_ppocr_cls_mobile_weights(WeightStore& ws);
+// the four map sizes CLS_WANT_STAGES hands out for an H x W input (rows; the width is (W - 1) / 2 + 1 for all), and whether every map of
+// the graph down to the 2 x 2 pooling window is non-empty
+bool cls_mobile_geometry(int H, int W, int rows[4], int* cols);
+// default route of the classifier: true = cls_line_kernel (from the alternating A/B of tools/mb_cls_mobile.py at B = 6 and B = 1440,
+// docs/notebook/cls_mobile.md); the route goes by the network, never by the batch
+bool cls_fused_default();
 void build_pphgnetv2_b4(Builder& b, int B, int H, int W);
 // PP-FormulaNet_plus encoder; flags bit 0: the caller's image has 1 channel (replicated to 3 like the reference)
 void build_pphgnetv2_b6_formula(Builder& b, int B, int H, int W, int flags);

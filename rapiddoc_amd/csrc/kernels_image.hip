@@ -258,6 +258,36 @@ int launch_line_resize_norm(const LineCropParams& p, hipStream_t s) {
     hipLaunchKernelGGL(line_resize_norm_kernel, dim3(img_grid((long)p.OH * p.OWp, 64), p.n), dim3(256), 0, s, p);
     return 0;
 }
+// cv2.rotate(ROTATE_180) in place of the crops the direction classifier calls turned: pixel i of the packed [crop_h][crop_w][3] image
+// changes places with pixel total - 1 - i.  One thread owns both pixels of a pair (the middle pixel of an odd count stays), so no two
+// threads touch the same byte; the rule (label 1 AND its score at or above the threshold) is evaluated by every thread of the line from
+// the same two floats.  Grid: (blocks, lines), grid-stride over the pairs
+__global__ void __launch_bounds__(256) line_flip180_kernel(const LineCropDesc* __restrict__ descs, const float* __restrict__ prob, float thresh,
+                                                           uint8_t* __restrict__ scratch, int32_t* __restrict__ flipped) {
+    const int i = blockIdx.y;
+    const float p0 = prob[2 * i], p1 = prob[2 * i + 1];
+    const bool turn = p1 > p0 && p1 >= thresh;
+    if (blockIdx.x == 0 && threadIdx.x == 0) flipped[i] = turn ? 1 : 0;
+    if (!turn) return;
+    const LineCropDesc d = descs[i];
+    const long total = (long)d.crop_w * d.crop_h;
+    uint8_t* img = scratch + d.scratch_off;
+    for (long a = (long)blockIdx.x * 256 + threadIdx.x; a < total / 2; a += (long)gridDim.x * 256) {
+        const long b = total - 1 - a;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const uint8_t u = img[a * 3 + c], v = img[b * 3 + c];
+            img[a * 3 + c] = v;
+            img[b * 3 + c] = u;
+        }
+    }
+}
+int launch_line_flip180(const LineCropDesc* descs, int n, const float* prob, float thresh, uint8_t* scratch, int32_t* flipped, hipStream_t s) {
+    if (n <= 0) return 0;
+    if (n > 65535) return 1;
+    hipLaunchKernelGGL(line_flip180_kernel, dim3(16, n), dim3(256), 0, s, descs, prob, thresh, scratch, flipped);
+    return 0;
+}
 int launch_line_crops(const LineCropParams& p, hipStream_t s) {
     if (launch_line_warp(p, s) != 0) return 1;
     return launch_line_resize_norm(p, s);

@@ -1122,4 +1122,106 @@ void build_ppocrv3_det_mobile(Builder& b, int B, int H, int W, int flags) {
     rsefpn_db_tail(b, in, B, H, W, flags, out);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Text-line direction classifier (arch_config.yaml ch_ptocr_mobile_v2.0_cls_mobile): MobileNetV3(small, scale 0.35;
+// backbones/rec_mobilenet_v3.py) -> no neck -> ClsHead(class_dim 2).  248 tensors.  conv1 (3x3 / (2,2), 3 -> 8) writes convolution + bias;
+// its hardswish runs once through lcv3_act (block 0's expand is a matrix kernel).  Every block strides the height only.
+// A block = expand 1x1 + act -> depthwise k x k / (s, 1) + act -> [SE over the ACTIVATED depthwise output: GAP -> 1x1 mid -> mid / 4 + ReLU ->
+// 1x1 back -> paddle hard-sigmoid clamp(0.2 x + 0.5, 0, 1) -> scale] -> linear 1x1 (+ input where s == 1 and cin == cout); every
+// Conv + BatchNorm folded in double at load time.  Activations as in build_ppocrv3_det_mobile: a ReLU expand activates in the matrix
+// kernel's epilogue, a hardswish expand writes convolution + bias and mbv3s_dw_kernel activates on load, inside the map only.
+// conv2 (1x1, 32 -> 200) writes convolution + bias; cls_tail_kernel does hardswish, MaxPool2d(2, 2), the average, the FC and the softmax,
+// so the activated 200-channel map is never written.
+// ---------------------------------------------------------------------------------------------------
+struct Mbv3sCfg { int k, cin, mid, cout, s; bool se; int act; };
+static const Mbv3sCfg kMbv3sCls[11] = {
+    {3, 8, 8, 8, 2, true, MBV3_RELU},        {3, 8, 24, 8, 2, false, MBV3_RELU},      {3, 8, 32, 8, 1, false, MBV3_RELU},
+    {5, 8, 32, 16, 2, true, MBV3_HSWISH},    {5, 16, 88, 16, 1, true, MBV3_HSWISH},   {5, 16, 88, 16, 1, true, MBV3_HSWISH},
+    {5, 16, 40, 16, 1, true, MBV3_HSWISH},   {5, 16, 48, 16, 1, true, MBV3_HSWISH},   {5, 16, 104, 32, 2, true, MBV3_HSWISH},
+    {5, 32, 200, 32, 1, true, MBV3_HSWISH},  {5, 32, 200, 32, 1, true, MBV3_HSWISH},
+};
+static const int kClsStageBlock[4] = {0, 3, 8, 10};
+
+void derive_ppocr_cls_mobile_weights(WeightStore& ws) {
+    for (int i = 0; i < 11; ++i)            // (conv1 is folded by Builder::stem3x3s2, as every stem here)
+        for (const char* layer : {".expand_conv", ".bottleneck_conv", ".linear_conv"}) fold_conv_bn(ws, "backbone.blocks." + std::to_string(i) + layer, ".conv", ".bn");
+    fold_conv_bn(ws, "backbone.conv2", ".conv", ".bn");
+}
+
+bool cls_mobile_geometry(int H, int W, int rows[4], int* cols) {
+    if (H < 1 || W < 1) return false;
+    int h = (H - 1) / 2 + 1;
+    const int w = (W - 1) / 2 + 1;
+    int tap = 0;
+    for (int i = 0; i < 11; ++i) {
+        h = (h - 1) / kMbv3sCls[i].s + 1;
+        if (tap < 4 && i == kClsStageBlock[tap]) rows[tap++] = h;
+    }
+    *cols = w;
+    return h >= 2 && w >= 2;       // MaxPool2d(2, 2) needs one whole window
+}
+
+void build_ppocr_cls_mobile(Builder& b, int B, int H, int W, int flags) {
+    RD_CHECK((flags & ~(CLS_WANT_AUX | CLS_WANT_STAGES)) == 0, "text-line classifier: unknown flag");
+    int rows[4], cols = 0;
+    RD_CHECK(B >= 1 && cls_mobile_geometry(H, W, rows, &cols),
+             "text-line classifier: input " + std::to_string(H) + " x " + std::to_string(W) + " leaves an empty map in front of the 2 x 2 max-pool (H >= 33 and W >= 3 are needed)");
+    TView x = b.external(0, B, H, W, 3);
+    TView prob = b.external(1, B, 1, 1, 2);
+    // the fused route: the whole network in one launch, where cls_line_kernel holds the shape and RD_CLS_FUSED / the measured default say so
+    {
+        std::vector<Builder::ClsBlockDesc> blocks;
+        for (int i = 0; i < 11; ++i) {
+            const Mbv3sCfg& c = kMbv3sCls[i];
+            blocks.push_back({"backbone.blocks." + std::to_string(i), c.k, c.cin, c.mid, c.cout, c.s, c.se, c.act});
+        }
+        TView aux{}, st[4];
+        if (flags & CLS_WANT_AUX) aux = b.external(2, B, 1, 1, 2 + 200);
+        if (flags & CLS_WANT_STAGES)
+            for (int i = 0; i < 4; ++i) st[i] = b.external(3 + i, B, rows[i], cols, kMbv3sCls[kClsStageBlock[i]].cout);
+        if (b.cls_line("backbone.conv1.conv.weight", "backbone.conv1.bn", blocks, "backbone.conv2.fold", "head.fc", x, prob, (flags & CLS_WANT_AUX) ? &aux : nullptr,
+                       (flags & CLS_WANT_STAGES) ? st : nullptr, kClsStageBlock))
+            return;
+    }
+    TView raw = b.stem3x3s2("backbone.conv1.conv.weight", "backbone.conv1.bn", x, ACT_NONE);
+    TView h = b.lcv3_act(raw, Builder::Affine{});
+    b.release(raw);
+    int tap = 0;
+    for (int i = 0; i < 11; ++i) {
+        const Mbv3sCfg& c = kMbv3sCls[i];
+        const std::string p = "backbone.blocks." + std::to_string(i);
+        RD_CHECK(h.c == c.cin, "MobileNetV3 small: channel chain: " + p);
+        const bool shortcut = c.s == 1 && c.cin == c.cout;
+        const bool relu = c.act == MBV3_RELU;
+        TView e = b.conv(p + ".expand_conv.fold.weight", p + ".expand_conv.fold.bias", "", h, geom(1), relu ? ACT_RELU : ACT_NONE);
+        RD_CHECK(e.c == c.mid, "MobileNetV3 small: expanded width: " + p);
+        TView d = b.mbv3s_dw(p + ".bottleneck_conv.fold.weight", p + ".bottleneck_conv.fold.bias", e, c.k, c.s, 1, relu ? MBV3_NONE : MBV3_HSWISH, c.act);
+        b.release(e);
+        if (c.se) {
+            const std::string s = p + ".mid_se.";
+            TView gate = b.se_gate(s + "conv1.weight", s + "conv1.bias", s + "conv2.weight", s + "conv2.bias", d, ACT_HSIG_PADDLE);
+            b.scale(d, gate, 0.f, d);      // d * gate, in place
+            b.release(gate);
+        }
+        TView y = b.conv(p + ".linear_conv.fold.weight", p + ".linear_conv.fold.bias", "", d, geom(1), ACT_NONE, nullptr, shortcut ? &h : nullptr);
+        b.release(d);
+        b.release(h);
+        h = y;
+        RD_CHECK(h.c == c.cout, "MobileNetV3 small: channel chain: " + p);
+        if ((flags & CLS_WANT_STAGES) && tap < 4 && i == kClsStageBlock[tap]) {
+            b.to_nchw(h, b.external(3 + tap, h.n, h.h, h.w, h.c));
+            ++tap;
+        }
+    }
+    TView t = b.conv("backbone.conv2.fold.weight", "backbone.conv2.fold.bias", "", h, geom(1), ACT_NONE);
+    b.release(h);
+    if (flags & CLS_WANT_AUX) {
+        TView aux = b.external(2, B, 1, 1, 2 + t.c);
+        b.cls_tail("head.fc", t, prob, &aux);
+    } else {
+        b.cls_tail("head.fc", t, prob, nullptr);
+    }
+    b.release(t);
+}
+
 }  // namespace rd

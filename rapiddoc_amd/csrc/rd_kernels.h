@@ -289,6 +289,69 @@ struct Mbv3BlockParams {
 // aligned views, a non-empty map, OH / OW as above, a grid below 2^31 workgroups.  Null pointers pass (a planner fills them in later)
 bool mbv3_block_launch_ok(const Mbv3BlockParams& p);
 bool launch_mbv3_block(const Mbv3BlockParams& p, hipStream_t s);   // false: not launched (launch_ok says no, or a pointer is null)
+// MobileNetV3 small in the text-line geometry (kernels_mbv3s.hip; the text-line direction classifier).  Depthwise layer with separate row
+// and column strides: y = post(dw_kxk(pre(x)) + bias), zero padding around pre(x); k = 3 / 5, strides (1,1) / (2,1), C % 8 == 0,
+// OH = (H - 1) / SH + 1, OW = (W - 1) / SW + 1
+struct Mbv3sDwParams {
+    const float* x; int xld;
+    int N, H, W, C;
+    const float* w;      // [K*K][C]
+    const float* bias;   // [C]
+    float* y; int yld;
+    int OH, OW, K, SH, SW;
+    int pre_act, post_act;   // Mbv3Act
+    int max_blocks = 0;      // > 0: cap of the grid (default 65536 workgroups; the kernel walks the rest in a grid-stride loop)
+};
+bool mbv3s_dw_shape_ok(int k, int sh, int sw, int c);
+bool mbv3s_dw_launch_ok(const Mbv3sDwParams& p);    // shape, strides and 16-byte alignment of every pointer that is set
+bool launch_mbv3s_dw(const Mbv3sDwParams& p, hipStream_t s);   // false: not launched (launch_ok says no, or a pointer is null)
+// The classifier's end: x = conv2's convolution + bias [N][H][W][xld >= C] -> hardswish -> MaxPool2d(2, 2) -> global average ->
+// Linear C -> 2 -> softmax; prob [N][2]; aux (optional) [N][2 + C] = logits | pooled features.  H, W >= 2 (a non-empty pooled map), C <= 1024
+struct ClsTailParams {
+    const float* x; int xld;
+    int N, H, W, C;
+    const float* w;      // [2][C]
+    const float* bias;   // [2]
+    float* prob;
+    float* aux;
+};
+bool cls_tail_launch_ok(const ClsTailParams& p);
+bool launch_cls_tail(const ClsTailParams& p, hipStream_t s);
+// One inverted-residual block of the fused classifier route (cls_line_kernel / cls_block_kernel), on folded weights:
+// we [mid][cin], be [mid], wd [K*K][mid], bd [mid], squeeze-excite w1 [mid/4][mid], b1, w2 [mid][mid/4], b2 (se != 0), wl [cout][mid], bl
+struct ClsBlockParams {
+    const float *we, *be, *wd, *bd, *w1, *b1, *w2, *b2, *wl, *bl;
+    int k, cin, mid, cout, sh;       // kernel 3 / 5, row stride 1 / 2 (the column stride is 1)
+    int se, act, shortcut;           // act: MBV3_RELU / MBV3_HSWISH
+    int ms, es_ld;                   // cls_block_plan: mid channels per expand / depthwise slice, LDS row stride of the slice
+};
+bool cls_block_plan(ClsBlockParams& L, int H, int W);
+size_t cls_block_scratch_floats(const ClsBlockParams& L, int H, int W);   // per workgroup (min(N, 512) of them)
+bool cls_block_launch_ok(const ClsBlockParams& L, int N, int H, int W, int xld, int yld);
+bool launch_cls_block(const ClsBlockParams& L, const float* x, int xld, float* y, int yld, int N, int H, int W, float* scratch, hipStream_t s);
+// The whole classifier in one launch: x NCHW [B][3][H][W] -> prob [B][2] (aux [B][2 + c2], stage_out[i] NCHW: optional).  conv1 as the stem
+// builder folds it (w1c [27][c1], b1c [c1]), conv2 w2c [c2][32], b2c [c2], the head wf [2][c2], bf [2].  scratch: cls_line_scratch_floats
+struct ClsLineParams {
+    const float* x; int B, H, W;
+    const float* w1c; const float* b1c; int c1;
+    ClsBlockParams blk[11]; int n_blocks;
+    const float* w2c; const float* b2c; int c2;
+    const float* wf; const float* bf;
+    float* prob; float* aux;
+    float* stage_out[4]; int stage_block[4];
+    float* scratch;
+    size_t act_floats, d_floats, per_wg;      // cls_line_plan
+    int max_blocks = 0;                       // > 0: cap of the persistent grid (default 512 workgroups), a test's way to the line loop
+};
+bool cls_line_plan(ClsLineParams& p);
+size_t cls_line_scratch_floats(const ClsLineParams& p);
+int cls_line_grid(int B, int max_blocks);
+bool cls_line_launch_ok(const ClsLineParams& p);     // the plan is current, the shape fits, the views are aligned (null pointers pass)
+bool launch_cls_line(const ClsLineParams& p, hipStream_t s);
+// cv2.rotate(ROTATE_180) of the packed uint8 crops (LineCropDesc::scratch_off, crop_w x crop_h x 3) of the lines whose classifier output says
+// "turned": prob[2 i + 1] > prob[2 i] and prob[2 i + 1] >= thresh; flipped[i] = that decision (0 / 1).  In place: one thread owns both pixels of a pair
+struct LineCropDesc;
+int launch_line_flip180(const LineCropDesc* descs, int n, const float* prob, float thresh, uint8_t* scratch, int32_t* flipped, hipStream_t s);
 // partial[n][h][c] = sum over w < line_w[n * stride] (or W) of x[n][h][w][c]: the SE pooling partial sums, one chunk per map row
 bool lcv3_gap_shape_ok(int c);      // c % 4 == 0, c <= 4096
 void launch_lcv3_gap_rows(const float* x, int xld, int N, int H, int W, int C, float* partial, const int32_t* line_w, int stride, hipStream_t s);

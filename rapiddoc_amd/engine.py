@@ -18,7 +18,9 @@ REC_NECK_DIMS = {"ppocr_rec_mv1e": 64}      # the SVTR neck's `dims` where it is
 DET_WANT_NECK = 1           # ppocrv5_det_server / ppocrv5_det_mobile / ppocrv3_det_mobile: also hand out the neck's output `fuse` [B, 256 / 96, H/4, W/4]
 DET_NECK_CHANNELS = {"ppocrv5_det_server": 256, "ppocrv5_det_mobile": 96}
 DET_NECK_CHANNELS_V3_MOBILE = {"ppocrv3_det_mobile": 96}    # the PP-OCRv3 multilingual detector: the same RSEFPN
-KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv3_det_mobile", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "ppocr_rec_mv1e", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
+CLS_WANT_AUX = 1            # ppocr_cls_mobile: also hand out [B, 2 logits | 200 pooled features]
+CLS_FEATURES = 200          # channels of the classifier's pooled features (conv2 of MobileNetV3 small scale 0.35)
+KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv3_det_mobile", "ppocr_cls_mobile", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "ppocr_rec_mv1e", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
 
 
 def rec_line_table(widths, first_tokens) -> np.ndarray:
@@ -202,6 +204,47 @@ class RdEngine:
                 after_launch()
         self._guarded(launch)
         return (out, neck) if want_neck else out
+
+    def cls_forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, want_aux: bool = False, want_stages: bool = False):
+        """Text-line direction classifier (ppocr_cls_mobile): x [B,3,H,W] (the classifier's pre-process gives 48 x 192) -> the head's
+        softmax [B,2] = (P(0 deg), P(180 deg)).  `out`: a caller-owned contiguous float32 [B,2] result tensor.  `want_aux`
+        (RD_CLS_WANT_AUX): returns (prob, aux [B, 2 + 200] = logits | pooled features).  `want_stages` (developer,
+        rd_debug_cls_forward_stages): returns (prob, aux, [the outputs of blocks 0, 3, 8, 10 as NCHW])."""
+        if self.kind != "ppocr_cls_mobile":
+            raise EngineError("cls_forward: the handle is not a ppocr_cls_mobile model")
+        x = self._prep(x)
+        B, Cc, H, W_ = x.shape
+        if out is None:
+            out = self._out("cls", (B, 2), torch.float32, x.device)
+        elif out.shape != (B, 2) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise EngineError("cls_forward: `out` does not match the forward's shape")
+        aux = torch.empty((B, 2 + CLS_FEATURES), dtype=torch.float32, device=x.device) if (want_aux or want_stages) else None
+        if want_stages:
+            rows, h = [], (H - 1) // 2 + 1
+            for i, s in enumerate((2, 2, 1, 2, 1, 1, 1, 1, 2, 1, 1)):
+                h = (h - 1) // s + 1
+                if i in (0, 3, 8, 10):
+                    rows.append(h)
+            cols = (W_ - 1) // 2 + 1
+            shapes = [(B, c, r, cols) for c, r in zip((8, 16, 32, 32), rows)]
+            sizes = [int(np.prod(s)) for s in shapes]
+            stages = torch.empty((sum(sizes),), dtype=torch.float32, device=x.device)
+
+            def launch_stages():
+                fn = self._l.rd_debug_cls_forward_stages       # developer entry, not in the public header
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+                self._chk(fn(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), aux.data_ptr(), stages.data_ptr(), _stream_ptr()))
+                self._log()
+            self._guarded(launch_stages)
+            return out, aux, [t.view(s) for t, s in zip(torch.split(stages, sizes), shapes)]
+
+        def launch():
+            self._chk(self._l.rd_cls_forward(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), CLS_WANT_AUX if want_aux else 0,
+                                             aux.data_ptr() if want_aux else None, None, 0, _stream_ptr()))
+            self._log()
+        self._guarded(launch)
+        return (out, aux) if want_aux else out
 
     def rec_forward(self, x: torch.Tensor, flags: int = 0, out: Optional[tuple] = None,
                     after_launch=None) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:

@@ -30,6 +30,21 @@ class CropDesc(C.Structure):
                 ("m", C.c_float * 9), ("rot90", C.c_int32), ("pad_", C.c_int32)]
 
 
+CLS_IMG_H, CLS_IMG_W = 48, 192       # the text-line classifier's input (PaddleOCR cls_image_shape "3, 48, 192")
+
+
+def cls_flip_rule(prob: np.ndarray, thresh: float) -> np.ndarray:
+    """The decision rd_line_flip180_batch makes per line from the classifier's softmax [n,2], restated on the host: turned when label 1
+    (180 degrees) wins and its score is at or above the threshold."""
+    p = np.asarray(prob, dtype=np.float32).reshape(-1, 2)
+    return (p[:, 1] > p[:, 0]) & (p[:, 1] >= np.float32(thresh))
+
+
+def flip180(crop: np.ndarray) -> np.ndarray:
+    """cv2.rotate(crop, cv2.ROTATE_180) of an [h,w,3] image: the pixel order reversed (what rd_line_flip180_batch does in place)."""
+    return np.ascontiguousarray(np.asarray(crop)[::-1, ::-1])
+
+
 CROP_DTYPE = np.dtype([("page", "<i4"), ("out_w", "<i4"), ("crop_w", "<f4"), ("crop_h", "<f4"), ("m", "<f4", (9,)),
                        ("rot90", "<i4"), ("pad_", "<i4")])
 assert CROP_DTYPE.itemsize == C.sizeof(CropDesc)
@@ -110,12 +125,15 @@ def boxes_to_quads(boxes_xyxy: np.ndarray) -> np.ndarray:
 class PageResult:
     lines: List[Tuple[np.ndarray, str, float]] = field(default_factory=list)  # (quad 4x2, text, score)
     layout_feats: Optional[List[torch.Tensor]] = None
+    # PagePipeline(use_cls=True): per line (turned by 180 degrees before recognition?, the classifier's label 0 / 1, that label's
+    # probability) - rapidocr's ClsPostProcess pair plus the decision of its threshold rule; None when the stage is off
+    cls: Optional[List[Tuple[bool, int, float]]] = None
 
 
 class PagePipeline:
     def __init__(self, states: Dict[str, object], device: int = 0, characters: Optional[Sequence[str]] = None,
                  rec_batch_num: Optional[int] = None, rec_width_multiple: int = 32, keep_feats: bool = False, n_rec_streams: int = 4,
-                 rec_mode: Optional[str] = None, rec_chunking: Optional[str] = None):
+                 rec_mode: Optional[str] = None, rec_chunking: Optional[str] = None, use_cls: bool = False, cls_thresh: float = 0.9):
         """`states`: {'ppocrv6_det': ..., 'ppocrv6_rec': ..., 'pphgnetv2_b4': ...}, each a .safetensors path,
         bytes, or name->ndarray dict.  The detector may be given as 'ppocrv5_det_server' instead of 'ppocrv6_det' (PPHGNetV2-B4 + LKPAN +
         PFHeadLocal) or as 'ppocrv5_det_mobile' (PPLCNetV3 + RSEFPN + DBHead) or as 'ppocrv3_det_mobile' (MobileNetV3 + RSEFPN + DBHead: the multilingual and the
@@ -142,7 +160,23 @@ class PagePipeline:
                         `rec_batch_num` is given - what bench.py measures) lets the chunk SIZE follow the width:
                         `ocr_host.rec_batches_adaptive` picks, chunk by chunk, the size with the most lines per estimated
                         microsecond, i.e. tile counts of the persistent kernels that fill whole rounds of the 256 CUs (64 lines
-                        of width 1056 are 3.09 rounds of mixer tiles and cost four)."""
+                        of width 1056 are 3.09 rounds of mixer tiles and cost four).
+
+        `use_cls` (default False: RapidDoc's own page driver never classifies, rapid_ocr.py:51 turns `Global.use_cls` off): rapidocr's
+        det -> crop -> cls -> rec order on the device.  `states` must then carry 'ppocr_cls_mobile' (ch_ptocr_mobile_v2.0_cls_mobile).
+        Per rec batch, on that batch's stream, between the warp and the recogniser's resize: the classifier's pre-process (linear resize
+        to 48 rows, width min(192, ceil(48 w / h)), (x / 255 - 0.5) / 0.5, zero right-padding to 192 - the arithmetic of
+        rd_line_resize_norm_batch with a second descriptor array), `rd_cls_forward` on all lines of the batch at once (the reference's
+        chunks of cls_batch_num = 6 cannot change a result: the width is fixed and BatchNorm / squeeze-excite work per image), and
+        `rd_line_flip180_batch`, which turns every crop with label 1 and a score >= `cls_thresh` by 180 degrees in place.  No host
+        synchronisation is added; the decisions come home with the step's results (`PageResult.cls`).  (+) rapidocr's TextClassifier
+        source is not available to this project's build: the pre-process and the threshold rule are restated from the public PaddleOCR
+        definition (ppocr ClsPostProcess / tools/infer/predict_cls.py: cls_image_shape 3 x 48 x 192, `'180' in label and score >
+        cls_thresh` - here label 1 with score >= cls_thresh) and are NOT pinned against the package.  With `want_words` the stage
+        raises ValueError: rapidocr defines no word-box mapping for turned lines."""
+        self.use_cls, self.cls_thresh = bool(use_cls), float(cls_thresh)
+        if self.use_cls and "ppocr_cls_mobile" not in states:
+            raise ValueError("use_cls=True needs the text-line classifier's weights: states['ppocr_cls_mobile'] (ch_ptocr_mobile_v2.0_cls_mobile)")
         if rec_mode is None:
             rec_mode = "strict" if rec_batch_num is None and rec_chunking is None else "throughput"
         if rec_mode not in ("strict", "throughput"):
@@ -183,6 +217,10 @@ class PagePipeline:
         self.rec_streams = [torch.cuda.Stream(device=self.tdev) for _ in self.rec_engines]
         # neck + CTC head of the two-stage recogniser: own handle (own workspace) and stream, it runs under the next backbones
         self.rec_tail = RdEngine(self.rec_kind, device, guard="deferred").load_weights(states[self.rec_kind])
+        # the optional text-line direction classifier: one handle (one workspace) per rec stream, as the recogniser's
+        self.cls_engines = ([RdEngine("ppocr_cls_mobile", device, guard="deferred").load_weights(states["ppocr_cls_mobile"]) for _ in self.rec_engines]
+                            if self.use_cls else [])
+        self.last_cls = None
         self.tail_stream = torch.cuda.Stream(device=self.tdev)
         self.layout_stream = torch.cuda.Stream(device=self.tdev)
         # det runs on a stream of its own, so that the NEXT batch's det + layout forwards can be enqueued under this batch's
@@ -286,7 +324,7 @@ class PagePipeline:
         # a pass can trip a LATER stage only once the earlier one runs in fp32 (an overflowed backbone feeds the tail NaNs or
         # finite-but-huge tokens), so check after every pass; a tripped engine stays in fp32, which bounds the loop
         for _ in range(3):
-            if not any([e.check_range_and_fallback() for e in self.rec_engines + [self.rec_tail]]):     # list: check every engine
+            if not any([e.check_range_and_fallback() for e in self.rec_engines + [self.rec_tail] + self.cls_engines]):     # list: check every engine
                 break
             self.stats["range_fallbacks"] = self.stats.get("range_fallbacks", 0) + 1
             out = self._rec_forward_sources_once(sources, image_keys, want_words)
@@ -353,6 +391,9 @@ class PagePipeline:
 
     def _rec_forward_sources_once(self, sources, image_keys=None, want_words=False):
         t0 = time.perf_counter()
+        if self.use_cls and want_words:
+            raise ValueError("use_cls together with want_words: rapidocr defines no word-box mapping for lines turned by 180 degrees")
+        self.last_cls = None
         if not sources:                 # nothing to read on this rank: it still takes part in the batch's width exchange
             if self.rec_width_sync is not None and self.rec_mode == "strict" and self.rec_two_stage and self._sync_this_call:
                 self._synced_widths(self.rec_width_sync, np.zeros(0, np.int64), np.zeros(0))
@@ -388,9 +429,12 @@ class PagePipeline:
         keep = np.nonzero(ok)[0]                      # degenerate quads (zero-area / collinear corners) get ("", 0.0)
         n = len(keep)
         texts: List[tuple] = [("", 0.0, None) if want_words else ("", 0.0)] * n_all
+        cls_of: List[tuple] = [(False, 0, 0.0)] * n_all if self.use_cls else []
         if n == 0:
             if sync is not None:
                 self._synced_widths(sync, np.zeros(0, np.int64), np.zeros(0))
+            if self.use_cls:
+                self.last_cls = self._scatter_texts(cls_of, src_of, page_of, n_img, perm)
             return self._scatter_texts(texts, src_of, page_of, n_img, perm)
         mats, cws_a, chs_a = mats[keep], cws_a[keep], chs_a[keep]
         rots_a = (chs_a / cws_a >= 2.0).astype(np.int32)  # ocr_utils.py:531-534 rotates crops with h/w >= 2
@@ -467,9 +511,22 @@ class PagePipeline:
             for b in range(len(batches)):
                 lo, hi = int(starts[b]), int(starts[b + 1])
                 warp_jobs.append([(0, lo, hi - lo, int(crop_px[lo:hi].max()))])
+        if self.use_cls:
+            # the classifier's pre-process: the same crops, resized to 48 x min(192, ceil(48 w / h)) and zero-padded to 192 columns
+            descs_cls = descs.copy()
+            descs_cls["out_w"] = np.minimum(CLS_IMG_W, np.ceil(CLS_IMG_H * (eff_w / eff_h)[order_all])).astype(np.int32)
         self.stats["t_descs_ms"] = (time.perf_counter() - t0) * 1e3
         descs_dev = torch.from_numpy(descs.view(np.uint8)).to(dev, non_blocking=True)
+        if self.use_cls:
+            descs_cls_dev = torch.from_numpy(descs_cls.view(np.uint8)).to(dev, non_blocking=True)
+            cls_prob = self._buf("cls_prob", 2 * n).view(n, 2)
+            cls_flip = self._buf("cls_flip", n, torch.int32)
+            cls_prob_h = torch.empty((n, 2), dtype=torch.float32, pin_memory=True)
+            cls_flip_h = torch.empty((n,), dtype=torch.int32, pin_memory=True)
         descs_warp_dev = torch.from_numpy(descs_warp.view(np.uint8)).to(dev, non_blocking=True) if multi else descs_dev
+        if self.keep_rec_inputs:          # tests: the descriptors in launch order, every batch's scratch base and first line; the classifier's inputs
+            self.last_rec_descs = (descs.copy(), np.asarray(batch_base, dtype=np.int64), np.asarray(starts, dtype=np.int64))
+            self.last_cls_inputs = []
         outs = []
         pos = 0
         main = torch.cuda.current_stream()
@@ -563,6 +620,22 @@ class PagePipeline:
                                                       st.cuda_stream)
                     if rc != 0:
                         raise RuntimeError("rd_line_warp_batch failed")
+                if self.use_cls:              # classify the crops and turn the upside-down ones in the scratch, before the recogniser reads it
+                    xc = self._buf(("cls_x", k), nb * 3 * CLS_IMG_H * CLS_IMG_W).view(nb, 3, CLS_IMG_H, CLS_IMG_W)
+                    rc = self._lib.rd_line_resize_norm_batch(self.device, descs_cls_dev.data_ptr() + pos * LINE_DTYPE.itemsize, nb, scratch,
+                                                             CLS_IMG_H, CLS_IMG_W, 1, xc.data_ptr(), st.cuda_stream)
+                    if rc != 0:
+                        raise RuntimeError("rd_line_resize_norm_batch (classifier) failed")
+                    self.cls_engines[k].cls_forward(xc, out=cls_prob[pos: pos + nb])
+                    if self.keep_rec_inputs:
+                        self.last_cls_inputs.append((keep[np.asarray(chunk)], xc.clone()))
+                    rc = self._lib.rd_line_flip180_batch(self.device, descs_dev.data_ptr() + pos * LINE_DTYPE.itemsize, nb,
+                                                         cls_prob[pos: pos + nb].data_ptr(), self.cls_thresh, scratch,
+                                                         cls_flip[pos: pos + nb].data_ptr(), st.cuda_stream)
+                    if rc != 0:
+                        raise RuntimeError("rd_line_flip180_batch failed")
+                    cls_prob_h[pos: pos + nb].copy_(cls_prob[pos: pos + nb], non_blocking=True)     # home with the step's results: the
+                    cls_flip_h[pos: pos + nb].copy_(cls_flip[pos: pos + nb], non_blocking=True)     # host reads them behind the batch's `done`
                 rc = self._lib.rd_line_resize_norm_batch(self.device, descs_dev.data_ptr() + pos * LINE_DTYPE.itemsize, nb, scratch,
                                                          ocr_host.REC_IMG_H, wpad, 1, x.data_ptr(), st.cuda_stream)   # stage 2
                 if rc != 0:
@@ -664,6 +737,13 @@ class PagePipeline:
         self.stats["rec_lines"] = n
         self.stats["rec_batches"] = len(batches)
         self.last_pool_order = perm
+        if self.use_cls:       # (every batch's `done` has been waited for above: the copies enqueued in front of its recogniser are complete)
+            ph, fh = cls_prob_h.numpy(), cls_flip_h.numpy()
+            for j, i in enumerate(keep[order_all].tolist()):
+                label = int(ph[j, 1] > ph[j, 0])
+                cls_of[i] = (bool(fh[j]), label, float(ph[j, label]))
+            self.last_cls = self._scatter_texts(cls_of, src_of, page_of, n_img, perm)
+            self.last_cls_prob = (keep[order_all], ph.copy())      # tests: pooled line ids and the raw probabilities
         return self._scatter_texts(texts, src_of, page_of, n_img, perm)
 
     @staticmethod
@@ -862,6 +942,8 @@ class PagePipeline:
             results[i].lines = [(qs[j], t, s) for j, (t, s) in enumerate(texts[i])]
             if h["feats"] is not None:
                 results[i].layout_feats = h["feats"][i]
+            if self.use_cls and self.last_cls is not None:
+                results[i].cls = list(self.last_cls[0][i])
         return results
 
 

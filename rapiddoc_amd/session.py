@@ -415,6 +415,55 @@ class Mi355RecSession(_BaseSession):
             return idx.cpu().numpy(), prob.cpu().numpy()
 
 
+# The text-line direction classifier this engine serves, by weight-file stem (arch_config.yaml's one `model_type: cls` graph)
+CLS_ARCH_BY_STEM = {
+    "ch_ptocr_mobile_v2.0_cls_mobile": "ppocr_cls_mobile",
+}
+
+
+def resolve_cls_kind(weights: WeightSrc) -> str:
+    """Engine kind of a text-line classifier's weights, built like `resolve_rec_kind`: a file goes by its stem (an unknown one is an
+    error), a state dict or a nameless safetensors image by `head.fc.weight` of shape [2, *] (ClsHead with two classes) together with
+    `backbone.blocks.0.mid_se.conv1.weight` (MobileNetV3 small: squeeze-excite inside its first inverted-residual block).  A recogniser
+    or a detector is refused."""
+    if isinstance(weights, (str, Path)):
+        stem = Path(str(weights)).stem
+        if stem not in CLS_ARCH_BY_STEM:
+            raise ValueError(f"architecture {stem} is not in the text-line classifiers this engine serves {sorted(CLS_ARCH_BY_STEM)}")
+        return CLS_ARCH_BY_STEM[stem]
+    if isinstance(weights, (bytes, bytearray, memoryview)):
+        import json
+        import struct
+        (hlen,) = struct.unpack("<Q", bytes(weights[:8]))
+        header = json.loads(bytes(weights[8:8 + hlen]))
+        shapes = {k: tuple(v["shape"]) for k, v in header.items() if k != "__metadata__"}
+    else:
+        shapes = {k: tuple(np.shape(v)) for k, v in weights.items()}
+    shapes = {k[len("model."):] if k.startswith("model.") else k: v for k, v in shapes.items()}
+    fc = shapes.get("head.fc.weight")
+    if fc is not None and len(fc) == 2 and fc[0] == 2 and "backbone.blocks.0.mid_se.conv1.weight" in shapes:
+        return "ppocr_cls_mobile"
+    raise ValueError("architecture of the classifier weights is not in the text-line classifiers this engine serves (head.fc.weight of shape "
+                     "[2, *] together with backbone.blocks.0.mid_se.conv1.weight is not among the tensors)")
+
+
+class Mi355ClsSession(_BaseSession):
+    """ch_ptocr_mobile_v2.0_cls_mobile, the 0 / 180 degree text-line classifier: [B,3,48,192] -> softmax [B,2] - the tensor the reference's
+    `TorchInferSession._to_numpy_output` returns for this graph (ClsHead applies the softmax itself, heads/cls_head.py).  The kind
+    follows from the weights (`resolve_cls_kind`) unless `kind` names it."""
+    kind = "ppocr_cls_mobile"
+
+    def __init__(self, weights: WeightSrc, device: int = 0, kind: Optional[str] = None):
+        self.kind = kind or resolve_cls_kind(weights)
+        super().__init__(weights, device)
+
+    def __call__(self, img: np.ndarray) -> np.ndarray:
+        with torch.cuda.stream(self.stream):
+            x = self._to_dev(img)
+            out = self._dev_buffer("prob", (x.shape[0], 2), torch.float32)
+            return self._to_host(self.engine.cls_forward(x, out=out))
+
+
 class Mi355LayoutBackboneSession(_BaseSession):
     """PPHGNetV2-B4 backbone of PP-DocLayout-L/plus-L/V2/V3: [B,3,S,S] -> 4 NCHW feature maps."""
     kind = "pphgnetv2_b4"
@@ -437,6 +486,8 @@ def install_into_rapidocr() -> None:
             # arch_config.yaml ("ch_PP-OCRv6_det_small", rapid_doc/model/ocr/torch.py:70-77): used when task_type is absent
             get = (lambda k: getattr(cfg, k, None)) if not hasattr(cfg, "get") else (lambda k: cfg.get(k, None) or getattr(cfg, k, None))
             task = str(get("task_type") or Path(str(get("model_path") or "")).stem).lower()
+            if "cls" in task:          # rapidocr's TextClassifier (Global.use_cls): task_type `cls`, or the stem ch_ptocr_mobile_v2.0_cls_mobile
+                return Mi355ClsSession.from_cfg(cfg)
             return (Mi355DetSession if "det" in task else Mi355RecSession).from_cfg(cfg)
 
     try:

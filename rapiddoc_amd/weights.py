@@ -59,6 +59,17 @@ _KIND_GAINS["ppocrv3_det_mobile"] = (
     (lambda n: n.startswith("backbone.stages.3.") and n.endswith(".linear_conv.conv.weight"), 0.7),
     (lambda n: n == "head.binarize.conv3.weight", 3.0),
 )
+# Text-line direction classifier (MobileNetV3 small scale 0.35 + ClsHead): under the plain rule the two logits stay together and the
+# softmax answers 0.46-0.47 for every line.  The gain on the head spreads the logit difference across lines; the additive term on the
+# head's bias (_KIND_OFFSETS: (name test, per-element values)) centres it, so that both labels and both sides of the 0.9 threshold occur
+_KIND_GAINS["ppocr_cls_mobile"] = (
+    (lambda n: n == "head.fc.weight", 300.0),
+)
+_KIND_OFFSETS = {
+    "ppocr_cls_mobile": (
+        (lambda n: n == "head.fc.bias", (-11.6, 11.6)),
+    ),
+}
 _NORM_TOKENS = (".normalization.", ".norm.", ".bn.", "layer_norm", ".norm1.", ".norm2.")
 
 
@@ -134,7 +145,28 @@ def synth_state_dict(manifest: Manifest, seed: int = 0, kind: str = None) -> Dic
             for applies, f in _KIND_GAINS[kind]:
                 if applies(name):
                     state[name] = (arr * np.float32(f)).astype(np.float32)
+        for name, arr in state.items():
+            for applies, add in _KIND_OFFSETS.get(kind, ()):
+                if applies(name):
+                    state[name] = (arr + np.asarray(add, dtype=np.float32).reshape(arr.shape)).astype(np.float32)
     return state
+
+
+def synth_cls_lines(seed: int, b: int, h: int = 48, w: int = 192) -> Tuple[np.ndarray, np.ndarray]:
+    """Synthetic classifier input [b,3,h,w] in [-1, 1] and its content widths: line i carries noise of its own brightness and contrast over
+    its first widths[i] columns (12 ... w, ragged) and the zero right-padding of the classifier's pre-process behind them.  A pure
+    function of the arguments (numpy only), so that a fixture stores the recipe instead of the tensor."""
+    rng = np.random.default_rng([seed, b, h, w])
+    lo = min(12, w)
+    widths = np.linspace(lo, w, b).round().astype(np.int64) if b > 1 else np.array([w], dtype=np.int64)
+    widths = widths[rng.permutation(b)]
+    x = np.zeros((b, 3, h, w), dtype=np.float32)
+    for i in range(b):
+        mean, contrast = rng.uniform(-0.6, 0.6), rng.uniform(0.1, 0.8)
+        tint = rng.uniform(-0.15, 0.15, (3, 1, 1))
+        u = rng.uniform(-1.0, 1.0, (3, h, int(widths[i])))
+        x[i, :, :, : widths[i]] = np.clip(mean + tint + contrast * u, -1.0, 1.0).astype(np.float32)
+    return x, widths
 
 
 def checksum(state: Dict[str, np.ndarray]) -> float:
