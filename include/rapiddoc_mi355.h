@@ -45,7 +45,9 @@ const char* rd_version(void);
 /* model_kind: "ppocrv6_det" | "ppocrv5_det_server" (PPHGNetV2-B4 + LKPAN + PFHeadLocal; rd_det_forward / rd_det_forward_ex) |
  * "ppocrv5_det_mobile" (PPLCNetV3 scale 0.75 + RSEFPN + DBHead; the same two calls) |
  * "ppocrv3_det_mobile" (MobileNetV3 large scale 0.5 without SE + RSEFPN + DBHead - multi_ / en_PP-OCRv3_det_mobile; the same two calls) |
- * "ppocr_cls_mobile" (MobileNetV3 small scale 0.35 with squeeze-excite + ClsHead - ch_ptocr_mobile_v2.0_cls_mobile, the 0 / 180 degree text-line classifier; rd_cls_forward) | "ppocrv6_rec" | "ppocrv5_rec_server" (PPHGNetV2-B4 + SVTR neck + CTC; every rd_rec_* call except
+ * "ppocr_cls_mobile" (MobileNetV3 small scale 0.35 with squeeze-excite + ClsHead - ch_ptocr_mobile_v2.0_cls_mobile, the 0 / 180 degree text-line classifier; rd_cls_forward) |
+ * "unitable_encoder" (the ViT-B encoder of the UniTable table-structure recogniser; rd_table_encoder_forward) |
+ * "unitable_decoder" (its GPT decoder and greedy loop; rd_table_decode) | "ppocrv6_rec" | "ppocrv5_rec_server" (PPHGNetV2-B4 + SVTR neck + CTC; every rd_rec_* call except
  * rd_rec_backbone_forward_lines) | "ppocrv5_rec_mobile" (PPLCNetV3 scale 0.95 + the same SVTR neck + CTC; every rd_rec_* call) | "ppocr_rec_mv1e" (MobileNetV1Enhance scale 0.5 + SVTR neck dims 64 + CTC:
  * the ten multilingual PP-OCRv3 / v4 mobile files latin_ / cyrillic_ / chinese_cht_PP-OCRv3_rec_mobile, arabic_ / korean_ / japan_ / ta_ / te_ / ka_ /
  * devanagari_PP-OCRv4_rec_mobile, which differ in their class count only; every rd_rec_* call) | "pphgnetv2_b4" | "pphgnetv2_b6_formula" | "ppformulanet_head".  NULL on failure -> rd_create_error(). */
@@ -188,6 +190,25 @@ int rd_line_resize_norm_batch(int device_id, const rd_line_crop_desc* descs_dev,
 #define RD_CLS_WANT_AUX 1
 int rd_cls_forward(rd_handle* h, const float* x_nchw_dev, int B, int H, int W, float* prob_b2_dev, int flags, float* aux_dev, void* ws_dev,
                    size_t ws_bytes, void* stream);
+/* Table-structure encoder ("unitable_encoder": UniTable's ViT-B - 16 x 16 patches, learned positions, 12 pre-norm encoder layers of d = 768,
+ * 12 heads of 64, FFN 3072, final LayerNorm): x [B,3,H,W], already normalised (H, W multiples of 16, (H / 16) (W / 16) <= 1024 patches; the
+ * product shape is 448 x 448, T = 784) -> memory [B,T,768], the tensor the reference's decoder attends over.  A shape outside those
+ * limits fails, and rd_last_error says so.  rd_query_workspace takes the same B, H, W with flags 0. */
+int rd_table_encoder_forward(rd_handle* h, const float* x_nchw_dev, int B, int H, int W, float* memory_bt768_dev, void* ws_dev, size_t ws_bytes,
+                             void* stream);
+/* Table-structure decoder ("unitable_decoder": UniTable's GPTFastDecoder - 4 pre-norm blocks of d = 768 with a 1024-row KV cache and
+ * cross-attention over `memory`, generator 768 -> 960) with the reference's greedy loop, for B <= 8 tables at once (a larger B fails with a
+ * message); every table gets exactly the ids it gets alone.  memory [B,S,768] as rd_table_encoder_forward wrote it.  Per step the next token
+ * is the argmax over the module's whitelist (ids 1 and 12 .. 509); a token inside [bbox_first_id, bbox_last_id] raises the table's counter,
+ * and when the counter exceeds 4 the token is replaced by bbox_close_id and the counter returns to 0 (no other token resets it).  The ids
+ * come from the vocabulary file, so they are the caller's.  ids_dev int64 [B][max_new_tokens + 1]: column 0 = prefix_id, then the emitted
+ * tokens; a table that emitted eos_id keeps its slot and writes pad_id behind it.  n_tokens (HOST int32 [B], may be NULL): tokens of
+ * every table with the prefix and the EOS (max_new_tokens + 1 where it never stopped).  1 <= max_new_tokens <= 1024.  Synchronises the stream. */
+typedef struct {
+    int32_t prefix_id, eos_id, pad_id, bbox_close_id, bbox_first_id, bbox_last_id;
+} rd_table_decode_cfg;
+int rd_table_decode(rd_handle* h, const float* memory_dev, int B, int S, int max_new_tokens, const rd_table_decode_cfg* cfg, int64_t* ids_dev,
+                    int32_t* n_tokens, void* stream);
 /* The classifier's verdict applied on the device, between rd_line_warp_batch and rd_line_resize_norm_batch: every line with
  * prob[1] > prob[0] and prob[1] >= thresh has its packed uint8 crop in scratch_u8_dev turned by 180 degrees in place
  * (cv2.rotate(ROTATE_180): the pixel order reversed); flipped_out_dev[i] = 1 for those lines, 0 for the others.  The scratch holds the

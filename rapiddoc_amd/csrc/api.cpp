@@ -21,11 +21,17 @@ int debug_dec_attention(int route, int self, int B, int T, float* kc, float* vc,
 int debug_dec_select(int mode, const float* logits, int V, int B, int step, long long* ids, int ids_ld, int* unfinished, int n_unfinished, int max_new,
                      const float* emb, const float* pos, const float* g, const float* b, float* x, int* state_out);
 int formula_decoder_max_new(FormulaDecoder* d);
+class TableDecoder;
+TableDecoder* table_decoder_create(int device, const void* blob, size_t nbytes);
+void table_decoder_destroy(TableDecoder* d);
+int table_decoder_decode(TableDecoder* d, const float* memory, int B, int S, int max_new, const int* cfg6, long long* ids, int* n_tokens, hipStream_t s,
+                         const int* forced, float* trace_hidden, float* trace_logits, int* trace_chosen, int* trace_emitted);
 }  // namespace rd
 
 struct rd_handle {
     rd::Engine* eng = nullptr;           // convolutional networks (plan-based)
     rd::FormulaDecoder* dec = nullptr;   // "ppformulanet_head": autoregressive decoder
+    rd::TableDecoder* tdec = nullptr;    // "unitable_decoder": autoregressive decoder
     int device = 0;
     std::string kind;
     std::string err;
@@ -36,7 +42,7 @@ static thread_local std::string g_create_err;
 
 template <typename F>
 static int guarded(rd_handle* h, F&& f) {
-    if (!h || (!h->eng && h->kind != "ppformulanet_head")) return 2;
+    if (!h || (!h->eng && h->kind != "ppformulanet_head" && h->kind != "unitable_decoder")) return 2;
     try {
         f();
         h->err.clear();
@@ -60,7 +66,7 @@ rd_handle* rd_create(int device_id, const char* model_kind) {
         auto* h = new rd_handle();
         h->device = device_id;
         h->kind = model_kind;
-        if (h->kind == "ppformulanet_head") {
+        if (h->kind == "ppformulanet_head" || h->kind == "unitable_decoder") {
             int count = 0;
             if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device_id < 0 || device_id >= count) {
                 delete h;
@@ -82,6 +88,7 @@ void rd_destroy(rd_handle* h) {
     if (!h) return;
     delete h->eng;
     if (h->dec) rd::formula_decoder_destroy(h->dec);
+    if (h->tdec) rd::table_decoder_destroy(h->tdec);
     delete h;
 }
 const char* rd_last_error(rd_handle* h) { return h ? h->err.c_str() : "null handle"; }
@@ -91,6 +98,9 @@ int rd_load_weights(rd_handle* h, const void* img, size_t nbytes) {
         if (h->kind == "ppformulanet_head") {
             RD_CHECK(!h->dec, "weights already loaded for this handle");
             h->dec = rd::formula_decoder_create(h->device, img, nbytes);
+        } else if (h->kind == "unitable_decoder") {
+            RD_CHECK(!h->tdec, "weights already loaded for this handle");
+            h->tdec = rd::table_decoder_create(h->device, img, nbytes);
         } else {
             h->eng->load_weights(img, nbytes);
         }
@@ -176,6 +186,57 @@ int rd_debug_cls_forward_stages(rd_handle* h, const float* x, int B, int H, int 
             q += (size_t)B * kC[i] * rows[i] * cols;
         }
         h->eng->run(B, H, W, rd::CLS_WANT_AUX | rd::CLS_WANT_STAGES, ext, nullptr, 0, (hipStream_t)stream);
+    });
+}
+
+int rd_table_encoder_forward(rd_handle* h, const float* x, int B, int H, int W, float* memory, void* ws, size_t ws_bytes, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->eng && h->eng->kind() == "unitable_encoder", "handle is not a table-structure encoder (unitable_encoder) model");
+        RD_CHECK(x && memory && B > 0, "null input/output");
+        h->eng->run(B, H, W, 0, {(void*)x, (void*)memory}, ws, ws_bytes, (hipStream_t)stream);
+    });
+}
+
+static void table_cfg6(const rd_table_decode_cfg* cfg, int out[6]) {
+    RD_CHECK(cfg, "cfg is NULL");
+    out[0] = cfg->prefix_id; out[1] = cfg->eos_id; out[2] = cfg->pad_id; out[3] = cfg->bbox_close_id; out[4] = cfg->bbox_first_id; out[5] = cfg->bbox_last_id;
+}
+
+int rd_table_decode(rd_handle* h, const float* memory, int B, int S, int max_new_tokens, const rd_table_decode_cfg* cfg, int64_t* ids, int32_t* n_tokens,
+                    void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->kind == "unitable_decoder" && h->tdec, "handle is not a loaded table-structure decoder (unitable_decoder)");
+        int c[6];
+        table_cfg6(cfg, c);
+        rd::table_decoder_decode(h->tdec, memory, B, S, max_new_tokens, c, (long long*)ids, (int*)n_tokens, (hipStream_t)stream, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr);
+    });
+}
+
+// developer entry ("unitable_decoder"): `steps` decode steps with traces.  forced_dev (int32 [B][steps], or null): the token fed to step t
+// of table b (the EOS latch is off); null = the free loop of rd_table_decode.  Traces (device, each may be null): hidden [steps][4][B][768]
+// = the row after each block, logits [steps][B][960] (before the whitelist), chosen / emitted int32 [steps][B] = the whitelist argmax and the
+// token after the bbox rule.  Rows of steps the loop did not run stay as they were.  Not part of the public header.
+int rd_debug_table_decode(rd_handle* h, const float* memory, int B, int S, int steps, const rd_table_decode_cfg* cfg, const int32_t* forced,
+                          int64_t* ids, float* trace_hidden, float* trace_logits, int32_t* trace_chosen, int32_t* trace_emitted, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->kind == "unitable_decoder" && h->tdec, "handle is not a loaded table-structure decoder (unitable_decoder)");
+        int c[6];
+        table_cfg6(cfg, c);
+        rd::table_decoder_decode(h->tdec, memory, B, S, steps, c, (long long*)ids, nullptr, (hipStream_t)stream, (const int*)forced, trace_hidden,
+                                 trace_logits, (int*)trace_chosen, (int*)trace_emitted);
+    });
+}
+
+// developer entry ("unitable_encoder" only): rd_table_encoder_forward plus three taps, each [B,T,768], back to back in taps_dev: the patch
+// embedding (before the position rows) and the outputs of encoder layers 0 and 11.  The plan of the engine's VIT_WANT_TAPS variant; the
+// internal workspace.  Not part of the public header.
+int rd_debug_table_encoder_taps(rd_handle* h, const float* x, int B, int H, int W, float* memory, float* taps, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->eng && h->eng->kind() == "unitable_encoder", "handle is not a unitable_encoder model");
+        RD_CHECK(x && memory && taps && B > 0 && H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0, "null input/output, or H / W no multiple of 16");
+        const size_t n = (size_t)B * (H / 16) * (W / 16) * 768;
+        h->eng->run(B, H, W, rd::VIT_WANT_TAPS, {(void*)x, (void*)memory, (void*)taps, (void*)(taps + n), (void*)(taps + 2 * n)}, nullptr, 0, (hipStream_t)stream);
     });
 }
 
@@ -1148,6 +1209,13 @@ int rd_debug_attention(int B, int T, int heads, int hd, float scale, float* qkv,
     else rd::launch_attention_h3(qkv, o, B, T, heads, hd, scale, nullptr, seg, flag);
     return debug_finish(flag, range_out);
 }
+// developer entry: vit_attention_kernel alone (kernels_vit_attn.hip) on packed qkv [B][T][3 heads 64] fp32 -> o [B][T][heads 64]; one launch,
+// synchronised.  Returns 0, or -1 for a head size or length the kernel does not serve (hd = 64, 1 <= T <= 1024).
+int rd_debug_vit_attention(int B, int T, int heads, int hd, float scale, float* qkv, float* o) {
+    if (B <= 0 || B > 65535 || heads <= 0 || heads > 65535 || !qkv || !o || !rd::vit_attention_applies(T, hd)) return -1;
+    rd::launch_vit_attention(qkv, o, B, T, heads, scale, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
 // *h3_max_t = the longest line the matrix-core kernel serves at this head size (0: it has none), *valu_lds_keys = the keys the VALU kernel
 // holds in LDS at once (longer lines run over key tiles).  Returns -1 for a head size the library does not have.
 int rd_debug_attention_limits(int hd, int* h3_max_t, int* valu_lds_keys) {
@@ -1157,9 +1225,16 @@ int rd_debug_attention_limits(int hd, int* h3_max_t, int* valu_lds_keys) {
     return 0;
 }
 
-// developer entry: LayerNorm over the last dimension, y[M][yld] = (x[M][xld] - mean) * rstd * g + b on the first C columns.  -1 for C > 512.
+// developer entry: LayerNorm over the last dimension, y[M][yld] = (x[M][xld] - mean) * rstd * g + b on the first C columns.  -1 for C > 512,
+// except C = 768 (layernorm768_kernel; xld and yld multiples of 4).
 int rd_debug_layernorm(int M, int C, float* x, int xld, float* y, int yld, float* g, float* b, float eps) {
-    if (M <= 0 || C <= 0 || C > 512 || xld < C || yld < C) return -1;
+    if (M <= 0 || C <= 0 || xld < C || yld < C) return -1;
+    if (C == 768) {
+        if (xld % 4 || yld % 4) return -1;
+        rd::launch_layernorm768(x, xld, y, yld, g, b, M, eps, nullptr);
+        return debug_finish(nullptr, nullptr);
+    }
+    if (C > 512) return -1;
     rd::launch_layernorm(x, xld, y, yld, g, b, M, C, eps, nullptr);
     return debug_finish(nullptr, nullptr);
 }

@@ -1811,7 +1811,9 @@ void Builder::upsample(const TView& x, const TView& out, int f, bool accumulate)
 }
 
 TView Builder::layernorm(const std::string& prefix, const TView& x, float eps) {
-    RD_CHECK(x.c <= 512, "layernorm: C <= 512");
+    const bool wide = x.c == 768;     // the ViT width: layernorm768_kernel (kernels_vit_attn.hip)
+    RD_CHECK(x.c <= 512 || wide, "layernorm: C <= 512, or C = 768");
+    if (wide) RD_CHECK(x.coff % 4 == 0 && plan_->ld(x) % 4 == 0, "layernorm: a C = 768 view must be 16-byte aligned");
     TView y = alloc(x.n, x.h, x.w, x.c);
     if (!planning()) {
         if (!pb_->has(prefix + ".weight")) {
@@ -1830,11 +1832,68 @@ TView Builder::layernorm(const std::string& prefix, const TView& x, float eps) {
     r.kind = "layernorm";
     r.bytes = 8.0 * x.pixels() * x.c;
     const TView xv = x, yv = y;
-    r.run = [xv, yv, g, b, eps](const Plan& pl, const RunCtx& c) {
-        launch_layernorm(pl.vptr(xv, c), pl.ld(xv), pl.vptr(yv, c), pl.ld(yv), g, b, (int)xv.pixels(), xv.c, eps, c.stream);
+    r.run = [xv, yv, g, b, eps, wide](const Plan& pl, const RunCtx& c) {
+        if (wide) launch_layernorm768(pl.vptr(xv, c), pl.ld(xv), pl.vptr(yv, c), pl.ld(yv), g, b, (int)xv.pixels(), eps, c.stream);
+        else launch_layernorm(pl.vptr(xv, c), pl.ld(xv), pl.vptr(yv, c), pl.ld(yv), g, b, (int)xv.pixels(), xv.c, eps, c.stream);
     };
     emit(std::move(r));
     return y;
+}
+
+TView Builder::vit_attention(const TView& qkv, int B, int T, int heads) {
+    const int hd = 64;
+    RD_CHECK(qkv.c == 3 * heads * hd && qkv.coff == 0 && plan_->ld(qkv) == qkv.c, "vit_attention: packed qkv expected");
+    RD_CHECK(qkv.pixels() == (long)B * T && vit_attention_applies(T, hd), "vit_attention: dense [B][T] batch, 1 <= T <= 1024");
+    TView o = alloc(qkv.n, qkv.h, qkv.w, heads * hd);
+    if (!planning()) return o;
+    OpRecord r;
+    r.name = "self_attn";
+    r.kind = "vit_attention";
+    r.shape = "B" + std::to_string(B) + "_T" + std::to_string(T);
+    r.flops = 4.0 * B * heads * (double)T * T * hd;
+    r.bytes = 16.0 * B * T * heads * hd;
+    const TView qv = qkv, ov = o;
+    r.run = [qv, ov, B, T, heads](const Plan& pl, const RunCtx& c) {
+        launch_vit_attention(pl.vptr(qv, c), pl.vptr(ov, c), B, T, heads, 0.125f, c.stream);
+    };
+    emit(std::move(r));
+    return o;
+}
+
+TView Builder::vit_patchify(const TView& x) {
+    RD_CHECK(x.c == 3 && x.h % 16 == 0 && x.w % 16 == 0 && x.h >= 16 && x.w >= 16, "vit_patchify: [B,3,H,W] with H, W multiples of 16");
+    TView y = alloc(x.n, 1, (x.h / 16) * (x.w / 16), 768);
+    if (!planning()) return y;
+    OpRecord r;
+    r.name = "patchify";
+    r.kind = "layout";
+    r.bytes = 8.0 * y.pixels() * y.c;
+    const TView xv = x, yv = y;
+    r.run = [xv, yv](const Plan& pl, const RunCtx& c) { launch_vit_patchify(pl.vptr(xv, c), pl.vptr(yv, c), xv.n, xv.h, xv.w, c.stream); };
+    emit(std::move(r));
+    return y;
+}
+
+void Builder::add_pos(const std::string& wname, const TView& x, int B, int T) {
+    RD_CHECK(x.pixels() == (long)B * T && x.coff == 0 && plan_->ld(x) == x.c && x.c % 4 == 0, "add_pos: a full-width [B][T][C] tensor expected");
+    if (!planning()) {
+        if (!pb_->has(wname)) {
+            const HostTensor& w = ws_->get(wname);
+            RD_CHECK(w.shape.size() == 2 && (int)w.shape[1] == x.c, "add_pos: table width: " + wname);
+            pb_->add(wname, std::vector<float>(w.f32(), w.f32() + w.numel()));
+        }
+        return;
+    }
+    RD_CHECK(T <= (int)ws_->get(wname).shape[0], "add_pos: more tokens than position rows: " + wname);
+    const float* pos = pb_->ptr(wname);
+    OpRecord r;
+    r.name = wname;
+    r.kind = "add";
+    r.bytes = 12.0 * x.pixels() * x.c;
+    const TView xv = x;
+    const int C = x.c;
+    r.run = [xv, pos, B, T, C](const Plan& pl, const RunCtx& c) { launch_vit_add_pos(pl.vptr(xv, c), pos, B, T, C, c.stream); };
+    emit(std::move(r));
 }
 
 TView Builder::attention(const TView& qkv, int B, int T, int heads, int hd, const TView* seg) {
@@ -2019,7 +2078,7 @@ Engine::Engine(int device, const std::string& kind) : device_(device), kind_(kin
         precision_ = v == "h3" ? PREC_H3 : v == "fp32" ? PREC_FP32 : PREC_AUTO;
     }
     RD_CHECK(kind == "ppocrv6_det" || kind == "ppocrv6_rec" || kind == "ppocrv5_rec_server" || kind == "ppocrv5_rec_mobile" || kind == "ppocr_rec_mv1e" || kind == "ppocrv5_det_server" ||
-                 kind == "ppocrv5_det_mobile" || kind == "ppocrv3_det_mobile" || kind == "ppocr_cls_mobile" ||
+                 kind == "ppocrv5_det_mobile" || kind == "ppocrv3_det_mobile" || kind == "ppocr_cls_mobile" || kind == "unitable_encoder" ||
                  kind == "pphgnetv2_b4" || kind == "pphgnetv2_b6_formula",
              "unknown model kind '" + kind + "'");
     int count = 0;
@@ -2073,6 +2132,7 @@ void Engine::build(Builder& b, int B, int H, int W, int flags) {
     else if (kind_ == "ppocrv5_det_mobile") build_ppocrv5_det_mobile(b, B, H, W, flags);
     else if (kind_ == "ppocrv3_det_mobile") build_ppocrv3_det_mobile(b, B, H, W, flags);
     else if (kind_ == "ppocr_cls_mobile") build_ppocr_cls_mobile(b, B, H, W, flags);
+    else if (kind_ == "unitable_encoder") build_unitable_encoder(b, B, H, W, flags);
     else if (kind_ == "pphgnetv2_b6_formula") build_pphgnetv2_b6_formula(b, B, H, W, flags);
     else build_pphgnetv2_b4(b, B, H, W);
 }
@@ -2100,6 +2160,8 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
         derive_ppocrv3_det_mobile_weights(store_);
     } else if (kind_ == "ppocr_cls_mobile") {
         derive_ppocr_cls_mobile_weights(store_);
+    } else if (kind_ == "unitable_encoder") {
+        derive_unitable_encoder_weights(store_);
     }
     Plan dummy;
     h3_prepared_ = precision_ == PREC_H3;
@@ -2112,6 +2174,7 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
     // smallest legal geometry; only weight names/shapes matter in PREPARE mode
     if (kind_ == "ppocrv6_rec" || kind_ == "ppocrv5_rec_server" || kind_ == "ppocrv5_rec_mobile" || kind_ == "ppocr_rec_mv1e") build(b, 1, 48, 64, 0), build(b, 1, 48, 64, REC_UNFUSED_CTC);
     else if (kind_ == "ppocr_cls_mobile") build(b, 1, 48, 192, 0);
+    else if (kind_ == "unitable_encoder") build(b, 1, 16, 16, 0);
     else build(b, 1, 64, 64, 0);
     params_.upload();
     loaded_ = true;

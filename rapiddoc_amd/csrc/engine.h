@@ -271,6 +271,10 @@ class Builder {
     TView layernorm(const std::string& prefix, const TView& x, float eps);
     // seg: ragged batch - int32 external [B][2] = (first token, tokens) of every sequence; T = the longest sequence
     TView attention(const TView& qkv, int B, int T, int heads, int hd, const TView* seg = nullptr);
+    // ViT pieces (kernels_vit_attn.hip).  vit_attention: head dimension 64, dense [B][T] batches, T <= 1024, every precision mode alike
+    TView vit_attention(const TView& qkv, int B, int T, int heads);
+    TView vit_patchify(const TView& x_nchw);                       // [B,H,W,3]-described NCHW external -> [B,1,T,768] patch rows
+    void add_pos(const std::string& wname, const TView& x, int B, int T);   // x [B][T][C] += rows 0..T-1 of the embedding table `wname`, in place
     TView add(const TView& a, const TView& b);
     void to_nchw(const TView& x, const TView& out_ext);
     void copy(const TView& x, const TView& out);   // same geometry, possibly different channel strides
@@ -434,6 +438,14 @@ bool cls_mobile_geometry(int H, int W, int rows[4], int* cols);
 // default route of the classifier: true = cls_line_kernel (from the alternating A/B of tools/mb_cls_mobile.py at B = 6 and B = 1440,
 // docs/notebook/cls_mobile.md); the route goes by the network, never by the batch
 bool cls_fused_default();
+// UniTable table-structure encoder (ViT-B: Conv2d(3, 768, 16, stride 16) patches + learned positions, 12 pre-norm encoder layers of 12 heads
+// of 64 and FFN 3072 with erf GELU, final LayerNorm eps 1e-6): ext[0] = x NCHW [B,3,H,W] (H, W multiples of 16, T = HW / 256 <= 1024),
+// ext[1] = memory [B,T,768].  VIT_WANT_TAPS (developer, rd_debug_table_encoder_taps): ext[2..4] = the patch embedding (before the
+// position rows), the outputs of layers 0 and 11, each [B,T,768]
+enum VitFlags : int { VIT_WANT_TAPS = 1 };
+void build_unitable_encoder(Builder& b, int B, int H, int W, int flags);
+// the tensor build_unitable_encoder reads that is not in the file: conv_proj's weight as a [768][768] matrix
+void derive_unitable_encoder_weights(WeightStore& ws);
 void build_pphgnetv2_b4(Builder& b, int B, int H, int W);
 // PP-FormulaNet_plus encoder; flags bit 0: the caller's image has 1 channel (replicated to 3 like the reference)
 void build_pphgnetv2_b6_formula(Builder& b, int B, int H, int W, int flags);

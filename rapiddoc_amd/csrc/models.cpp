@@ -1224,4 +1224,58 @@ void build_ppocr_cls_mobile(Builder& b, int B, int H, int W, int flags) {
     b.release(t);
 }
 
+// =================================================================================================
+// UniTable table-structure encoder (unitable_modules.py Encoder): ImgLinearBackbone (Conv2d(3, 768, 16, stride 16), flattened to token
+// rows) + PositionEmbedding + 12 nn.TransformerEncoderLayer (norm_first, erf GELU, eps 1e-5) + LayerNorm (eps 1e-6)
+// =================================================================================================
+static const int kVitD = 768, kVitHeads = 12, kVitLayers = 12, kVitPatch = 16, kVitMaxT = 1024;
+
+void derive_unitable_encoder_weights(WeightStore& ws) {
+    // conv_proj [768][3][16][16] read as the [768][768] matrix of the patch GEMM: Builder::vit_patchify gathers a patch in (c, ky, kx) order,
+    // the order of the weight's rows as they are stored
+    const HostTensor& w = ws.get("backbone.conv_proj.weight");
+    RD_CHECK(w.shape.size() == 4 && w.shape[0] == kVitD && w.shape[1] == 3 && w.shape[2] == kVitPatch && w.shape[3] == kVitPatch,
+             "unitable encoder: backbone.conv_proj.weight must be [768,3,16,16]");
+    ws.add_derived("backbone.conv_proj.patch.weight", {kVitD, 3 * kVitPatch * kVitPatch}, std::vector<float>(w.f32(), w.f32() + w.numel()));
+}
+
+void build_unitable_encoder(Builder& b, int B, int H, int W, int flags) {
+    RD_CHECK((flags & ~VIT_WANT_TAPS) == 0, "unitable encoder: unknown flag");
+    RD_CHECK(B >= 1 && H >= kVitPatch && W >= kVitPatch && H % kVitPatch == 0 && W % kVitPatch == 0,
+             "unitable encoder: input " + std::to_string(H) + " x " + std::to_string(W) + ": H and W must be multiples of 16");
+    const int T = (H / kVitPatch) * (W / kVitPatch);
+    RD_CHECK(T <= kVitMaxT, "unitable encoder: " + std::to_string(T) + " patches, the position table holds 1024");
+    const bool taps = (flags & VIT_WANT_TAPS) != 0;
+    TView x = b.external(0, B, H, W, 3);
+    TView memory = b.external(1, B, 1, T, kVitD);
+    TView patches = b.vit_patchify(x);
+    TView t = b.conv("backbone.conv_proj.patch.weight", "backbone.conv_proj.bias", "", patches, geom(1), ACT_NONE);
+    b.release(patches);
+    if (taps) b.copy(t, b.external(2, B, 1, T, kVitD));
+    b.add_pos("pos_embed.embedding.weight", t, B, T);
+    for (int i = 0; i < kVitLayers; ++i) {
+        const std::string p = "encoder.layers." + std::to_string(i);
+        TView y = b.layernorm(p + ".norm1", t, 1e-5f);
+        TView qkv = b.conv(p + ".self_attn.in_proj_weight", p + ".self_attn.in_proj_bias", "", y, geom(1), ACT_NONE);
+        b.release(y);
+        TView a = b.vit_attention(qkv, B, T, kVitHeads);
+        b.release(qkv);
+        TView t2 = b.linear(p + ".self_attn.out_proj", a, ACT_NONE, nullptr, &t);
+        b.release(a);
+        b.release(t);
+        TView y2 = b.layernorm(p + ".norm2", t2, 1e-5f);
+        TView m = b.linear(p + ".linear1", y2, ACT_GELU);
+        b.release(y2);
+        t = b.linear(p + ".linear2", m, ACT_NONE, nullptr, &t2);
+        b.release(m);
+        b.release(t2);
+        if (taps && (i == 0 || i == kVitLayers - 1)) b.copy(t, b.external(i == 0 ? 3 : 4, B, 1, T, kVitD));
+    }
+    // the final LayerNorm writes into a workspace buffer; the result leaves through one copy (a [B,T,768] tensor is NHWC [B,1,T,768] as it is)
+    TView n = b.layernorm("norm", t, 1e-6f);
+    b.release(t);
+    b.copy(n, memory);
+    b.release(n);
+}
+
 }  // namespace rd

@@ -419,6 +419,17 @@ void launch_attention(const float* qkv, float* o, int B, int T, int heads, int h
 // the VALU kernel (native fp32) for EVERY line, whatever its length: precision "fp32", developer entries
 void launch_attention_valu(const float* qkv, float* o, int B, int T, int heads, int hd, float scale, hipStream_t s, const int32_t* seg = nullptr);
 
+// kernels_vit_attn.hip (the UniTable encoder, a plain ViT-B).  The same attention contract at head dimension 64, T <= 1024, dense batches:
+// keys in tiles of 64 with an online softmax, both products on the fp32-input matrix cores - one kernel for every precision mode, no range flag
+bool vit_attention_applies(int T, int hd);
+void launch_vit_attention(const float* qkv, float* o, int B, int T, int heads, float scale, hipStream_t s);
+// x NCHW [B][3][H][W] (H, W multiples of 16) -> y [B * (H/16) * (W/16)][768], column (c * 16 + ky) * 16 + kx: the rows of the patch-embedding GEMM
+void launch_vit_patchify(const float* x, float* y, int B, int H, int W, hipStream_t s);
+// x [B][T][C] += pos [T][C], in place (C % 4 == 0)
+void launch_vit_add_pos(float* x, const float* pos, int B, int T, int C, hipStream_t s);
+// launch_layernorm's arithmetic at C = 768 exactly (xld, yld multiples of 4)
+void launch_layernorm768(const float* x, int xld, float* y, int yld, const float* g, const float* b, int M, float eps, hipStream_t s);
+
 // y = a + b (same geometry, views)
 void launch_add(const float* a, int ald, const float* b, int bld, float* y, int yld, int M, int C, hipStream_t s);
 

@@ -1,0 +1,461 @@
+// UniTable table-structure decoder (unitable_modules.py GPTFastDecoder + UniTableStructure.loop_decode): greedy autoregressive decode of B <= 8
+// tables at once over the encoder's `memory`, D = 768, 12 heads of 64, FFN 3072, 4 pre-norm blocks, no final norm, generator 768 -> 960.
+// Structure as formula_decoder.hip: the fused weights per load; K and V of `memory` for the 4 layers once per table batch (the fp32 MFMA
+// GEMM at M = B S); per token step a chain of launches with constant arguments (the step index lives in device memory), captured once into
+// a hipGraph and replayed; the host looks at the per-table EOS flags every 8 steps.
+//   td_gemv_kernel    weight-streaming GEMV at M = B: one wavefront per output column streams its weight row once and serves all B rows;
+//                     a (row, column) sum has the same order whatever B is
+//   td_attn_kernel    one workgroup per (table, head): scores into LDS, max, exp, sum, P V; the self form appends the step's K / V row to
+//                     the cache (1024 rows, fp32) and attends rows 0 .. step (the causal mask at input_pos)
+//   td_select_kernel  whitelist argmax (ids 1 and 12 .. 509; NaN counts as -inf, so the winner is always an id below 960), the bbox rule
+//                     (a counter per table that ONLY a bbox token raises and only its overflow clears), the per-table EOS latch (a
+//                     finished table keeps its slot and writes `pad`), and the next step's embedding + position row
+// No atomics: every table has its own flag, counter and token word.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "engine.h"
+#include "rd_device.h"
+
+namespace rd {
+
+namespace {
+constexpr int TD_D = 768, TD_HEADS = 12, TD_HD = 64, TD_FFN = 3072, TD_LAYERS = 4, TD_VOCAB = 960, TD_MAXPOS = 1024, TD_MAXB = 8;
+}
+
+struct TdCfg { int prefix, eos, pad, close_id, bbox_lo, bbox_hi; };
+struct TdState { int step; };
+
+__device__ __forceinline__ bool td_whitelisted(int v) { return v == 1 || (v >= 12 && v <= 509); }
+
+// x[b] = emb[tok] + pos[p]
+__device__ __forceinline__ void td_embed_row(const float* emb, const float* pos, int tok, int p, float* x) {
+    for (int c = threadIdx.x; c < TD_D; c += blockDim.x) x[c] = emb[(size_t)tok * TD_D + c] + pos[(size_t)p * TD_D + c];
+}
+
+__global__ void __launch_bounds__(256) td_init_kernel(TdState* st, int* finished, int* boxcount, int* tok, long long* ids, int ids_ld, TdCfg cfg,
+                                                      const int* forced, int forced_ld, const float* emb, const float* pos, float* x) {
+    const int b = blockIdx.x;
+    const int t0 = min(max(forced ? forced[(size_t)b * forced_ld] : cfg.prefix, 0), TD_VOCAB - 1);     // (an embedding row: clamped as every later token)
+    if (threadIdx.x == 0) {
+        if (b == 0) st->step = 0;
+        finished[b] = 0;
+        boxcount[b] = 0;
+        tok[b] = t0;
+    }
+    for (int c = threadIdx.x; c < ids_ld; c += blockDim.x) ids[(size_t)b * ids_ld + c] = c == 0 ? t0 : cfg.pad;
+    td_embed_row(emb, pos, t0, 0, x + (size_t)b * TD_D);
+}
+
+__global__ void td_advance_kernel(TdState* st) { st->step += 1; }
+
+__global__ void __launch_bounds__(256) td_trace_kernel(const float* src, float* dst, long long n, long long step_stride, const TdState* st) {
+    float* d = dst + (size_t)st->step * step_stride;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) d[i] = src[i];
+}
+
+// y[b][n] = act(x[b] . w[n] + bias[n]) (+ res[b][n]); K % 256 == 0; grid N / 4, wavefront per column
+__global__ void __launch_bounds__(256) td_gemv_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                      const float* __restrict__ res, float* __restrict__ y, int B, int K, int N, int act) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    float acc[TD_MAXB];
+#pragma unroll
+    for (int b = 0; b < TD_MAXB; ++b) acc[b] = 0.f;
+    const float* wr = w + (size_t)n * K;
+    for (int k = 4 * lane; k < K; k += 256) {
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(wr + k);
+#pragma unroll
+        for (int b = 0; b < TD_MAXB; ++b)
+            if (b < B) {
+                const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)b * K + k);
+                acc[b] = fmaf(wv[0], xv[0], acc[b]);
+                acc[b] = fmaf(wv[1], xv[1], acc[b]);
+                acc[b] = fmaf(wv[2], xv[2], acc[b]);
+                acc[b] = fmaf(wv[3], xv[3], acc[b]);
+            }
+    }
+#pragma unroll
+    for (int b = 0; b < TD_MAXB; ++b)
+        if (b < B) {
+            float v = acc[b];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) {
+                v = rd_act(v + (bias ? bias[n] : 0.f), act);
+                if (res) v += res[(size_t)b * N + n];
+                y[(size_t)b * N + n] = v;
+            }
+        }
+}
+
+struct TdAttn {
+    const float* q; int ldq;            // [B][ldq], head h at column 64 h
+    float* kc; float* vc;               // rows [b * seq_stride + j * ldkv + 64 h]
+    int ldkv; long long seq_stride;
+    const float* kcur; const float* vcur; int ldcur;   // self form: the step's K / V rows (appended at row `step`), else null
+    const TdState* st; int fixed_T;     // keys = fixed_T, or step + 1 in the self form
+    float* out; int ldo;
+};
+
+__global__ void __launch_bounds__(256) td_attn_kernel(TdAttn p) {
+    __shared__ float sc[TD_MAXPOS];
+    __shared__ float qs[TD_HD];
+    __shared__ float red[4];
+    __shared__ float part[4][TD_HD];
+    const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool self = p.kcur != nullptr;
+    const int pos = self ? min(p.st->step, TD_MAXPOS - 1) : 0;
+    const int T = self ? pos + 1 : p.fixed_T;
+    float* kb = p.kc + (size_t)b * p.seq_stride + h * TD_HD;
+    float* vb = p.vc + (size_t)b * p.seq_stride + h * TD_HD;
+    const float* kcur = self ? p.kcur + (size_t)b * p.ldcur + h * TD_HD : nullptr;
+    const float* vcur = self ? p.vcur + (size_t)b * p.ldcur + h * TD_HD : nullptr;
+    if (tid < TD_HD) {
+        qs[tid] = p.q[(size_t)b * p.ldq + h * TD_HD + tid] * 0.125f;
+        if (self) {       // append to the cache; this launch reads the row from kcur / vcur, later steps from the cache
+            kb[(size_t)pos * p.ldkv + tid] = kcur[tid];
+            vb[(size_t)pos * p.ldkv + tid] = vcur[tid];
+        }
+    }
+    __syncthreads();
+    float m = -INFINITY;
+    for (int j = tid; j < T; j += 256) {
+        const float* kr = (self && j == pos) ? kcur : kb + (size_t)j * p.ldkv;
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < TD_HD; d += 4) {
+            const f32x4 kv = *reinterpret_cast<const f32x4*>(kr + d);
+            s = fmaf(qs[d], kv[0], s); s = fmaf(qs[d + 1], kv[1], s); s = fmaf(qs[d + 2], kv[2], s); s = fmaf(qs[d + 3], kv[3], s);
+        }
+        sc[j] = s;
+        m = fmaxf(m, s);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float l = 0.f;
+    for (int j = tid; j < T; j += 256) {
+        const float e = expf(sc[j] - m);
+        sc[j] = e;
+        l += e;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) l += __shfl_xor(l, o, 64);
+    if (lane == 0) red[wave] = l;
+    __syncthreads();
+    l = (red[0] + red[1]) + (red[2] + red[3]);
+    float acc = 0.f;
+    for (int j = wave; j < T; j += 4) {
+        const float* vr = (self && j == pos) ? vcur : vb + (size_t)j * p.ldkv;
+        acc = fmaf(sc[j], vr[lane], acc);
+    }
+    part[wave][lane] = acc;
+    __syncthreads();
+    if (tid < TD_HD) p.out[(size_t)b * p.ldo + h * TD_HD + tid] = ((part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid])) / l;
+}
+
+struct TdSelect {
+    const float* logits; long long* ids; int ids_ld; int* finished; int* boxcount; int* tok; const TdState* st; TdCfg cfg; int max_new;
+    const int* forced; int forced_ld;          // developer: the tokens fed to steps 0 .. (the EOS latch is off)
+    int* trace_chosen; int* trace_emitted; int B;
+    const float* emb; const float* pos; float* x;
+};
+
+__global__ void __launch_bounds__(1024) td_select_kernel(TdSelect p) {
+    __shared__ float bv[1024];
+    __shared__ int bi[1024];
+    __shared__ int next_tok;
+    const int b = blockIdx.x, tid = threadIdx.x, step = p.st->step;
+    float v = -INFINITY;
+    if (tid < TD_VOCAB) {
+        v = td_whitelisted(tid) ? p.logits[(size_t)b * TD_VOCAB + tid] : -1e9f;
+        if (!(v == v)) v = -INFINITY;          // NaN never wins
+    }
+    bv[tid] = v;
+    bi[tid] = tid < TD_VOCAB ? tid : TD_VOCAB - 1;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {        // the larger value, the lower id among equals
+        if (tid < s) {
+            const float a = bv[tid], c = bv[tid + s];
+            if (c > a || (c == a && bi[tid + s] < bi[tid])) { bv[tid] = c; bi[tid] = bi[tid + s]; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int chosen = bi[0];
+        int emitted = chosen;
+        if (chosen >= p.cfg.bbox_lo && chosen <= p.cfg.bbox_hi) {
+            int c = p.boxcount[b] + 1;
+            if (c > 4) { emitted = p.cfg.close_id; c = 0; }
+            p.boxcount[b] = c;
+        }
+        if (p.trace_chosen) p.trace_chosen[(size_t)step * p.B + b] = chosen;
+        if (p.trace_emitted) p.trace_emitted[(size_t)step * p.B + b] = emitted;
+        const bool was_done = p.finished[b] != 0;
+        if (step + 1 < p.ids_ld) p.ids[(size_t)b * p.ids_ld + step + 1] = was_done ? p.cfg.pad : emitted;
+        if (!p.forced && !was_done && emitted == p.cfg.eos) p.finished[b] = 1;
+        int nt = (was_done || emitted == p.cfg.eos) ? p.cfg.eos : emitted;
+        if (p.forced) nt = step + 1 < p.forced_ld ? p.forced[(size_t)b * p.forced_ld + step + 1] : p.cfg.eos;
+        nt = min(max(nt, 0), TD_VOCAB - 1);
+        p.tok[b] = nt;
+        next_tok = nt;
+    }
+    __syncthreads();
+    if (step + 1 < TD_MAXPOS) td_embed_row(p.emb, p.pos, next_tok, step + 1, p.x + (size_t)b * TD_D);
+}
+
+// =================================================================================================
+class TableDecoder {
+   public:
+    explicit TableDecoder(int device) : device_(device) {}
+    ~TableDecoder() {
+        (void)hipSetDevice(device_);
+        if (buf_) (void)hipFree(buf_);
+    }
+    void load(const WeightStore& ws);
+    int decode(const float* memory, int B, int S, int max_new, const TdCfg& cfg, long long* ids_out, int* n_tokens, hipStream_t s, const int* forced,
+               float* trace_hidden, float* trace_logits, int* trace_chosen, int* trace_emitted);
+
+   private:
+    void gemm(const float* x, int M, int K, const std::string& key, int N, float* y, hipStream_t s);
+    void gemv(const float* x, int B, int K, const std::string& key, int N, float* y, int act, const float* res, hipStream_t s) {
+        hipLaunchKernelGGL(td_gemv_kernel, dim3((N + 3) / 4), dim3(256), 0, s, x, params_.ptr(key + "#w"), params_.ptr(key + "#b"), res, y, B, K, N, act);
+    }
+    void ln(const float* x, const std::string& key, float* y, int M, hipStream_t s) {
+        launch_layernorm768(x, TD_D, y, TD_D, params_.ptr(key + ".weight"), params_.ptr(key + ".bias"), M, 1e-5f, s);
+    }
+    int device_;
+    ParamBlock params_;
+    uint8_t* buf_ = nullptr;
+    size_t buf_bytes_ = 0;
+};
+
+static std::vector<float> td_vec(const HostTensor& t) { return std::vector<float>(t.f32(), t.f32() + t.numel()); }
+
+void TableDecoder::load(const WeightStore& ws) {
+    auto shape2 = [&](const std::string& n, int a, int b) {
+        const HostTensor& t = ws.get(n);
+        RD_CHECK(t.shape.size() == 2 && t.shape[0] == a && t.shape[1] == b, "table decoder: unexpected shape of " + n);
+    };
+    shape2("token_embed.embedding.weight", TD_VOCAB, TD_D);
+    shape2("pos_embed.embedding.weight", TD_MAXPOS, TD_D);
+    shape2("generator.weight", TD_VOCAB, TD_D);
+    params_.add("emb", td_vec(ws.get("token_embed.embedding.weight")));
+    params_.add("pos", td_vec(ws.get("pos_embed.embedding.weight")));
+    auto lin = [&](const std::string& name, const std::string& key, int n, int k) {
+        shape2(name + ".weight", n, k);
+        params_.add(key + "#w", td_vec(ws.get(name + ".weight")));
+        params_.add(key + "#b", td_vec(ws.get(name + ".bias")));
+    };
+    auto add_ln = [&](const std::string& name, const std::string& key) {
+        params_.add(key + ".weight", td_vec(ws.get(name + ".weight")));
+        params_.add(key + ".bias", td_vec(ws.get(name + ".bias")));
+    };
+    for (int l = 0; l < TD_LAYERS; ++l) {
+        const std::string L = "layers." + std::to_string(l) + ".", K = "l" + std::to_string(l) + ".";
+        add_ln(L + "norm1", K + "ln1");
+        add_ln(L + "norm2", K + "ln2");
+        add_ln(L + "norm3", K + "ln3");
+        lin(L + "self_attn.wqkv", K + "qkv", 3 * TD_D, TD_D);
+        lin(L + "self_attn.wo", K + "wo", TD_D, TD_D);
+        lin(L + "multihead_attn.query", K + "cq", TD_D, TD_D);
+        lin(L + "multihead_attn.key", K + "ck", TD_D, TD_D);
+        lin(L + "multihead_attn.value", K + "cv", TD_D, TD_D);
+        lin(L + "multihead_attn.out", K + "co", TD_D, TD_D);
+        lin(L + "linear1", K + "fc1", TD_FFN, TD_D);
+        lin(L + "linear2", K + "fc2", TD_D, TD_FFN);
+    }
+    lin("generator", "gen", TD_VOCAB, TD_D);
+    params_.upload();
+}
+
+// y [M][N] = x [M][K] . W^T + b on the fp32 MFMA GEMM (the once-per-batch projections of `memory`)
+void TableDecoder::gemm(const float* x, int M, int K, const std::string& key, int N, float* y, hipStream_t s) {
+    ConvParams p{};
+    p.x = x; p.xld = K; p.N = 1; p.H = 1; p.W = M; p.Cin = K;
+    p.w = params_.ptr(key + "#w");
+    p.bias = params_.ptr(key + "#b");
+    p.y = y; p.yld = N; p.OH = 1; p.OW = M; p.Cout = N;
+    p.KH = p.KW = p.SH = p.SW = 1;
+    p.act = ACT_NONE; p.out_mode = OUT_NHWC;
+    p.M = M; p.K = K; p.Ng = N;
+    launch_conv_igemm(p, s);
+}
+
+int TableDecoder::decode(const float* memory, int B, int S, int max_new, const TdCfg& cfg, long long* ids_out, int* n_tokens, hipStream_t s,
+                         const int* forced, float* trace_hidden, float* trace_logits, int* trace_chosen, int* trace_emitted) {
+    RD_HIP(hipSetDevice(device_));
+    RD_CHECK(memory && ids_out, "table decode: null input/output");
+    RD_CHECK(B >= 1 && B <= TD_MAXB, "table decode: this build serves batches of 1 .. 8 tables; got B = " + std::to_string(B));
+    RD_CHECK(S >= 1 && S <= TD_MAXPOS, "table decode: 1 <= S <= 1024 memory rows per table");
+    RD_CHECK(max_new >= 1 && max_new <= TD_MAXPOS, "table decode: 1 <= max_new_tokens <= 1024");
+    auto in_vocab = [](int v) { return v >= 0 && v < TD_VOCAB; };
+    RD_CHECK(in_vocab(cfg.prefix) && in_vocab(cfg.eos) && in_vocab(cfg.close_id), "table decode: prefix, eos and close ids must lie in 0 .. 959");
+    RD_CHECK(cfg.bbox_lo <= cfg.bbox_hi, "table decode: empty bbox id range");
+    const int ids_ld = max_new + 1;
+    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t f = sizeof(float);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    const size_t o_state = take(sizeof(TdState)), o_fin = take(TD_MAXB * sizeof(int)), o_box = take(TD_MAXB * sizeof(int)), o_tok = take(TD_MAXB * sizeof(int));
+    const size_t o_ck = take((size_t)TD_LAYERS * B * S * TD_D * f), o_cv = take((size_t)TD_LAYERS * B * S * TD_D * f);
+    const size_t o_kc = take((size_t)TD_LAYERS * B * TD_MAXPOS * TD_D * f), o_vc = take((size_t)TD_LAYERS * B * TD_MAXPOS * TD_D * f);
+    const size_t o_x = take((size_t)B * TD_D * f), o_x2 = take((size_t)B * TD_D * f), o_h = take((size_t)B * TD_D * f);
+    const size_t o_qkv = take((size_t)B * 3 * TD_D * f), o_a = take((size_t)B * TD_D * f), o_f = take((size_t)B * TD_FFN * f);
+    const size_t o_lg = take((size_t)B * TD_VOCAB * f);
+    if (off > buf_bytes_) {
+        RD_HIP(hipStreamSynchronize(s));
+        if (buf_) RD_HIP(hipFree(buf_));
+        buf_ = nullptr;
+        buf_bytes_ = 0;
+        RD_HIP(hipMalloc((void**)&buf_, off));
+        buf_bytes_ = off;
+    }
+    TdState* st = reinterpret_cast<TdState*>(buf_ + o_state);
+    int* fin = reinterpret_cast<int*>(buf_ + o_fin);
+    int* box = reinterpret_cast<int*>(buf_ + o_box);
+    int* tok = reinterpret_cast<int*>(buf_ + o_tok);
+    float* ck = reinterpret_cast<float*>(buf_ + o_ck);
+    float* cv = reinterpret_cast<float*>(buf_ + o_cv);
+    float* kc = reinterpret_cast<float*>(buf_ + o_kc);
+    float* vc = reinterpret_cast<float*>(buf_ + o_vc);
+    float* x = reinterpret_cast<float*>(buf_ + o_x);
+    float* x2 = reinterpret_cast<float*>(buf_ + o_x2);
+    float* h = reinterpret_cast<float*>(buf_ + o_h);
+    float* qkv = reinterpret_cast<float*>(buf_ + o_qkv);
+    float* a = reinterpret_cast<float*>(buf_ + o_a);
+    float* ff = reinterpret_cast<float*>(buf_ + o_f);
+    float* lg = reinterpret_cast<float*>(buf_ + o_lg);
+    const int forced_ld = max_new;
+
+    hipLaunchKernelGGL(td_init_kernel, dim3(B), dim3(256), 0, s, st, fin, box, tok, ids_out, ids_ld, cfg, forced, forced_ld, params_.ptr("emb"),
+                       params_.ptr("pos"), x);
+    // once per table batch: every layer's cross-attention K and V of `memory`
+    for (int l = 0; l < TD_LAYERS; ++l) {
+        const std::string K = "l" + std::to_string(l) + ".";
+        gemm(memory, B * S, TD_D, K + "ck", TD_D, ck + (size_t)l * B * S * TD_D, s);
+        gemm(memory, B * S, TD_D, K + "cv", TD_D, cv + (size_t)l * B * S * TD_D, s);
+    }
+    auto enqueue_step = [&]() {
+        float* cur = x;
+        float* nxt = x2;
+        for (int l = 0; l < TD_LAYERS; ++l) {
+            const std::string K = "l" + std::to_string(l) + ".";
+            ln(cur, K + "ln1", h, B, s);
+            gemv(h, B, TD_D, K + "qkv", 3 * TD_D, qkv, ACT_NONE, nullptr, s);
+            TdAttn sp{};
+            sp.q = qkv; sp.ldq = 3 * TD_D;
+            sp.kc = kc + (size_t)l * B * TD_MAXPOS * TD_D; sp.vc = vc + (size_t)l * B * TD_MAXPOS * TD_D; sp.ldkv = TD_D; sp.seq_stride = (long long)TD_MAXPOS * TD_D;
+            sp.kcur = qkv + TD_D; sp.vcur = qkv + 2 * TD_D; sp.ldcur = 3 * TD_D;
+            sp.st = st; sp.fixed_T = 0; sp.out = a; sp.ldo = TD_D;
+            hipLaunchKernelGGL(td_attn_kernel, dim3(TD_HEADS, B), dim3(256), 0, s, sp);
+            gemv(a, B, TD_D, K + "wo", TD_D, nxt, ACT_NONE, cur, s);
+            std::swap(cur, nxt);
+            ln(cur, K + "ln2", h, B, s);
+            gemv(h, B, TD_D, K + "cq", TD_D, qkv, ACT_NONE, nullptr, s);
+            TdAttn cp{};
+            cp.q = qkv; cp.ldq = TD_D;
+            cp.kc = ck + (size_t)l * B * S * TD_D; cp.vc = cv + (size_t)l * B * S * TD_D; cp.ldkv = TD_D; cp.seq_stride = (long long)S * TD_D;
+            cp.st = st; cp.fixed_T = S; cp.out = a; cp.ldo = TD_D;
+            hipLaunchKernelGGL(td_attn_kernel, dim3(TD_HEADS, B), dim3(256), 0, s, cp);
+            gemv(a, B, TD_D, K + "co", TD_D, nxt, ACT_NONE, cur, s);
+            std::swap(cur, nxt);
+            ln(cur, K + "ln3", h, B, s);
+            gemv(h, B, TD_D, K + "fc1", TD_FFN, ff, ACT_GELU, nullptr, s);
+            gemv(ff, B, TD_FFN, K + "fc2", TD_D, nxt, ACT_NONE, cur, s);
+            std::swap(cur, nxt);
+            if (trace_hidden)
+                hipLaunchKernelGGL(td_trace_kernel, dim3(8), dim3(256), 0, s, cur, trace_hidden + (size_t)l * B * TD_D, (long long)B * TD_D,
+                                   (long long)TD_LAYERS * B * TD_D, st);
+        }
+        gemv(cur, B, TD_D, "gen", TD_VOCAB, lg, ACT_NONE, nullptr, s);
+        if (trace_logits) hipLaunchKernelGGL(td_trace_kernel, dim3(8), dim3(256), 0, s, lg, trace_logits, (long long)B * TD_VOCAB, (long long)B * TD_VOCAB, st);
+        RD_CHECK(cur == x, "table decode: the layer stack must end in the buffer the next embedding is written to");
+        TdSelect sel{lg, ids_out, ids_ld, fin, box, tok, st, cfg, max_new, forced, forced_ld, trace_chosen, trace_emitted, B, params_.ptr("emb"),
+                     params_.ptr("pos"), x};
+        hipLaunchKernelGGL(td_select_kernel, dim3(B), dim3(1024), 0, s, sel);
+        hipLaunchKernelGGL(td_advance_kernel, dim3(1), dim3(1), 0, s, st);
+    };
+    struct StepGraph {          // the captured step; freed on every way out of this function, a throwing RD_HIP included
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        hipStream_t stream = nullptr;
+        ~StepGraph() {
+            if (exec) {
+                (void)hipStreamSynchronize(stream);
+                (void)hipGraphExecDestroy(exec);
+            }
+            if (graph) (void)hipGraphDestroy(graph);
+        }
+    } sg;
+    sg.stream = s;
+    if (max_new > 2 && s != nullptr) {          // (the null stream cannot be captured: direct launches there)
+        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            enqueue_step();
+            if (hipStreamEndCapture(s, &sg.graph) != hipSuccess || hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0) != hipSuccess) {
+                if (sg.graph) (void)hipGraphDestroy(sg.graph);
+                sg.graph = nullptr;
+                sg.exec = nullptr;
+                (void)hipGetLastError();
+            }
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    int hfin[TD_MAXB] = {0};
+    for (int t = 0; t < max_new; ++t) {
+        if (sg.exec) RD_HIP(hipGraphLaunch(sg.exec, s));
+        else enqueue_step();
+        if (!forced && ((t & 7) == 7 || t + 1 == max_new)) {      // all tables ended? (every 8 steps: one small D2H + sync)
+            RD_HIP(hipMemcpyAsync(hfin, fin, sizeof(hfin), hipMemcpyDeviceToHost, s));
+            RD_HIP(hipStreamSynchronize(s));
+            bool all = true;
+            for (int b = 0; b < B; ++b) all = all && hfin[b] != 0;
+            if (all) break;
+        }
+    }
+    RD_HIP(hipStreamSynchronize(s));
+    RD_HIP(hipGetLastError());
+    if (n_tokens) {       // tokens of every table, the prefix and its EOS included (max_new + 1 where it never stopped)
+        std::vector<long long> ids((size_t)B * ids_ld);
+        RD_HIP(hipMemcpy(ids.data(), ids_out, ids.size() * sizeof(long long), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b) {
+            int n = ids_ld;
+            for (int c = 1; c < ids_ld; ++c)
+                if (ids[(size_t)b * ids_ld + c] == cfg.eos) { n = c + 1; break; }
+            n_tokens[b] = n;
+        }
+    }
+    return 0;
+}
+
+TableDecoder* table_decoder_create(int device, const void* blob, size_t nbytes) {
+    RD_HIP(hipSetDevice(device));
+    WeightStore ws;
+    ws.load_safetensors(blob, nbytes);
+    auto* d = new TableDecoder(device);
+    try {
+        d->load(ws);
+    } catch (...) {
+        delete d;
+        throw;
+    }
+    return d;
+}
+void table_decoder_destroy(TableDecoder* d) { delete d; }
+int table_decoder_decode(TableDecoder* d, const float* memory, int B, int S, int max_new, const int* cfg6, long long* ids, int* n_tokens, hipStream_t s,
+                         const int* forced, float* trace_hidden, float* trace_logits, int* trace_chosen, int* trace_emitted) {
+    TdCfg c{cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5]};
+    return d->decode(memory, B, S, max_new, c, ids, n_tokens, s, forced, trace_hidden, trace_logits, trace_chosen, trace_emitted);
+}
+
+}  // namespace rd

@@ -20,7 +20,7 @@ DET_NECK_CHANNELS = {"ppocrv5_det_server": 256, "ppocrv5_det_mobile": 96}
 DET_NECK_CHANNELS_V3_MOBILE = {"ppocrv3_det_mobile": 96}    # the PP-OCRv3 multilingual detector: the same RSEFPN
 CLS_WANT_AUX = 1            # ppocr_cls_mobile: also hand out [B, 2 logits | 200 pooled features]
 CLS_FEATURES = 200          # channels of the classifier's pooled features (conv2 of MobileNetV3 small scale 0.35)
-KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv3_det_mobile", "ppocr_cls_mobile", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "ppocr_rec_mv1e", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
+KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv3_det_mobile", "ppocr_cls_mobile", "unitable_encoder", "unitable_decoder", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "ppocr_rec_mv1e", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
 
 
 def rec_line_table(widths, first_tokens) -> np.ndarray:
@@ -245,6 +245,86 @@ class RdEngine:
             self._log()
         self._guarded(launch)
         return (out, aux) if want_aux else out
+
+    def table_encoder_forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, want_taps: bool = False):
+        """UniTable table-structure encoder (unitable_encoder): x [B,3,H,W], already normalised (H, W multiples of 16, at most 1024
+        patches; the product shape is 448 x 448) -> memory [B,T,768].  `out`: a caller-owned contiguous float32 [B,T,768] result tensor.
+        `want_taps` (developer, rd_debug_table_encoder_taps): returns (memory, [patch embedding, layer 0 output, layer 11 output]), each
+        [B,T,768]."""
+        if self.kind != "unitable_encoder":
+            raise EngineError("table_encoder_forward: the handle is not a unitable_encoder model")
+        x = self._prep(x)
+        B, Cc, H, W_ = x.shape
+        if Cc != 3 or H % 16 or W_ % 16 or H < 16 or W_ < 16 or (H // 16) * (W_ // 16) > 1024:
+            raise EngineError(f"table_encoder_forward: input {tuple(x.shape)}: [B,3,H,W] with H, W multiples of 16 and at most 1024 patches")
+        T = (H // 16) * (W_ // 16)
+        if out is None:
+            out = self._out("vit", (B, T, 768), torch.float32, x.device)
+        elif out.shape != (B, T, 768) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise EngineError("table_encoder_forward: `out` does not match the forward's shape")
+        if want_taps:
+            taps = torch.empty((3, B, T, 768), dtype=torch.float32, device=x.device)
+
+            def launch_taps():
+                fn = self._l.rd_debug_table_encoder_taps       # developer entry, not in the public header
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+                self._chk(fn(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), taps.data_ptr(), _stream_ptr()))
+                self._log()
+            self._guarded(launch_taps)
+            return out, [taps[0], taps[1], taps[2]]
+
+        def launch():
+            self._chk(self._l.rd_table_encoder_forward(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), None, 0, _stream_ptr()))
+            self._log()
+        self._guarded(launch)
+        return out
+
+    def table_decode(self, memory: torch.Tensor, ids, max_new_tokens: int = 1024):
+        """UniTable decoder and greedy loop (unitable_decoder; rd_table_decode): memory [B,S,768] from `table_encoder_forward`, B <= 8;
+        `ids`: table_unitable.TableIds.  Returns (ids int64 [B, max_new_tokens + 1] on the device: prefix, emitted tokens, `pad` behind a
+        table's EOS; n_tokens: per table the tokens up to and including its EOS)."""
+        from .table_unitable import cfg_struct
+        if self.kind != "unitable_decoder":
+            raise EngineError("table_decode: the handle is not a unitable_decoder model")
+        if memory.dim() != 3 or memory.shape[2] != 768 or memory.shape[0] < 1 or memory.shape[1] < 1:
+            raise EngineError(f"table_decode: memory must be [B, S, 768], got {tuple(memory.shape)}")
+        memory = self._prep(memory)
+        B, S, _ = memory.shape
+        out = torch.empty((B, max_new_tokens + 1), dtype=torch.int64, device=memory.device)
+        n = (C.c_int32 * max(B, 1))()
+        cfg = cfg_struct(ids)
+        self._chk(self._l.rd_table_decode(self._h, memory.data_ptr(), B, S, max_new_tokens, C.byref(cfg), out.data_ptr(), n, _stream_ptr()))
+        return out, [int(v) for v in n]
+
+    def table_decode_debug(self, memory: torch.Tensor, ids, steps: int, forced: Optional[torch.Tensor] = None):
+        """Developer (rd_debug_table_decode): `steps` steps with traces; forced int32 [B, steps] = the token fed to every step (EOS latch
+        off), or None for the free loop.  Returns dict(ids [B, steps + 1], hidden [steps, 4, B, 768], logits [steps, B, 960], chosen /
+        emitted int32 [steps, B]); rows of steps the free loop did not run are NaN / -1."""
+        from .table_unitable import cfg_struct
+        if self.kind != "unitable_decoder":
+            raise EngineError("table_decode_debug: the handle is not a unitable_decoder model")
+        if memory.dim() != 3 or memory.shape[2] != 768 or memory.shape[0] < 1 or memory.shape[1] < 1:
+            raise EngineError(f"table_decode_debug: memory must be [B, S, 768], got {tuple(memory.shape)}")
+        memory = self._prep(memory)
+        B, S, _ = memory.shape
+        dev = memory.device
+        out = torch.empty((B, steps + 1), dtype=torch.int64, device=dev)
+        hidden = torch.full((steps, 4, B, 768), float("nan"), device=dev)
+        logits = torch.full((steps, B, 960), float("nan"), device=dev)
+        chosen = torch.full((steps, B), -1, dtype=torch.int32, device=dev)
+        emitted = torch.full((steps, B), -1, dtype=torch.int32, device=dev)
+        if forced is not None:
+            forced = forced.to(dev, torch.int32).contiguous()
+            if forced.shape != (B, steps):
+                raise EngineError("table_decode_debug: forced must be [B, steps]")
+        fn = self._l.rd_debug_table_decode                 # developer entry, not in the public header
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 7
+        cfg = cfg_struct(ids)
+        self._chk(fn(self._h, memory.data_ptr(), B, S, steps, C.byref(cfg), forced.data_ptr() if forced is not None else None, out.data_ptr(),
+                     hidden.data_ptr(), logits.data_ptr(), chosen.data_ptr(), emitted.data_ptr(), _stream_ptr()))
+        return dict(ids=out, hidden=hidden, logits=logits, chosen=chosen, emitted=emitted)
 
     def rec_forward(self, x: torch.Tensor, flags: int = 0, out: Optional[tuple] = None,
                     after_launch=None) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:

@@ -1,0 +1,177 @@
+"""UniTable table-structure recogniser on the MI355X engine: the drop-in for the reference's `UniTableStructure`
+(rapid_table_self/table_structure/unitable/main.py) - encoder (`unitable_encoder`), decoder and greedy loop (`unitable_decoder`,
+rd_table_decode), and the host restatements of `decode_tokens`, `rescale_bboxes` and `wrap_with_html_struct`.
+
+The token ids of the loop (prefix, eos, pad, `]</td>`, the bbox range) and the `id -> token` list come from the vocabulary file, which the
+product does not ship: they are the caller's (`TableIds`, `id_to_token`); there is no `tokenizers` dependency.  `STAND_IN_IDS` /
+`stand_in_tokens()` follow the order of the reference's VALID_HTML_BBOX_TOKENS (eos 1, the 49 HTML tokens 12 .. 60, bbox-0 .. bbox-448 =
+61 .. 509, the module's 499 whitelisted ids) - a stand-in for tests, not a fact about the shipped file."""
+from __future__ import annotations
+
+import ctypes as C
+import re
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+IMG_SIZE = 448
+MAX_SEQ_LEN = 1024
+MAX_BATCH = 8
+# pre_process.py: transforms.Normalize on the RGB image scaled to [0, 1]
+NORM_MEAN = (0.86597056, 0.88463002, 0.87491087)
+NORM_STD = (0.20686628, 0.18201602, 0.18485524)
+TASK_TOKENS = ["[table]", "[html]", "[cell]", "[bbox]", "[cell+bbox]", "[html+bbox]"]
+HTML_TOKENS = (["<td></td>", "<td>[", "]</td>", "<td", ">[", "></td>", "<tr>", "</tr>", "<tbody>", "</tbody>", "<thead>", "</thead>"]
+               + [f' rowspan="{i}"' for i in range(2, 20)] + [f' colspan="{i}"' for i in range(2, 20)] + [' colspan="25"'])
+
+
+@dataclass(frozen=True)
+class TableIds:
+    prefix: int
+    eos: int
+    pad: int
+    bbox_close: int          # `]</td>`
+    bbox_first: int          # bbox-0
+    bbox_last: int           # bbox-448
+
+
+STAND_IN_IDS = TableIds(prefix=11, eos=1, pad=2, bbox_close=14, bbox_first=61, bbox_last=509)
+
+
+def stand_in_tokens() -> List[str]:
+    """id -> token list of the stand-in vocabulary (960 entries)"""
+    toks = [f"<unused-{i}>" for i in range(960)]
+    toks[0], toks[1], toks[2] = "<bos>", "<eos>", "<pad>"
+    for i, t in enumerate(TASK_TOKENS):
+        toks[6 + i] = t
+    for i, t in enumerate(HTML_TOKENS):
+        toks[12 + i] = t
+    for i in range(IMG_SIZE + 1):
+        toks[61 + i] = f"bbox-{i}"
+    return toks
+
+
+class _Cfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("prefix_id", "eos_id", "pad_id", "bbox_close_id", "bbox_first_id", "bbox_last_id")]
+
+
+def cfg_struct(ids: TableIds) -> _Cfg:
+    return _Cfg(ids.prefix, ids.eos, ids.pad, ids.bbox_close, ids.bbox_first, ids.bbox_last)
+
+
+# ------------------------------------------------------------------------------------------------------------------ host restatements
+def loop_reference(next_token, ids: TableIds, max_steps: int = MAX_SEQ_LEN) -> List[int]:
+    """`UniTableStructure.loop_decode` for one table on the host: next_token(context) -> the decoder's whitelist argmax.  The counter
+    rises with every bbox token, is cleared only when it exceeds 4 (the token is then replaced by `]</td>`), and no other token resets it."""
+    ctx, count = [ids.prefix], 0
+    for _ in range(max_steps):
+        if ids.eos in ctx:
+            break
+        t = int(next_token(ctx))
+        if ids.bbox_first <= t <= ids.bbox_last:
+            count += 1
+            if count > 4:
+                t, count = ids.bbox_close, 0
+        ctx.append(t)
+    return ctx
+
+
+_TR = re.compile(r"<tr>(.*?)</tr>", re.DOTALL)
+_TD = re.compile(r"<td(.*?)>(.*?)</td>", re.DOTALL)
+_BBOX = re.compile(r"\[ bbox-(\d+) bbox-(\d+) bbox-(\d+) bbox-(\d+) \]")
+
+
+def decode_tokens(token_ids: Sequence[int], id_to_token: Sequence[str], joiner: str = " ") -> Tuple[np.ndarray, List[str]]:
+    """main.py `decode_tokens`: the ids as one string (tokens joined by `joiner`, what the vocabulary's decode gives with the special tokens
+    kept), then the three regexes.  As there, they run over the WHOLE string, not the part in front of <eos>.  Returns (bboxes float32
+    [n, 8] = the four corners clockwise from the top left, zeros for a cell without a box; the html token list)."""
+    pred_html = joiner.join(id_to_token[int(i)] for i in token_ids)
+    decoded, boxes = [], []
+    for tr in _TR.finditer(pred_html):
+        decoded.append("<tr>")
+        for td in _TD.finditer(tr.group(1)):
+            attrs, content = td.group(1).strip(), td.group(2).strip()
+            if attrs:
+                decoded.append("<td")
+                decoded.extend(" " + a for a in attrs.split())
+                decoded.extend([">", "</td>"])
+            else:
+                decoded.append("<td></td>")
+            m = _BBOX.search(content)
+            if m:
+                x0, y0, x1, y1 = map(int, m.groups())
+                boxes.append(np.array([x0, y0, x1, y0, x1, y1, x0, y1]))
+            else:
+                boxes.append(np.array([0, 0, 0, 0, 0, 0, 0, 0]))
+        decoded.append("</tr>")
+    return np.array(boxes).astype(np.float32), decoded
+
+
+def rescale_bboxes(ori_h: int, ori_w: int, bboxes: np.ndarray) -> np.ndarray:
+    """post_process.py: 448-space corners to the original image, clipped; in place, as there"""
+    bboxes[:, 0::2] *= ori_w / IMG_SIZE
+    bboxes[:, 1::2] *= ori_h / IMG_SIZE
+    bboxes[:, 0::2] = np.clip(bboxes[:, 0::2], 0, ori_w - 1)
+    bboxes[:, 1::2] = np.clip(bboxes[:, 1::2], 0, ori_h - 1)
+    return bboxes
+
+
+def wrap_with_html_struct(structure: List[str]) -> List[str]:
+    return ["<html>", "<body>", "<table>"] + structure + ["</table>", "</body>", "</html>"]
+
+
+# ------------------------------------------------------------------------------------------------------------------ the class
+class Mi355UniTableStructure:
+    """`UniTableStructure` on the engine.  encoder / decoder: path to / bytes of a .safetensors file, or a state dict."""
+
+    def __init__(self, encoder, decoder, ids: TableIds, id_to_token: Sequence[str], device: int = 0, max_new_tokens: int = MAX_SEQ_LEN):
+        from .engine import RdEngine
+        self.ids, self.id_to_token, self.max_new_tokens = ids, list(id_to_token), int(max_new_tokens)
+        self.encoder = RdEngine("unitable_encoder", device).load_weights(encoder)
+        self.decoder = RdEngine("unitable_decoder", device).load_weights(decoder)
+        self._dev = torch.device("cuda", device)
+
+    def preprocess(self, imgs: List[np.ndarray]) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
+        """BGR uint8 HWC images -> normalised [B,3,448,448] on the device.  The resize is the engine's linear one (rd_preproc_resize_norm),
+        not PIL's antialiased bilinear: restated, not pinned."""
+        from .engine import preproc_resize_norm
+        xs, shapes = [], []
+        for img in imgs:
+            if img is None:
+                continue
+            shapes.append(tuple(int(v) for v in img.shape[:2]))
+            u8 = torch.from_numpy(np.ascontiguousarray(img)).to(self._dev)
+            xs.append(preproc_resize_norm(u8, (IMG_SIZE, IMG_SIZE), mean=NORM_MEAN, std=NORM_STD, swap_rb=True))
+        return torch.stack(xs), shapes
+
+    def decode_ids(self, x: torch.Tensor) -> List[List[int]]:
+        """normalised [B,3,448,448] -> per table the context the reference's loop ends with (prefix ... eos)"""
+        out: List[List[int]] = []
+        for i in range(0, x.shape[0], MAX_BATCH):
+            memory = self.encoder.table_encoder_forward(x[i:i + MAX_BATCH])
+            ids, n = self.decoder.table_decode(memory, self.ids, self.max_new_tokens)
+            ids = ids.cpu().numpy()
+            out.extend(ids[b, :n[b]].tolist() for b in range(ids.shape[0]))
+        return out
+
+    def forward_tensor(self, x: torch.Tensor, ori_shapes: Optional[List[Tuple[int, int]]] = None):
+        """The pinned path: (struct_list, total_bboxes) as the reference's __call__ returns them, from an already normalised tensor"""
+        ori_shapes = ori_shapes or [(IMG_SIZE, IMG_SIZE)] * x.shape[0]
+        struct_list, total_bboxes = [], []
+        for ctx, (h, w) in zip(self.decode_ids(x), ori_shapes):
+            bboxes, html = decode_tokens(ctx, self.id_to_token)
+            total_bboxes.append(rescale_bboxes(h, w, bboxes) if len(bboxes) else bboxes)
+            struct_list.append((wrap_with_html_struct(html), 1.0))
+        return struct_list, total_bboxes
+
+    def batch_predict(self, image_list: List[np.ndarray], **kwargs) -> List[str]:
+        """The CustomBaseModel shape the page driver's table seam takes (`batch_predict(image_list, **kwargs) -> list[str]`): one HTML
+        string per table crop - the structure alone, cells empty (matching OCR text into cells is RapidTable's matcher, not this model)."""
+        structs, _ = self(list(image_list)) if len(image_list) else ([], [])
+        return ["".join(s) for s, _score in structs]
+
+    def __call__(self, imgs: List[np.ndarray]):
+        x, shapes = self.preprocess(imgs)
+        return self.forward_tensor(x, shapes)

@@ -169,6 +169,17 @@ def synth_cls_lines(seed: int, b: int, h: int = 48, w: int = 192) -> Tuple[np.nd
     return x, widths
 
 
+def synth_normal_image(seed: int, b: int, h: int, w: int) -> np.ndarray:
+    """Synthetic normalised image batch [b,3,h,w], standard normal (the UniTable pre-process divides by the ImageNet std, so a real input is
+    of that scale).  A pure function of the arguments (numpy only), so that a fixture stores the recipe instead of the tensor."""
+    return np.random.default_rng([seed, b, h, w]).standard_normal((b, 3, h, w)).astype(np.float32)
+
+
+def synth_memory(seed: int, b: int, s: int, d: int = 768) -> np.ndarray:
+    """Synthetic encoder output [b,s,d], standard normal (a LayerNorm output is of that scale).  A pure function of the arguments."""
+    return np.random.default_rng([seed, b, s, d]).standard_normal((b, s, d)).astype(np.float32)
+
+
 def checksum(state: Dict[str, np.ndarray]) -> float:
     """Order-independent float64 checksum used to pin the generator across machines."""
     tot = 0.0
