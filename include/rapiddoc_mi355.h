@@ -12,6 +12,8 @@
  *                           rapid_doc/model/layout/rapid_layout_self/inference_engine/onnxruntime/main.py:61-78
  *                           (network definition: .../formula/rapid_formula_self/networks/backbones/rec_pphgnetv2.py:1445-1477)
  *   rd_preproc_resize_norm <- PPPreProcess: .../model_handler/pp_doclayout/pre_process.py:22-42
+ *   rd_preproc_resize_aa_norm <- UniTable's TablePreprocess (PIL Resize + ToTensor + Normalize):
+ *                           rapid_doc/model/table/rapid_table_self/table_structure/unitable/pre_process.py
  *   rd_load_weights      <- `_load_state_dict` + `load_state_dict`: rapid_doc/model/ocr/torch.py:82-110
  *
  * Conventions: every pointer named *_dev is a DEVICE pointer on the handle's GPU (PyTorch-ROCm
@@ -139,6 +141,21 @@ int rd_preproc_resize_norm(int device_id, const uint8_t* hwc_u8_dev, int H, int 
  * loop over PPPreProcess / DetPreProcess, rapid_layout_self/main.py:41-56, rapid_ocr.py:474-536). */
 int rd_preproc_resize_norm_batch(int device_id, const uint8_t* pages_u8_dev, int P, int H, int W, int OH, int OW, const float mean[3],
                                  const float std[3], float scale, int interp, int swap_rb, float* out_nchw_dev, void* stream);
+
+/* u8 HWC (3 channels) device image -> Pillow's antialiased bilinear resample to OHxOW -> ((v / 255) - mean[c]) / std[c] -> CHW float32:
+ * transforms.Resize((OH, OW)) on a PIL image, ToTensor and Normalize, as UniTable's TablePreprocess runs them
+ * (rapid_table_self/table_structure/unitable/pre_process.py).  The resample is Pillow's 8-bit path bit for bit (Resample.c): per axis
+ * scale = in / out, support = max(scale, 1), triangle weights normalised in double and rounded to 22-bit fixed point (computed on the
+ * host, cached per (in, out), uploaded on `stream`), the horizontal pass first into a uint8 intermediate the library owns, then the
+ * vertical pass; a pass whose in == out does not run.  The normalisation is fp32 in that operation order with IEEE division.
+ * swap_rb = 1 reads the source as BGR (cv2.cvtColor(BGR2RGB) in front).  out_u8_hwc_dev (may be NULL): the resampled bytes [OH][OW][3].
+ * Bound: 1 <= H, W, OH, OW <= RD_RESIZE_AA_MAX_SIDE (any ratio between them: the tap count 2 ceil(max(in / out, 1)) + 1 is a loop bound,
+ * not a tile).  A size outside it, or a NULL image pointer, returns non-zero WITHOUT a launch; the message is in rd_create_error() (the
+ * calling thread's handle-less error string).  The first call with a new (in, out) pair or a larger intermediate allocates device
+ * memory (not capturable into a hipGraph); calls on one stream are ordered, calls on different streams use different intermediates. */
+#define RD_RESIZE_AA_MAX_SIDE 16384
+int rd_preproc_resize_aa_norm(int device_id, const uint8_t* hwc_u8_dev, int H, int W, int OH, int OW, const float mean[3],
+                              const float std[3], int swap_rb, float* out_chw_dev, uint8_t* out_u8_hwc_dev, void* stream);
 
 /* Text-line crops for one rec batch (replaces per-line cv2.warpPerspective + rapidocr resize_norm_img:
  * rapid_doc/utils/ocr_utils.py:494-536, rapid_doc/model/ocr/rapid_ocr.py:436-440).  pages_u8_dev: [P][H][W][3];

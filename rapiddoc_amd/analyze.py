@@ -538,7 +538,7 @@ class PageAnalyzer:
         4. OCR           det + rec of every text region (`RegionOcr`), or the custom-OCR seam (`RegionTextModel`-shaped object:
                          one string per region, :286-333) when `custom_ocr` is given
         5. tables        `table_model.batch_predict(table crops, fill_image_res_list=...)` for a CustomBaseModel-shaped model (seam
-                         S1, :359-379), or `TableOcr` + `table_model.predict(...)` for a RapidTableModel-shaped one (seam S3,
+                         S1, :359-379), or `TableOcr` + `table_model.predict(...)` for a RapidTableModel-shaped one - any model that has `predict` (seam S3,
                          `_process_single_table`); the reference's own table NETWORKS are ONNX-only and not built
         6. (rec post-process is part of RegionOcr here: spans get text / score / LowScoreText demotion, analyze_utils.py:216-292)
 
@@ -657,7 +657,8 @@ class PageAnalyzer:
                            page_keys=page_keys, all_langs=all_langs)
         # 5. tables: one pooled `batch_predict` of a CustomBaseModel-shaped model (seam S1, batch_analyze.py:359-379) or, for a
         #    `predict`-shaped one (RapidTableModel, seam S3), the reference's own table stage with the table OCR on the GPU
-        if self.table_model is not None and hasattr(self.table_model, "batch_predict"):
+        #    (a model that has `predict` is a RapidTableModel-shaped one even where, like the reference's, it also offers batch_predict)
+        if self.table_model is not None and hasattr(self.table_model, "batch_predict") and not hasattr(self.table_model, "predict"):
             crops, owners, fills = [], [], []
             for p in range(P):
                 _o, tables, _f = layout_host.split_regions(dets[p])

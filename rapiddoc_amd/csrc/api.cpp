@@ -362,6 +362,26 @@ int rd_preproc_resize_norm_batch(int device_id, const uint8_t* src, int P, int H
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+int rd_preproc_resize_aa_norm(int device_id, const uint8_t* src, int H, int W, int OH, int OW, const float mean[3], const float std[3],
+                              int swap_rb, float* out, uint8_t* out_u8, void* stream) {
+    std::string err;
+    const int rc = rd::launch_resize_aa_norm(device_id, src, H, W, OH, OW, mean, std, swap_rb, out, out_u8, (hipStream_t)stream, err);
+    if (rc != 0) g_create_err = err;        // no handle: the calling thread's rd_create_error() carries the message
+    return rc;
+}
+
+// developer entry (host only): the per-axis tables rd_preproc_resize_aa_norm uploads.  bounds_out int32 [out][2], kk_out int32 [out][ksize]
+// with kk_cap entries of room; returns ksize, or -1 on bad arguments / too little room.
+int rd_debug_resize_aa_coeffs(int in, int out, int32_t* bounds_out, int32_t* kk_out, int64_t kk_cap) {
+    if (in < 1 || out < 1 || in > RD_RESIZE_AA_MAX_SIDE || out > RD_RESIZE_AA_MAX_SIDE || !bounds_out || !kk_out) return -1;
+    std::vector<int32_t> bounds, kk;
+    const int ksize = rd::resize_aa_coeffs(in, out, bounds, kk);
+    if ((int64_t)kk.size() > kk_cap) return -1;
+    std::copy(bounds.begin(), bounds.end(), bounds_out);
+    std::copy(kk.begin(), kk.end(), kk_out);
+    return ksize;
+}
+
 int rd_crop_resize_norm_batch(int device_id, const uint8_t* pages, int P, int H, int W, const rd_crop_desc* descs, int n,
                               int out_h, int out_w_padded, const float mean[3], const float std[3], float scale, int swap_rb,
                               float* out, void* stream) {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 namespace rd {
@@ -469,6 +470,12 @@ struct PreprocParams {
     size_t src_stride = 0, dst_stride = 0;
 };
 void launch_preproc_resize_norm(const PreprocParams& p, hipStream_t s);
+
+// Pillow's antialiased bilinear resample + ToTensor / Normalize (kernels_resize_aa.hip; rd_preproc_resize_aa_norm).  Returns 0, or 1 with
+// the message in `err` (a size outside 1 .. RD_RESIZE_AA_MAX_SIDE never launches).  resize_aa_coeffs: the per-axis tables on the host.
+int resize_aa_coeffs(int in, int out, std::vector<int32_t>& bounds, std::vector<int32_t>& kk);
+int launch_resize_aa_norm(int device, const uint8_t* src, int H, int W, int OH, int OW, const float mean[3], const float std[3], int swap_rb,
+                          float* out, uint8_t* out_u8, hipStream_t s, std::string& err);
 
 // Text-line crops for the recogniser, one launch per rec batch: for crop i, output pixel (ox, oy) of the
 // 48 x out_w[i] resized line maps to crop coordinates, then through the 3x3 matrix m (crop -> page, i.e. the

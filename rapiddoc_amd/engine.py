@@ -578,3 +578,28 @@ def preproc_resize_norm_batch(imgs_u8_nhwc: torch.Tensor, out_hw: Tuple[int, int
     if rc != 0:
         raise EngineError("rd_preproc_resize_norm_batch failed")
     return out
+
+
+def preproc_resize_aa_norm(img_u8_hwc: torch.Tensor, out_hw: Tuple[int, int], mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), swap_rb: bool = False,
+                           return_u8: bool = False, out: Optional[torch.Tensor] = None):
+    """u8 HWC device image -> Pillow's antialiased bilinear resample (bit for bit) -> ((v / 255) - mean) / std -> CHW float32
+    (rd_preproc_resize_aa_norm: transforms.Resize on a PIL image + ToTensor + Normalize, UniTable's TablePreprocess).  `return_u8`: returns
+    (out, the resampled bytes [OH, OW, 3] uint8).  A size outside 1 .. 16384 raises EngineError; nothing is launched."""
+    lib = _lib.load()
+    if not (img_u8_hwc.is_cuda and img_u8_hwc.dtype == torch.uint8 and img_u8_hwc.is_contiguous() and img_u8_hwc.dim() == 3 and img_u8_hwc.shape[2] == 3):
+        raise EngineError("preproc_resize_aa_norm: the image must be a contiguous uint8 [H, W, 3] device tensor")
+    H, W_, _ = img_u8_hwc.shape
+    OH, OW = (int(v) for v in out_hw)
+    ok = 1 <= OH <= 16384 and 1 <= OW <= 16384
+    if out is None:
+        out = torch.empty((3, OH, OW) if ok else (0,), dtype=torch.float32, device=img_u8_hwc.device)
+    elif tuple(out.shape) != (3, OH, OW) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise EngineError("preproc_resize_aa_norm: `out` does not match [3, OH, OW] float32")
+    u8 = torch.empty((OH, OW, 3) if ok else (0,), dtype=torch.uint8, device=img_u8_hwc.device) if return_u8 else None
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    rc = lib.rd_preproc_resize_aa_norm(img_u8_hwc.device.index or 0, img_u8_hwc.data_ptr(), H, W_, OH, OW, m, s, 1 if swap_rb else 0,
+                                       out.data_ptr(), u8.data_ptr() if return_u8 else None, _stream_ptr())
+    if rc != 0:
+        raise EngineError(lib.rd_create_error().decode())
+    return (out, u8) if return_u8 else out

@@ -5,7 +5,10 @@ rd_table_decode), and the host restatements of `decode_tokens`, `rescale_bboxes`
 The token ids of the loop (prefix, eos, pad, `]</td>`, the bbox range) and the `id -> token` list come from the vocabulary file, which the
 product does not ship: they are the caller's (`TableIds`, `id_to_token`); there is no `tokenizers` dependency.  `STAND_IN_IDS` /
 `stand_in_tokens()` follow the order of the reference's VALID_HTML_BBOX_TOKENS (eos 1, the 49 HTML tokens 12 .. 60, bbox-0 .. bbox-448 =
-61 .. 509, the module's 499 whitelisted ids) - a stand-in for tests, not a fact about the shipped file."""
+61 .. 509, the module's 499 whitelisted ids) - a stand-in for tests, not a fact about the shipped file.
+
+`Mi355RapidTable` is the whole table path around it, the drop-in for `RapidTableModel(model_type=UNITABLE)` (rapid_table.py): the
+reference's pixels in front (`resize="pil"`, rd_preproc_resize_aa_norm), RapidTable's matcher behind (rapiddoc_amd/table_match.py)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -126,25 +129,37 @@ def wrap_with_html_struct(structure: List[str]) -> List[str]:
 class Mi355UniTableStructure:
     """`UniTableStructure` on the engine.  encoder / decoder: path to / bytes of a .safetensors file, or a state dict."""
 
-    def __init__(self, encoder, decoder, ids: TableIds, id_to_token: Sequence[str], device: int = 0, max_new_tokens: int = MAX_SEQ_LEN):
+    def __init__(self, encoder, decoder, ids: TableIds, id_to_token: Sequence[str], device: int = 0, max_new_tokens: int = MAX_SEQ_LEN,
+                 resize: str = "linear"):
+        """`resize`: "linear" = the engine's 2-tap linear resize (rd_preproc_resize_norm), "pil" = Pillow's antialiased bilinear, the
+        reference's transforms.Resize on a PIL image, bit for bit (rd_preproc_resize_aa_norm)."""
         from .engine import RdEngine
-        self.ids, self.id_to_token, self.max_new_tokens = ids, list(id_to_token), int(max_new_tokens)
+        if resize not in ("linear", "pil"):
+            raise ValueError("resize must be 'linear' or 'pil'")
+        self.ids, self.id_to_token, self.max_new_tokens, self.resize = ids, list(id_to_token), int(max_new_tokens), resize
         self.encoder = RdEngine("unitable_encoder", device).load_weights(encoder)
         self.decoder = RdEngine("unitable_decoder", device).load_weights(decoder)
         self._dev = torch.device("cuda", device)
 
-    def preprocess(self, imgs: List[np.ndarray]) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
-        """BGR uint8 HWC images -> normalised [B,3,448,448] on the device.  The resize is the engine's linear one (rd_preproc_resize_norm),
-        not PIL's antialiased bilinear: restated, not pinned."""
-        from .engine import preproc_resize_norm
-        xs, shapes = [], []
-        for img in imgs:
-            if img is None:
-                continue
+    def preprocess(self, imgs: list) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
+        """BGR uint8 HWC images (numpy arrays or device tensors) -> normalised [B,3,448,448] on the device, every image written straight
+        into its row of the batch with no host synchronisation in between.  resize="linear": the engine's linear resize (restated, not
+        pinned); resize="pil": Pillow's antialiased bilinear, pinned to Pillow."""
+        from .engine import preproc_resize_aa_norm, preproc_resize_norm
+        imgs = [img for img in imgs if img is not None]
+        x = torch.empty((len(imgs), 3, IMG_SIZE, IMG_SIZE), dtype=torch.float32, device=self._dev)
+        shapes = []
+        for i, img in enumerate(imgs):
             shapes.append(tuple(int(v) for v in img.shape[:2]))
-            u8 = torch.from_numpy(np.ascontiguousarray(img)).to(self._dev)
-            xs.append(preproc_resize_norm(u8, (IMG_SIZE, IMG_SIZE), mean=NORM_MEAN, std=NORM_STD, swap_rb=True))
-        return torch.stack(xs), shapes
+            if isinstance(img, torch.Tensor):
+                u8 = img.to(self._dev, non_blocking=True).contiguous()
+            else:
+                u8 = torch.from_numpy(np.ascontiguousarray(img)).to(self._dev, non_blocking=True)
+            if self.resize == "pil":
+                preproc_resize_aa_norm(u8, (IMG_SIZE, IMG_SIZE), mean=NORM_MEAN, std=NORM_STD, swap_rb=True, out=x[i])
+            else:
+                preproc_resize_norm(u8, (IMG_SIZE, IMG_SIZE), mean=NORM_MEAN, std=NORM_STD, swap_rb=True, out=x[i])
+        return x, shapes
 
     def decode_ids(self, x: torch.Tensor) -> List[List[int]]:
         """normalised [B,3,448,448] -> per table the context the reference's loop ends with (prefix ... eos)"""
@@ -175,3 +190,75 @@ class Mi355UniTableStructure:
     def __call__(self, imgs: List[np.ndarray]):
         x, shapes = self.preprocess(imgs)
         return self.forward_tensor(x, shapes)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the whole table path
+@dataclass
+class TableOutput:
+    """What RapidTable.__call__ returns (RapidTableOutput), without the images and the timing"""
+    pred_htmls: list
+    cell_bboxes: list
+    logic_points: list
+
+
+class Mi355RapidTable:
+    """`RapidTableModel(model_type=UNITABLE)` on the engine: the structure model with the reference's pixels (resize="pil"), RapidTable's
+    matcher behind it (rapiddoc_amd/table_match.py) and the OCR-list preparation of RapidTableModel.predict in front.  It is a
+    `predict`-shaped table model: analyze.PageAnalyzer runs it through `TableOcr` (seam S3).
+
+    `structure`: a Mi355UniTableStructure built with resize="pil", or None with encoder / decoder / ids / id_to_token to build one."""
+
+    def __init__(self, structure: Optional[Mi355UniTableStructure] = None, encoder=None, decoder=None, ids: Optional[TableIds] = None,
+                 id_to_token: Optional[Sequence[str]] = None, device: int = 0, max_new_tokens: int = MAX_SEQ_LEN):
+        if structure is None:
+            structure = Mi355UniTableStructure(encoder, decoder, ids, id_to_token, device=device, max_new_tokens=max_new_tokens, resize="pil")
+        if structure.resize != "pil":
+            raise ValueError("Mi355RapidTable needs a structure model with resize='pil' (the reference's pixels)")
+        self.structure = structure
+
+    def __call__(self, bgr_images, ocr_results=None) -> TableOutput:
+        """The non-UNET branch of RapidTable.__call__: bgr_images = list of BGR uint8 [h,w,3] (numpy or device tensors), ocr_results = per
+        image [quads, texts, scores] or None (no OCR engine of our own: the cells of such a call stay unmatched, pred_htmls is empty)."""
+        from . import table_match as TM
+        if not isinstance(bgr_images, list):
+            bgr_images = [bgr_images]
+        pred_structures, cell_bboxes = self.structure(bgr_images)
+        logic_points = TM.decode_logic_points(pred_structures)
+        dt_boxes, rec_res = [], []
+        if ocr_results is not None:
+            if len(ocr_results) != len(bgr_images):
+                raise ValueError(f"Batch size mismatch: {len(bgr_images)} images but {len(ocr_results)} OCR results")
+            for img, res in zip(bgr_images, ocr_results):
+                d, r = TM.format_ocr_results(res, int(img.shape[0]), int(img.shape[1]))
+                dt_boxes.append(d)
+                rec_res.append(r)
+        htmls = TM.match_tables(pred_structures, cell_bboxes, dt_boxes, rec_res, cell_text=TM.normalize_table_cell_text)
+        return TableOutput(htmls, list(cell_bboxes), logic_points)
+
+    def predict(self, image, ocr_result=None, fill_image_res=None, mfd_res=None, skip_text_in_image=True, use_img2table=False,
+                skip_table_orientation=None):
+        """RapidTableModel.predict for ModelType.UNITABLE: RGB uint8 image + [quads, texts, scores] (three lists, extended in place as
+        there) -> the table's HTML, or None (no OCR rows; anything the reference's try / except swallows, such as a structure without a
+        cell).  The cell text goes through normalize_table_cell_text before the tokens are joined (the reference re-serialises the
+        finished HTML through BeautifulSoup instead: restated, not pinned)."""
+        from . import table_match as TM
+        if use_img2table:
+            raise NotImplementedError("use_img2table=True needs the img2table route and an OCR engine of RapidOcrTable's shape, which are not part of this package")
+        bgr = np.ascontiguousarray(np.asarray(image)[:, :, ::-1])                # cv2.cvtColor(RGB2BGR): a copy, the caller's image stays
+        if skip_table_orientation is None:
+            skip_table_orientation = ocr_result is not None
+        h, w = bgr.shape[:2]
+        if (h / w if w > 0 else 1.0) > 1.2 and not skip_table_orientation:
+            raise NotImplementedError("the portrait-rotation check needs a text detector on the table image (ocr_engine.ocr(rec=False)); "
+                                      "pass an ocr_result or skip_table_orientation=True")
+        if not ocr_result:
+            return None                  # (the reference would run its own OCR engine first; the page driver always hands the rows over)
+        TM.prepare_ocr_list(bgr, ocr_result, fill_image_res, mfd_res, skip_text_in_image)
+        try:
+            return self([bgr], [ocr_result]).pred_htmls[0]
+        except Exception:                # as the reference: logged there, None here
+            return None
+
+    def batch_predict(self, images: list, ocr_result=None, fill_image_res=None, mfd_res=None, skip_text_in_image=True, use_img2table=False,
+                      skip_table_orientation=None) -> list:
+        return [self.predict(im, ocr_result, fill_image_res, mfd_res, skip_text_in_image, use_img2table, skip_table_orientation) for im in images]

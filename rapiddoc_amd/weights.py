@@ -175,6 +175,32 @@ def synth_normal_image(seed: int, b: int, h: int, w: int) -> np.ndarray:
     return np.random.default_rng([seed, b, h, w]).standard_normal((b, 3, h, w)).astype(np.float32)
 
 
+def _mix64(v: np.ndarray) -> np.ndarray:
+    """splitmix64's finaliser on uint64 arrays (wrapping integer arithmetic: the same bits on every machine and numpy version)"""
+    v = (v ^ (v >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    v = (v ^ (v >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return v ^ (v >> np.uint64(31))
+
+
+def synth_table_crop(seed: int, h: int, w: int) -> np.ndarray:
+    """Synthetic table crop [h,w,3] uint8 (BGR or RGB, as the caller reads it): a near-white page, ruled lines every 37 rows / 113 columns,
+    and in every cell text-like bars (9 rows high, ragged runs, per-pixel texture of 48 grey levels) with a faint tint per channel.  A pure
+    function of the arguments built on an integer hash of its own (no numpy Generator stream), so that a fixture stores the recipe."""
+    with np.errstate(over="ignore"):
+        yy, xx = np.meshgrid(np.arange(h, dtype=np.uint64), np.arange(w, dtype=np.uint64), indexing="ij")
+        s = np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15)
+        pix = _mix64(s + yy * np.uint64(0x100000001B3) + xx)                       # per pixel
+        run = _mix64(s + (yy // np.uint64(14)) * np.uint64(7919) + (xx // np.uint64(23)) + np.uint64(1 << 40))       # per 14 x 23 block
+    img = np.full((h, w), 246, dtype=np.int64) + (pix & np.uint64(7)).astype(np.int64)
+    bar = ((yy % np.uint64(14)) >= np.uint64(3)) & ((yy % np.uint64(14)) < np.uint64(12)) & ((run & np.uint64(3)) != np.uint64(0))
+    ink = 20 + ((pix >> np.uint64(8)) % np.uint64(48)).astype(np.int64) + ((run >> np.uint64(4)) % np.uint64(90)).astype(np.int64)
+    img = np.where(bar, ink, img)
+    rule = ((yy % np.uint64(37)) == np.uint64(0)) | ((xx % np.uint64(113)) < np.uint64(2))
+    img = np.where(rule, 12, img)
+    out = np.stack([np.clip(img + t, 0, 255) for t in (0, -3, 4)], axis=-1)
+    return np.ascontiguousarray(out.astype(np.uint8))
+
+
 def synth_memory(seed: int, b: int, s: int, d: int = 768) -> np.ndarray:
     """Synthetic encoder output [b,s,d], standard normal (a LayerNorm output is of that scale).  A pure function of the arguments."""
     return np.random.default_rng([seed, b, s, d]).standard_normal((b, s, d)).astype(np.float32)
