@@ -1,0 +1,749 @@
+// The developer entries of librapiddoc_mi355.so (rd_debug_*): single kernels and plan variants with taps, for the tests, tools/ and the
+// micro-benchmarks.  None of them is part of the public header; the product C surface is api.cpp.
+#include <algorithm>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "api_handle.h"
+
+extern "C" {
+
+// shared by the timing entries below: one untimed launch (so `iters` = 0 still runs the kernel once: the correctness tests rely on
+// that), `after_first` (when given: what an entry launches once behind it, untimed), then `iters` timed launches between two events;
+// ms per timed launch.  A developer tool: HIP return codes are not looked at
+static float rd_debug_time(int iters, const std::function<void()>& launch, const std::function<void()>& after_first = nullptr) {
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    launch();
+    if (after_first) after_first();
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) launch();
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return iters > 0 ? ms / iters : 0.f;
+}
+
+// developer entry ("ppocrv3_det_mobile" only): rd_det_forward plus `fuse` and the backbone's four stage features, written as NCHW back to
+// back into aux_dev: [B,96,H/4,W/4], [B,16,H/4,W/4], [B,24,H/8,W/8], [B,56,H/16,W/16], [B,480,H/32,W/32].  The plan of the engine's
+// DET_WANT_NECK | DET_WANT_STAGES variant; the internal workspace.  Not part of the public header.
+int rd_debug_det_forward_stages(rd_handle* h, const float* x, int B, int H, int W, float* prob, float* aux, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->eng && h->eng->kind() == "ppocrv3_det_mobile", "handle is not a ppocrv3_det_mobile model");
+        RD_CHECK(x && prob && aux && B > 0 && H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0, "null input/output, or H / W no multiple of 32");
+        static const int kC[5] = {96, 16, 24, 56, 480}, kR[5] = {4, 4, 8, 16, 32};
+        std::vector<void*> ext = {(void*)x, (void*)prob};
+        float* q = aux;
+        for (int i = 0; i < 5; ++i) {
+            ext.push_back(q);
+            q += (size_t)B * kC[i] * (H / kR[i]) * (W / kR[i]);
+        }
+        h->eng->run(B, H, W, rd::DET_WANT_NECK | rd::DET_WANT_STAGES, ext, nullptr, 0, (hipStream_t)stream);
+    });
+}
+
+// developer entry ("ppocr_cls_mobile" only): rd_cls_forward with RD_CLS_WANT_AUX plus the outputs of blocks 0, 3, 8, 10, written as NCHW back
+// to back into stages_dev ([B,8,r0,w], [B,16,r1,w], [B,32,r2,w], [B,32,r3,w]: rd::cls_mobile_geometry).  The internal workspace.  Not part
+// of the public header.
+int rd_debug_cls_forward_stages(rd_handle* h, const float* x, int B, int H, int W, float* prob, float* aux, float* stages, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->eng && h->eng->kind() == "ppocr_cls_mobile", "handle is not a ppocr_cls_mobile model");
+        RD_CHECK(x && prob && aux && stages && B > 0, "null input/output");
+        int rows[4], cols = 0;
+        RD_CHECK(rd::cls_mobile_geometry(H, W, rows, &cols), "text-line classifier: H x W leaves an empty map");
+        static const int kC[4] = {8, 16, 32, 32};
+        std::vector<void*> ext = {(void*)x, (void*)prob, (void*)aux};
+        float* q = stages;
+        for (int i = 0; i < 4; ++i) {
+            ext.push_back(q);
+            q += (size_t)B * kC[i] * rows[i] * cols;
+        }
+        h->eng->run(B, H, W, rd::CLS_WANT_AUX | rd::CLS_WANT_STAGES, ext, nullptr, 0, (hipStream_t)stream);
+    });
+}
+
+// developer entry ("unitable_decoder"): `steps` decode steps with traces.  forced_dev (int32 [B][steps], or null): the token fed to step t
+// of table b (the EOS latch is off); null = the free loop of rd_table_decode.  Traces (device, each may be null): hidden [steps][4][B][768]
+// = the row after each block, logits [steps][B][960] (before the whitelist), chosen / emitted int32 [steps][B] = the whitelist argmax and the
+// token after the bbox rule.  Rows of steps the loop did not run stay as they were.  Not part of the public header.
+int rd_debug_table_decode(rd_handle* h, const float* memory, int B, int S, int steps, const rd_table_decode_cfg* cfg, const int32_t* forced,
+                          int64_t* ids, float* trace_hidden, float* trace_logits, int32_t* trace_chosen, int32_t* trace_emitted, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->kind == "unitable_decoder" && h->tdec, "handle is not a loaded table-structure decoder (unitable_decoder)");
+        int c[6];
+        table_cfg6(cfg, c);
+        rd::table_decoder_decode(h->tdec, memory, B, S, steps, c, (long long*)ids, nullptr, (hipStream_t)stream, (const int*)forced, trace_hidden,
+                                 trace_logits, (int*)trace_chosen, (int*)trace_emitted);
+    });
+}
+
+// developer entry ("unitable_encoder" only): rd_table_encoder_forward plus three taps, each [B,T,768], back to back in taps_dev: the patch
+// embedding (before the position rows) and the outputs of encoder layers 0 and 11.  The plan of the engine's VIT_WANT_TAPS variant; the
+// internal workspace.  Not part of the public header.
+int rd_debug_table_encoder_taps(rd_handle* h, const float* x, int B, int H, int W, float* memory, float* taps, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->eng && h->eng->kind() == "unitable_encoder", "handle is not a unitable_encoder model");
+        RD_CHECK(x && memory && taps && B > 0 && H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0, "null input/output, or H / W no multiple of 16");
+        const size_t n = (size_t)B * (H / 16) * (W / 16) * 768;
+        h->eng->run(B, H, W, rd::VIT_WANT_TAPS, {(void*)x, (void*)memory, (void*)taps, (void*)(taps + n), (void*)(taps + 2 * n)}, nullptr, 0, (hipStream_t)stream);
+    });
+}
+
+// developer entry: rd_formula_decode plus two optional traces written inside every step (graph replay included): the step's logits
+// trace_logits [max_new_tokens][B][V] and the hidden row in front of the final LayerNorm trace_hidden [max_new_tokens][B][512].  With both
+// null it enqueues exactly what rd_formula_decode enqueues.
+int rd_debug_formula_decode(rd_handle* h, const float* enc, int B, int S, int max_new_tokens, int64_t* ids, int32_t* n_cols, void* stream,
+                            float* trace_logits, float* trace_hidden) {
+    return guarded(h, [&] {
+        RD_CHECK(h->kind == "ppformulanet_head" && h->dec, "handle is not a loaded ppformulanet_head model");
+        RD_CHECK(enc && ids && n_cols, "null input/output");
+        *n_cols = rd::formula_decoder_decode(h->dec, enc, B, S, max_new_tokens, reinterpret_cast<long long*>(ids), (hipStream_t)stream,
+                                             trace_logits, trace_hidden);
+    });
+}
+
+// developer entry (host only): the per-axis tables rd_preproc_resize_aa_norm uploads.  bounds_out int32 [out][2], kk_out int32 [out][ksize]
+// with kk_cap entries of room; returns ksize, or -1 on bad arguments / too little room.
+int rd_debug_resize_aa_coeffs(int in, int out, int32_t* bounds_out, int32_t* kk_out, int64_t kk_cap) {
+    if (in < 1 || out < 1 || in > RD_RESIZE_AA_MAX_SIDE || out > RD_RESIZE_AA_MAX_SIDE || !bounds_out || !kk_out) return -1;
+    std::vector<int32_t> bounds, kk;
+    const int ksize = rd::resize_aa_coeffs(in, out, bounds, kk);
+    if ((int64_t)kk.size() > kk_cap) return -1;
+    std::copy(bounds.begin(), bounds.end(), bounds_out);
+    std::copy(kk.begin(), kk.end(), kk_out);
+    return ksize;
+}
+
+// ---- developer micro-benchmarks (not part of the public header): time one kernel on caller-provided buffers
+float rd_debug_time_mixer(int C, int M, int variant, int iters, float* x, float* y, float* w1, float* b1, float* w2, float* b2) {
+    rd::MixerParams p{};
+    p.x = x; p.xld = C; p.y = y; p.yld = C; p.M = M; p.HW = M; p.C = C; p.gate = nullptr;
+    p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2;
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    void* hbuf[4] = {nullptr, nullptr, nullptr, nullptr};
+    int ws_abl = 0;                       // 1000 + 256 * bits: ablations of the ws kernel (C = 192, results are garbage)
+    if (variant >= 1000) { ws_abl = (variant - 1000) & ~0xff; variant = 200 + ((variant - 1000) & 0xff); }
+    if (variant >= 600) variant -= 300;   // (600+ = 300+: keeps the resident-weights variants clear of the 400..599 PF range)
+    if (variant >= 300 && variant < 400) {  // resident-weights split mixer (kernels_mixer_res.hip)
+        std::vector<float> hw1((size_t)2 * C * C), hw2((size_t)2 * C * C);
+        (void)hipMemcpy(hw1.data(), w1, hw1.size() * 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(hw2.data(), w2, hw2.size() * 4, hipMemcpyDeviceToHost);
+        std::vector<uint16_t> img;
+        float inv[2];
+        rd::prepare_mixer_weights_res(hw1.data(), hw2.data(), C, img, inv);
+        p.ws_inv1 = inv[0]; p.ws_inv2 = inv[1];
+        (void)hipMalloc(&hbuf[0], img.size() * 2);
+        (void)hipMemcpy(hbuf[0], img.data(), img.size() * 2, hipMemcpyHostToDevice);
+        p.w1h = (const uint16_t*)hbuf[0];
+    } else if (variant >= 200) {  // weight-streaming split mixer (kernels_mixer_ws.hip); 400+: the prefetching form (PF)
+        const bool pf = variant >= 400 && variant < 600;
+        if (pf) variant -= 200;
+        p.ws_pf = pf;
+        p.dbg = (variant - 200) | ws_abl;
+        std::vector<float> hw1((size_t)2 * C * C), hw2((size_t)2 * C * C);
+        (void)hipMemcpy(hw1.data(), w1, hw1.size() * 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(hw2.data(), w2, hw2.size() * 4, hipMemcpyDeviceToHost);
+        std::vector<uint16_t> img;
+        float inv[2];
+        rd::prepare_mixer_weights_ws(hw1.data(), hw2.data(), C, img, inv);
+        p.ws_inv1 = inv[0]; p.ws_inv2 = inv[1];
+        (void)hipMalloc(&hbuf[0], img.size() * 2);
+        (void)hipMemcpy(hbuf[0], img.data(), img.size() * 2, hipMemcpyHostToDevice);
+        p.w1h = (const uint16_t*)hbuf[0];
+    } else if (variant >= 100) {  // fp16x3 mixer (+ ablation bits)
+        p.dbg = variant - 100;
+        std::vector<float> hw1((size_t)2 * C * C), hw2((size_t)2 * C * C);
+        (void)hipMemcpy(hw1.data(), w1, hw1.size() * 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(hw2.data(), w2, hw2.size() * 4, hipMemcpyDeviceToHost);
+        std::vector<uint16_t> v[4];
+        rd::prepare_mixer_weights_h3(hw1.data(), hw2.data(), C, v[0], v[1], v[2], v[3]);
+        for (int i = 0; i < 4; ++i) {
+            (void)hipMalloc(&hbuf[i], v[i].size() * 2);
+            (void)hipMemcpy(hbuf[i], v[i].data(), v[i].size() * 2, hipMemcpyHostToDevice);
+        }
+        p.w1h = (const uint16_t*)hbuf[0]; p.w1l = (const uint16_t*)hbuf[1];
+        p.w2h = (const uint16_t*)hbuf[2]; p.w2l = (const uint16_t*)hbuf[3];
+    }
+    auto go = [&] {
+        if (variant >= 300 && !p.ws_pf) rd::launch_mixer_fused_res(p, nullptr);
+        else if (variant >= 200) rd::launch_mixer_fused_ws(p, nullptr);
+        else if (variant >= 100) rd::launch_mixer_fused_h3(p, nullptr);
+        else rd::launch_mixer_debug(p, variant, nullptr);
+    };
+    go();
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) go();
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    for (void* b : hbuf) if (b) (void)hipFree(b);
+    return ms / iters;
+}
+// h1 image of device weights w [N][K] (single-accumulator split GEMM, kernels_gemm_h1.hip): uploaded into fresh device buffers
+static bool debug_h1_image(const float* w_dev, int N, int K, void** img_dev, float* inv) {
+    if (!rd::gemm_h1_shape_ok(K, N)) return false;
+    std::vector<float> hw((size_t)N * K);
+    if (hipMemcpy(hw.data(), w_dev, hw.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    std::vector<uint16_t> img;
+    *inv = rd::prepare_gemm_h1_weights(hw.data(), N, K, img);
+    if (hipMalloc(img_dev, img.size() * 2) != hipSuccess) return false;
+    (void)hipMemcpy(*img_dev, img.data(), img.size() * 2, hipMemcpyHostToDevice);
+    return true;
+}
+float rd_debug_time_gemm(int M, int K, int N, int act, int iters, float* x, float* w, float* b, float* y, void* wh, void* wl) {
+    rd::ConvParams p{};
+    p.wh = (const uint16_t*)wh; p.wl = (const uint16_t*)wl;
+    p.x = x; p.xld = K; p.N = 1; p.H = 1; p.W = M; p.Cin = K; p.w = w; p.bias = b; p.y = y; p.yld = N;
+    p.OH = 1; p.OW = M; p.Cout = N; p.KH = p.KW = p.SH = p.SW = 1; p.act = act; p.out_mode = rd::OUT_NHWC;
+    p.M = M; p.K = K; p.Ng = N;
+    void* img = nullptr;
+    float inv = 0.f;
+    if (wh && debug_h1_image(w, N, K, &img, &inv)) { p.w1 = (const uint16_t*)img; p.w1_inv = inv; }   // as the engine prepares it
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    auto go = [&] { if (wh) rd::launch_conv_igemm_h3(p, nullptr); else rd::launch_conv_igemm(p, nullptr); };
+    go();
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; ++i) go();
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (img) (void)hipFree(img);
+    return ms / iters;
+}
+// developer entry: the single-accumulator split GEMM alone, with strides, residual and the range flag:
+// y[M][yld] = act(x[M][xld(K used)] * w[N][K]^T + b) + res[M][rld].  Returns ms per launch, or -1 when the kernel does not take the shape.
+// *range_out (optional) receives 1 when the kernel raised its range flag.
+float rd_debug_gemm_h1(int M, int K, int N, int act, int iters, float* x, int xld, float* w, float* b, float* res, int rld, float* y, int yld,
+                       int* range_out) {
+    rd::ConvParams p{};
+    p.x = x; p.xld = xld; p.N = 1; p.H = 1; p.W = M; p.Cin = K; p.w = w; p.bias = b; p.y = y; p.yld = yld;
+    p.OH = 1; p.OW = M; p.Cout = N; p.KH = p.KW = p.SH = p.SW = 1; p.act = act; p.out_mode = rd::OUT_NHWC;
+    p.res = res; p.rld = rld;
+    p.M = M; p.K = K; p.Ng = N;
+    void* img = nullptr;
+    float inv = 0.f;
+    if (!debug_h1_image(w, N, K, &img, &inv)) return -1.f;
+    p.w1 = (const uint16_t*)img; p.w1_inv = inv;
+    unsigned* flag = nullptr;
+    (void)hipHostMalloc((void**)&flag, sizeof(unsigned), hipHostMallocMapped);
+    *flag = 0;
+    p.range_flag = flag;
+    float ms = -1.f;
+    if (rd::gemm_h1_applies(p)) ms = rd_debug_time(iters, [&] { rd::launch_gemm_h1(p, nullptr); });
+    (void)hipDeviceSynchronize();
+    if (range_out) *range_out = (int)*flag;
+    (void)hipHostFree(flag);
+    (void)hipFree(img);
+    return ms;
+}
+
+// developer entry: the 1 x 3 sequence convolution alone (kernels_seqconv.hip).  x0 [M][ld0] / x1 [M][ld1] (or null) = the two K segments,
+// w [N][3 (C0 + C1)] fp32 in the kernel's order (tap, then segment 0 | segment 1 channels), tokinfo [M] (or null: uniform lines of T
+// tokens), split != 0: the split-fp16 route (the weights are split here the way the engine splits them), else native fp32.
+// Returns ms per launch (iters timed launches after one untimed), or -1 when the kernel does not take the shape.
+float rd_debug_seqconv(int M, int C0, int C1, int N, int T, int act, int split, int iters, float* x0, int ld0, float* x1, int ld1, float* w, float* b,
+                       const int32_t* tokinfo, float* y, int yld, int* range_out) {
+    if (M <= 0 || !rd::seqconv_shape_ok(C0, C1, N) || ld0 % 4 || ld1 % 4 || (!tokinfo && T <= 0)) return -1.f;
+    rd::SeqConvParams p{};
+    p.x0 = x0; p.ld0 = ld0; p.C0 = C0; p.x1 = C1 ? x1 : nullptr; p.ld1 = C1 ? ld1 : 0; p.C1 = C1;
+    p.w = w; p.bias = b; p.y = y; p.yld = yld; p.M = M; p.N = N; p.T = T; p.tokinfo = tokinfo; p.act = act;
+    const int K = 3 * (C0 + C1);
+    void *dh = nullptr, *dl = nullptr;
+    unsigned* flag = nullptr;
+    (void)hipHostMalloc((void**)&flag, sizeof(unsigned), hipHostMallocMapped);
+    *flag = 0;
+    if (split) {
+        std::vector<float> hw((size_t)N * K);
+        if (hipMemcpy(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+        std::vector<uint16_t> hi, lo;
+        rd::split_weights_h3(hw.data(), N, K, hi, lo);
+        if (hipMalloc(&dh, hi.size() * 2) != hipSuccess || hipMalloc(&dl, lo.size() * 2) != hipSuccess) return -1.f;
+        (void)hipMemcpy(dh, hi.data(), hi.size() * 2, hipMemcpyHostToDevice);
+        (void)hipMemcpy(dl, lo.data(), lo.size() * 2, hipMemcpyHostToDevice);
+        p.wh = (const uint16_t*)dh; p.wl = (const uint16_t*)dl;
+        p.range_flag = flag;
+    }
+    float ms = rd_debug_time(iters, [&] { rd::launch_seqconv(p, nullptr); });
+    (void)hipDeviceSynchronize();
+    if (hipGetLastError() != hipSuccess) ms = -1.f;
+    if (range_out) *range_out = (int)*flag;
+    (void)hipHostFree(flag);
+    if (dh) (void)hipFree(dh);
+    if (dl) (void)hipFree(dl);
+    return ms;
+}
+
+// developer entry: the fused local tail of PFHeadLocal alone (kernels_det_local.hip).  Device pointers: f NHWC [N][H/2][W/2][64], shrink
+// [N][H][W], w3 = last_3's folded weights [64][65][3][3] (input channel 0 = shrink), b3 [64], w1 [64], y [N][H][W]; split != 0: the
+// split-fp16 route, else native fp32.  Returns ms per launch (iters timed launches after one untimed), or -1 for a geometry it does not take.
+float rd_debug_det_local(int N, int H, int W, int split, int iters, float* f, float* shrink, float* w3, float* b3, float* w1, float b1, float* y,
+                         int* range_out) {
+    if (N <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return -1.f;
+    std::vector<float> hw((size_t)64 * 65 * 9);
+    if (hipMemcpy(hw.data(), w3, hw.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    std::vector<float> img32;
+    std::vector<uint16_t> img16;
+    const float inv = rd::prepare_det_local_weights(hw.data(), img32, img16);
+    void *d32 = nullptr, *d16 = nullptr;
+    if (hipMalloc(&d32, img32.size() * 4) != hipSuccess || hipMalloc(&d16, img16.size() * 2) != hipSuccess) return -1.f;
+    (void)hipMemcpy(d32, img32.data(), img32.size() * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(d16, img16.data(), img16.size() * 2, hipMemcpyHostToDevice);
+    unsigned* flag = nullptr;
+    (void)hipHostMalloc((void**)&flag, sizeof(unsigned), hipHostMallocMapped);
+    *flag = 0;
+    rd::DetLocalParams p{};
+    p.f = f; p.fld = 64; p.shrink = shrink; p.y = y; p.N = N; p.H = H; p.W = W;
+    p.wimg32 = (const float*)d32; p.b3 = b3; p.w1 = w1; p.b1 = b1;
+    if (split) { p.wimg16 = (const uint16_t*)d16; p.w_inv = inv; p.range_flag = flag; }
+    float ms = rd_debug_time(iters, [&] { rd::launch_det_local(p, nullptr); });
+    (void)hipDeviceSynchronize();
+    if (hipGetLastError() != hipSuccess) ms = -1.f;
+    if (range_out) *range_out = (int)*flag;
+    (void)hipHostFree(flag);
+    (void)hipFree(d32);
+    (void)hipFree(d16);
+    return ms;
+}
+
+// developer entry: one dense convolution on prepared operands (x NHWC fp32 [N][H][W][Cin]; w folded [Cout][K], k = (kh*KW+kw)*Cin+ci;
+// wh / wl its fp16 split with rows padded to Kp = ceil32(K), or null for the fp32 MFMA kernels; y NHWC [N][OH][OW][Cout]).
+// Returns ms per launch (iters timed launches after one untimed).  *used_direct: in = 1 forces the direct k x k kernel when it
+// supports the geometry, in = 2 the small-K streaming kernel, in = 4 the direct 9x9 kernel (kernels_conv9x9_h1.hip; in = 0 leaves a 9x9 layer
+// on the generic k x k implicit GEMM it displaces); out = 1 / 2 / 4 when the direct / streaming / 9x9 kernel ran (3: the one-accumulator 3x3).
+float rd_debug_conv(int N, int H, int W, int Cin, int Cout, int KH, int KW, int S, int PT, int PL, int PB, int PR, int act, int iters,
+                    float* x, float* w, void* wh, void* wl, float* bias, float* res, float* y, int* used_direct) {
+    rd::ConvParams p{};
+    p.x = x; p.xld = Cin; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.w = w; p.bias = bias; p.y = y; p.yld = Cout;
+    p.wh = (const uint16_t*)wh; p.wl = (const uint16_t*)wl;
+    p.OH = (H + PT + PB - KH) / S + 1; p.OW = (W + PL + PR - KW) / S + 1; p.Cout = Cout;
+    p.KH = KH; p.KW = KW; p.SH = p.SW = S; p.PT = PT; p.PL = PL; p.act = act; p.out_mode = rd::OUT_NHWC;
+    p.res = res; p.rld = Cout;
+    p.M = N * p.OH * p.OW; p.K = KH * KW * Cin; p.Ng = Cout;
+    // the one-accumulator 3x3 kernel needs its own weight image, prepared here the way the engine prepares it (RD_CONV3X3_H1=0 or
+    // *used_direct = 1 / 2 on entry: the older kernels).  Reported as *used_direct = 3.
+    void* img3 = nullptr;
+    if (wh && !(used_direct && *used_direct) && rd::conv3x3_h1_shape_ok(KH, KW, Cin, Cout)) {
+        std::vector<float> hw((size_t)Cout * p.K);
+        if (hipMemcpy(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
+            std::vector<uint16_t> img;
+            const float inv = rd::prepare_conv3x3_h1_weights(hw.data(), Cout, Cin, img);
+            if (hipMalloc(&img3, img.size() * 2) == hipSuccess) {
+                (void)hipMemcpy(img3, img.data(), img.size() * 2, hipMemcpyHostToDevice);
+                p.w3 = (const uint16_t*)img3;
+                p.w3_inv = inv;
+            }
+        }
+    }
+    void* img9 = nullptr;
+    if (wh && used_direct && *used_direct == 4 && rd::conv9x9_h1_shape_ok(KH, KW, Cin, Cout)) {
+        std::vector<float> hw((size_t)Cout * p.K);
+        if (hipMemcpy(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
+            std::vector<uint16_t> img;
+            const float inv = rd::prepare_conv9x9_h1_weights(hw.data(), Cout, Cin, img);
+            if (hipMalloc(&img9, img.size() * 2) == hipSuccess) {
+                (void)hipMemcpy(img9, img.data(), img.size() * 2, hipMemcpyHostToDevice);
+                p.w9 = (const uint16_t*)img9;
+                p.w9_inv = inv;
+            }
+        }
+    }
+    const bool c9 = wh && rd::conv9x9_h1_applies(p);
+    const bool c3 = wh && rd::conv3x3_h1_applies(p);
+    const bool force = used_direct && *used_direct == 1 && wh && rd::conv_direct_h3_supported(p);
+    const bool force_stream = used_direct && *used_direct == 2 && wh && rd::conv_stream_h3_supported(p);
+    if (used_direct) *used_direct = c9 ? 4 : c3 ? 3 : force_stream ? 2 : (force || (wh && !rd::conv_stream_h3_applies(p) && rd::conv_direct_h3_applies(p))) ? 1
+                                    : (wh && rd::conv_stream_h3_applies(p)) ? 2 : 0;
+    auto go = [&] {
+        if (force_stream) rd::launch_conv_stream_h3(p, nullptr);
+        else if (force) rd::launch_conv_direct_h3(p, nullptr);
+        else if (wh) rd::launch_conv_igemm_h3(p, nullptr);
+        else rd::launch_conv_igemm(p, nullptr);
+    };
+    const float ms = rd_debug_time(iters, go);
+    if (img3) (void)hipFree(img3);
+    if (img9) (void)hipFree(img9);
+    return ms;
+}
+
+// developer entry: the fused stem tail (kernels_stem34.hip).  x NHWC fp32 [N][H][W][xld >= Cin]; w3 [N1][9 Cin] with k = (kh * 3 + kw) * Cin + ci,
+// w4 [N2][N1], biases [N1] / [N2] (device pointers); y NHWC [N][OH][OW][yld >= N2].  Images are prepared here the way the engine prepares them.
+// Returns ms per launch, -1 when the shape is not covered.
+float rd_debug_stem34(int N, int H, int W, int Cin, int xld, int N1, int N2, int yld, int act3, int act4, int iters, float* x, float* w3, float* b3,
+                      float* w4, float* b4, float* y, unsigned* range_flag) {
+    if (!rd::stem34_shape_ok(Cin, N1, N2)) return -1.f;
+    std::vector<float> h3((size_t)N1 * 9 * Cin), h4((size_t)N2 * N1), hb3((size_t)((N1 + 31) / 32) * 32, 0.f);
+    if (hipMemcpy(h3.data(), w3, h3.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    if (hipMemcpy(h4.data(), w4, h4.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    if (hipMemcpy(hb3.data(), b3, (size_t)N1 * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    std::vector<uint16_t> i3, i4;
+    float inv[2];
+    rd::prepare_stem34_weights(h3.data(), h4.data(), Cin, N1, N2, i3, i4, inv);
+    void *d3 = nullptr, *d4 = nullptr, *db3 = nullptr;
+    if (hipMalloc(&d3, i3.size() * 2) != hipSuccess || hipMalloc(&d4, i4.size() * 2) != hipSuccess || hipMalloc(&db3, hb3.size() * 4) != hipSuccess) return -1.f;
+    (void)hipMemcpy(d3, i3.data(), i3.size() * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(d4, i4.data(), i4.size() * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(db3, hb3.data(), hb3.size() * 4, hipMemcpyHostToDevice);
+    rd::Stem34Params p{};
+    p.x = x; p.xld = xld; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.y = y; p.yld = yld;
+    p.OH = (H - 1) / 2 + 1; p.OW = (W - 1) / 2 + 1; p.N1 = N1; p.N2 = N2;
+    p.w3 = (const uint16_t*)d3; p.w3_inv = inv[0]; p.b3 = (const float*)db3;
+    p.w4 = (const uint16_t*)d4; p.w4_inv = inv[1]; p.b4 = b4;
+    p.act3 = act3; p.act4 = act4; p.range_flag = range_flag;
+    const float ms = rd_debug_time(iters, [&] { rd::launch_stem34(p, nullptr); });
+    (void)hipFree(d3); (void)hipFree(d4); (void)hipFree(db3);
+    return ms;
+}
+
+// developer entry: one depthwise convolution through launch_dwconv (x NHWC fp32 [N][H][W][C], w [KH*KW][C], bias [C] or null,
+// res NHWC or null, line_w int32 [N] valid widths or null, gap = [N][chunks][C] partial sums of the output or null).
+// *gap_chunks receives the chunk count the launcher uses for this geometry.  Returns ms per launch.
+float rd_debug_dwconv(int N, int H, int W, int C, int K, int SH, int act, int iters, float* x, float* w, float* bias, float* res, float* y,
+                      const int32_t* line_w, float* gap, int* gap_chunks) {
+    rd::DwParams p{};
+    p.x = x; p.xld = C; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = C;
+    p.KH = p.KW = K; p.SH = SH; p.SW = 1; p.PT = p.PL = K / 2;
+    p.OH = (H + 2 * p.PT - K) / SH + 1; p.OW = W; p.act = act; p.res = res; p.rld = C;
+    const int chunks = rd::dwconv_gap_chunks(p);
+    if (gap_chunks) *gap_chunks = chunks;
+    p.gap_partial = chunks > 0 ? gap : nullptr; p.gap_chunks = chunks;
+    p.line_w = line_w; p.line_w_stride = 1;
+    if (gap_chunks && rd::dwconv_kxk_lds_applies(p)) *gap_chunks = -1;      // (tests: the one-channel-per-lane 5x5 / 7x7 kernel takes this call)
+    return rd_debug_time(iters, [&] { rd::launch_dwconv(p, nullptr); });
+}
+
+// developer entry: one PPLCNetV3 depthwise layer through launch_lcv3_dw (kernels_lcv3.hip; x NHWC fp32 [N][H][W][C], w [K*K][C], bias [C],
+// y [N][OH][OW][C]; aff = {pre_s, pre_b, post_s, post_b}, pre_act: hardswish + (pre_s, pre_b) on load; line_in / line_out int32 [N] valid
+// widths or null; gap: [N][OH][C] row sums of y over the output width, or null).  Returns ms per launch, < 0: geometry not served.
+float rd_debug_lcv3_dw(int N, int H, int W, int C, int K, int SH, int SW, int pre_act, int iters, const float* aff, float* x, float* w, float* bias,
+                       float* y, const int32_t* line_in, const int32_t* line_out, float* gap) {
+    if (!rd::lcv3_dw_shape_ok(K, SH, SW, C) || !aff || (gap && !rd::lcv3_gap_shape_ok(C))) return -1.f;
+    rd::Lcv3DwParams p{};
+    p.x = x; p.xld = C; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = C;
+    p.K = K; p.SH = SH; p.SW = SW;
+    p.OH = (H + 2 * (K / 2) - K) / SH + 1; p.OW = (W + 2 * (K / 2) - K) / SW + 1;
+    p.pre_act = pre_act; p.pre_s = aff[0]; p.pre_b = aff[1]; p.post_s = aff[2]; p.post_b = aff[3]; p.post_act = 1;
+    p.line_in = line_in; p.line_out = line_out; p.line_stride = 1;
+    return rd_debug_time(iters, [&] { rd::launch_lcv3_dw(p, nullptr); },
+                         [&] { if (gap) rd::launch_lcv3_gap_rows(y, C, N, p.OH, p.OW, C, gap, line_out, 1, nullptr); });
+}
+
+// developer entry: one 5x5 depthwise layer of the recogniser geometry through launch_dw5_strip (kernels_mv1e.hip; x NHWC fp32 [N][H][W][xld],
+// w [25][C], bias [C], y [N][OH][OW][yld], OH = (H - 1) / SH + 1, OW = (W - 1) / SW + 1; aff = {pre_s, pre_b, post_s, post_b}; pre_act:
+// hardswish + (pre_s, pre_b) on load; post_act 0: convolution + bias only; line_in / line_out int32 [N] valid widths or null).  Returns ms
+// per launch, < 0: geometry not served (dw5_strip_launch_ok).
+float rd_debug_dw5_strip(int N, int H, int W, int C, int SH, int SW, int pre_act, int post_act, int xld, int yld, int iters, const float* aff, float* x,
+                         float* w, float* bias, float* y, const int32_t* line_in, const int32_t* line_out) {
+    if (!aff || SH < 1 || SW < 1) return -1.f;
+    rd::Lcv3DwParams p{};
+    p.x = x; p.xld = xld; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = yld;
+    p.K = 5; p.SH = SH; p.SW = SW;
+    p.OH = (H - 1) / SH + 1; p.OW = (W - 1) / SW + 1;
+    p.pre_act = pre_act; p.pre_s = aff[0]; p.pre_b = aff[1]; p.post_s = aff[2]; p.post_b = aff[3]; p.post_act = post_act;
+    p.line_in = line_in; p.line_out = line_out; p.line_stride = 1;
+    if (!rd::dw5_strip_launch_ok(p)) return -1.f;
+    return rd_debug_time(iters, [&] { (void)rd::launch_dw5_strip(p, nullptr); });
+}
+
+// developer entry: MobileNetV1Enhance's final pooling through launch_mv1e_pool (x NHWC [N][H][W][C], H >= 2; y [N][W / 2][C], or with
+// line_tab int32 [N][4] the compact token rows it names).  Returns 0, < 0: geometry not served.
+int rd_debug_mv1e_pool(int N, int H, int W, int C, float* x, float* y, const int32_t* line_tab) {
+    if (N < 1 || H < 2 || W < 2 || C < 4 || C % 4 != 0) return -1;
+    rd::launch_mv1e_pool(x, C, y, C, N, H, W, C, nullptr, line_tab);
+    return hipStreamSynchronize(nullptr) == hipSuccess ? 0 : -2;
+}
+
+// developer entry, host only (no device is touched): the load-time derived tensor `name` of "ppocrv5_det_mobile" - a folded
+// LearnableRepLayer (`<layer>.fold.weight / .bias`) or `neck.ins_conv.<i>.fold.*` - or of "ppocrv3_det_mobile" - a folded Conv + BatchNorm
+// (`backbone.stages.<s>.<i>.{expand,bottleneck,linear}_conv.fold.*`, `backbone.stages.3.3.fold.*`) - from a safetensors image.  Copies at most
+// `capacity` floats to `out` and returns the tensor's element count; -1: unknown kind, name or a malformed image.
+long rd_debug_derived_tensor(const char* kind, const void* img, size_t nbytes, const char* name, float* out, long capacity) {
+    try {
+        if (!kind || !img || !name) return -1;
+        const std::string k(kind);
+        rd::WeightStore ws;
+        ws.load_safetensors(img, nbytes);
+        const rd::ModelDesc* m = rd::find_model(k);
+        if (!m || !m->derived_tensors) return -1;
+        m->derive(ws);
+        if (!ws.has(name)) return -1;
+        const rd::HostTensor& t = ws.get(name);
+        const long n = (long)t.numel();
+        if (out) std::copy(t.f32(), t.f32() + std::min(n, capacity), out);
+        return n;
+    } catch (const std::exception&) {
+        return -1;
+    }
+}
+
+// developer entry: one MobileNetV3 depthwise layer through launch_mbv3_dw (kernels_mbv3.hip; x NHWC fp32 [N][H][W][xld >= C], w [K*K][C], bias
+// [C], y [N][OH][OW][yld >= C], OH = (H - 1) / S + 1; pre_act / post_act: 0 none, 1 ReLU, 2 hardswish - the producer's on load inside the map,
+// the layer's own in the epilogue; max_blocks > 0 caps the grid, so that a small map meets the grid-stride loop).  Returns ms per launch, < 0: not served (mbv3_dw_launch_ok).
+float rd_debug_mbv3_dw(int N, int H, int W, int C, int K, int S, int pre_act, int post_act, int xld, int yld, int iters, int max_blocks, float* x, float* w,
+                       float* bias, float* y) {
+    if (S < 1) return -1.f;
+    rd::Mbv3DwParams p{};
+    p.x = x; p.xld = xld; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = yld;
+    p.K = K; p.S = S; p.OH = (H - 1) / S + 1; p.OW = (W - 1) / S + 1;
+    p.pre_act = pre_act; p.post_act = post_act; p.max_blocks = max_blocks;
+    if (!x || !w || !bias || !y || !rd::mbv3_dw_launch_ok(p)) return -1.f;
+    return rd_debug_time(iters, [&] { (void)rd::launch_mbv3_dw(p, nullptr); });
+}
+
+// developer entry: one MobileNetV3 inverted-residual block through launch_mbv3_block (kernels_mbv3.hip; x NHWC fp32 [N][H][W][xld >= cin],
+// we [mid][cin], be [mid], wd [K*K][mid], bd [mid], wl [cout][mid], bl [cout], y [N][OH][OW][yld >= cout]; act 1 ReLU / 2 hardswish;
+// in_hswish: hardswish on load; shortcut: y += x').  Returns ms per launch, < 0: not served (mbv3_block_launch_ok).
+float rd_debug_mbv3_block(int N, int H, int W, int cin, int mid, int cout, int K, int S, int act, int in_hswish, int shortcut, int xld, int yld, int iters,
+                          float* x, float* we, float* be, float* wd, float* bd, float* wl, float* bl, float* y) {
+    if (S < 1) return -1.f;
+    rd::Mbv3BlockParams p{};
+    p.x = x; p.xld = xld; p.N = N; p.H = H; p.W = W; p.cin = cin; p.mid = mid; p.cout = cout;
+    p.we = we; p.be = be; p.wd = wd; p.bd = bd; p.wl = wl; p.bl = bl; p.y = y; p.yld = yld;
+    p.K = K; p.S = S; p.OH = (H - 1) / S + 1; p.OW = (W - 1) / S + 1;
+    p.act = act; p.in_hswish = in_hswish; p.shortcut = shortcut;
+    if (!x || !we || !be || !wd || !bd || !wl || !bl || !y || !rd::mbv3_block_launch_ok(p)) return -1.f;
+    return rd_debug_time(iters, [&] { (void)rd::launch_mbv3_block(p, nullptr); });
+}
+// host only: would mbv3_block_kernel serve this geometry (contiguous, aligned views assumed)?  1 yes, 0 no
+int rd_debug_mbv3_block_ok(int N, int H, int W, int cin, int mid, int cout, int K, int S, int act, int shortcut, int xld, int yld) {
+    if (S < 1) return 0;
+    rd::Mbv3BlockParams p{};
+    p.xld = xld; p.N = N; p.H = H; p.W = W; p.cin = cin; p.mid = mid; p.cout = cout; p.yld = yld;
+    p.K = K; p.S = S; p.OH = (H - 1) / S + 1; p.OW = (W - 1) / S + 1;
+    p.act = act; p.shortcut = shortcut;
+    return rd::mbv3_block_launch_ok(p) ? 1 : 0;
+}
+
+// developer entry: one MobileNetV3-small depthwise layer through launch_mbv3s_dw (kernels_mbv3s.hip; x NHWC fp32 [N][H][W][xld >= C], w [K*K][C],
+// bias [C], y [N][OH][OW][yld >= C], OH = (H - 1) / SH + 1, OW = (W - 1) / SW + 1; pre_act / post_act / max_blocks as rd_debug_mbv3_dw).
+// Returns ms per launch, < 0: not served (mbv3s_dw_launch_ok).
+float rd_debug_mbv3s_dw(int N, int H, int W, int C, int K, int SH, int SW, int pre_act, int post_act, int xld, int yld, int iters, int max_blocks, float* x,
+                        float* w, float* bias, float* y) {
+    if (SH < 1 || SW < 1) return -1.f;
+    rd::Mbv3sDwParams p{};
+    p.x = x; p.xld = xld; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = yld;
+    p.K = K; p.SH = SH; p.SW = SW; p.OH = (H - 1) / SH + 1; p.OW = (W - 1) / SW + 1;
+    p.pre_act = pre_act; p.post_act = post_act; p.max_blocks = max_blocks;
+    if (!x || !w || !bias || !y || !rd::mbv3s_dw_launch_ok(p)) return -1.f;
+    return rd_debug_time(iters, [&] { (void)rd::launch_mbv3s_dw(p, nullptr); });
+}
+
+// developer entry: one MobileNetV3-small inverted-residual block with optional squeeze-excite on caller-supplied FOLDED weights, through the
+// operators the engine's plan chains for it (route 0) or through cls_block_kernel, the block as the one-launch classifier runs it (route 1).
+// Route 0: fp32 1x1 (launch_conv_igemm; a ReLU block activates in its
+// epilogue, a hardswish block in the depthwise kernel's load) -> launch_mbv3s_dw -> [launch_gap_partial -> launch_se_fc with the paddle
+// hard-sigmoid -> launch_scale_channels] -> fp32 1x1 (+ x).  x NHWC [N][H][W][xld >= cin], we [mid][cin], be [mid], wd [K*K][mid], bd [mid],
+// w1 [mid/4][mid], b1 [mid/4], w2 [mid][mid/4], b2 [mid] (se != 0), wl [cout][mid], bl [cout], y [N][OH][W][yld >= cout]; act 1 ReLU / 2
+// hardswish.  Temporaries are allocated per call.  Returns ms per block, < 0: not served (another route, a geometry a kernel declines,
+// or no memory).
+float rd_debug_mbv3s_block(int route, int N, int H, int W, int cin, int mid, int cout, int K, int SH, int act, int se, int shortcut, int xld, int yld,
+                           int iters, float* x, float* we, float* be, float* wd, float* bd, float* w1, float* b1, float* w2, float* b2, float* wl,
+                           float* bl, float* y) {
+    if ((route != 0 && route != 1) || SH < 1 || N < 1 || H < 1 || W < 1 || cin % 4 != 0 || mid % 8 != 0 || cout % 4 != 0 || mid > 512) return -1.f;
+    if (act != rd::MBV3_RELU && act != rd::MBV3_HSWISH) return -1.f;
+    if (shortcut && (SH != 1 || cin != cout)) return -1.f;
+    if (!x || !we || !be || !wd || !bd || !wl || !bl || !y || (se && (!w1 || !b1 || !w2 || !b2))) return -1.f;
+    if (route == 1) {       // the block as cls_line_kernel runs it, one workgroup per image
+        rd::ClsBlockParams L{};
+        L.we = we; L.be = be; L.wd = wd; L.bd = bd; L.w1 = w1; L.b1 = b1; L.w2 = w2; L.b2 = b2; L.wl = wl; L.bl = bl;
+        L.k = K; L.cin = cin; L.mid = mid; L.cout = cout; L.sh = SH; L.se = se ? 1 : 0; L.act = act; L.shortcut = shortcut ? 1 : 0;
+        if (!rd::cls_block_plan(L, H, W) || !rd::cls_block_launch_ok(L, N, H, W, xld, yld)) return -1.f;
+        float* scratch = nullptr;
+        if (hipMalloc((void**)&scratch, (size_t)std::min(N, 512) * rd::cls_block_scratch_floats(L, H, W) * sizeof(float)) != hipSuccess) return -1.f;
+        const float t = rd_debug_time(iters, [&] { (void)rd::launch_cls_block(L, x, xld, y, yld, N, H, W, scratch, nullptr); });
+        (void)hipFree(scratch);
+        return t;
+    }
+    const int OH = (H - 1) / SH + 1, hw = OH * W;
+    const int chunks = std::max(1, std::min(64, hw / 256));
+    const size_t ne = (size_t)N * H * W * mid, nd = (size_t)N * OH * W * mid, np = (size_t)N * chunks * mid, ng = (size_t)N * mid;
+    float* tmp = nullptr;
+    if (hipMalloc((void**)&tmp, (ne + nd + np + ng) * sizeof(float)) != hipSuccess) return -1.f;
+    float *e = tmp, *d = e + ne, *partial = d + nd, *gate = partial + np;
+    rd::Mbv3sDwParams q{};
+    q.x = e; q.xld = mid; q.N = N; q.H = H; q.W = W; q.C = mid; q.w = wd; q.bias = bd; q.y = d; q.yld = mid;
+    q.K = K; q.SH = SH; q.SW = 1; q.OH = OH; q.OW = W;
+    q.pre_act = act == rd::MBV3_RELU ? rd::MBV3_NONE : rd::MBV3_HSWISH; q.post_act = act;
+    if (!rd::mbv3s_dw_launch_ok(q)) {
+        (void)hipFree(tmp);
+        return -1.f;
+    }
+    auto pointwise = [&](const float* in, int ild, int pixels_h, int ci, const float* w, const float* b, float* out, int old, int co, int a, const float* res) {
+        rd::ConvParams c{};
+        c.x = in; c.xld = ild; c.N = N; c.H = pixels_h; c.W = W; c.Cin = ci; c.w = w; c.bias = b; c.y = out; c.yld = old;
+        c.OH = pixels_h; c.OW = W; c.Cout = co; c.KH = c.KW = c.SH = c.SW = 1;
+        c.res = res; c.rld = res ? xld : 0; c.act = a; c.out_mode = rd::OUT_NHWC;
+        c.M = N * pixels_h * W; c.K = ci; c.Ng = co;
+        rd::launch_conv_igemm(c, nullptr);
+    };
+    const float ms = rd_debug_time(iters, [&] {
+        pointwise(x, xld, H, cin, we, be, e, mid, mid, act == rd::MBV3_RELU ? rd::ACT_RELU : rd::ACT_NONE, nullptr);
+        (void)rd::launch_mbv3s_dw(q, nullptr);
+        if (se) {
+            rd::launch_gap_partial(d, mid, N, hw, mid, partial, chunks, nullptr);
+            rd::SeFcParams f{};
+            f.partial = partial; f.chunks = chunks; f.N = N; f.C = mid; f.Cr = mid / 4; f.inv_hw = 1.f / (float)hw;
+            f.w1 = w1; f.b1 = b1; f.w2 = w2; f.b2 = b2; f.gate = rd::ACT_HSIG_PADDLE; f.scale = gate; f.H = OH;
+            rd::launch_se_fc(f, nullptr);
+            rd::launch_scale_channels(d, mid, d, mid, gate, 0.f, N, hw, mid, nullptr);
+        }
+        pointwise(d, mid, OH, mid, wl, bl, y, yld, cout, rd::ACT_NONE, shortcut ? x : nullptr);
+    });
+    (void)hipFree(tmp);
+    return ms;
+}
+
+// developer entry: one PPLCNetV3 depthwise layer in the detector geometry (x NHWC fp32 [N][H][W][C], w [K*K][C], bias [C], y [N][OH][OW][C] with
+// OH = (H + 2 (K / 2) - K) / S + 1; aff as above; post_act 0: convolution + bias only).  route 0: launch_lcv3_dw (kernels_lcv3.hip), 1: the
+// LDS-staged launch_lcv3_dw2d (kernels_lcv3_det.hip).  Returns ms per launch, < 0: geometry not served by that route.
+float rd_debug_lcv3_dw_det(int N, int H, int W, int C, int K, int S, int pre_act, int post_act, int route, int iters, const float* aff, float* x,
+                           float* w, float* bias, float* y) {
+    if (!aff || N < 1 || H < 1 || W < 1 || (S != 1 && S != 2) || (route != 0 && route != 1)) return -1.f;
+    if (route == 0 && !rd::lcv3_dw_shape_ok(K, S, S, C)) return -1.f;
+    rd::Lcv3DwParams p{};
+    p.x = x; p.xld = C; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = C;
+    p.K = K; p.SH = p.SW = S;
+    p.OH = (H + 2 * (K / 2) - K) / S + 1; p.OW = (W + 2 * (K / 2) - K) / S + 1;
+    p.pre_act = pre_act; p.pre_s = aff[0]; p.pre_b = aff[1]; p.post_s = aff[2]; p.post_b = aff[3]; p.post_act = post_act;
+    if (route == 1 && !rd::lcv3_dw2d_launch_ok(p)) return -1.f;         // shape, or a grid beyond 2^31 workgroups
+    return rd_debug_time(iters, [&] { if (route) (void)rd::launch_lcv3_dw2d(p, nullptr); else rd::launch_lcv3_dw(p, nullptr); });
+}
+
+// developer entry: one PPLCNetV3 block (depthwise 3x3 stride 1 -> pointwise) through launch_lcv3_block (kernels_lcv3_block.hip; x NHWC fp32
+// [N][H][W][cin], dw_w [9][cin], dw_b [cin], pw_w [cout][cin], pw_b [cout], y [N][H][W][cout]; aff = {pre_s, pre_b, mid_s, mid_b, out_s,
+// out_b}; pre_act / out_act: hardswish + affine on load / in the epilogue; split: 1 = split-fp16 product raising *range_flag (a device-
+// visible word) on an operand beyond the fp16 range, 0 = fp32 product; line_w int32 [N] valid widths or null).  Returns ms per launch,
+// < 0: geometry not served.
+float rd_debug_lcv3_block(int N, int H, int W, int cin, int cout, int pre_act, int out_act, int split, int iters, const float* aff, float* x,
+                          float* dw_w, float* dw_b, float* pw_w, float* pw_b, float* y, const int32_t* line_w, unsigned* range_flag) {
+    if (!rd::lcv3_block_shape_ok(cin, cout) || !aff || N < 1 || H < 1 || W < 1) return -1.f;
+    rd::Lcv3BlockParams p{};
+    p.x = x; p.xld = cin; p.N = N; p.H = H; p.W = W; p.cin = cin; p.cout = cout;
+    p.dw_w = dw_w; p.dw_b = dw_b; p.pw_w = pw_w; p.pw_b = pw_b; p.y = y; p.yld = cout;
+    p.pre_act = pre_act; p.pre_s = aff[0]; p.pre_b = aff[1]; p.mid_s = aff[2]; p.mid_b = aff[3];
+    p.out_act = out_act; p.out_s = aff[4]; p.out_b = aff[5];
+    p.line_w = line_w; p.line_stride = 1; p.split = split; p.range_flag = range_flag;
+    return rd_debug_time(iters, [&] { rd::launch_lcv3_block(p, nullptr); });
+}
+
+// developer timing of the fused CTC head on prepared weights: wp = W' [C][128] fp32 (bias in column K), wh / wl its fp16 split
+// (null: fp32 MFMA kernel); part = workspace of M * 64 * 4 floats.  Returns ms per launch; *nsplit_out = the split count used.
+float rd_debug_time_ctc(int M, int K, int Ccls, int iters, float* x, float* wp, void* wh, void* wl, float* part, int32_t* idx, float* prob,
+                        int nsplit_override, int* nsplit_out) {
+    rd::CtcParams p{};
+    p.x = x; p.xld = K; p.w = wp; p.M = M; p.K = K; p.C = Ccls; p.part = part;
+    p.nsplit = nsplit_override > 0 ? nsplit_override : rd::ctc_head_nsplit(M, Ccls, wh != nullptr);
+    p.idx = idx; p.prob = prob;
+    p.wh = (const uint16_t*)wh; p.wl = (const uint16_t*)wl;
+    if (nsplit_out) *nsplit_out = p.nsplit;
+    return rd_debug_time(iters, [&] { rd::launch_ctc_head(p, nullptr); });
+}
+
+// A range-flag word for the developer entries below: pinned, device-mapped host memory, as the engine's own (engine.cpp load_weights).
+static unsigned* debug_flag_new() {
+    unsigned* flag = nullptr;
+    if (hipHostMalloc((void**)&flag, sizeof(unsigned), hipHostMallocMapped) != hipSuccess || !flag) return nullptr;
+    *flag = 0;
+    return flag;
+}
+static int debug_finish(unsigned* flag, int* range_out) {
+    const bool ok = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
+    if (range_out) *range_out = flag ? (int)*flag : 0;
+    if (flag) (void)hipHostFree(flag);
+    return ok ? 0 : -1;
+}
+
+// developer entry: the self-attention alone on packed qkv [tokens][3 heads hd] fp32 -> o [tokens][heads hd].  seg = int32 [B][2] (first token,
+// tokens) on the device, or null: B dense lines of T tokens.  route 0 = launch_attention exactly as the engine calls it (kernel per line),
+// 1 = the VALU kernel for every line, 2 = the matrix-core kernel only (lines beyond its limit are left untouched).  One launch, synchronised.
+// *range_out (optional) receives 1 when the matrix-core kernel raised its range flag.  Returns 0, or -1 for a head size or route the
+// library does not have.
+int rd_debug_attention(int B, int T, int heads, int hd, float scale, float* qkv, float* o, const int32_t* seg, int route, int* range_out) {
+    if (range_out) *range_out = 0;
+    if (B <= 0 || T <= 0 || heads <= 0 || !(hd == 15 || hd == 16 || hd == 32) || route < 0 || route > 2) return -1;
+    if (route == 2 && !rd::attention_h3_applies(1, hd)) return -1;
+    unsigned* flag = debug_flag_new();
+    if (!flag) return -1;
+    if (route == 0) rd::launch_attention(qkv, o, B, T, heads, hd, scale, nullptr, seg, flag);
+    else if (route == 1) rd::launch_attention_valu(qkv, o, B, T, heads, hd, scale, nullptr, seg);
+    else rd::launch_attention_h3(qkv, o, B, T, heads, hd, scale, nullptr, seg, flag);
+    return debug_finish(flag, range_out);
+}
+// developer entry: vit_attention_kernel alone (kernels_vit_attn.hip) on packed qkv [B][T][3 heads 64] fp32 -> o [B][T][heads 64]; one launch,
+// synchronised.  Returns 0, or -1 for a head size or length the kernel does not serve (hd = 64, 1 <= T <= 1024).
+int rd_debug_vit_attention(int B, int T, int heads, int hd, float scale, float* qkv, float* o) {
+    if (B <= 0 || B > 65535 || heads <= 0 || heads > 65535 || !qkv || !o || !rd::vit_attention_applies(T, hd)) return -1;
+    rd::launch_vit_attention(qkv, o, B, T, heads, scale, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
+// *h3_max_t = the longest line the matrix-core kernel serves at this head size (0: it has none), *valu_lds_keys = the keys the VALU kernel
+// holds in LDS at once (longer lines run over key tiles).  Returns -1 for a head size the library does not have.
+int rd_debug_attention_limits(int hd, int* h3_max_t, int* valu_lds_keys) {
+    if (!(hd == 15 || hd == 16 || hd == 32)) return -1;
+    if (h3_max_t) *h3_max_t = rd::attention_h3_applies(1, hd) ? rd::attention_h3_max_t() : 0;
+    if (valu_lds_keys) *valu_lds_keys = rd::attention_lds_keys(hd);
+    return 0;
+}
+
+// developer entry: LayerNorm over the last dimension, y[M][yld] = (x[M][xld] - mean) * rstd * g + b on the first C columns.  -1 for C > 512,
+// except C = 768 (layernorm768_kernel; xld and yld multiples of 4).
+int rd_debug_layernorm(int M, int C, float* x, int xld, float* y, int yld, float* g, float* b, float eps) {
+    if (M <= 0 || C <= 0 || xld < C || yld < C) return -1;
+    if (C == 768) {
+        if (xld % 4 || yld % 4) return -1;
+        rd::launch_layernorm768(x, xld, y, yld, g, b, M, eps, nullptr);
+        return debug_finish(nullptr, nullptr);
+    }
+    if (C > 512) return -1;
+    rd::launch_layernorm(x, xld, y, yld, g, b, M, C, eps, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
+
+// developer entry: ONE launch of the fused CTC head on prepared weights (as rd_debug_time_ctc), synchronised, with a free row stride of x
+// (xld >= K, a multiple of 4: rows are read as float4).  part = workspace of M * 64 * 4 floats.  *nsplit_out = the split count used,
+// *range_out = 1 when the split kernel raised its range flag.  Returns 0, or -1 for a shape the kernels do not take.
+int rd_debug_ctc_head(int M, int K, int Ccls, float* x, int xld, float* wp, void* wh, void* wl, float* part, int32_t* idx, float* prob,
+                      int nsplit_override, int* nsplit_out, int* range_out) {
+    if (range_out) *range_out = 0;
+    if (M <= 0 || Ccls <= 0 || K <= 0 || K >= 128 || K % 4 || xld < K || xld % 4 || nsplit_override > 64 || (wh == nullptr) != (wl == nullptr)) return -1;
+    rd::CtcParams p{};
+    p.x = x; p.xld = xld; p.w = wp; p.M = M; p.K = K; p.C = Ccls; p.part = part;
+    p.nsplit = nsplit_override > 0 ? nsplit_override : rd::ctc_head_nsplit(M, Ccls, wh != nullptr);
+    p.idx = idx; p.prob = prob;
+    p.wh = (const uint16_t*)wh; p.wl = (const uint16_t*)wl;
+    if (nsplit_out) *nsplit_out = p.nsplit;
+    unsigned* flag = debug_flag_new();
+    if (!flag) return -1;
+    p.range_flag = flag;
+    rd::launch_ctc_head(p, nullptr);
+    return debug_finish(flag, range_out);
+}
+
+// developer entries for the formula decoder's kernels (csrc/formula_decoder.hip): one synchronised launch each through the decode step's own
+// routing on caller-provided device buffers.  rd_debug_dec_gemv returns the dec_gemv_kernel instantiation that ran as
+// MT * 10000 + CW * 1000 + KPL * 100 + DB * 10 + DX, 0 where the routing declines the shape (nothing launched); the others return 0.
+// All return -1 for arguments the launch cannot take.
+int rd_debug_dec_gemv(int M, int K, int N, int act, const float* x, const float* w, const float* bias, const float* ln_g, const float* ln_b,
+                      const float* res, float* y) {
+    return rd::debug_dec_gemv(M, K, N, act, x, w, bias, ln_g, ln_b, res, y);
+}
+int rd_debug_dec_attention(int route, int self, int B, int T, float* kc, float* vc, int ldkv, long long seq_stride, const float* x,
+                           const float* ln_g, const float* ln_b, const float* w, const float* bias, const float* q, int ldq, const float* kcur,
+                           const float* vcur, int ldcur, float* out, int ldo) {
+    return rd::debug_dec_attention(route, self, B, T, kc, vc, ldkv, seq_stride, x, ln_g, ln_b, w, bias, q, ldq, kcur, vcur, ldcur, out, ldo);
+}
+int rd_debug_dec_select(int mode, const float* logits, int V, int B, int step, int64_t* ids, int ids_ld, int32_t* unfinished, int n_unfinished,
+                        int max_new, const float* emb, const float* pos, const float* g, const float* b, float* x, int32_t* state_out) {
+    return rd::debug_dec_select(mode, logits, V, B, step, reinterpret_cast<long long*>(ids), ids_ld, unfinished, n_unfinished, max_new, emb, pos, g,
+                                b, x, state_out);
+}
+
+}  // extern "C"

@@ -229,6 +229,10 @@ class Builder {
                       int level);
     bool lcv3_dw_common(const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, const Affine* pre, const Affine* post,
                         TView* y, Lcv3DwParams* p, OpRecord* r);   // shared by the two builders above; false in PREPARE mode
+    // shared by mbv3_dw (P = Mbv3DwParams, net "mbv3") and mbv3s_dw (P = Mbv3sDwParams, net "mbv3s") below, in the same way (builder_mobile.cpp)
+    template <typename P>
+    bool mbv3_dw_common(const std::string& net, const std::string& wname, const std::string& bname, const TView& x, int k, int sh, int sw, int pre_act,
+                        int post_act, TView* y, P* p, OpRecord* r);
     TView lcv3_act(const TView& x, Affine a);             // a hardswish(x) + b, elementwise (kernels_lcv3_det.hip)
     // MobileNetV3 in the detector geometry (kernels_mbv3.hip).  The depthwise layer alone: pre_act = the producer's activation, applied on
     // load inside the map; post_act = the layer's own (Mbv3Act)
@@ -303,11 +307,35 @@ class Builder {
 };
 
 // ------------------------------------------------------------------------------------------------
+// The model table (models.cpp): every engine kind is described ONCE, in the row next to its builder.  The Engine and the C surface look
+// a kind up here; nothing else lists the kinds.  (The two autoregressive decoders, "ppformulanet_head" and "unitable_decoder", are not
+// Engines and are not in the table.)
+enum class ModelFamily { Detector, Recogniser, Classifier, TableEncoder, Backbone, FormulaEncoder };
+struct ModelDesc {
+    const char* kind;
+    ModelFamily family;
+    void (*build)(Builder& b, int B, int H, int W, int flags);
+    void (*derive)(WeightStore& ws);       // adds the tensors `build` reads that are not in the file; null: there are none
+    // PREPARE mode folds the weights by building these geometries (the smallest legal ones; only weight names / shapes matter there)
+    struct Geom { int B, H, W, flags; };
+    std::vector<Geom> prepare;
+    // recognisers: n_classes = shape[0] of the first tensor, rec_token_dim = shape[1] of the second
+    const char* n_classes_tensor;
+    const char* token_dim_tensor;
+    // what the C surface offers for the kind
+    bool rec_line_widths;    // rd_rec_backbone_forward_lines (REC_LINE_WIDTHS)
+    bool det_want_neck;      // rd_det_forward_ex with RD_DET_WANT_NECK
+    bool derived_tensors;    // rd_debug_derived_tensor
+};
+const std::vector<ModelDesc>& model_table();
+const ModelDesc* find_model(const std::string& kind);   // null: not an engine kind
+
 class Engine {
    public:
     explicit Engine(int device, const std::string& kind);
     ~Engine();
     const std::string& kind() const { return kind_; }
+    const ModelDesc& model() const { return *model_; }   // the kind's row of the model table, resolved by the constructor
     void load_weights(const void* blob, size_t nbytes);
     bool loaded() const { return loaded_; }
 
@@ -345,9 +373,9 @@ class Engine {
     std::string last_error;
 
    private:
-    void build(Builder& b, int B, int H, int W, int flags);
     int device_;
     std::string kind_;
+    const ModelDesc* model_ = nullptr;
     bool loaded_ = false;
     bool profiling_ = false;
     int precision_ = PREC_AUTO;
@@ -377,8 +405,8 @@ class Engine {
     std::vector<hipEvent_t> events_;
 };
 
-// model builders (models.cpp)
-void build_ppocrv6_det(Builder& b, int B, int H, int W);
+// model builders (models.cpp), all behind the one signature of ModelDesc::build
+void build_ppocrv6_det(Builder& b, int B, int H, int W, int flags);   // (no plan variants: flags is ignored)
 // REC_STAGE_BACKBONE: image -> pooled tokens only (ext[1] = [B][T][C] out).  REC_STAGE_TAIL: the LightSVTR neck + CTC head over
 // the tokens of MANY batches at once (B = text lines, H = longest line in tokens, W = all tokens; ext: 0 tokens, 1 idx,
 // 2 prob, 4 seg int32 [B][2], 5 tokinfo int32 [W]) - see build_ppocrv6_rec
@@ -446,7 +474,7 @@ enum VitFlags : int { VIT_WANT_TAPS = 1 };
 void build_unitable_encoder(Builder& b, int B, int H, int W, int flags);
 // the tensor build_unitable_encoder reads that is not in the file: conv_proj's weight as a [768][768] matrix
 void derive_unitable_encoder_weights(WeightStore& ws);
-void build_pphgnetv2_b4(Builder& b, int B, int H, int W);
+void build_pphgnetv2_b4(Builder& b, int B, int H, int W, int flags);   // (no plan variants: flags is ignored)
 // PP-FormulaNet_plus encoder; flags bit 0: the caller's image has 1 channel (replicated to 3 like the reference)
 void build_pphgnetv2_b6_formula(Builder& b, int B, int H, int W, int flags);
 

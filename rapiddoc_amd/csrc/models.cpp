@@ -131,7 +131,7 @@ static std::vector<TView> lcnetv4(Builder& b, const TView& x_nchw, const std::ve
 // ---------------------------------------------------------------------------------------------------
 // PP-OCRv6 det small.   ext[0] = x NCHW [B,3,H,W];  ext[1] = prob map [B,1,H,W]
 // ---------------------------------------------------------------------------------------------------
-void build_ppocrv6_det(Builder& b, int B, int H, int W) {
+void build_ppocrv6_det(Builder& b, int B, int H, int W, int /*flags*/) {
     RD_CHECK(H % 32 == 0 && W % 32 == 0 && H >= 32 && W >= 32, "det input H, W must be multiples of 32");
     TView x = b.external(0, B, H, W, 3);
     TView out = b.external(1, B, H, W, 1);
@@ -510,7 +510,7 @@ void build_ppocrv5_det_server(Builder& b, int B, int H, int W, int flags) {
     b.release(ff);
 }
 
-void build_pphgnetv2_b4(Builder& b, int B, int H, int W) {
+void build_pphgnetv2_b4(Builder& b, int B, int H, int W, int /*flags*/) {
     RD_CHECK(H % 32 == 0 && W % 32 == 0 && H >= 64 && W >= 64, "backbone input H, W must be multiples of 32 (>= 64)");
     TView x = b.external(0, B, H, W, 3);
     build_pphgnetv2(b, x, kB4Det, "", [&](int si, const TView& v) {
@@ -1276,6 +1276,40 @@ void build_unitable_encoder(Builder& b, int B, int H, int W, int flags) {
     b.release(t);
     b.copy(n, memory);
     b.release(n);
+}
+
+// =================================================================================================
+// The model table: one row per engine kind (ModelDesc, engine.h).  A new kind is a builder above and a row here.
+// =================================================================================================
+const std::vector<ModelDesc>& model_table() {
+    using F = ModelFamily;
+    static const std::vector<ModelDesc::Geom> page = {{1, 64, 64, 0}}, line = {{1, 48, 64, 0}, {1, 48, 64, REC_UNFUSED_CTC}};
+    // kind, family, build, derive, PREPARE geometries, (n_classes, rec_token_dim) tensors, REC_LINE_WIDTHS, DET_WANT_NECK, derived tensors
+    static const std::vector<ModelDesc> table = {
+        {"ppocrv6_det", F::Detector, build_ppocrv6_det, nullptr, page, nullptr, nullptr, false, false, false},
+        {"ppocrv5_det_server", F::Detector, build_ppocrv5_det_server, derive_ppocrv5_det_server_weights, page, nullptr, nullptr, false, true, false},
+        {"ppocrv5_det_mobile", F::Detector, build_ppocrv5_det_mobile, derive_ppocrv5_det_mobile_weights, page, nullptr, nullptr, false, true, true},
+        {"ppocrv3_det_mobile", F::Detector, build_ppocrv3_det_mobile, derive_ppocrv3_det_mobile_weights, page, nullptr, nullptr, false, true, true},
+        {"ppocrv6_rec", F::Recogniser, build_ppocrv6_rec, nullptr, line, "head.head.weight" /* torch.py:112-116 */,
+         "head.encoder.conv_block.0.convolution.weight", true, false, false},
+        {"ppocrv5_rec_server", F::Recogniser, build_ppocrv5_rec_server, nullptr, line, "head.ctc_head.fc.weight",
+         "head.ctc_encoder.encoder.conv1.conv.weight", false, false, false},
+        {"ppocrv5_rec_mobile", F::Recogniser, build_ppocrv5_rec_mobile, derive_ppocrv5_rec_mobile_weights, line, "head.ctc_head.fc.weight",
+         "head.ctc_encoder.encoder.conv1.conv.weight", true, false, false},
+        {"ppocr_rec_mv1e", F::Recogniser, build_ppocr_rec_mv1e, derive_ppocr_rec_mv1e_weights, line, "head.fc.weight", "neck.encoder.conv1.conv.weight", true,
+         false, false},
+        {"ppocr_cls_mobile", F::Classifier, build_ppocr_cls_mobile, derive_ppocr_cls_mobile_weights, {{1, 48, 192, 0}}, nullptr, nullptr, false, false, false},
+        {"unitable_encoder", F::TableEncoder, build_unitable_encoder, derive_unitable_encoder_weights, {{1, 16, 16, 0}}, nullptr, nullptr, false, false, false},
+        {"pphgnetv2_b4", F::Backbone, build_pphgnetv2_b4, nullptr, page, nullptr, nullptr, false, false, false},
+        {"pphgnetv2_b6_formula", F::FormulaEncoder, build_pphgnetv2_b6_formula, nullptr, page, nullptr, nullptr, false, false, false},
+    };
+    return table;
+}
+
+const ModelDesc* find_model(const std::string& kind) {
+    for (const ModelDesc& m : model_table())
+        if (kind == m.kind) return &m;
+    return nullptr;
 }
 
 }  // namespace rd

@@ -152,7 +152,7 @@ def _hswish64(t):
 
 
 def _debug_dw(x, w, b, K, S, pre_act, post_act, aff, route):
-    """One layer through rd_debug_lcv3_dw_det (api.cpp).  route 0: lcv3_dw_kernel, 1: lcv3_dw2d_kernel.  The output buffer is prefilled
+    """One layer through rd_debug_lcv3_dw_det (api_debug.cpp).  route 0: lcv3_dw_kernel, 1: lcv3_dw2d_kernel.  The output buffer is prefilled
     with NaN and followed by a guard band that must come back untouched."""
     from rapiddoc_amd import _lib
     lib = _lib.load()

@@ -92,7 +92,7 @@ def test_an_image_does_not_depend_on_the_launch_it_rides_in(golden_dir, precisio
 
 # ---------------------------------------------------------------------------------------------------------------- the 9x9 kernel alone
 def _debug_conv9(x_nhwc, w_oihw, bias, act, res, route):
-    """One 9x9 / pad 4 convolution through rd_debug_conv (api.cpp): route 4 forces the direct kernel (kernels_conv9x9_h1.hip), 0 leaves the
+    """One 9x9 / pad 4 convolution through rd_debug_conv (api_debug.cpp): route 4 forces the direct kernel (kernels_conv9x9_h1.hip), 0 leaves the
     layer on the generic k x k split implicit GEMM.  Returns (y NHWC, the route the call reports)."""
     from rapiddoc_amd import _lib
     lib = _lib.load()

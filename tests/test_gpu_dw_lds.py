@@ -1,5 +1,5 @@
 """The LDS-DMA-staged depthwise 3x3 (kernels_dw_lds.hip; reference rec_lcnetv4.py:187-206) against torch's fp64 grouped conv,
-through the library's own launcher (api.cpp rd_debug_dwconv): every instantiation, strips that end inside a tile, one-column maps,
+through the library's own launcher (api_debug.cpp rd_debug_dwconv): every instantiation, strips that end inside a tile, one-column maps,
 per-line widths, the residual and activation epilogue and the fused squeeze-excite partial sums."""
 import ctypes as C
 

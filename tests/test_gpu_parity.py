@@ -604,7 +604,7 @@ def test_pipeline_two_stage_rec_gives_the_single_stage_results(engines, golden_d
 
 
 def _debug_conv(x_nhwc, w_oihw, bias, stride, pads, act=0, res=None, split=True, iters=0, force_direct=False, force_stream=False):
-    """One convolution through the library's dense-conv launcher on prepared operands (api.cpp rd_debug_conv)."""
+    """One convolution through the library's dense-conv launcher on prepared operands (api_debug.cpp rd_debug_conv)."""
     import ctypes as C
     from rapiddoc_amd import _lib
     lib = _lib.load()

@@ -8,7 +8,7 @@ classifies, and stays as it is).
      process: `--warmup` untimed rounds, then `--steps` timed ones of `iters` forwards each between two HIP events (the replayed hipGraph
      of the plan, as the pipeline runs it).  Per route the median ms per forward and the spread (max - min) / median of THAT route;
      `fused wins` = its median lies below the unfused one by more than the larger of the two spreads - the rule that sets
-     cls_fused_default (csrc/engine.cpp).  Then the per-op-kind table of one profiled unfused launch (HIP events around every op, launch
+     cls_fused_default (csrc/builder_mobile.cpp).  Then the per-op-kind table of one profiled unfused launch (HIP events around every op, launch
      gaps included: the launch-chain share of the route), and the plans' workspace sizes.
   2. --pipeline: PagePipeline on 32 synthetic pages (1440 lines), use_cls=True against use_cls=False built in the same process, steps
      alternating; median ms per step of either and the added ms per step.

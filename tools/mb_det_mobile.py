@@ -9,7 +9,7 @@
      kernel (csrc/kernels_lcv3_det.hip): same operands, same run, the routes alternating (rd_debug_lcv3_dw_det, iters > 0, `reps`
      repeats per route).  Per route the median, the repeat spread (max - min) / median of THAT route, GB/s on algorithmic bytes (input
      read once + output written once).  `staged wins` = the staged median is below the direct median by more than the larger of the two
-     spreads: the rule that sets lcv3_dw2d_default (csrc/engine.cpp).
+     spreads: the rule that sets lcv3_dw2d_default (csrc/builder_mobile.cpp).
 
     python tools/mb_det_mobile.py [--steps 7] [--warmup 3] [--pages 32] > profiles/mb_det_mobile.txt
 """

@@ -9,7 +9,7 @@
      alternating).  Per block: unfused = the sum of its expand, depthwise and linear ops (block 0: plus the hardswish pass over conv1's
      output that the fused kernel applies on load), fused = its one op.  Per route the median, the spread (max - min) / median of THAT
      route, and GB/s counted on the block's input read once plus its output written once.  `fused wins` = the fused median lies below
-     the unfused one by more than the larger of the two spreads: the rule that sets mbv3_fused_default (csrc/engine.cpp).  Per-op HIP
+     the unfused one by more than the larger of the two spreads: the rule that sets mbv3_fused_default (csrc/builder_mobile.cpp).  Per-op HIP
      events include the launch gap of every op, which the unfused route pays three times: that is part of what a forward pays, too.
      Then the whole forward under either setting, alternating; and the hardswish depthwise layers with C % 16 == 0 alone at their real
      shapes on mbv3_dw_kernel and on the LDS-staged lcv3_dw2d_kernel (csrc/kernels_lcv3_det.hip), alternating, by the same rule: the

@@ -36,7 +36,7 @@ def mixer(C_, M, variant, iters=20, check=False):
 
 
 def ctc(M, Ccls=18385, K=120, nsplit=0, iters=20, split=True):
-    """Fused CTC head in isolation (weights prepared here the way engine.cpp does: bias in column K, hi/lo fp16 split)."""
+    """Fused CTC head in isolation (weights prepared here the way Builder::ctc_head (csrc/builder.cpp) does: bias in column K, hi/lo fp16 split)."""
     lib.rd_debug_time_ctc.restype = C.c_float
     lib.rd_debug_time_ctc.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
     g = torch.Generator(device="cuda").manual_seed(0)
