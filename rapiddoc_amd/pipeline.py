@@ -19,7 +19,9 @@ import numpy as np
 import torch
 
 from . import _lib, ocr_host
-from .engine import RdEngine, pad_tail_lengths, rec_line_table, preproc_resize_norm, preproc_resize_norm_batch
+from .engine import RdEngine, preproc_resize_norm, preproc_resize_norm_batch
+from .rec_plan import (CLS_IMG_H, CLS_IMG_W, LINE_DTYPE, RecPlan, plan_rec,     # noqa: F401  (the crop helpers are imported from here)
+                       quad_to_crop_matrix, quads_to_crop_matrices)
 
 LAYOUT_SIZE = 800          # PP-DocLayout-L/plus-L/V2/V3 input (pp_doclayout/main.py:17-29)
 DET_LIMIT = 960            # rapidocr Det.limit_side_len (rapid_ocr.py:517-518)
@@ -28,9 +30,6 @@ DET_LIMIT = 960            # rapidocr Det.limit_side_len (rapid_ocr.py:517-518)
 class CropDesc(C.Structure):
     _fields_ = [("page", C.c_int32), ("out_w", C.c_int32), ("crop_w", C.c_float), ("crop_h", C.c_float),
                 ("m", C.c_float * 9), ("rot90", C.c_int32), ("pad_", C.c_int32)]
-
-
-CLS_IMG_H, CLS_IMG_W = 48, 192       # the text-line classifier's input (PaddleOCR cls_image_shape "3, 48, 192")
 
 
 def cls_flip_rule(prob: np.ndarray, thresh: float) -> np.ndarray:
@@ -48,72 +47,6 @@ def flip180(crop: np.ndarray) -> np.ndarray:
 CROP_DTYPE = np.dtype([("page", "<i4"), ("out_w", "<i4"), ("crop_w", "<f4"), ("crop_h", "<f4"), ("m", "<f4", (9,)),
                        ("rot90", "<i4"), ("pad_", "<i4")])
 assert CROP_DTYPE.itemsize == C.sizeof(CropDesc)
-# rd_line_crop_desc (include/rapiddoc_mi355.h): the reference-shaped two-stage crop (cubic warp to the integer-sized uint8
-# crop, rotation of tall crops, linear resize to height 48), homography in float64 like cv2's
-LINE_DTYPE = np.dtype([("page", "<i4"), ("out_w", "<i4"), ("crop_w", "<i4"), ("crop_h", "<i4"), ("rot90", "<i4"),
-                       ("scratch_off", "<i4"), ("m", "<f8", (9,))])
-assert LINE_DTYPE.itemsize == 96
-
-
-def quad_to_crop_matrix(quad: np.ndarray) -> Tuple[np.ndarray, float, float]:
-    """Inverse of the reference's perspective rectification (utils/ocr_utils.py:494-536): returns the 3x3 matrix
-    that maps rectified-crop pixel (x, y, 1) to page coordinates plus the crop size.  `quad`: 4x2 points
-    (tl, tr, br, bl)."""
-    q = np.asarray(quad, dtype=np.float64).reshape(4, 2)
-    cw = max(np.linalg.norm(q[0] - q[1]), np.linalg.norm(q[2] - q[3]))
-    ch = max(np.linalg.norm(q[0] - q[3]), np.linalg.norm(q[1] - q[2]))
-    cw, ch = float(int(cw)), float(int(ch))  # ocr_utils.py:508-519 casts to int
-    cw, ch = max(cw, 1.0), max(ch, 1.0)
-    src = np.array([[0, 0], [cw, 0], [cw, ch], [0, ch]], dtype=np.float64)
-    # solve the homography src -> q (8 unknowns)
-    A, b = [], []
-    for (x, y), (u, v) in zip(src, q):
-        A.append([x, y, 1, 0, 0, 0, -u * x, -u * y]); b.append(u)
-        A.append([0, 0, 0, x, y, 1, -v * x, -v * y]); b.append(v)
-    h = np.linalg.solve(np.asarray(A), np.asarray(b))
-    return np.append(h, 1.0).astype(np.float32), cw, ch
-
-
-def quads_to_crop_matrices(quads: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
-    """Vectorised `quad_to_crop_matrix` for [n,4,2] quads -> ([n,9] float64, crop widths, crop heights, ok mask).
-    Crop size as `get_rotate_crop_image` computes it (utils/ocr_utils.py:508-519): `int(max(np.linalg.norm(p0 - p1),
-    np.linalg.norm(p2 - p3)))` on FLOAT32 points - float32 subtraction, float32 norm (sqrt of the float32 sum of the two
-    float32 squares), truncation - so an edge whose length is within float32 rounding of an integer gets the crop size
-    the reference gives it.  `ok` is False for quads no homography exists for (zero-size crop, collinear corners): the
-    reference's cv2.warpPerspective raises on them; callers here skip them."""
-    q32 = np.asarray(quads, dtype=np.float32).reshape(-1, 4, 2)
-    q = q32.astype(np.float64)
-    n = len(q)
-
-    def norm32(a, b):
-        d = a - b                                               # float32
-        return np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])   # float32 throughout, like np.linalg.norm on a float32 vector
-    cw = np.maximum(norm32(q32[:, 0], q32[:, 1]), norm32(q32[:, 2], q32[:, 3])).astype(np.float64)
-    ch = np.maximum(norm32(q32[:, 0], q32[:, 3]), norm32(q32[:, 1], q32[:, 2])).astype(np.float64)
-    cw, ch = np.floor(cw), np.floor(ch)
-    ok = (cw >= 1.0) & (ch >= 1.0) & np.isfinite(cw) & np.isfinite(ch)
-    cw, ch = np.where(ok, cw, 1.0), np.where(ok, ch, 1.0)
-    z = np.zeros(n)
-    src = np.stack([np.stack([z, z], 1), np.stack([cw, z], 1), np.stack([cw, ch], 1), np.stack([z, ch], 1)], axis=1)  # [n,4,2]
-    A = np.zeros((n, 8, 8))
-    b = np.zeros((n, 8))
-    x, y, u, v = src[..., 0], src[..., 1], q[..., 0], q[..., 1]
-    A[:, 0::2, 0], A[:, 0::2, 1], A[:, 0::2, 2] = x, y, 1.0
-    A[:, 0::2, 6], A[:, 0::2, 7] = -u * x, -u * y
-    A[:, 1::2, 3], A[:, 1::2, 4], A[:, 1::2, 5] = x, y, 1.0
-    A[:, 1::2, 6], A[:, 1::2, 7] = -v * x, -v * y
-    b[:, 0::2], b[:, 1::2] = u, v
-    # a singular system (three collinear corners, repeated points) must not abort the whole page batch
-    # scale-aware test: a homography of the crop rectangle exists iff no three corners of the quad are collinear - every corner
-    # triangle must have an area that is not vanishing next to the crop's (an absolute bound on det(A), whose entries reach
-    # coordinate^2, lets near-collinear quads through)
-    with np.errstate(all="ignore"):
-        for i, j, k in ((0, 1, 2), (1, 2, 3), (2, 3, 0), (3, 0, 1)):
-            cross = (q[:, j, 0] - q[:, i, 0]) * (q[:, k, 1] - q[:, i, 1]) - (q[:, j, 1] - q[:, i, 1]) * (q[:, k, 0] - q[:, i, 0])
-            ok &= np.isfinite(cross) & (np.abs(cross) > 1e-6 * cw * ch)
-    A[~ok] = np.eye(8)
-    h = np.linalg.solve(A, b[..., None])[..., 0]
-    return np.concatenate([h, np.ones((n, 1))], axis=1), cw, ch, ok
 
 
 def boxes_to_quads(boxes_xyxy: np.ndarray) -> np.ndarray:
@@ -128,6 +61,21 @@ class PageResult:
     # PagePipeline(use_cls=True): per line (turned by 180 degrees before recognition?, the classifier's label 0 / 1, that label's
     # probability) - rapidocr's ClsPostProcess pair plus the decision of its threshold rule; None when the stage is off
     cls: Optional[List[Tuple[bool, int, float]]] = None
+
+
+@dataclass(slots=True)
+class _RecLaunch:
+    """One launch of the recogniser stage, filled as its work is enqueued.  With the two-stage recogniser in lines mode the tail call of
+    a group of launches has ONE set of products: they sit on the group's last launch (`rows`, `cols`; `idx`, `prob` when tests keep them)."""
+    x: Optional[torch.Tensor] = None                # the input tensor (a clone under keep_rec_inputs: the buffer is reused)
+    event: Optional[torch.cuda.Event] = None        # its backbone (or whole network) is done: what the tail and the prefetch wait for
+    done: Optional[torch.cuda.Event] = None         # its rows are home
+    idx: Optional[torch.Tensor] = None
+    prob: Optional[torch.Tensor] = None
+    rows: Optional[torch.Tensor] = None             # pinned CTC rows (None: device_ctc off)
+    cols: Optional[Tuple[torch.Tensor, torch.Tensor]] = None    # want_words: pinned kept columns and their probabilities
+    cls_prob: Optional[torch.Tensor] = None         # use_cls: pinned softmax and turn decisions of its lines
+    cls_flip: Optional[torch.Tensor] = None
 
 
 class PagePipeline:
@@ -340,23 +288,31 @@ class PagePipeline:
         self._width_sync_cache = (sig, res)
         return res
 
+    def _collapse_home(self, name: str, n: int, T: int, call, *extra: torch.Tensor) -> List[torch.Tensor]:
+        """What both device CTC collapses share, on the current stream: the row buffer for `n` lines of at most `T` time steps,
+        `call(rows pointer, row_bytes)` = the library call, then the rows (and the `extra` device tensors it filled) copied into pinned
+        memory; returns the pinned tensors."""
+        row_bytes = (16 + T * self._ctc_max_len + 15) // 16 * 16
+        rows = torch.empty((n, row_bytes), dtype=torch.uint8, device=self.tdev)
+        if call(rows.data_ptr(), row_bytes) != 0:
+            raise RuntimeError(f"{name} failed")
+        home = []
+        for t in (rows,) + extra:
+            h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            h.copy_(t, non_blocking=True)
+            home.append(h)
+        return home
+
     def _collapse_rows(self, idx: torch.Tensor, prob: torch.Tensor, nb: int, st, record: bool = True):
         """Device CTC collapse of one batch's (idx, prob) [nb, T] on stream `st` + the D2H of its rows into pinned memory;
         returns (rows or None, event recorded after it or None)."""
-        rows = None
+        rows = done = None
         with torch.cuda.stream(st):
             if self.device_ctc:
                 T = idx.shape[1]
-                row_bytes = (16 + T * self._ctc_max_len + 15) // 16 * 16
-                rows = torch.empty((nb, row_bytes), dtype=torch.uint8, device=idx.device)
-                rc = self._lib.rd_ctc_collapse(self.device, idx.data_ptr(), prob.data_ptr(), nb, T, self._ctc_table.data_ptr(),
-                                               self._ctc_max_len, len(self.characters), rows.data_ptr(), row_bytes, st.cuda_stream)
-                if rc != 0:
-                    raise RuntimeError("rd_ctc_collapse failed")
-                rows_h = torch.empty((nb, row_bytes), dtype=torch.uint8, pin_memory=True)
-                rows_h.copy_(rows, non_blocking=True)
-                rows = rows_h
-            done = None
+                rows, = self._collapse_home("rd_ctc_collapse", nb, T, lambda out, row_bytes: self._lib.rd_ctc_collapse(
+                    self.device, idx.data_ptr(), prob.data_ptr(), nb, T, self._ctc_table.data_ptr(), self._ctc_max_len, len(self.characters),
+                    out, row_bytes, st.cuda_stream))
             if record:
                 done = torch.cuda.Event()
                 done.record(st)
@@ -365,246 +321,106 @@ class PagePipeline:
     def _collapse_lines(self, idx_all: torch.Tensor, prob_all: torch.Tensor, tables: torch.Tensor, n_lines: int, max_tokens: int, st,
                         want_cols: bool = False):
         """Device CTC collapse of the RAGGED lines of one tail call (`tables` = its seg / tokinfo tensor; the first `n_lines` are the
-        real ones) on stream `st` + the D2H of the rows into pinned memory; returns (rows, event) or (rows, event, kept columns)."""
+        real ones) on stream `st` + the D2H of the rows into pinned memory; returns (rows, event, kept columns or None)."""
         with torch.cuda.stream(st):
-            row_bytes = (16 + max_tokens * self._ctc_max_len + 15) // 16 * 16
-            rows = torch.empty((n_lines, row_bytes), dtype=torch.uint8, device=idx_all.device)
-            cols = torch.empty((n_lines, max_tokens), dtype=torch.int16, device=idx_all.device) if want_cols else None
-            confs = torch.empty((n_lines, max_tokens), dtype=torch.float32, device=idx_all.device) if want_cols else None
-            rc = self._lib.rd_ctc_collapse_lines(self.device, idx_all.data_ptr(), prob_all.data_ptr(), n_lines, tables.data_ptr(), max_tokens,
-                                                 self._ctc_table.data_ptr(), self._ctc_max_len, len(self.characters), rows.data_ptr(),
-                                                 row_bytes, cols.data_ptr() if want_cols else None, confs.data_ptr() if want_cols else None,
-                                                 st.cuda_stream)
-            if rc != 0:
-                raise RuntimeError("rd_ctc_collapse_lines failed")
-            rows_h = torch.empty((n_lines, row_bytes), dtype=torch.uint8, pin_memory=True)
-            rows_h.copy_(rows, non_blocking=True)
-            cols_h = None
-            if want_cols:
-                cols_h = (torch.empty((n_lines, max_tokens), dtype=torch.int16, pin_memory=True),
-                          torch.empty((n_lines, max_tokens), dtype=torch.float32, pin_memory=True))
-                cols_h[0].copy_(cols, non_blocking=True)
-                cols_h[1].copy_(confs, non_blocking=True)
+            cols = torch.empty((n_lines, max_tokens), dtype=torch.int16, device=self.tdev) if want_cols else None
+            confs = torch.empty((n_lines, max_tokens), dtype=torch.float32, device=self.tdev) if want_cols else None
+            rows, *cols_h = self._collapse_home("rd_ctc_collapse_lines", n_lines, max_tokens, lambda out, row_bytes: self._lib.rd_ctc_collapse_lines(
+                self.device, idx_all.data_ptr(), prob_all.data_ptr(), n_lines, tables.data_ptr(), max_tokens, self._ctc_table.data_ptr(),
+                self._ctc_max_len, len(self.characters), out, row_bytes, cols.data_ptr() if want_cols else None,
+                confs.data_ptr() if want_cols else None, st.cuda_stream), *((cols, confs) if want_cols else ()))
             done = torch.cuda.Event()
             done.record(st)
-        return (rows_h, done, cols_h) if want_cols else (rows_h, done)
+        return rows, done, tuple(cols_h) if want_cols else None
 
     def _rec_forward_sources_once(self, sources, image_keys=None, want_words=False):
+        """One pass of the recogniser stage: plan (host arithmetic, rec_plan.plan_rec), enqueue, decode, scatter."""
         t0 = time.perf_counter()
         if self.use_cls and want_words:
             raise ValueError("use_cls together with want_words: rapidocr defines no word-box mapping for lines turned by 180 degrees")
         self.last_cls = None
-        if not sources:                 # nothing to read on this rank: it still takes part in the batch's width exchange
-            if self.rec_width_sync is not None and self.rec_mode == "strict" and self.rec_two_stage and self._sync_this_call:
-                self._synced_widths(self.rec_width_sync, np.zeros(0, np.int64), np.zeros(0))
-            return []
-        dev = sources[0][0].device
-        # flat line list in source-major, image-major order (the reference's pooled order: pages, then a page's spans)
-        src_of, page_of, quad_list, n_img = [], [], [], []
-        for si, (imgs, quads_per_img) in enumerate(sources):
+        for imgs, _quads in sources:
             assert imgs.is_cuda and imgs.dtype == torch.uint8 and imgs.dim() == 4 and imgs.is_contiguous()
-            n_img.append(imgs.shape[0])
-            for pi, q in enumerate(quads_per_img):
-                q = np.asarray(q, dtype=np.float64).reshape(-1, 4, 2)
-                if len(q):
-                    quad_list.append(q)
-                    src_of.append(np.full(len(q), si, np.int32))
-                    page_of.append(np.full(len(q), pi, np.int32))
-        empty = [[[] for _ in range(k)] for k in n_img]
-        sync = self.rec_width_sync if (self.rec_mode == "strict" and self.rec_two_stage and self._sync_this_call) else None
-        if not quad_list:
-            if sync is not None:
-                self._synced_widths(sync, np.zeros(0, np.int64), np.zeros(0))       # every rank makes the same calls
-            return empty
-        quads = np.concatenate(quad_list, axis=0)
-        src_of, page_of = np.concatenate(src_of), np.concatenate(page_of)
-        if image_keys is not None:      # pooled order: by key (page), then source / image / line as collected
-            key = np.array([image_keys[si][pi] for si, pi in zip(src_of.tolist(), page_of.tolist())], dtype=np.int64)
-            perm = np.argsort(key, kind="stable")
-            quads, src_of, page_of, key = quads[perm], src_of[perm], page_of[perm], key[perm]
-        else:
-            perm = None
-        mats, cws_a, chs_a, ok = quads_to_crop_matrices(quads)
-        n_all = len(quads)
-        keep = np.nonzero(ok)[0]                      # degenerate quads (zero-area / collinear corners) get ("", 0.0)
-        n = len(keep)
-        texts: List[tuple] = [("", 0.0, None) if want_words else ("", 0.0)] * n_all
-        cls_of: List[tuple] = [(False, 0, 0.0)] * n_all if self.use_cls else []
-        if n == 0:
-            if sync is not None:
-                self._synced_widths(sync, np.zeros(0, np.int64), np.zeros(0))
-            if self.use_cls:
-                self.last_cls = self._scatter_texts(cls_of, src_of, page_of, n_img, perm)
-            return self._scatter_texts(texts, src_of, page_of, n_img, perm)
-        mats, cws_a, chs_a = mats[keep], cws_a[keep], chs_a[keep]
-        rots_a = (chs_a / cws_a >= 2.0).astype(np.int32)  # ocr_utils.py:531-534 rotates crops with h/w >= 2
-        eff_w = np.where(rots_a == 1, chs_a, cws_a)
-        eff_h = np.where(rots_a == 1, cws_a, chs_a)
-        ratios = (eff_w / eff_h).tolist()
         strict = self.rec_mode == "strict"
-        two_stage = self.rec_two_stage
-        lines_mode = strict and two_stage          # reference widths per LINE inside GPU-sized launches
-        if want_words and not lines_mode:
-            raise RuntimeError("word boxes need the strict two-stage recogniser (rec_mode='strict', RD_REC_TWO_STAGE unset)")
-        if lines_mode:
-            given = None
-            if sync is not None:        # the widths come from the pooled lines of every rank; key = the image key (global page index)
-                line_keys = key[keep] if image_keys is not None else page_of[keep].astype(np.int64)
-                given = self._synced_widths(sync, line_keys, np.asarray(ratios, dtype=np.float64))
-            batches, line_w, line_ratio = ocr_host.rec_batches_lines(ratios, n_cu=self.n_cu, with_ratio=True, given=given, native=self.host_native)
-            if not self.rec_lines_in_launch:
-                # same lines, same order, same reference width per line - but a launch holds lines of ONE width (a line's result depends
-                # on its pixels and its padded width only, so the launch boundaries do not enter the result)
-                batches = ocr_host.rec_batches_equal_width(np.concatenate([c for c, _w in batches]), line_w)
-        elif not strict and self.rec_chunking == "adaptive":
-            batches = ocr_host.rec_batches_adaptive(ratios, width_multiple=self.rec_width_multiple, n_cu=self.n_cu)
-        else:
-            batches = ocr_host.rec_batches(ratios, self.rec_batch_num, width_multiple=self.rec_width_multiple, strict=strict,
-                                           merge_equal_width=strict)
-        order_all = np.concatenate([c for c, _ in batches])
-        wpad_all = np.concatenate([np.full(len(c), w) for c, w in batches])
-        if not lines_mode:
-            line_w = wpad_all                           # every line of a launch is as wide as the launch
-        descs = np.zeros(n, dtype=LINE_DTYPE)
-        descs["page"] = page_of[keep][order_all]
-        descs["out_w"] = np.minimum(line_w, np.ceil(ocr_host.REC_IMG_H * (eff_w / eff_h)[order_all])).astype(np.int32)
-        descs["crop_w"] = cws_a[order_all].astype(np.int32)
-        descs["crop_h"] = chs_a[order_all].astype(np.int32)
-        descs["m"] = mats[order_all]
-        descs["rot90"] = rots_a[order_all]
-        # packed uint8 scratch of the rectified crops, one region per rec batch (batches run on different streams)
-        crop_bytes = (descs["crop_w"].astype(np.int64) * descs["crop_h"] * 3 + 15) // 16 * 16
-        batch_lens = [len(c) for c, _ in batches]
-        starts = np.cumsum([0] + batch_lens)
-        offs = np.zeros(n, np.int64)
-        batch_scratch = []
-        for b in range(len(batches)):
-            cb = crop_bytes[starts[b]:starts[b + 1]]
-            offs[starts[b]:starts[b + 1]] = np.cumsum(cb) - cb
-            batch_scratch.append(int(cb.sum()))
-        if max(batch_scratch) >= 2 ** 31:
-            raise RuntimeError("a rec batch needs >= 2 GB of crop scratch: lower rec_batch_num")
-        descs["scratch_off"] = offs.astype(np.int32)
-        batch_base = np.cumsum([0] + batch_scratch)
-        if getattr(self, "_crop_scratch", None) is None or self._crop_scratch.numel() < int(batch_base[-1]):
-            self._crop_scratch = torch.empty(int(batch_base[-1] * 1.25) + 1024, dtype=torch.uint8, device=dev)
-        # stage-1 (warp) launches: per rec batch, one per source image array present in it.  A single source (the page
-        # pipeline) needs no second descriptor array: the batch's own descriptors are the launch's.
-        multi = len(sources) > 1
-        src_sorted = src_of[keep][order_all]
-        crop_px = descs["crop_w"].astype(np.int64) * descs["crop_h"]
-        warp_jobs: List[List[Tuple[int, int, int, int]]] = []        # per batch: (source, first desc, count, max crop pixels)
-        if multi:
-            warp_order = np.concatenate([starts[b] + np.argsort(src_sorted[starts[b]:starts[b + 1]], kind="stable")
-                                         for b in range(len(batches))])
-            descs_warp = descs[warp_order]
-            ws_sorted = src_sorted[warp_order]
-            px_sorted = crop_px[warp_order]
-            for b in range(len(batches)):
-                jobs, lo = [], int(starts[b])
-                hi = int(starts[b + 1])
-                cuts = [lo] + [i for i in range(lo + 1, hi) if ws_sorted[i] != ws_sorted[i - 1]] + [hi]
-                for a, e in zip(cuts[:-1], cuts[1:]):
-                    jobs.append((int(ws_sorted[a]), a, e - a, int(px_sorted[a:e].max())))
-                warp_jobs.append(jobs)
-        else:
-            for b in range(len(batches)):
-                lo, hi = int(starts[b]), int(starts[b + 1])
-                warp_jobs.append([(0, lo, hi - lo, int(crop_px[lo:hi].max()))])
-        if self.use_cls:
-            # the classifier's pre-process: the same crops, resized to 48 x min(192, ceil(48 w / h)) and zero-padded to 192 columns
-            descs_cls = descs.copy()
-            descs_cls["out_w"] = np.minimum(CLS_IMG_W, np.ceil(CLS_IMG_H * (eff_w / eff_h)[order_all])).astype(np.int32)
+        sync = None         # the width collective: a pooled call of the strict two-stage mode of a page-sharded run
+        if self.rec_width_sync is not None and strict and self.rec_two_stage and self._sync_this_call:
+            sync = lambda keys, ratios: self._synced_widths(self.rec_width_sync, keys, ratios)      # noqa: E731
+        plan = plan_rec([(imgs.shape[0], quads) for imgs, quads in sources], image_keys, strict=strict, two_stage=self.rec_two_stage,
+                        lines_in_launch=self.rec_lines_in_launch, chunking=self.rec_chunking, rec_batch_num=self.rec_batch_num,
+                        rec_width_multiple=self.rec_width_multiple, n_cu=self.n_cu, n_streams=len(self.rec_engines), use_cls=self.use_cls,
+                        host_native=self.host_native, want_words=want_words, width_sync=sync)
+        scatter = lambda per_line: self._scatter_texts(per_line, plan.src_of, plan.page_of, plan.n_img, plan.perm)      # noqa: E731
+        cls_of: List[tuple] = [(False, 0, 0.0)] * plan.n_all
+        if plan.n == 0:                 # nothing to recognise: degenerate quads get ("", 0.0)
+            if self.use_cls and plan.n_all:
+                self.last_cls = scatter(cls_of)
+            return scatter([("", 0.0, None) if want_words else ("", 0.0)] * plan.n_all)
+        if getattr(self, "_crop_scratch", None) is None or self._crop_scratch.numel() < plan.scratch_bytes:
+            self._crop_scratch = torch.empty(int(plan.scratch_bytes * 1.25) + 1024, dtype=torch.uint8, device=sources[0][0].device)
         self.stats["t_descs_ms"] = (time.perf_counter() - t0) * 1e3
-        descs_dev = torch.from_numpy(descs.view(np.uint8)).to(dev, non_blocking=True)
-        if self.use_cls:
-            descs_cls_dev = torch.from_numpy(descs_cls.view(np.uint8)).to(dev, non_blocking=True)
-            cls_prob = self._buf("cls_prob", 2 * n).view(n, 2)
-            cls_flip = self._buf("cls_flip", n, torch.int32)
-            cls_prob_h = torch.empty((n, 2), dtype=torch.float32, pin_memory=True)
-            cls_flip_h = torch.empty((n,), dtype=torch.int32, pin_memory=True)
-        descs_warp_dev = torch.from_numpy(descs_warp.view(np.uint8)).to(dev, non_blocking=True) if multi else descs_dev
-        if self.keep_rec_inputs:          # tests: the descriptors in launch order, every batch's scratch base and first line; the classifier's inputs
-            self.last_rec_descs = (descs.copy(), np.asarray(batch_base, dtype=np.int64), np.asarray(starts, dtype=np.int64))
+        main = torch.cuda.current_stream()
+        launches = self._enqueue_rec(plan, sources, want_words)
+        self.stats["t_rec_enqueue_ms"] = (time.perf_counter() - t0) * 1e3 - self.stats["t_descs_ms"]
+        hook, self._after_rec_enqueue = self._after_rec_enqueue, None
+        if hook is not None:
+            t_h = time.perf_counter()
+            S, nb = len(self.rec_engines), len(launches)
+            m = max(1, min(nb, int(np.ceil(self.prefetch_gate * nb))))
+            hook([l.event for l in launches[max(0, m - S): m]])   # streams run their launches in order: the last S up to m cover all before them
+            self.stats["t_front_next_ms"] = (time.perf_counter() - t_h) * 1e3
+        texts = self._decode_rec(plan, launches, want_words)
+        for st in self.rec_streams + [self.tail_stream]:
+            main.wait_stream(st)
+        self.stats["rec_lines"] = plan.n
+        self.stats["rec_batches"] = len(launches)
+        self.last_pool_order = plan.perm
+        if self.use_cls:       # (every batch's `done` has been waited for above: the copies enqueued in front of its recogniser are complete)
+            ph = np.concatenate([l.cls_prob.numpy() for l in launches])
+            fh = np.concatenate([l.cls_flip.numpy() for l in launches])
+            for j, i in enumerate(plan.line_ids.tolist()):
+                label = int(ph[j, 1] > ph[j, 0])
+                cls_of[i] = (bool(fh[j]), label, float(ph[j, label]))
+            self.last_cls = scatter(cls_of)
+            self.last_cls_prob = (plan.line_ids, ph)      # tests: pooled line ids and the raw probabilities
+        return scatter(texts)
+
+    def _enqueue_rec(self, plan: RecPlan, sources, want_words: bool) -> List[_RecLaunch]:
+        """Everything the stage puts on the GPU, in launch order: the descriptor uploads, then per launch `bi` on stream `bi % S` the warp
+        jobs, the optional classifier, the recogniser's resize and its forward; with the two-stage recogniser `_enqueue_tail(g)` directly
+        after the last launch of group g."""
+        dev, S, lib = sources[0][0].device, len(self.rec_engines), self._lib
+        keep_inputs = self.keep_rec_inputs
+        upload = lambda descs: torch.from_numpy(descs.view(np.uint8)).to(dev, non_blocking=True)      # noqa: E731
+        descs_dev = upload(plan.descs)
+        cls = None
+        if self.use_cls:     # (descriptors, device probabilities and flips, their pinned copies)
+            cls = (upload(plan.descs_cls), self._buf("cls_prob", 2 * plan.n).view(plan.n, 2), self._buf("cls_flip", plan.n, torch.int32),
+                   torch.empty((plan.n, 2), dtype=torch.float32, pin_memory=True), torch.empty((plan.n,), dtype=torch.int32, pin_memory=True))
+        descs_warp_dev = upload(plan.descs_warp) if plan.descs_warp is not None else descs_dev
+        if keep_inputs:          # tests: the descriptors in launch order, every batch's scratch base and first line; the classifier's inputs
+            self.last_rec_descs = (plan.descs.copy(), np.asarray(plan.batch_base, dtype=np.int64), np.asarray(plan.starts, dtype=np.int64))
             self.last_cls_inputs = []
-        outs = []
-        pos = 0
         main = torch.cuda.current_stream()
         ready = torch.cuda.Event()
         ready.record(main)
-        S = len(self.rec_engines)
-        if two_stage:
-            # the batches run the backbone only, each into its slice of one token buffer; the neck + CTC head then run once per
-            # GROUP of S consecutive batches (one per stream) on the tail stream, under the backbones of the next group
-            w2_ = (np.asarray(line_w, dtype=np.int64) - 1) // 2 + 1
-            seq_line = ((w2_ - 1) // 2 + 1) // 2                  # tokens per line (rd_rec_seq_len of its padded width)
-            groups = [list(range(g, min(g + S, len(batches)))) for g in range(0, len(batches), S)]
-            group_lens = [seq_line[int(starts[grp[0]]): int(starts[grp[-1] + 1])] for grp in groups]
-            # every group's tail call is padded with dummy lines onto a coarse (lines, longest line, tokens) grid: the plan cache
-            # of the tail handle then sees a handful of keys instead of a new one per group (engine.pad_tail_lengths)
-            group_pad = [pad_tail_lengths(l) for l in group_lens]
-            group_base = np.cumsum([0] + [int(lp.sum()) for lp, _t in group_pad])
-            first_tok = np.zeros(n, np.int64)                      # first token of every line in the token buffer
-            for gi, grp in enumerate(groups):
-                lo, hi = int(starts[grp[0]]), int(starts[grp[-1] + 1])
-                first_tok[lo:hi] = int(group_base[gi]) + np.cumsum(seq_line[lo:hi]) - seq_line[lo:hi]
-            tok_lo = [int(first_tok[int(starts[bi])]) for bi in range(len(batches))]
-            dim = self.rec.rec_token_dim
-            tokens = self._buf("rec_tokens", int(group_base[-1]) * dim).view(int(group_base[-1]), dim)
-            for gi in range(len(groups)):         # the dummy lines' tokens: finite values (their outputs are ignored)
-                tokens[int(group_base[gi]) + int(group_lens[gi].sum()): int(group_base[gi + 1])].zero_()
-            group_tables = [self.rec_tail.rec_tail_tables(lp, dev, out=self._buf(("tail_tab", gi), 2 * len(lp) + int(lp.sum()), torch.int32))
-                            for gi, (lp, _t) in enumerate(group_pad)]   # uploaded now, used later
-            if lines_mode and self.rec_lines_in_launch:
-                tab_h = torch.from_numpy(rec_line_table(line_w, first_tok)).pin_memory()
-                linetab = self._buf("rec_linetab", 4 * n, torch.int32).view(n, 4)
+        tokens = linetab = tables = None
+        if plan.two_stage:
+            base = plan.group_base
+            tokens = self._buf("rec_tokens", int(base[-1]) * self.rec.rec_token_dim).view(int(base[-1]), self.rec.rec_token_dim)
+            for gi, lens in enumerate(plan.group_lens):         # the dummy lines' tokens: finite values (their outputs are ignored)
+                tokens[int(base[gi]) + int(lens.sum()): int(base[gi + 1])].zero_()
+            tables = [self.rec_tail.rec_tail_tables(lp, dev, out=self._buf(("tail_tab", gi), 2 * len(lp) + int(lp.sum()), torch.int32))
+                      for gi, (lp, _t) in enumerate(plan.group_pad)]   # uploaded now, used later
+            if plan.linetab is not None:
+                tab_h = torch.from_numpy(plan.linetab).pin_memory()
+                linetab = self._buf("rec_linetab", 4 * plan.n, torch.int32).view(plan.n, 4)
                 linetab.copy_(tab_h, non_blocking=True)
                 self._keep_linetab = tab_h                        # the pinned source must outlive the asynchronous copy
             ready.record(main)
             self.tail_stream.wait_event(ready)
-        group_rows = {}
-        bb_events: List[torch.cuda.Event] = []        # per rec launch: its backbone (or whole network) is done
-
-        def run_tail(gi):
-            grp = groups[gi]
-            t_lo, t_hi = int(group_base[gi]), int(group_base[gi + 1])
-            for bi in grp:
-                self.tail_stream.wait_event(outs[bi][2])
-            with torch.cuda.stream(self.tail_stream):
-                n_tok = t_hi - t_lo
-                idx_all, prob_all = self.rec_tail.rec_tail_forward(
-                    tokens[t_lo:t_hi], group_pad[gi][0], group_tables[gi], max_tokens=group_pad[gi][1],
-                    out=(self._buf(("tail_idx", gi), n_tok, torch.int32), self._buf(("tail_prob", gi), n_tok)))
-            if lines_mode:
-                # ragged lines: ONE collapse launch over the group's real lines (the seg table of the tail call), one copy back
-                n_real = len(group_lens[gi])
-                cols_h = None
-                if want_words:
-                    rows, done, cols_h = self._collapse_lines(idx_all, prob_all, group_tables[gi], n_real, group_pad[gi][1], self.tail_stream, True)
-                else:
-                    rows, done = self._collapse_lines(idx_all, prob_all, group_tables[gi], n_real, group_pad[gi][1], self.tail_stream)
-                kept = None
-                if self.keep_rec_inputs:
-                    with torch.cuda.stream(self.tail_stream):        # (after the tail call, on its stream)
-                        kept = (idx_all.clone(), prob_all.clone())
-                group_rows[gi] = (rows, done, kept, cols_h)
-                for bi in grp:
-                    outs[bi] = (None, None, done, outs[bi][3], None)
-                return
-            done = None
-            for bi in grp:
-                nb, t = len(batches[bi][0]), int(seq_line[int(starts[bi])])
-                lo = tok_lo[bi] - t_lo
-                hi = lo + nb * t
-                idx, prob = idx_all[lo:hi].view(nb, t), prob_all[lo:hi].view(nb, t)
-                rows, ev = self._collapse_rows(idx, prob, nb, self.tail_stream, record=bi == grp[-1])
-                done = ev or done
-                outs[bi] = (idx, prob, None, outs[bi][3], rows)
-            for bi in grp:
-                outs[bi] = outs[bi][:2] + (done,) + outs[bi][3:]
-
-        for bi, (chunk, wpad) in enumerate(batches):
-            nb = len(chunk)
+        launches: List[_RecLaunch] = []
+        for bi, (chunk, wpad) in enumerate(plan.batches):
+            nb, pos = len(chunk), int(plan.starts[bi])
             k = bi % S
             st = self.rec_streams[k]
             if bi < S:
@@ -612,139 +428,165 @@ class PagePipeline:
             with torch.cuda.stream(st):
                 # one input buffer per stream (batches bi, bi + S, ... of a stream run one after the other)
                 x = self._buf(("rec_x", k), nb * 3 * ocr_host.REC_IMG_H * wpad).view(nb, 3, ocr_host.REC_IMG_H, wpad)
-                scratch = self._crop_scratch.data_ptr() + int(batch_base[bi])
-                for si, first, cnt, max_px in warp_jobs[bi]:            # stage 1: page / canvas -> rectified uint8 crops
+                scratch = self._crop_scratch.data_ptr() + int(plan.batch_base[bi])
+                for si, first, cnt, max_px in plan.warp_jobs[bi]:            # stage 1: page / canvas -> rectified uint8 crops
                     imgs = sources[si][0]
-                    rc = self._lib.rd_line_warp_batch(self.device, imgs.data_ptr(), imgs.shape[0], imgs.shape[1], imgs.shape[2],
-                                                      descs_warp_dev.data_ptr() + first * LINE_DTYPE.itemsize, cnt, max_px, scratch,
-                                                      st.cuda_stream)
+                    rc = lib.rd_line_warp_batch(self.device, imgs.data_ptr(), imgs.shape[0], imgs.shape[1], imgs.shape[2],
+                                                descs_warp_dev.data_ptr() + first * LINE_DTYPE.itemsize, cnt, max_px, scratch, st.cuda_stream)
                     if rc != 0:
                         raise RuntimeError("rd_line_warp_batch failed")
-                if self.use_cls:              # classify the crops and turn the upside-down ones in the scratch, before the recogniser reads it
-                    xc = self._buf(("cls_x", k), nb * 3 * CLS_IMG_H * CLS_IMG_W).view(nb, 3, CLS_IMG_H, CLS_IMG_W)
-                    rc = self._lib.rd_line_resize_norm_batch(self.device, descs_cls_dev.data_ptr() + pos * LINE_DTYPE.itemsize, nb, scratch,
-                                                             CLS_IMG_H, CLS_IMG_W, 1, xc.data_ptr(), st.cuda_stream)
-                    if rc != 0:
-                        raise RuntimeError("rd_line_resize_norm_batch (classifier) failed")
-                    self.cls_engines[k].cls_forward(xc, out=cls_prob[pos: pos + nb])
-                    if self.keep_rec_inputs:
-                        self.last_cls_inputs.append((keep[np.asarray(chunk)], xc.clone()))
-                    rc = self._lib.rd_line_flip180_batch(self.device, descs_dev.data_ptr() + pos * LINE_DTYPE.itemsize, nb,
-                                                         cls_prob[pos: pos + nb].data_ptr(), self.cls_thresh, scratch,
-                                                         cls_flip[pos: pos + nb].data_ptr(), st.cuda_stream)
-                    if rc != 0:
-                        raise RuntimeError("rd_line_flip180_batch failed")
-                    cls_prob_h[pos: pos + nb].copy_(cls_prob[pos: pos + nb], non_blocking=True)     # home with the step's results: the
-                    cls_flip_h[pos: pos + nb].copy_(cls_flip[pos: pos + nb], non_blocking=True)     # host reads them behind the batch's `done`
-                rc = self._lib.rd_line_resize_norm_batch(self.device, descs_dev.data_ptr() + pos * LINE_DTYPE.itemsize, nb, scratch,
-                                                         ocr_host.REC_IMG_H, wpad, 1, x.data_ptr(), st.cuda_stream)   # stage 2
+                launch = _RecLaunch()
+                if cls is not None:           # classify the crops and turn the upside-down ones in the scratch, before the recogniser reads it
+                    self._enqueue_cls(launch, cls, descs_dev, k, pos, nb, scratch, plan.line_ids[pos: pos + nb])
+                rc = lib.rd_line_resize_norm_batch(self.device, descs_dev.data_ptr() + pos * LINE_DTYPE.itemsize, nb, scratch,
+                                                   ocr_host.REC_IMG_H, wpad, 1, x.data_ptr(), st.cuda_stream)   # stage 2
                 if rc != 0:
                     raise RuntimeError("rd_line_resize_norm_batch failed")
-                if lines_mode and self.rec_lines_in_launch:
+                if plan.lines_in_launch:
                     self.rec_engines[k].rec_backbone_forward_lines(x, linetab[pos: pos + nb], tokens)
-                    ev = torch.cuda.Event()
-                    ev.record(st)
-                    outs.append((None, None, ev, x.clone() if self.keep_rec_inputs else x, None))
-                elif two_stage:
-                    self.rec_engines[k].rec_backbone_forward(x, tokens[tok_lo[bi]: tok_lo[bi] + nb * int(seq_line[pos])])
-                    ev = torch.cuda.Event()
-                    ev.record(st)
-                    outs.append((None, None, ev, x.clone() if self.keep_rec_inputs else x, None))
+                elif plan.two_stage:
+                    self.rec_engines[k].rec_backbone_forward(x, tokens[plan.tok_lo[bi]: plan.tok_lo[bi] + nb * int(plan.seq_line[pos])])
                 else:
-                    idx, prob, _ = self.rec_engines[k].rec_forward(x)
-                    rows, done = self._collapse_rows(idx, prob, nb, st)
-                    outs.append((idx, prob, done, x.clone() if self.keep_rec_inputs else x, rows))
-            bb_events.append(outs[-1][2])
-            pos += nb
-            if two_stage and (bi + 1) % S == 0:
-                run_tail(bi // S)
-        if two_stage and len(batches) % S:
-            run_tail(len(groups) - 1)
-        self.stats["t_rec_enqueue_ms"] = (time.perf_counter() - t0) * 1e3 - self.stats["t_descs_ms"]
-        hook, self._after_rec_enqueue = self._after_rec_enqueue, None
-        if hook is not None:
-            t_h = time.perf_counter()
-            m = max(1, min(len(batches), int(np.ceil(self.prefetch_gate * len(batches)))))
-            hook(bb_events[max(0, m - S): m])          # streams run their launches in order: the last S up to m cover all before them
-            self.stats["t_front_next_ms"] = (time.perf_counter() - t_h) * 1e3
-        # D2H per batch result (small) as soon as that batch is done, host CTC decode (rapidocr CTCLabelDecode)
-        # overlaps the GPU work of the batches still in flight
+                    launch.idx, launch.prob, _ = self.rec_engines[k].rec_forward(x)
+                    launch.rows, launch.done = self._collapse_rows(launch.idx, launch.prob, nb, st)
+                launch.event = launch.done
+                if plan.two_stage:
+                    launch.event = torch.cuda.Event()
+                    launch.event.record(st)
+                launch.x = x.clone() if keep_inputs else x
+            launches.append(launch)
+            if plan.two_stage and ((bi + 1) % S == 0 or bi + 1 == len(plan.batches)):
+                self._enqueue_tail(plan, launches, bi // S, tokens, tables[bi // S], want_words)
+        return launches
+
+    def _enqueue_cls(self, launch: _RecLaunch, cls, descs_dev, k: int, pos: int, nb: int, scratch: int, line_ids: np.ndarray) -> None:
+        """On the current stream (launch's, engine k), for its `nb` lines from position `pos`: the classifier's resize, its forward, the
+        180-degree turn of the crops in the scratch and the two copies home."""
+        descs_cls_dev, cls_prob, cls_flip, cls_prob_h, cls_flip_h = cls
+        stream = torch.cuda.current_stream().cuda_stream
+        sl = slice(pos, pos + nb)
+        xc = self._buf(("cls_x", k), nb * 3 * CLS_IMG_H * CLS_IMG_W).view(nb, 3, CLS_IMG_H, CLS_IMG_W)
+        rc = self._lib.rd_line_resize_norm_batch(self.device, descs_cls_dev.data_ptr() + pos * LINE_DTYPE.itemsize, nb, scratch,
+                                                 CLS_IMG_H, CLS_IMG_W, 1, xc.data_ptr(), stream)
+        if rc != 0:
+            raise RuntimeError("rd_line_resize_norm_batch (classifier) failed")
+        self.cls_engines[k].cls_forward(xc, out=cls_prob[sl])
+        if self.keep_rec_inputs:
+            self.last_cls_inputs.append((line_ids, xc.clone()))
+        rc = self._lib.rd_line_flip180_batch(self.device, descs_dev.data_ptr() + pos * LINE_DTYPE.itemsize, nb, cls_prob[sl].data_ptr(),
+                                             self.cls_thresh, scratch, cls_flip[sl].data_ptr(), stream)
+        if rc != 0:
+            raise RuntimeError("rd_line_flip180_batch failed")
+        launch.cls_prob, launch.cls_flip = cls_prob_h[sl], cls_flip_h[sl]
+        launch.cls_prob.copy_(cls_prob[sl], non_blocking=True)     # home with the step's results: the host reads them
+        launch.cls_flip.copy_(cls_flip[sl], non_blocking=True)     # behind the batch's `done`
+
+    def _enqueue_tail(self, plan: RecPlan, launches: List[_RecLaunch], gi: int, tokens: torch.Tensor, tables: torch.Tensor, want_words: bool) -> None:
+        """Neck + CTC head over the tokens of group `gi` on the tail stream, behind the group's backbones, and the device CTC collapse:
+        ONE launch over the group's ragged lines in lines mode (its products go to the group's last launch), one per launch otherwise.
+        Every launch of the group gets the event to wait for in `done`."""
+        grp = [launches[bi] for bi in plan.groups[gi]]
+        t_lo, t_hi = int(plan.group_base[gi]), int(plan.group_base[gi + 1])
+        lens_pad, max_tokens = plan.group_pad[gi]
+        for launch in grp:
+            self.tail_stream.wait_event(launch.event)
+        with torch.cuda.stream(self.tail_stream):
+            n_tok = t_hi - t_lo
+            idx_all, prob_all = self.rec_tail.rec_tail_forward(
+                tokens[t_lo:t_hi], lens_pad, tables, max_tokens=max_tokens,
+                out=(self._buf(("tail_idx", gi), n_tok, torch.int32), self._buf(("tail_prob", gi), n_tok)))
+        done = None
+        if plan.lines_mode:
+            last = grp[-1]
+            last.rows, done, last.cols = self._collapse_lines(idx_all, prob_all, tables, len(plan.group_lens[gi]), max_tokens, self.tail_stream,
+                                                              want_words)
+            if self.keep_rec_inputs:
+                with torch.cuda.stream(self.tail_stream):        # (after the tail call, on its stream)
+                    last.idx, last.prob = idx_all.clone(), prob_all.clone()
+        else:
+            for bi, launch in zip(plan.groups[gi], grp):
+                nb, t = len(plan.batches[bi][0]), int(plan.seq_line[int(plan.starts[bi])])
+                lo = plan.tok_lo[bi] - t_lo
+                launch.idx, launch.prob = idx_all[lo: lo + nb * t].view(nb, t), prob_all[lo: lo + nb * t].view(nb, t)
+                launch.rows, ev = self._collapse_rows(launch.idx, launch.prob, nb, self.tail_stream, record=launch is grp[-1])
+                done = ev or done
+        for launch in grp:
+            launch.done = done
+
+    def _texts_from_rows(self, rows_np: np.ndarray, line_ids: np.ndarray, texts: list) -> None:
+        """Collapsed CTC rows -> texts[pooled line] = (text, score as analyze_utils.py:280 prints it), in the library or in Python."""
+        if self.host_native:
+            txt, _conf, conf3 = ocr_host.parse_ctc_rows_native(rows_np)
+            for i, t, s in zip(line_ids.tolist(), txt, conf3):
+                texts[i] = (t, s)
+        else:
+            for i, (t, s) in zip(line_ids.tolist(), ocr_host.parse_ctc_rows(rows_np)):
+                texts[i] = (t, ocr_host.format_score(s))
+
+    def _words_from_rows(self, plan: RecPlan, lo: int, rows_np: np.ndarray, cols, texts: list) -> None:
+        """`want_words`: rows and kept columns of the lines from launch position `lo` -> texts[pooled line] = (text, raw score, words)
+        (raw: the reference's ocr(det=False) returns rapidocr's float as it is, rapid_ocr.py:295-297)."""
+        n_kept = rows_np[:, 8:12].copy().view("<i4")[:, 0]
+        cols_np, confs_np = cols[0].numpy(), cols[1].numpy()
+        for j, (t, sc) in enumerate(ocr_host.parse_ctc_rows(rows_np)):
+            i, k = int(plan.order_all[lo + j]), int(n_kept[j])
+            words = {"cols": cols_np[j, :k].astype(np.int64).tolist(), "confs": confs_np[j, :k].astype(np.float64).tolist(),
+                     "n_steps": int(plan.seq_line[lo + j]), "wh_ratio": float(plan.ratios[i]), "max_wh_ratio": float(plan.line_ratio[lo + j]),
+                     "crop_hw": (int(plan.eff_h[i]), int(plan.eff_w[i]))}
+            texts[int(plan.keep[i])] = (t, sc, words)
+
+    def _decode_groups(self, plan: RecPlan, launches: List[_RecLaunch], want_words: bool, texts: list) -> list:
+        """`_decode_rec` in lines mode: one wait and one set of rows per group of launches (on the group's last launch)."""
+        ids, starts = plan.line_ids, plan.starts
+        t_dec = 0.0
+        for gi, grp in enumerate(plan.groups):
+            tail = launches[grp[-1]]
+            tail.done.synchronize()
+            t1 = time.perf_counter()
+            lo, hi = int(starts[grp[0]]), int(starts[grp[-1] + 1])
+            if want_words:
+                self._words_from_rows(plan, lo, tail.rows.numpy(), tail.cols, texts)
+            else:
+                self._texts_from_rows(tail.rows.numpy(), ids[lo:hi], texts)
+            t_dec += time.perf_counter() - t1
+            if tail.idx is not None:    # tests: per rec batch (pooled line ids, input tensor, reference width per line, per-line idx, prob)
+                g0 = int(plan.group_base[gi])
+                for bi in grp:
+                    a, e = int(starts[bi]), int(starts[bi + 1])
+                    sl = [(int(plan.first_tok[i]) - g0, int(plan.seq_line[i])) for i in range(a, e)]
+                    self.last_rec_batches.append((ids[a:e], launches[bi].x, np.asarray(plan.line_w[a:e]),
+                                                  [tail.idx[o: o + t] for o, t in sl], [tail.prob[o: o + t] for o, t in sl]))
+        self.stats["t_decode_ms"] = t_dec * 1e3
+        return texts
+
+    def _decode_rec(self, plan: RecPlan, launches: List[_RecLaunch], want_words: bool) -> list:
+        """Waits group by group (lines mode) or launch by launch and turns the rows that came home into the pooled lines' results; the host
+        decode of one overlaps the GPU work of those still in flight.  -> per pooled line (text, score[, words])."""
+        texts: List[tuple] = [("", 0.0, None) if want_words else ("", 0.0)] * plan.n_all
+        ids, starts = plan.line_ids, plan.starts
         t_dec = 0.0
         if self.keep_rec_inputs:
-            self.last_rec_crop_sizes = (cws_a.astype(np.int64), chs_a.astype(np.int64), rots_a, keep)
-        if lines_mode:
+            self.last_rec_crop_sizes = (plan.crop_w.astype(np.int64), plan.crop_h.astype(np.int64), plan.rot90, plan.keep)
+        if self.keep_rec_inputs or plan.lines_mode:
             self.last_rec_batches = []
-            for gi, grp in enumerate(groups):
-                rows, done, kept, cols_h = group_rows[gi]
-                done.synchronize()
-                t1 = time.perf_counter()
-                lo = int(starts[grp[0]])
-                rows_np = rows.numpy()
-                if self.host_native and not want_words:
-                    txt, _conf, conf3 = ocr_host.parse_ctc_rows_native(rows_np)
-                    for i, t, sc in zip(keep[order_all[lo: lo + len(txt)]].tolist(), txt, conf3):
-                        texts[i] = (t, sc)
-                    dec = ()
-                else:
-                    dec = ocr_host.parse_ctc_rows(rows_np)
-                if want_words:
-                    n_kept = rows_np[:, 8:12].copy().view("<i4")[:, 0]
-                    cols_np, confs_np = cols_h[0].numpy(), cols_h[1].numpy()
-                for j, (t, sc) in enumerate(dec):
-                    if want_words:       # (raw score: the reference's ocr(det=False) returns rapidocr's float as it is, rapid_ocr.py:295-297)
-                        i = int(order_all[lo + j])
-                        k = int(n_kept[j])
-                        words = {"cols": cols_np[j, :k].astype(np.int64).tolist(), "confs": confs_np[j, :k].astype(np.float64).tolist(),
-                                 "n_steps": int(seq_line[lo + j]), "wh_ratio": float(ratios[i]), "max_wh_ratio": float(line_ratio[lo + j]),
-                                 "crop_hw": (int(eff_h[i]), int(eff_w[i]))}
-                        texts[int(keep[i])] = (t, sc, words)
-                        continue
-                    texts[int(keep[order_all[lo + j]])] = (t, ocr_host.format_score(sc))
-                t_dec += time.perf_counter() - t1
-                if kept is not None:        # tests: per rec batch (pooled line ids, input tensor, reference width per line, per-line idx, prob)
-                    g0 = int(group_base[gi])
-                    for bi in grp:
-                        a, e = int(starts[bi]), int(starts[bi + 1])
-                        sl = [(int(first_tok[i]) - g0, int(seq_line[i])) for i in range(a, e)]
-                        self.last_rec_batches.append((keep[np.asarray(batches[bi][0])], outs[bi][3], np.asarray(line_w[a:e]),
-                                                      [kept[0][o: o + t] for o, t in sl], [kept[1][o: o + t] for o, t in sl]))
-        else:
+        if plan.lines_mode:
+            return self._decode_groups(plan, launches, want_words, texts)
+        for bi, launch in enumerate(launches):
+            ids_b = ids[int(starts[bi]): int(starts[bi + 1])]
             if self.keep_rec_inputs:
-                self.last_rec_batches = [(keep[np.asarray(chunk)], x, idx, prob) for (chunk, _w), (idx, prob, _d, x, _r) in zip(batches, outs)]
-            for (chunk, wpad), (idx, prob, done, _x, rows) in zip(batches, outs):
-                done.synchronize()
-                if rows is not None and self.host_native:
-                    t1 = time.perf_counter()
-                    txt, _conf, conf3 = ocr_host.parse_ctc_rows_native(rows.numpy())
-                    for i, t, s in zip(keep[np.asarray(chunk)].tolist(), txt, conf3):
-                        texts[i] = (t, s)
-                    t_dec += time.perf_counter() - t1
-                    continue
-                if rows is not None:
-                    t1 = time.perf_counter()
-                    dec = ocr_host.parse_ctc_rows(rows.numpy())
-                else:
-                    idx_h, prob_h = idx.cpu().numpy(), prob.cpu().numpy()
-                    t1 = time.perf_counter()
-                    dec = ocr_host.ctc_decode(idx_h, prob_h, self.characters)
-                for j, i in enumerate(chunk):
-                    t, s = dec[j]
-                    texts[int(keep[i])] = (t, ocr_host.format_score(s))
-                t_dec += time.perf_counter() - t1
+                self.last_rec_batches.append((ids_b, launch.x, launch.idx, launch.prob))
+            launch.done.synchronize()
+            if launch.rows is not None:
+                t1 = time.perf_counter()
+                self._texts_from_rows(launch.rows.numpy(), ids_b, texts)
+            else:                       # device_ctc off: the raw (idx, prob) come home and the host collapses them
+                idx_h, prob_h = launch.idx.cpu().numpy(), launch.prob.cpu().numpy()
+                t1 = time.perf_counter()
+                for i, (t, s) in zip(ids_b.tolist(), ocr_host.ctc_decode(idx_h, prob_h, self.characters)):
+                    texts[i] = (t, ocr_host.format_score(s))
+            t_dec += time.perf_counter() - t1
         self.stats["t_decode_ms"] = t_dec * 1e3
-        for st in self.rec_streams + [self.tail_stream]:
-            main.wait_stream(st)
-        self.stats["rec_lines"] = n
-        self.stats["rec_batches"] = len(batches)
-        self.last_pool_order = perm
-        if self.use_cls:       # (every batch's `done` has been waited for above: the copies enqueued in front of its recogniser are complete)
-            ph, fh = cls_prob_h.numpy(), cls_flip_h.numpy()
-            for j, i in enumerate(keep[order_all].tolist()):
-                label = int(ph[j, 1] > ph[j, 0])
-                cls_of[i] = (bool(fh[j]), label, float(ph[j, label]))
-            self.last_cls = self._scatter_texts(cls_of, src_of, page_of, n_img, perm)
-            self.last_cls_prob = (keep[order_all], ph.copy())      # tests: pooled line ids and the raw probabilities
-        return self._scatter_texts(texts, src_of, page_of, n_img, perm)
+        return texts
 
     @staticmethod
     def _scatter_texts(texts, src_of, page_of, n_img, perm=None):

@@ -460,3 +460,23 @@ def test_det_range_trip_under_the_width_exchange_makes_one_collective_call(golde
     assert len(calls) == 2 and pipe.det.range_fallbacks == 1
     assert [[t for _q, t, _s in r.lines] for r in res] == [[t for _q, t, _s in r.lines] for r in res2]
     pipe.rec_width_sync = None
+
+
+@pytest.mark.parametrize("name", ["a", "b", "d", "f"])
+def test_the_stage_reads_what_it_read_before_it_was_split(golden_dir, monkeypatch, name):
+    """Cases of tests/golden/rec_plan_parent.npz (recorded at the commit before the recogniser stage was split into plan / enqueue /
+    decode, tests/golden/make_golden_rec_plan.py) through `rec_forward_sources` with the same weights: strict two-stage with a full and a
+    partial group of launches, two sources under a key sort, throughput, strict launch by launch.  The same kernels run on the same
+    inputs: texts and scores are equal, the scores as floats."""
+    from rapiddoc_amd.pipeline import PagePipeline
+    from test_rec_plan import load_cases
+    c = load_cases()[name]
+    monkeypatch.setenv("RD_REC_TWO_STAGE", "1" if c["two_stage"] else "0")
+    pipe = PagePipeline({k: _state(golden_dir, k) for k in c["kinds"]}, **c["kw"])
+    pipe.keep_rec_inputs = True
+    sources = [(torch.zeros(tuple(shape) + (3,), dtype=torch.uint8, device="cuda"), quads) for shape, quads in c["sources"]]
+    res = pipe.rec_forward_sources(sources, image_keys=c["image_keys"])
+    assert pipe.last_rec_descs[0].tobytes() == c["descs"].tobytes() and len(pipe.last_rec_batches) == len(c["launch_w"])
+    assert [[[t for t, _s in img] for img in src] for src in res] == c["texts"]
+    scores = np.array([s for src in res for img in src for _t, s in img], np.float64)
+    assert scores.shape == c["scores"].shape and (scores == c["scores"]).all()
