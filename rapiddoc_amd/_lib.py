@@ -75,6 +75,46 @@ SYMBOLS = {
     "rd_profile_json": (C.c_char_p, [C.c_void_p]),
 }
 
+# The developer entries (csrc/api_debug.cpp; not in the public header), one row per exported rd_debug_* in the order of that file.
+# tests/test_cabi.py holds both tables to the C prototypes.
+_I, _P, _F = C.c_int, C.c_void_p, C.c_float
+DEBUG_SYMBOLS = {
+    "rd_debug_det_forward_stages": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "rd_debug_cls_forward_stages": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "rd_debug_table_decode": (_I, [_P, _P, _I, _I, _I, _P] + [_P] * 7),
+    "rd_debug_table_encoder_taps": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "rd_debug_formula_decode": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(C.c_int32), _P, _P, _P]),
+    "rd_debug_resize_aa_coeffs": (_I, [_I, _I, _P, _P, C.c_int64]),
+    "rd_debug_time_mixer": (_F, [_I] * 4 + [_P] * 6),
+    "rd_debug_time_gemm": (_F, [_I] * 5 + [_P] * 6),
+    "rd_debug_gemm_h1": (_F, [_I] * 5 + [_P, _I, _P, _P, _P, _I, _P, _I, _P]),
+    "rd_debug_seqconv": (_F, [_I] * 8 + [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
+    "rd_debug_det_local": (_F, [_I] * 5 + [_P] * 5 + [_F, _P, C.POINTER(C.c_int)]),
+    "rd_debug_conv": (_F, [_I] * 14 + [_P] * 8),
+    "rd_debug_stem34": (_F, [_I] * 11 + [_P] * 7),
+    "rd_debug_dwconv": (_F, [_I] * 8 + [_P] * 8),
+    "rd_debug_lcv3_dw": (_F, [_I] * 9 + [_P] * 8),
+    "rd_debug_dw5_strip": (_F, [_I] * 11 + [_P] * 7),
+    "rd_debug_mv1e_pool": (_I, [_I] * 4 + [_P] * 3),
+    "rd_debug_derived_tensor": (C.c_long, [C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, _P, C.c_long]),
+    "rd_debug_mbv3_dw": (_F, [_I] * 12 + [_P] * 4),
+    "rd_debug_mbv3_block": (_F, [_I] * 14 + [_P] * 8),
+    "rd_debug_mbv3_block_ok": (_I, [_I] * 12),
+    "rd_debug_mbv3s_dw": (_F, [_I] * 13 + [_P] * 4),
+    "rd_debug_mbv3s_block": (_F, [_I] * 15 + [_P] * 12),
+    "rd_debug_lcv3_dw_det": (_F, [_I] * 10 + [_P] * 5),
+    "rd_debug_lcv3_block": (_F, [_I] * 9 + [_P] * 9),
+    "rd_debug_time_ctc": (_F, [_I] * 4 + [_P] * 7 + [_I, _P]),
+    "rd_debug_attention": (_I, [_I] * 4 + [_F, _P, _P, _P, _I, _P]),
+    "rd_debug_vit_attention": (_I, [_I] * 4 + [_F, _P, _P]),
+    "rd_debug_attention_limits": (_I, [_I, _P, _P]),
+    "rd_debug_layernorm": (_I, [_I, _I, _P, _I, _P, _I, _P, _P, _F]),
+    "rd_debug_ctc_head": (_I, [_I] * 3 + [_P, _I] + [_P] * 6 + [_I, _P, _P]),
+    "rd_debug_dec_gemv": (_I, [_I] * 4 + [_P] * 7),
+    "rd_debug_dec_attention": (_I, [_I] * 4 + [_P, _P, _I, C.c_longlong] + [_P] * 5 + [_P, _I, _P, _P, _I, _P, _I]),
+    "rd_debug_dec_select": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _I] + [_P] * 6),
+}
+
 
 class NativeLibraryError(RuntimeError):
     pass
@@ -94,8 +134,8 @@ def load():
     # /opt/rocm's copy and leave the process with two runtimes.
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)  # AttributeError = a symbol of include/rapiddoc_mi355.h is not exported
+    for name, (res, args) in {**SYMBOLS, **DEBUG_SYMBOLS}.items():
+        fn = getattr(lib, name)  # AttributeError = a symbol of include/rapiddoc_mi355.h or a developer entry is not exported
         fn.restype = res
         fn.argtypes = args
     _lib = lib

@@ -180,8 +180,6 @@ class RdEngine:
 
             def launch_stages():
                 fn = self._l.rd_debug_det_forward_stages       # developer entry, not in the public header
-                fn.restype = C.c_int
-                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
                 self._chk(fn(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), aux.data_ptr(), _stream_ptr()))
                 self._log()
             self._guarded(launch_stages)
@@ -232,8 +230,6 @@ class RdEngine:
 
             def launch_stages():
                 fn = self._l.rd_debug_cls_forward_stages       # developer entry, not in the public header
-                fn.restype = C.c_int
-                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
                 self._chk(fn(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), aux.data_ptr(), stages.data_ptr(), _stream_ptr()))
                 self._log()
             self._guarded(launch_stages)
@@ -267,8 +263,6 @@ class RdEngine:
 
             def launch_taps():
                 fn = self._l.rd_debug_table_encoder_taps       # developer entry, not in the public header
-                fn.restype = C.c_int
-                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
                 self._chk(fn(self._h, x.data_ptr(), B, H, W_, out.data_ptr(), taps.data_ptr(), _stream_ptr()))
                 self._log()
             self._guarded(launch_taps)
@@ -319,8 +313,6 @@ class RdEngine:
             if forced.shape != (B, steps):
                 raise EngineError("table_decode_debug: forced must be [B, steps]")
         fn = self._l.rd_debug_table_decode                 # developer entry, not in the public header
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 7
         cfg = cfg_struct(ids)
         self._chk(fn(self._h, memory.data_ptr(), B, S, steps, C.byref(cfg), forced.data_ptr() if forced is not None else None, out.data_ptr(),
                      hidden.data_ptr(), logits.data_ptr(), chosen.data_ptr(), emitted.data_ptr(), _stream_ptr()))

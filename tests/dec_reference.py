@@ -1,12 +1,10 @@
-"""References, input builders and the ctypes bindings shared by the formula decoder's kernel tests (tests/test_gpu_dec_*.py; the helpers
+"""References and input builders shared by the formula decoder's kernel tests (tests/test_gpu_dec_*.py; the helpers
 themselves are tested on the CPU in tests/test_dec_reference.py).
 
 Every reference takes a `dtype`: float64 is the reference proper, float32 the YARDSTICK - the same operation in plain torch fp32 on the CPU.
 Bound (one for all cases): the kernel's max-abs error against fp64 may be at most 4 x the yardstick's + 2^-22 max|ref|.  The factor is the
 convention of tests/test_gpu_attention.py / test_gpu_layernorm.py (it covers `__expf`'s extra rounding of its argument and the kernels'
 re-association of sums); nothing in it comes from the code under test.  The measured ratios are in docs/notebook/formula_decode_kernels.md."""
-import ctypes as C
-
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -17,24 +15,9 @@ EOS, PAD = 2, 1
 FORCED_EOS_LEN = 1537
 ACT_NONE, ACT_GELU = 0, 2
 
-_LIB = {}
-
-
 def lib():
-    if not _LIB:
-        from rapiddoc_amd import _lib
-        l = _lib.load()
-        P, I = C.c_void_p, C.c_int
-        l.rd_debug_dec_gemv.restype = I
-        l.rd_debug_dec_gemv.argtypes = [I] * 4 + [P] * 7
-        l.rd_debug_dec_attention.restype = I
-        l.rd_debug_dec_attention.argtypes = [I] * 4 + [P, P, I, C.c_longlong] + [P] * 5 + [P, I, P, P, I, P, I]
-        l.rd_debug_dec_select.restype = I
-        l.rd_debug_dec_select.argtypes = [I, P, I, I, I, P, I, P, I, I] + [P] * 6
-        l.rd_debug_formula_decode.restype = I
-        l.rd_debug_formula_decode.argtypes = [P, P, I, I, I, P, C.POINTER(C.c_int32), P, P, P]
-        _LIB["lib"] = l
-    return _LIB["lib"]
+    from rapiddoc_amd import _lib
+    return _lib.load()
 
 
 def ptr(t):

@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from kind_helpers import synth_state
 from rapiddoc_amd import weights as W
 
 KIND = "ppocr_cls_mobile"
@@ -27,7 +28,7 @@ FIXTURE_TOL = 1e-3          # the project's fixture bound
 
 
 def state(golden_dir):
-    return W.synth_state_dict(W.load_manifest(golden_dir / f"manifest_{KIND}.json"), 0, kind=KIND)
+    return synth_state(golden_dir, KIND, kind=KIND)
 
 
 def golden_x(g):

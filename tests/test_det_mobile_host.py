@@ -1,12 +1,12 @@
 """CPU: the host side of the PP-OCRv5 mobile detector (`ppocrv5_det_mobile`) - kind selection by stem / tensor names, the reference-minted
 fixtures and their summary, that the opt-in synthetic-weight gains of this kind leave every earlier manifest's tensors alone, and the
 load-time folds (read back through the host-only entry rd_debug_derived_tensor) against float64 restatements from the state dict."""
-import ctypes as C
 import json
 
 import numpy as np
 import pytest
 
+from kind_helpers import synth_state
 from rapiddoc_amd import weights as W
 
 KIND = "ppocrv5_det_mobile"
@@ -29,7 +29,7 @@ PARENT_CHECKSUMS = {
 
 
 def _state(golden_dir):
-    return W.synth_state_dict(W.load_manifest(golden_dir / f"manifest_{KIND}.json"), 0, kind=KIND)
+    return synth_state(golden_dir, KIND, kind=KIND)
 
 
 def test_kind_is_listed():
@@ -119,8 +119,6 @@ def _derived(blob, name, shape):
     from rapiddoc_amd import _lib
     lib = _lib.load()
     fn = lib.rd_debug_derived_tensor
-    fn.restype = C.c_long
-    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_void_p, C.c_long]
     out = np.full(shape, np.nan, np.float32)
     n = fn(KIND.encode(), blob, len(blob), name.encode(), out.ctypes.data, out.size)
     assert n == out.size, (name, n, shape)
@@ -130,8 +128,6 @@ def _derived(blob, name, shape):
 def test_the_derived_tensor_entry_serves_this_kind_only(golden_dir):
     from rapiddoc_amd import _lib
     fn = _lib.load().rd_debug_derived_tensor
-    fn.restype = C.c_long
-    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_void_p, C.c_long]
     blob = W.to_safetensors_bytes(_state(golden_dir))
     assert fn(b"ppocrv5_rec_mobile", blob, len(blob), b"backbone.blocks2.0.dw_conv.fold.weight", None, 0) == -1
     assert fn(KIND.encode(), blob, len(blob), b"no.such.tensor", None, 0) == -1

@@ -3,7 +3,6 @@ DBHead; the files multi_PP-OCRv3_det_mobile and en_PP-OCRv3_det_mobile) - kind s
 fixtures and their summary, the opt-in synthetic-weight gains, the load-time Conv + BatchNorm folds (read back through the host-only entry
 rd_debug_derived_tensor) against float64, and a float64 restatement of the FOLDED graph - the graph the engine runs - against the
 fixtures."""
-import ctypes as C
 import json
 
 import numpy as np
@@ -11,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from kind_helpers import hswish64, synth_state
 from rapiddoc_amd import weights as W
 
 KIND = "ppocrv3_det_mobile"
@@ -41,7 +41,7 @@ EARLIER_CHECKSUMS = {
 
 
 def _state(golden_dir):
-    return W.synth_state_dict(W.load_manifest(golden_dir / f"manifest_{KIND}.json"), 0, kind=KIND)
+    return synth_state(golden_dir, KIND, kind=KIND)
 
 
 def test_kind_is_listed():
@@ -130,8 +130,6 @@ def test_the_earlier_kind_with_gains_keeps_its_summary(golden_dir):
 def _derived_fn():
     from rapiddoc_amd import _lib
     fn = _lib.load().rd_debug_derived_tensor
-    fn.restype = C.c_long
-    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_void_p, C.c_long]
     return fn
 
 
@@ -181,10 +179,6 @@ def test_c_abi_accepts_the_kind_name():
     """Host only: rd_create reaches the device check (or succeeds) for this kind, and still names an unknown kind as unknown."""
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_create.restype = C.c_void_p
-    lib.rd_create.argtypes = [C.c_int, C.c_char_p]
-    lib.rd_create_error.restype = C.c_char_p
-    lib.rd_destroy.argtypes = [C.c_void_p]
     for name in ("rd_debug_mbv3_dw", "rd_debug_mbv3_block", "rd_debug_mbv3_block_ok"):
         assert hasattr(lib, name)
     h = lib.rd_create(0, b"ppocrv3_det_mobile_x")
@@ -200,8 +194,6 @@ def test_block_launch_ok_refuses_what_the_kernel_does_not_serve():
     """Host only (rd_debug_mbv3_block_ok): every block of the 1/2, 1/4 and 1/8 levels but the 120-wide one is served, and each refusal."""
     from rapiddoc_amd import _lib
     fn = _lib.load().rd_debug_mbv3_block_ok
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_int] * 12
 
     def ok(N=2, H=9, W_=35, cin=16, mid=40, cout=16, K=3, S=1, act=1, shortcut=0, xld=None, yld=None):
         return fn(N, H, W_, cin, mid, cout, K, S, act, shortcut, cin if xld is None else xld, cout if yld is None else yld)
@@ -221,10 +213,6 @@ def test_block_launch_ok_refuses_what_the_kernel_does_not_serve():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the folded graph in float64
-def _hswish(t):
-    return t * torch.clamp(t + 3.0, 0.0, 6.0) / 6.0
-
-
 def folded_graph_fp64(st, blob, x):
     """What the engine computes, restated in float64 from the FOLDED tensors (float32 values, as rounded at load time) and the rest of
     the state dict: conv1 + hardswish, fifteen blocks (expand + act, zero padding, depthwise + act, linear, shortcut), conv_last +
@@ -245,19 +233,19 @@ def folded_graph_fp64(st, blob, x):
         g = torch.clamp(0.2 * F.conv2d(g, t(p + ".se_block.conv2.weight"), t(p + ".se_block.conv2.bias")) + 0.5, 0.0, 1.0)
         return y + y * g
 
-    h = _hswish(bn(F.conv2d(d(x), t("backbone.conv.conv.weight"), stride=2, padding=1), "backbone.conv.bn"))
+    h = hswish64(bn(F.conv2d(d(x), t("backbone.conv.conv.weight"), stride=2, padding=1), "backbone.conv.bn"))
     feats = []
     for n, (s, i, k, cin, mid, cout, stride, act) in enumerate(BLOCKS):
         if stride == 2 and n > 2:
             feats.append(h)
-        a = F.relu if act == "relu" else _hswish
+        a = F.relu if act == "relu" else hswish64
         p = f"backbone.stages.{s}.{i}"
         e = a(F.conv2d(h, *fold(p + ".expand_conv", (mid, cin, 1, 1))))
         w, b = fold(p + ".bottleneck_conv", (mid, 1, k, k))
         dw = a(F.conv2d(F.pad(e, (k // 2,) * 4), w, b, stride=stride, groups=mid))
         y = F.conv2d(dw, *fold(p + ".linear_conv", (cout, mid, 1, 1)))
         h = h + y if stride == 1 and cin == cout else y
-    feats.append(_hswish(F.conv2d(h, *fold("backbone.stages.3.3", (480, 80, 1, 1)))))
+    feats.append(hswish64(F.conv2d(h, *fold("backbone.stages.3.3", (480, 80, 1, 1)))))
     ins = [rse(F.conv2d(f, t(f"neck.ins_conv.{i}.in_conv.weight")), f"neck.ins_conv.{i}") for i, f in enumerate(feats)]
     for i in (2, 1, 0):
         ins[i] = ins[i] + F.interpolate(ins[i + 1], scale_factor=2, mode="nearest")

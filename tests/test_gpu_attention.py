@@ -73,19 +73,9 @@ def rising_qkv(B, T, heads, hd, scale, seed, rise=3.0):
     return x.reshape(B * T, 3 * heads * hd).contiguous()
 
 
-_LIB = {}
-
-
 def _lib():
-    if not _LIB:
-        from rapiddoc_amd import _lib
-        lib = _lib.load()
-        lib.rd_debug_attention.restype = C.c_int
-        lib.rd_debug_attention.argtypes = [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        lib.rd_debug_attention_limits.restype = C.c_int
-        lib.rd_debug_attention_limits.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-        _LIB["lib"] = lib
-    return _LIB["lib"]
+    from rapiddoc_amd import _lib
+    return _lib.load()
 
 
 def limits(hd):

@@ -7,7 +7,6 @@ float64 restatement of the folded graph: tests/test_cls_mobile_host.py, whose or
 Bounds: probabilities 1e-3 absolute; logits, pooled features and block outputs 1e-3 * max(1, max |ref|) (the project's fixture bounds); a
 kernel alone against float64 2e-5 * max(1, max |ref|), the bound kernels_mbv3 is held to.  Figures are printed before they are asserted
 (run with -s)."""
-import ctypes as C
 import json
 import os
 
@@ -16,6 +15,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from kind_helpers import HSWISH, RELU, act64, check_out, engine_cache, out_buffer, strided, write_weights
+from rapiddoc_amd import _lib
 from rapiddoc_amd import weights as W
 from test_cls_mobile_host import KIND, STEM, block64, golden_x, hsig_paddle64, oracle64, state
 
@@ -24,27 +25,9 @@ TOL = 1e-3
 KTOL = 2e-5
 TAGS = ["b7_h48_w192", "b1_h48_w192", "b3_h40_w100"]
 THRESH, NEAR = 0.9, 1e-3
-RELU, HSWISH = 1, 2
 
-_ENGINES = {}
-
-
-def _engine(golden_dir, precision="auto", fused="0"):
-    """One engine per (precision, route) for the module: RD_PRECISION is read when the handle is created, RD_CLS_FUSED when a plan is built
-    (every plan of such a handle is built inside `_with_route`)."""
-    from rapiddoc_amd.engine import RdEngine
-    key = (precision, fused)
-    if key not in _ENGINES:
-        old = os.environ.get("RD_PRECISION")
-        os.environ["RD_PRECISION"] = precision
-        try:
-            _ENGINES[key] = RdEngine(KIND, guard="off").load_weights(state(golden_dir))
-        finally:
-            if old is None:
-                del os.environ["RD_PRECISION"]
-            else:
-                os.environ["RD_PRECISION"] = old
-    return _ENGINES[key]
+# one engine per (precision, route): RD_CLS_FUSED is read when a plan is built, and every plan of such a handle is built inside `_with_route`
+_engine = engine_cache(KIND, state=lambda golden_dir, _fused: state(golden_dir))
 
 
 class _with_route:
@@ -174,66 +157,29 @@ def test_op_list_follows_the_network_not_the_batch(golden_dir, fused):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the kernels alone
-GUARD = 4096
-SENTINEL = 12345.0
 MAPS = [(2, 3), (3, 35), (6, 33), (12, 70)]
 # (cin, mid, cout, k, row stride, squeeze-excite, act, shortcut)
 KBLOCKS = [(8, 8, 8, 3, 2, True, RELU, False), (8, 32, 8, 3, 1, False, RELU, True), (16, 88, 16, 5, 1, True, HSWISH, True),
            (16, 104, 32, 5, 2, True, HSWISH, False), (32, 200, 32, 5, 1, True, HSWISH, True)]
 
 
-def _lib():
-    from rapiddoc_amd import _lib
-    return _lib.load()
-
-
-def _act64(t, a):
-    return F.relu(t) if a == RELU else t * torch.clamp(t + 3.0, 0.0, 6.0) / 6.0 if a == HSWISH else t
-
-
-def _strided(t, ld):
-    buf = torch.full((*t.shape[:3], ld), SENTINEL, device=t.device)
-    buf[..., :t.shape[3]] = t
-    return buf
-
-
-def _out_buffer(N, OH, OW, Cn, yld):
-    n_out = N * OH * OW * yld
-    buf = torch.full((n_out + GUARD,), float("nan"), device="cuda")
-    buf[n_out:] = SENTINEL
-    view = buf[:n_out].view(N, OH, OW, yld)
-    view[..., Cn:] = SENTINEL
-    return buf, view, n_out
-
-
-def _check_out(buf, view, n_out, Cn):
-    torch.cuda.synchronize()
-    assert bool((buf[n_out:] == SENTINEL).all()), "the guard band behind the output was written"
-    assert bool((view[..., Cn:] == SENTINEL).all()), "the padding channels of the output were written"
-    y = view[..., :Cn]
-    assert not bool(torch.isnan(y).any()), "an output element was not written"
-    return y
-
-
 def _debug_dw(x, w, b, K, SH, pre_act, post_act, xld=None, yld=None, max_blocks=0):
-    fn = _lib().rd_debug_mbv3s_dw
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 13 + [C.c_void_p] * 4
+    fn = _lib.load().rd_debug_mbv3s_dw
     N, H, W_, Cn = x.shape
     xld, yld = xld or Cn, yld or Cn
     OH = (H - 1) // SH + 1
-    xb = _strided(x, xld)
-    buf, view, n_out = _out_buffer(N, OH, W_, Cn, yld)
+    xb = strided(x, xld)
+    buf, view, n_out = out_buffer(N, OH, W_, Cn, yld)
     wk = w.reshape(Cn, K * K).t().contiguous()                           # [K*K][C]
     ms = fn(N, H, W_, Cn, K, SH, 1, pre_act, post_act, xld, yld, 0, max_blocks, xb.data_ptr(), wk.data_ptr(), b.data_ptr(), buf.data_ptr())
     assert ms >= 0, "the kernel does not serve this geometry"
-    return _check_out(buf, view, n_out, Cn)
+    return check_out(buf, view, n_out, Cn)
 
 
 def _dw_ref(x, w, b, K, SH, pre_act, post_act):
-    xd = _act64(x.permute(0, 3, 1, 2).double(), pre_act)
+    xd = act64(x.permute(0, 3, 1, 2).double(), pre_act)
     y = F.conv2d(xd, w.double(), b.double(), stride=(SH, 1), padding=K // 2, groups=x.shape[3])
-    return _act64(y, post_act).permute(0, 2, 3, 1)
+    return act64(y, post_act).permute(0, 2, 3, 1)
 
 
 @pytest.mark.parametrize("K,SH,Cn,pre_act,post_act", [(3, 2, 8, 0, RELU), (3, 1, 32, 0, RELU), (5, 1, 88, HSWISH, HSWISH), (5, 2, 104, HSWISH, HSWISH),
@@ -255,9 +201,7 @@ def test_depthwise_kernel_matches_fp64(K, SH, Cn, pre_act, post_act):
 
 
 def test_depthwise_kernel_declines_what_it_does_not_serve():
-    fn = _lib().rd_debug_mbv3s_dw
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 13 + [C.c_void_p] * 4
+    fn = _lib.load().rd_debug_mbv3s_dw
     t = torch.zeros(4096, device="cuda")
     for Cn, K, SH, SW in ((12, 3, 1, 1), (8, 7, 1, 1), (8, 3, 3, 1), (8, 3, 1, 2)):
         assert fn(1, 4, 4, Cn, K, SH, SW, 0, 0, Cn, Cn, 0, 0, t.data_ptr(), t.data_ptr(), t.data_ptr(), t.data_ptr()) < 0
@@ -312,14 +256,12 @@ def _block_ref(x, p, K, SH, act, se, shortcut, gate_fn=hsig_paddle64, halo_act_b
 
 
 def _debug_block(route, x, p, K, SH, act, se, shortcut, xld, yld):
-    fn = _lib().rd_debug_mbv3s_block
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 15 + [C.c_void_p] * 12
+    fn = _lib.load().rd_debug_mbv3s_block
     N, H, W_, cin = x.shape
     mid, cout = p["we"].shape[0], p["wl"].shape[0]
     OH = (H - 1) // SH + 1
-    xb = _strided(x, xld)
-    buf, view, n_out = _out_buffer(N, OH, W_, cout, yld)
+    xb = strided(x, xld)
+    buf, view, n_out = out_buffer(N, OH, W_, cout, yld)
     wd = p["wd"].reshape(mid, K * K).t().contiguous()
     keep = [p["we"].contiguous(), p["wl"].contiguous()] + ([p["w1"].contiguous(), p["w2"].contiguous()] if se else [])
     ptr = lambda k: p[k].data_ptr() if k in p else None
@@ -327,7 +269,7 @@ def _debug_block(route, x, p, K, SH, act, se, shortcut, xld, yld):
             wd.data_ptr(), ptr("bd"), keep[2].data_ptr() if se else None, ptr("b1"), keep[3].data_ptr() if se else None, ptr("b2"), keep[1].data_ptr(),
             ptr("bl"), buf.data_ptr())
     assert ms >= 0, "the route does not serve this geometry"
-    return _check_out(buf, view, n_out, cout)
+    return check_out(buf, view, n_out, cout)
 
 
 @pytest.mark.parametrize("route", [0, 1])
@@ -366,9 +308,7 @@ def test_fused_block_declines_what_it_cannot_hold():
     cin, mid, cout, K, SH, se, act, shortcut = KBLOCKS[1]
     p = _block_weights(cin, mid, cout, K, se, 5)
     x = torch.zeros((1, 50, 100, cin), device="cuda")
-    fn = _lib().rd_debug_mbv3s_block
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 15 + [C.c_void_p] * 12
+    fn = _lib.load().rd_debug_mbv3s_block
     y = torch.zeros((1, 50, 100, cout), device="cuda")
     wd = p["wd"].reshape(mid, K * K).t().contiguous()
     args = lambda route: (route, 1, 50, 100, cin, mid, cout, K, SH, act, 0, 1, cin, cout, 0, x.data_ptr(), p["we"].data_ptr(), p["be"].data_ptr(), wd.data_ptr(),
@@ -427,15 +367,15 @@ def test_flip_kernel_turns_the_flagged_crops_only(golden_dir):
     descs_dev = torch.from_numpy(descs.view(np.uint8)).cuda()
     prob_dev = torch.from_numpy(prob).cuda()
     flipped = torch.full((len(sizes),), -1, dtype=torch.int32, device="cuda")
-    rc = _lib().rd_line_flip180_batch(0, descs_dev.data_ptr(), len(sizes), prob_dev.data_ptr(), thresh, scratch.data_ptr(), flipped.data_ptr(), None)
+    rc = _lib.load().rd_line_flip180_batch(0, descs_dev.data_ptr(), len(sizes), prob_dev.data_ptr(), thresh, scratch.data_ptr(), flipped.data_ptr(), None)
     torch.cuda.synchronize()
     assert rc == 0
     assert flipped.cpu().numpy().tolist() == want.astype(np.int32).tolist()
     assert np.array_equal(scratch.cpu().numpy(), expect)       # flipped crops byte for byte; unflagged crops and the gaps untouched
-    rc = _lib().rd_line_flip180_batch(0, descs_dev.data_ptr(), len(sizes), prob_dev.data_ptr(), thresh, scratch.data_ptr(), flipped.data_ptr(), None)
+    rc = _lib.load().rd_line_flip180_batch(0, descs_dev.data_ptr(), len(sizes), prob_dev.data_ptr(), thresh, scratch.data_ptr(), flipped.data_ptr(), None)
     torch.cuda.synchronize()
     assert rc == 0 and np.array_equal(scratch.cpu().numpy(), host)       # turning twice is the identity
-    assert _lib().rd_line_flip180_batch(0, descs_dev.data_ptr(), 0, prob_dev.data_ptr(), thresh, scratch.data_ptr(), flipped.data_ptr(), None) == 0
+    assert _lib.load().rd_line_flip180_batch(0, descs_dev.data_ptr(), 0, prob_dev.data_ptr(), thresh, scratch.data_ptr(), flipped.data_ptr(), None) == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------- session, dispatch
@@ -443,8 +383,7 @@ def test_session_from_a_file_and_dispatch(tmp_path, golden_dir, monkeypatch):
     import sys
     import types
     from rapiddoc_amd import session as S
-    path = tmp_path / f"{STEM}.safetensors"
-    path.write_bytes(W.to_safetensors_bytes({"model." + k: v for k, v in state(golden_dir).items()}))
+    path = write_weights(tmp_path, STEM, state(golden_dir))
     sess = S.Mi355ClsSession.from_cfg({"model_path": str(path)})
     assert sess.kind == KIND and sess.engine.kind == KIND
     g = np.load(golden_dir / "cls_seed0_b7_h48_w192.npz")
@@ -560,8 +499,8 @@ def test_page_pipeline_turns_the_lines_the_classifier_flags(golden_dir):
     for b, entry in enumerate(off.last_rec_batches):
         nb, wpad = entry[1].shape[0], entry[1].shape[3]
         exp = torch.empty((nb, 3, 48, wpad), device="cuda")
-        rc = _lib().rd_line_resize_norm_batch(0, descs_dev.data_ptr() + int(starts[b]) * LINE_DTYPE.itemsize, nb, fs.data_ptr() + int(batch_base[b]), 48, wpad, 1,
-                                              exp.data_ptr(), None)
+        rc = _lib.load().rd_line_resize_norm_batch(0, descs_dev.data_ptr() + int(starts[b]) * LINE_DTYPE.itemsize, nb, fs.data_ptr() + int(batch_base[b]), 48, wpad, 1,
+                                                   exp.data_ptr(), None)
         torch.cuda.synchronize()
         assert rc == 0
         for j, i in enumerate(np.asarray(entry[0]).tolist()):

@@ -30,10 +30,7 @@ SHAPES = [(MS[(i + j) % 6], c, 136 if (i + j) % 2 else 120) for i, c in enumerat
 
 def _lib():
     from rapiddoc_amd import _lib
-    lib = _lib.load()
-    lib.rd_debug_ctc_head.restype = C.c_int
-    lib.rd_debug_ctc_head.argtypes = [C.c_int] * 3 + [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p]
-    return lib
+    return _lib.load()
 
 
 @functools.lru_cache(maxsize=4)

@@ -7,13 +7,12 @@ tests/test_det_mobile_host.py.)
 Bounds: `maps` 1e-3 max-abs, the project's stated bound (tests/test_gpu_parity.py); the neck output 1e-3 * max(1, max |ref|), as
 tests/test_gpu_det_server.py; a kernel alone against float64 2e-5 * max(1, max |ref|) (the project's bound for its direct convolutions).
 Figures are printed before they are asserted (run with -s to see them)."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 import torch
 
+from kind_helpers import GUARD, SENTINEL, check_det_fixture, engine_cache, golden_x, hswish64, synth_state, write_weights
+from rapiddoc_amd import _lib
 from rapiddoc_amd import weights as W
 
 pytestmark = pytest.mark.gpu
@@ -23,52 +22,14 @@ TAGS = ["b2_h64_w96", "b1_h160_w224", "b3_h96_w352", "b1_h960_w704"]
 
 
 def _state(golden_dir, kind=KIND):
-    return W.synth_state_dict(W.load_manifest(golden_dir / f"manifest_{kind}.json"), 0, kind=KIND if kind == KIND else None)
+    return synth_state(golden_dir, kind, kind=KIND if kind == KIND else None)
 
 
-_ENGINES = {}
-
-
-def _engine(golden_dir, precision="auto"):
-    """One engine per precision for the module (RD_PRECISION is read when the handle is created)."""
-    from rapiddoc_amd.engine import RdEngine
-    if precision not in _ENGINES:
-        old = os.environ.get("RD_PRECISION")
-        os.environ["RD_PRECISION"] = precision
-        try:
-            _ENGINES[precision] = RdEngine(KIND, guard="off").load_weights(_state(golden_dir))
-        finally:
-            if old is None:
-                del os.environ["RD_PRECISION"]
-            else:
-                os.environ["RD_PRECISION"] = old
-    return _ENGINES[precision]
-
-
-def _golden_x(g):
-    assert str(g["x_kind"]) == "pm1"
-    return np.random.default_rng(int(g["x_seed"])).uniform(-1.0, 1.0, tuple(int(v) for v in g["x_shape"])).astype(np.float32)
+_engine = engine_cache(KIND, state=_state)
 
 
 def _check_against_fixture(eng, golden_dir, tag, label):
-    g = np.load(golden_dir / f"det5m_seed0_{tag}.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
-    maps, fuse = eng.det_forward(x, want_neck=True)
-    plain = eng.det_forward(x)
-    assert torch.equal(plain, maps)                                   # the debug output does not move the result
-    maps, fuse = maps.cpu().numpy(), fuse.cpu().numpy()
-    B, _, H, W_ = x.shape
-    assert maps.shape == (B, 1, H, W_) and fuse.shape == (B, 96, H // 4, W_ // 4)
-    ps, cs, fps = int(g["maps_ps"]), int(g["fuse_cs"]), int(g["fuse_ps"])
-    e_maps = float(np.abs(maps[:, :, ::ps, ::ps] - g["maps"]).max())
-    ref_fuse = g["fuse"]
-    e_fuse = float(np.abs(fuse[:, ::cs, ::fps, ::fps] - ref_fuse).max())
-    b_fuse = TOL * max(1.0, float(np.abs(ref_fuse).max()))
-    print(f"\n[det mobile {tag} {label}] max-abs errors: maps {e_maps:.3e} (bound {TOL:.0e}), fuse {e_fuse:.3e} (bound {b_fuse:.3e}, "
-          f"max |ref| {float(np.abs(ref_fuse).max()):.1f})")
-    assert not eng.range_overflow()
-    assert e_maps <= TOL
-    assert e_fuse <= b_fuse
+    check_det_fixture(eng, golden_dir, tag, label, prefix="det5m", neck_channels=96, name="det mobile", tol=TOL)
 
 
 @pytest.mark.parametrize("precision", ["auto", "fp32"])
@@ -126,7 +87,7 @@ def test_a_file_without_the_unused_act_lab_of_the_stride_2_layers_loads(golden_d
     drop = [f"backbone.blocks{i}.0.dw_conv.act.lab.{leaf}" for i in (3, 4, 5, 6) for leaf in ("scale", "bias")]
     assert all(k in st for k in drop)
     slim = {k: v for k, v in st.items() if k not in drop}
-    x = torch.from_numpy(_golden_x(np.load(golden_dir / "det5m_seed0_b2_h64_w96.npz"))).cuda()
+    x = torch.from_numpy(golden_x(np.load(golden_dir / "det5m_seed0_b2_h64_w96.npz"))).cuda()
     got = RdEngine(KIND, guard="off").load_weights(slim).det_forward(x)
     assert torch.equal(got, _engine(golden_dir, "auto").det_forward(x))
 
@@ -135,7 +96,7 @@ def test_a_file_without_the_unused_act_lab_of_the_stride_2_layers_loads(golden_d
 def test_an_image_does_not_depend_on_the_launch_it_rides_in(golden_dir, precision):
     eng = _engine(golden_dir, precision)
     g = np.load(golden_dir / "det5m_seed0_b3_h96_w352.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     m3, f3 = eng.det_forward(x, want_neck=True)
     m3, f3 = m3.clone(), f3.clone()
     m1, f1 = eng.det_forward(x[1:2].contiguous(), want_neck=True)
@@ -143,22 +104,11 @@ def test_an_image_does_not_depend_on_the_launch_it_rides_in(golden_dir, precisio
 
 
 # ---------------------------------------------------------------------------------------------------------------- the depthwise kernels alone
-GUARD = 4096
-SENTINEL = 12345.0
-
-
-def _hswish64(t):
-    return t * torch.clamp(t + 3.0, 0.0, 6.0) / 6.0
-
-
 def _debug_dw(x, w, b, K, S, pre_act, post_act, aff, route):
     """One layer through rd_debug_lcv3_dw_det (api_debug.cpp).  route 0: lcv3_dw_kernel, 1: lcv3_dw2d_kernel.  The output buffer is prefilled
     with NaN and followed by a guard band that must come back untouched."""
-    from rapiddoc_amd import _lib
     lib = _lib.load()
     fn = lib.rd_debug_lcv3_dw_det
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 10 + [C.c_void_p] * 5
     N, H, W_, Cn = x.shape
     OH, OW = (H + 2 * (K // 2) - K) // S + 1, (W_ + 2 * (K // 2) - K) // S + 1
     n_out = N * OH * OW * Cn
@@ -181,12 +131,12 @@ def _dw_ref(x, w, b, K, S, pre_act, post_act, aff, pad_value=None):
     import torch.nn.functional as F
     xd = x.permute(0, 3, 1, 2).double()
     if pre_act:
-        xd = aff[0] * _hswish64(xd) + aff[1]
+        xd = aff[0] * hswish64(xd) + aff[1]
     P = K // 2
     xd = F.pad(xd, (P, P, P, P), value=0.0 if pad_value is None else pad_value)
     y = F.conv2d(xd, w.double(), b.double(), stride=S, groups=x.shape[3])
     if post_act:
-        y = aff[2] * _hswish64(y) + aff[3]
+        y = aff[2] * hswish64(y) + aff[3]
     return y.permute(0, 2, 3, 1)
 
 
@@ -243,13 +193,10 @@ def test_a_stride_2_block_matches_fp64_from_the_state_dict(golden_dir):
     NO act.lab (stride == 2), then pw_conv = act.lab(hardswish(lab(sum of branches))).  The engine's form: the folded depthwise layer
     through the debug entry with post_act = 0, the folded pointwise layer as a matrix product, then the consumer's hardswish + affine."""
     import torch.nn.functional as F
-    from rapiddoc_amd import _lib
     st = {k: torch.from_numpy(v) for k, v in _state(golden_dir).items()}
     blob = W.to_safetensors_bytes(_state(golden_dir))
     lib = _lib.load()
     fn = lib.rd_debug_derived_tensor
-    fn.restype = C.c_long
-    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_void_p, C.c_long]
 
     def derived(name, shape):
         out = np.full(shape, np.nan, np.float32)
@@ -269,7 +216,7 @@ def test_a_stride_2_block_matches_fp64_from_the_state_dict(golden_dir):
         assert f"{p}.identity.weight" not in st
         out = out * st[f"{p}.lab.scale"].double() + st[f"{p}.lab.bias"].double()
         if act:
-            out = _hswish64(out) * st[f"{p}.act.lab.scale"].double() + st[f"{p}.act.lab.bias"].double()
+            out = hswish64(out) * st[f"{p}.act.lab.scale"].double() + st[f"{p}.act.lab.bias"].double()
         return out
 
     p = "backbone.blocks3.0"
@@ -286,7 +233,7 @@ def test_a_stride_2_block_matches_fp64_from_the_state_dict(golden_dir):
         t = _debug_dw(x.cuda(), dw_w, dw_b, 3, 2, 0, 0, (1, 0, 1, 0), route)
         e_mid = (t.double().cpu() - mid.permute(0, 2, 3, 1)).abs().max().item()
         y = t.double() @ pw_w.double().t() + pw_b.double()
-        y = (_hswish64(y) * float(st[p + ".pw_conv.act.lab.scale"]) + float(st[p + ".pw_conv.act.lab.bias"])).cpu()
+        y = (hswish64(y) * float(st[p + ".pw_conv.act.lab.scale"]) + float(st[p + ".pw_conv.act.lab.bias"])).cpu()
         e = (y - ref).abs().max().item()
         print(f"\n[blocks3.0 route {route}] max |dw - fp64| = {e_mid:.3e}, max |block - fp64| = {e:.3e} (bound {bound:.3e}, max |ref| {ref.abs().max().item():.2f}); "
               f"with the unused act.lab applied the block would be off by {(wrong - ref).abs().max().item():.3e}")
@@ -304,7 +251,7 @@ def test_range_guard_falls_back_to_the_fp32_mode_bit_for_bit(golden_dir, monkeyp
     big = dict(_state(golden_dir))
     big["backbone.layer_list.1.bias"] = big["backbone.layer_list.1.bias"] * np.float32(1e7)
     g = np.load(golden_dir / "det5m_seed0_b2_h64_w96.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     ref = RdEngine(KIND, guard="off").load_weights(big).set_precision("fp32").det_forward(x)
     assert bool(torch.isfinite(ref).all())
     raw = RdEngine(KIND, guard="off").load_weights(big)
@@ -318,12 +265,11 @@ def test_range_guard_falls_back_to_the_fp32_mode_bit_for_bit(golden_dir, monkeyp
 
 def test_session_from_cfg_resolves_the_kind_by_stem(tmp_path, golden_dir):
     from rapiddoc_amd.session import Mi355DetSession
-    p = tmp_path / "ch_PP-OCRv5_det_mobile.safetensors"
-    p.write_bytes(W.to_safetensors_bytes({"model." + k: v for k, v in _state(golden_dir).items()}))
+    p = write_weights(tmp_path, "ch_PP-OCRv5_det_mobile", _state(golden_dir))
     sess = Mi355DetSession.from_cfg({"model_path": str(p)})
     assert sess.kind == KIND and sess.engine.kind == KIND
     g = np.load(golden_dir / "det5m_seed0_b2_h64_w96.npz")
-    y = sess(_golden_x(g))
+    y = sess(golden_x(g))
     ps = int(g["maps_ps"])
     assert type(y) is np.ndarray and y.shape == (2, 1, 64, 96) and y.dtype == np.float32
     e = float(np.abs(y[:, :, ::ps, ::ps] - g["maps"]).max())

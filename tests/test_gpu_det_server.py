@@ -6,13 +6,13 @@ Bounds: `maps` 1e-3 max-abs, the project's stated bound (tests/test_gpu_parity.p
 tests/test_gpu_rec_lines.py uses; a kernel alone against float64 2e-5 (the project's bound for its direct convolutions).  Figures are
 printed before they are asserted (run with -s to see them)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from rapiddoc_amd import weights as W
+from kind_helpers import check_det_fixture, engine_cache, golden_x, synth_state, write_weights
+from rapiddoc_amd import _lib
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -21,52 +21,14 @@ TAGS = ["b2_h64_w96", "b1_h160_w224", "b3_h96_w352", "b1_h960_w704"]
 
 
 def _state(golden_dir, kind=KIND):
-    return W.synth_state_dict(W.load_manifest(golden_dir / f"manifest_{kind}.json"), 0)
+    return synth_state(golden_dir, kind)
 
 
-_ENGINES = {}
-
-
-def _engine(golden_dir, precision="auto"):
-    """One engine per precision for the module (RD_PRECISION is read when the handle is created)."""
-    from rapiddoc_amd.engine import RdEngine
-    if precision not in _ENGINES:
-        old = os.environ.get("RD_PRECISION")
-        os.environ["RD_PRECISION"] = precision
-        try:
-            _ENGINES[precision] = RdEngine(KIND, guard="off").load_weights(_state(golden_dir))
-        finally:
-            if old is None:
-                del os.environ["RD_PRECISION"]
-            else:
-                os.environ["RD_PRECISION"] = old
-    return _ENGINES[precision]
-
-
-def _golden_x(g):
-    assert str(g["x_kind"]) == "pm1"
-    return np.random.default_rng(int(g["x_seed"])).uniform(-1.0, 1.0, tuple(int(v) for v in g["x_shape"])).astype(np.float32)
+_engine = engine_cache(KIND)
 
 
 def _check_against_fixture(eng, golden_dir, tag, label):
-    g = np.load(golden_dir / f"det5s_seed0_{tag}.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
-    maps, fuse = eng.det_forward(x, want_neck=True)
-    plain = eng.det_forward(x)
-    assert torch.equal(plain, maps)                                   # the debug output does not move the result
-    maps, fuse = maps.cpu().numpy(), fuse.cpu().numpy()
-    B, _, H, W_ = x.shape
-    assert maps.shape == (B, 1, H, W_) and fuse.shape == (B, 256, H // 4, W_ // 4)
-    ps, cs, fps = int(g["maps_ps"]), int(g["fuse_cs"]), int(g["fuse_ps"])
-    e_maps = float(np.abs(maps[:, :, ::ps, ::ps] - g["maps"]).max())
-    ref_fuse = g["fuse"]
-    e_fuse = float(np.abs(fuse[:, ::cs, ::fps, ::fps] - ref_fuse).max())
-    b_fuse = TOL * max(1.0, float(np.abs(ref_fuse).max()))
-    print(f"\n[det server {tag} {label}] max-abs errors: maps {e_maps:.3e} (bound {TOL:.0e}), fuse {e_fuse:.3e} (bound {b_fuse:.3e}, "
-          f"max |ref| {float(np.abs(ref_fuse).max()):.1f})")
-    assert not eng.range_overflow()
-    assert e_maps <= TOL
-    assert e_fuse <= b_fuse
+    check_det_fixture(eng, golden_dir, tag, label, prefix="det5s", neck_channels=256, name="det server", tol=TOL)
 
 
 @pytest.mark.parametrize("precision", ["auto", "fp32"])
@@ -83,7 +45,7 @@ def test_whole_network_in_h3_mode(golden_dir):
 def test_an_image_does_not_depend_on_the_launch_it_rides_in(golden_dir, precision):
     eng = _engine(golden_dir, precision)
     g = np.load(golden_dir / "det5s_seed0_b3_h96_w352.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     m3, f3 = eng.det_forward(x, want_neck=True)
     m3, f3 = m3.clone(), f3.clone()
     m1, f1 = eng.det_forward(x[1:2].contiguous(), want_neck=True)
@@ -94,10 +56,7 @@ def test_an_image_does_not_depend_on_the_launch_it_rides_in(golden_dir, precisio
 def _debug_conv9(x_nhwc, w_oihw, bias, act, res, route):
     """One 9x9 / pad 4 convolution through rd_debug_conv (api_debug.cpp): route 4 forces the direct kernel (kernels_conv9x9_h1.hip), 0 leaves the
     layer on the generic k x k split implicit GEMM.  Returns (y NHWC, the route the call reports)."""
-    from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_conv.restype = C.c_float
-    lib.rd_debug_conv.argtypes = [C.c_int] * 14 + [C.c_void_p] * 7 + [C.c_void_p]
     N, H, W_, Cin = x_nhwc.shape
     Cout = w_oihw.shape[0]
     K = 81 * Cin
@@ -142,11 +101,8 @@ def test_direct_9x9_conv_matches_fp64(N, H, W_, Cin, extras):
 
 # ---------------------------------------------------------------------------------------------------------------- the fused tail alone
 def _debug_det_local(f, shrink, w3, b3, w1, b1, split):
-    from rapiddoc_amd import _lib
     lib = _lib.load()
     fn = lib.rd_debug_det_local
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.POINTER(C.c_int)]
     N, H, W_ = shrink.shape
     y = torch.empty((N, H, W_), device="cuda")
     rng = C.c_int(0)
@@ -220,7 +176,7 @@ def test_range_guard_falls_back_to_the_fp32_mode_bit_for_bit(golden_dir, monkeyp
     big = dict(_state(golden_dir))
     big["backbone.stem.stem1.conv.weight"] = big["backbone.stem.stem1.conv.weight"] * 3e5
     g = np.load(golden_dir / "det5s_seed0_b2_h64_w96.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     ref = RdEngine(KIND, guard="off").load_weights(big).set_precision("fp32").det_forward(x)
     raw = RdEngine(KIND, guard="off").load_weights(big)
     raw.det_forward(x)
@@ -233,12 +189,11 @@ def test_range_guard_falls_back_to_the_fp32_mode_bit_for_bit(golden_dir, monkeyp
 
 def test_session_from_cfg_resolves_the_kind_by_stem(tmp_path, golden_dir):
     from rapiddoc_amd.session import Mi355DetSession
-    p = tmp_path / "ch_PP-OCRv5_det_server.safetensors"
-    p.write_bytes(W.to_safetensors_bytes({"model." + k: v for k, v in _state(golden_dir).items()}))
+    p = write_weights(tmp_path, "ch_PP-OCRv5_det_server", _state(golden_dir))
     sess = Mi355DetSession.from_cfg({"model_path": str(p)})
     assert sess.kind == KIND and sess.engine.kind == KIND
     g = np.load(golden_dir / "det5s_seed0_b2_h64_w96.npz")
-    y = sess(_golden_x(g))
+    y = sess(golden_x(g))
     ps = int(g["maps_ps"])
     assert type(y) is np.ndarray and y.shape == (2, 1, 64, 96) and y.dtype == np.float32
     e = float(np.abs(y[:, :, ::ps, ::ps] - g["maps"]).max())

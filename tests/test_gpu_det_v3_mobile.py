@@ -17,6 +17,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from kind_helpers import HSWISH, RELU, act64, check_out, engine_cache, golden_x, out_buffer, strided, synth_state, write_weights
+from rapiddoc_amd import _lib
 from rapiddoc_amd import weights as W
 
 pytestmark = pytest.mark.gpu
@@ -27,36 +29,15 @@ STAGE_CH = (16, 24, 56, 480)
 
 
 def _state(golden_dir, kind=KIND, gains=None):
-    return W.synth_state_dict(W.load_manifest(golden_dir / f"manifest_{kind}.json"), 0, kind=gains if gains else (KIND if kind == KIND else None))
+    return synth_state(golden_dir, kind, kind=gains if gains else (KIND if kind == KIND else None))
 
 
-_ENGINES = {}
-
-
-def _engine(golden_dir, precision="auto"):
-    """One engine per precision for the module (RD_PRECISION is read when the handle is created)."""
-    from rapiddoc_amd.engine import RdEngine
-    if precision not in _ENGINES:
-        old = os.environ.get("RD_PRECISION")
-        os.environ["RD_PRECISION"] = precision
-        try:
-            _ENGINES[precision] = RdEngine(KIND, guard="off").load_weights(_state(golden_dir))
-        finally:
-            if old is None:
-                del os.environ["RD_PRECISION"]
-            else:
-                os.environ["RD_PRECISION"] = old
-    return _ENGINES[precision]
-
-
-def _golden_x(g):
-    assert str(g["x_kind"]) == "pm1"
-    return np.random.default_rng(int(g["x_seed"])).uniform(-1.0, 1.0, tuple(int(v) for v in g["x_shape"])).astype(np.float32)
+_engine = engine_cache(KIND, state=_state)
 
 
 def _check_against_fixture(eng, golden_dir, tag, label):
     g = np.load(golden_dir / f"det3m_seed0_{tag}.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     B, _, H, W_ = x.shape
     # every output is handed over prefilled with NaN and must come back fully written
     out = torch.full((B, 1, H, W_), float("nan"), device="cuda")
@@ -147,7 +128,7 @@ def test_whole_network_on_either_block_route_in_a_fresh_process(golden_dir, rout
 def test_an_image_does_not_depend_on_the_launch_it_rides_in(golden_dir, precision):
     eng = _engine(golden_dir, precision)
     g = np.load(golden_dir / "det3m_seed0_b3_h96_w352.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     m3, f3 = eng.det_forward(x, want_neck=True)
     m3, f3 = m3.clone(), f3.clone()
     m1, f1 = eng.det_forward(x[1:2].contiguous(), want_neck=True)
@@ -182,64 +163,23 @@ def test_routes_follow_the_layer_not_the_batch_or_the_page(golden_dir, monkeypat
 
 
 # ---------------------------------------------------------------------------------------------------------------- the kernels alone
-GUARD = 4096
-SENTINEL = 12345.0
-RELU, HSWISH = 1, 2
-
-
-def _lib():
-    from rapiddoc_amd import _lib
-    return _lib.load()
-
-
-def _act64(t, a):
-    return F.relu(t) if a == RELU else t * torch.clamp(t + 3.0, 0.0, 6.0) / 6.0 if a == HSWISH else t
-
-
-def _strided(t, ld):
-    """t [N,H,W,C] -> the same values as a view of a [N,H,W,ld] buffer whose padding channels hold the sentinel"""
-    buf = torch.full((*t.shape[:3], ld), SENTINEL, device=t.device)
-    buf[..., :t.shape[3]] = t
-    return buf
-
-
-def _out_buffer(N, OH, OW, Cn, yld):
-    n_out = N * OH * OW * yld
-    buf = torch.full((n_out + GUARD,), float("nan"), device="cuda")
-    buf[n_out:] = SENTINEL
-    view = buf[:n_out].view(N, OH, OW, yld)
-    view[..., Cn:] = SENTINEL
-    return buf, view, n_out
-
-
-def _check_out(buf, view, n_out, Cn):
-    torch.cuda.synchronize()
-    assert bool((buf[n_out:] == SENTINEL).all()), "the guard band behind the output was written"
-    assert bool((view[..., Cn:] == SENTINEL).all()), "the padding channels of the output were written"
-    y = view[..., :Cn]
-    assert not bool(torch.isnan(y).any()), "an output element was not written"
-    return y
-
-
 def _debug_dw(x, w, b, K, S, pre_act, post_act, xld=None, yld=None, max_blocks=0):
-    fn = _lib().rd_debug_mbv3_dw
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 12 + [C.c_void_p] * 4
+    fn = _lib.load().rd_debug_mbv3_dw
     N, H, W_, Cn = x.shape
     xld, yld = xld or Cn, yld or Cn
     OH, OW = (H - 1) // S + 1, (W_ - 1) // S + 1
-    xb = _strided(x, xld)
-    buf, view, n_out = _out_buffer(N, OH, OW, Cn, yld)
+    xb = strided(x, xld)
+    buf, view, n_out = out_buffer(N, OH, OW, Cn, yld)
     wk = w.reshape(Cn, K * K).t().contiguous()                           # [K*K][C]
     ms = fn(N, H, W_, Cn, K, S, pre_act, post_act, xld, yld, 0, max_blocks, xb.data_ptr(), wk.data_ptr(), b.data_ptr(), buf.data_ptr())
     assert ms >= 0, "the kernel does not serve this geometry"
-    return _check_out(buf, view, n_out, Cn)
+    return check_out(buf, view, n_out, Cn)
 
 
 def _dw_ref(x, w, b, K, S, pre_act, post_act):
-    xd = _act64(x.permute(0, 3, 1, 2).double(), pre_act)
+    xd = act64(x.permute(0, 3, 1, 2).double(), pre_act)
     y = F.conv2d(F.pad(xd, (K // 2,) * 4), w.double(), b.double(), stride=S, groups=x.shape[3])
-    return _act64(y, post_act).permute(0, 2, 3, 1)
+    return act64(y, post_act).permute(0, 2, 3, 1)
 
 
 @pytest.mark.parametrize("K,S", [(3, 1), (3, 2), (5, 1), (5, 2)])
@@ -280,9 +220,7 @@ def test_depthwise_kernel_grid_stride_loop(K, S):
 
 def _debug_conv(x, w, b, act, res=None):
     """The unfused route's 1x1 layers on the fp32 matrix kernel (rd_debug_conv without split weights): x [N,H,W,Cin] contiguous"""
-    fn = _lib().rd_debug_conv
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 14 + [C.c_void_p] * 8
+    fn = _lib.load().rd_debug_conv
     N, H, W_, Cin = x.shape
     Cout = w.shape[0]
     y = torch.full((N, H, W_, Cout), float("nan"), device="cuda")
@@ -295,18 +233,16 @@ def _debug_conv(x, w, b, act, res=None):
 
 
 def _debug_block(x, p, K, S, act, in_hswish, shortcut, xld, yld):
-    fn = _lib().rd_debug_mbv3_block
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 14 + [C.c_void_p] * 8
+    fn = _lib.load().rd_debug_mbv3_block
     N, H, W_, cin = x.shape
     mid, cout = p["we"].shape[0], p["wl"].shape[0]
     OH, OW = (H - 1) // S + 1, (W_ - 1) // S + 1
-    xb = _strided(x, xld)
-    buf, view, n_out = _out_buffer(N, OH, OW, cout, yld)
+    xb = strided(x, xld)
+    buf, view, n_out = out_buffer(N, OH, OW, cout, yld)
     ms = fn(N, H, W_, cin, mid, cout, K, S, act, int(in_hswish), int(shortcut), xld, yld, 0, xb.data_ptr(), p["we"].data_ptr(), p["be"].data_ptr(),
             p["wd_k"].data_ptr(), p["bd"].data_ptr(), p["wl"].data_ptr(), p["bl"].data_ptr(), buf.data_ptr())
     assert ms >= 0, "the kernel does not serve this geometry"
-    return _check_out(buf, view, n_out, cout)
+    return check_out(buf, view, n_out, cout)
 
 
 def _block_ref(x, p, K, S, act, in_hswish, shortcut, halo_act_bias=False):
@@ -314,16 +250,16 @@ def _block_ref(x, p, K, S, act, in_hswish, shortcut, halo_act_bias=False):
     reading, where the padding of the depthwise layer holds act(expand bias) - to show that the test tells the two apart."""
     xd = x.permute(0, 3, 1, 2).double()
     if in_hswish:
-        xd = _act64(xd, HSWISH)
+        xd = act64(xd, HSWISH)
     mid = p["we"].shape[0]
-    e = _act64(F.conv2d(xd, p["we"].double()[:, :, None, None], p["be"].double()), act)
+    e = act64(F.conv2d(xd, p["we"].double()[:, :, None, None], p["be"].double()), act)
     P = K // 2
     ep = F.pad(e, (P, P, P, P))
     if halo_act_bias:
-        fill = _act64(p["be"].double(), act)[None, :, None, None].expand_as(ep).clone()
+        fill = act64(p["be"].double(), act)[None, :, None, None].expand_as(ep).clone()
         fill[:, :, P:-P, P:-P] = e
         ep = fill
-    d = _act64(F.conv2d(ep, p["wd"].double(), p["bd"].double(), stride=S, groups=mid), act)
+    d = act64(F.conv2d(ep, p["wd"].double(), p["bd"].double(), stride=S, groups=mid), act)
     y = F.conv2d(d, p["wl"].double()[:, :, None, None], p["bl"].double())
     return (y + xd if shortcut else y).permute(0, 2, 3, 1)
 
@@ -397,7 +333,7 @@ def test_range_guard_falls_back_to_the_fp32_mode_bit_for_bit(golden_dir, monkeyp
     big = dict(_state(golden_dir))
     big["neck.ins_conv.1.in_conv.weight"] = big["neck.ins_conv.1.in_conv.weight"] * np.float32(1e6)
     g = np.load(golden_dir / "det3m_seed0_b2_h64_w96.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     ref = RdEngine(KIND, guard="off").load_weights(big).set_precision("fp32").det_forward(x)
     assert bool(torch.isfinite(ref).all())
     raw = RdEngine(KIND, guard="off").load_weights(big)
@@ -412,12 +348,11 @@ def test_range_guard_falls_back_to_the_fp32_mode_bit_for_bit(golden_dir, monkeyp
 @pytest.mark.parametrize("stem", ["multi_PP-OCRv3_det_mobile", "en_PP-OCRv3_det_mobile"])
 def test_session_from_cfg_resolves_the_kind_by_stem(tmp_path, golden_dir, stem):
     from rapiddoc_amd.session import Mi355DetSession
-    p = tmp_path / f"{stem}.safetensors"
-    p.write_bytes(W.to_safetensors_bytes({"model." + k: v for k, v in _state(golden_dir).items()}))
+    p = write_weights(tmp_path, stem, _state(golden_dir))
     sess = Mi355DetSession.from_cfg({"model_path": str(p)})
     assert sess.kind == KIND and sess.engine.kind == KIND
     g = np.load(golden_dir / "det3m_seed0_b2_h64_w96.npz")
-    y = sess(_golden_x(g))
+    y = sess(golden_x(g))
     ps = int(g["maps_ps"])
     assert type(y) is np.ndarray and y.shape == (2, 1, 64, 96) and y.dtype == np.float32
     e = float(np.abs(y[:, :, ::ps, ::ps] - g["maps"]).max())

@@ -15,8 +15,6 @@ ACT_NONE, ACT_RELU = 0, 1
 def _run(N, H, W, Cn, act=ACT_NONE, res=False, widths=None, bias=True, seed=0, K=3, SH=1, use_gap=True):
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_dwconv.restype = C.c_float
-    lib.rd_debug_dwconv.argtypes = [C.c_int] * 8 + [C.c_void_p] * 8
     g = torch.Generator(device="cuda").manual_seed(seed)
     x = torch.rand((N, H, W, Cn), device="cuda", generator=g) - 0.5
     w = torch.rand((K * K, Cn), device="cuda", generator=g) - 0.5

@@ -5,7 +5,6 @@ seeded inputs, in the default `auto` precision AND in native `fp32`.
 
 Bar (north_star): logits / maps / features within 1e-3 absolute, CTC argmax identical wherever the oracle's top-2 logit
 gap exceeds 1e-2 (a tie inside fp32 noise is not a parity failure)."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -123,8 +122,6 @@ def test_split_gemm_wide_operand_range(M, K, N):
     fp32 FMA chain: |y - ref| <= 2e-6 * (|x| @ |w|^T) (each operand keeps 22 of 24 mantissa bits; fp32 accumulate)."""
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_time_gemm.restype = C.c_float
-    lib.rd_debug_time_gemm.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6
     g = torch.Generator(device="cuda").manual_seed(M + K)
     x = _wide_range((M, K), -5, 4, g)
     w = _wide_range((N, K), -5, 0, g)
@@ -151,8 +148,6 @@ def test_split_mixer_wide_operand_range():
     """The fused mixer with activations spanning 1e-5 .. 1e3 and weights 1e-4 .. 0.3 against fp64."""
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_time_mixer.restype = C.c_float
-    lib.rd_debug_time_mixer.argtypes = [C.c_int] * 4 + [C.c_void_p] * 6
     C_, M = 192, 5000
     g = torch.Generator(device="cuda").manual_seed(77)
     x = _wide_range((M, C_), -5, 3, g)

@@ -15,10 +15,7 @@ pytestmark = pytest.mark.gpu
 
 def _lib():
     from rapiddoc_amd import _lib
-    lib = _lib.load()
-    lib.rd_debug_gemm_h1.restype = C.c_float
-    lib.rd_debug_gemm_h1.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    return lib
+    return _lib.load()
 
 
 def _act(v, act):

@@ -130,8 +130,6 @@ CONV_CASES = [
 def test_one_layer_rows_do_not_depend_on_the_launch_size(case):
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_conv.restype = C.c_float
-    lib.rd_debug_conv.argtypes = [C.c_int] * 14 + [C.c_void_p] * 8
     cin, cout, k, s, pad, H, Wd, n_big = (case[n] for n in ("cin", "cout", "k", "s", "pad", "H", "W", "n_big"))
     g = torch.Generator(device="cuda").manual_seed(cin * 1000 + cout + k)
     x = torch.rand((n_big, H, Wd, cin), device="cuda", generator=g) * 2 - 1
@@ -166,8 +164,6 @@ def test_pointwise_gemm_rows_do_not_depend_on_m(K, N, act):
     rows of an M = 70 001 launch == an M = 517 launch == the first rows of an M = 2 049 launch, bit for bit."""
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_time_gemm.restype = C.c_float
-    lib.rd_debug_time_gemm.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6
     g = torch.Generator(device="cuda").manual_seed(K + N)
     M = 70001
     x = torch.rand((M, K), device="cuda", generator=g) * 2 - 1

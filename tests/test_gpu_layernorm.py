@@ -4,8 +4,6 @@ one), one element, the 512 limit, row counts around the 4 rows of a workgroup, r
 
 Reference: fp64 `layer_norm`.  Yardstick: torch's fp32 `layer_norm` on the same inputs; the kernel's max-abs error against fp64 may be at
 most 4 x the yardstick's + 2^-22 max|ref|.  Measured ratios: docs/notebook/rec_tail_kernels.md."""
-import ctypes as C
-
 import pytest
 import torch
 
@@ -17,10 +15,7 @@ WIDTHS = [1, 15, 64, 120, 121, 256, 511, 512]
 
 def _lib():
     from rapiddoc_amd import _lib
-    lib = _lib.load()
-    lib.rd_debug_layernorm.restype = C.c_int
-    lib.rd_debug_layernorm.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float]
-    return lib
+    return _lib.load()
 
 
 def _launch(x, Cn, g, b, eps, yld):

@@ -297,11 +297,8 @@ def test_formula_recognizer_batch_predict(golden_dir):
 def test_split_gemm_tails_match_fp64(M, K, N):
     """The split-fp16 GEMM kernels (LDS-DMA pipeline for K % 32 == 0 and N > 96, register-staged tiles otherwise) on
     ragged shapes: partial M / N tiles, K of 2..23 K tiles and K not a multiple of 32, against an fp64 product."""
-    import ctypes as C
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_time_gemm.restype = C.c_float
-    lib.rd_debug_time_gemm.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6
     g = torch.Generator(device="cuda").manual_seed(M + K + N)
     x = torch.rand((M, K), device="cuda", generator=g) - 0.5
     w = (torch.rand((N, K), device="cuda", generator=g) - 0.5) * 0.2
@@ -342,11 +339,8 @@ def test_fused_mixer_kernels_match_fp64(C_, M, variant):
     phases, +8 per-workgroup phases, +2 flipped residual policy), its prefetching form (400 + the same phase bits: next tile and residual
     re-fetched into the X registers, residual folded into the accumulator - what the engine launches at C = 192) and the
     resident-weights kernel of the narrow blocks (300) on ragged pixel counts incl. several persistent rounds, against fp64."""
-    import ctypes as C
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_time_mixer.restype = C.c_float
-    lib.rd_debug_time_mixer.argtypes = [C.c_int] * 4 + [C.c_void_p] * 6
     g = torch.Generator(device="cuda").manual_seed(C_ + M)
     x = torch.rand((M, C_), device="cuda", generator=g) - 0.5
     w1 = (torch.rand((2 * C_, C_), device="cuda", generator=g) - 0.5) * 0.2
@@ -369,11 +363,8 @@ def test_mixer_residual_from_split_fragments_small_inputs(C_, variant, xs):
     hold instead of reading the tile again (round 5).  hi + lo differs from x by lo's rounding: <= 2^-22 |x| where lo is a normal fp16,
     an ABSOLUTE 2^-25 (res kernel; ws: 2^-25 / the pixel's scale) where it is subnormal - so the output's error against fp64 stays
     bounded by that plus the products' own 2^-21-relative error, for activations of ordinary and of small magnitude."""
-    import ctypes as C
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_time_mixer.restype = C.c_float
-    lib.rd_debug_time_mixer.argtypes = [C.c_int] * 4 + [C.c_void_p] * 6
     M = 4099
     g = torch.Generator(device="cuda").manual_seed(C_ + variant)
     x = (torch.rand((M, C_), device="cuda", generator=g) - 0.5) * 2 * xs
@@ -608,8 +599,6 @@ def _debug_conv(x_nhwc, w_oihw, bias, stride, pads, act=0, res=None, split=True,
     import ctypes as C
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_conv.restype = C.c_float
-    lib.rd_debug_conv.argtypes = [C.c_int] * 14 + [C.c_void_p] * 7 + [C.c_void_p]
     N, H, W_, Cin = x_nhwc.shape
     Cout, _, KH, KW = w_oihw.shape
     K = KH * KW * Cin

@@ -7,7 +7,6 @@ counts.
 Bound of the numeric comparisons against the fixtures: 1e-3 * max(1, max |reference|), the project's rule for whole networks.  The strip
 kernel alone: 2e-5 * max(1, max |ref|), the bound tests/test_gpu_v5_mobile.py uses for the same 25-term arithmetic.  Everything that
 compares the engine with itself on one route is bit for bit.  Figures are printed before they are asserted (-s)."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -17,6 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+from kind_helpers import bound, engine_cache, golden_x, hswish64, line_launch, rand_lines, synth_state, write_weights
+from rapiddoc_amd import _lib
 from rapiddoc_amd import ocr_host
 from rapiddoc_amd import weights as W
 
@@ -28,38 +29,16 @@ STEP = {"korean": 61, "latin": 7}
 ROOT = Path(__file__).resolve().parents[1]
 
 
-def _bound(ref):
-    return TOL * max(1.0, float(np.abs(ref).max()))
-
-
 def _state(golden_dir, lang="korean"):
-    return W.synth_state_dict(W.load_manifest(golden_dir / f"manifest_{KIND}_{lang}.json"), 0, kind=KIND)
+    return synth_state(golden_dir, f"{KIND}_{lang}", kind=KIND)
 
 
-_ENGINES = {}
+_engines = engine_cache(KIND, state=_state)
 
 
 def _engine(golden_dir, precision="auto", lang="korean"):
-    """One engine per (file, precision) for the module (RD_PRECISION is read when the handle is created)."""
-    from rapiddoc_amd.engine import RdEngine
-    if (lang, precision) not in _ENGINES:
-        old = os.environ.get("RD_PRECISION")
-        os.environ["RD_PRECISION"] = precision
-        try:
-            _ENGINES[(lang, precision)] = RdEngine(KIND, guard="off").load_weights(_state(golden_dir, lang))
-        finally:
-            if old is None:
-                del os.environ["RD_PRECISION"]
-            else:
-                os.environ["RD_PRECISION"] = old
-    return _ENGINES[(lang, precision)]
-
-
-def _golden_x(g):
-    if "x" in g.files:
-        return g["x"]
-    assert str(g["x_kind"]) == "pm1"
-    return np.random.default_rng(int(g["x_seed"])).uniform(-1.0, 1.0, tuple(int(v) for v in g["x_shape"])).astype(np.float32)
+    """One engine per (precision, file) for the module"""
+    return _engines(golden_dir, precision, lang)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. parity
@@ -69,7 +48,7 @@ def test_whole_network_matches_the_reference_fixtures(golden_dir, lang, tag, pre
     from rapiddoc_amd.engine import REC_WANT_LOGITS, REC_WANT_NECK
     eng = _engine(golden_dir, precision, lang)
     g = np.load(golden_dir / f"recmv1e_{lang}_seed0_{tag}.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     cs = int(g["backbone_cs"])
     tok = eng.rec_backbone_forward(x).cpu().numpy()                                   # [B, T, 512]
     ref_tok = g["backbone"][:, :, 0, :].transpose(0, 2, 1)                            # [B, 512 / cs, 1, T] -> [B, T, 512 / cs]
@@ -87,12 +66,12 @@ def test_whole_network_matches_the_reference_fixtures(golden_dir, lang, tag, pre
     e_t0 = float(np.abs(logits.cpu().numpy()[:, 0, :] - g["logits_t0"]).max())
     safe = g["top2gap"] > 1e-2
     masked = float(1.0 - safe.mean())
-    print(f"\n[mv1e {lang} {tag} {precision}] max-abs errors: tokens {e_tok:.3e} (bound {_bound(ref_tok):.3e}) neck {e_neck:.3e} "
-          f"(bound {_bound(g['neck']):.3e}) prob {e_prob:.3e} logits {e_log:.3e} / t0 {e_t0:.3e} (bound {_bound(g['logits_sub']):.3e}); "
+    print(f"\n[mv1e {lang} {tag} {precision}] max-abs errors: tokens {e_tok:.3e} (bound {bound(ref_tok, TOL):.3e}) neck {e_neck:.3e} "
+          f"(bound {bound(g['neck'], TOL):.3e}) prob {e_prob:.3e} logits {e_log:.3e} / t0 {e_t0:.3e} (bound {bound(g['logits_sub'], TOL):.3e}); "
           f"masked share {masked:.4f}; idx mismatches at safe positions {int((idx != g['idx'])[safe].sum())}")
     assert not eng.range_overflow()
-    assert e_tok < _bound(ref_tok) and e_neck < _bound(g["neck"]) and e_prob < TOL
-    assert e_log < _bound(g["logits_sub"]) and e_t0 < _bound(g["logits_t0"])
+    assert e_tok < bound(ref_tok, TOL) and e_neck < bound(g["neck"], TOL) and e_prob < TOL
+    assert e_log < bound(g["logits_sub"], TOL) and e_t0 < bound(g["logits_t0"], TOL)
     assert masked <= 0.01
     assert (idx == g["idx"])[safe].all()
     assert (_i.cpu().numpy() == g["idx"])[safe].all()
@@ -102,47 +81,30 @@ def test_whole_network_matches_the_reference_fixtures(golden_dir, lang, tag, pre
 LINE_W = [96, 322, 330, 200, 640]            # w2 / w4 odd for some (161 / 81, 165 / 83), one line far narrower than the launch
 
 
-def _line_launch(lines, W_launch):
-    """Lines [1,3,48,w] -> one zero-padded [n,3,48,W_launch] tensor, the line table on the device, the token offsets."""
-    from rapiddoc_amd.engine import rec_line_table
-    x = torch.zeros((len(lines), 3, 48, W_launch), device="cuda")
-    for i, ln in enumerate(lines):
-        x[i, :, :, : ln.shape[3]] = ln[0]
-    T = [ocr_host.rec_seq_len(ln.shape[3]) for ln in lines]
-    first = np.concatenate([[0], np.cumsum(T)[:-1]])
-    tab = torch.from_numpy(rec_line_table([ln.shape[3] for ln in lines], first)).cuda()
-    return x, tab, T, first
-
-
-def _rand_lines(widths, seed):
-    g = torch.Generator().manual_seed(seed)
-    return [(torch.rand((1, 3, 48, w), generator=g) * 2 - 1).cuda() for w in widths]
-
-
 @pytest.mark.parametrize("precision", ["auto", "fp32"])
 def test_lines_of_different_widths_in_one_launch_equal_each_line_alone(golden_dir, precision):
     from rapiddoc_amd.engine import REC_WANT_NECK
     eng = _engine(golden_dir, precision)
     g = np.load(golden_dir / "recmv1e_width_pair.npz")
-    lines = _rand_lines(LINE_W, seed=31)
+    lines = rand_lines(LINE_W, seed=31)
     lines[3] = torch.from_numpy(g["x200"]).cuda()                                     # the 200-px line of the width-pair fixture
     alone = [eng.rec_backbone_forward(ln)[0].clone() for ln in lines]
-    x, tab, T, first = _line_launch(lines, 640)
+    x, tab, T, first = line_launch(lines, 640)
     tokens = torch.full((sum(T) + 3, eng.rec_token_dim), 7.0, device="cuda")
     eng.rec_backbone_forward_lines(x, tab, tokens)
     assert float((tokens[sum(T):] - 7.0).abs().max()) == 0.0                          # nothing past the last line's tokens
     for i, (a, t, f) in enumerate(zip(alone, T, first)):
         assert torch.equal(tokens[f: f + t], a), (precision, LINE_W[i], float((tokens[f: f + t] - a).abs().max()))
     # line 0 among other neighbours of other widths
-    others = [lines[0]] + _rand_lines([640, 100, 402], seed=32)
-    x2, tab2, T2, _f2 = _line_launch(others, 640)
+    others = [lines[0]] + rand_lines([640, 100, 402], seed=32)
+    x2, tab2, T2, _f2 = line_launch(others, 640)
     tokens2 = torch.zeros((sum(T2), eng.rec_token_dim), device="cuda")
     eng.rec_backbone_forward_lines(x2, tab2, tokens2)
     assert torch.equal(tokens2[: T2[0]], alone[0])
     # against the reference: the 200-px line at its own width and at table width 320, backbone and (through the ragged tail's input) neck
     ref200 = g["backbone200"][0, :, 0, :].T
     e200 = float(np.abs(tokens[first[3]: first[3] + T[3]].cpu().numpy() - ref200).max())
-    x3, tab3, T3, _f3 = _line_launch([torch.nn.functional.pad(lines[3], (0, 120))] + [lines[4]], 640)
+    x3, tab3, T3, _f3 = line_launch([torch.nn.functional.pad(lines[3], (0, 120))] + [lines[4]], 640)
     assert T3[0] == 40
     tokens3 = torch.zeros((sum(T3), eng.rec_token_dim), device="cuda")
     eng.rec_backbone_forward_lines(x3, tab3, tokens3)
@@ -151,11 +113,11 @@ def test_lines_of_different_widths_in_one_launch_equal_each_line_alone(golden_di
     n200 = eng.rec_forward(lines[3], REC_WANT_NECK)[2].cpu().numpy()
     n320 = eng.rec_forward(torch.nn.functional.pad(lines[3], (0, 120)), REC_WANT_NECK)[2].cpu().numpy()
     en200, en320 = float(np.abs(n200 - g["neck200"]).max()), float(np.abs(n320 - g["neck320"]).max())
-    print(f"\n[mv1e lines {precision}] 200-px line in a 640 launch: at width 200 {e200:.3e} (bound {_bound(ref200):.3e}), at table width 320 "
-          f"{e320:.3e} (bound {_bound(ref320):.3e}); neck alone {en200:.3e} / {en320:.3e} (bound {_bound(g['neck200']):.3e}), the two widths "
+    print(f"\n[mv1e lines {precision}] 200-px line in a 640 launch: at width 200 {e200:.3e} (bound {bound(ref200, TOL):.3e}), at table width 320 "
+          f"{e320:.3e} (bound {bound(ref320, TOL):.3e}); neck alone {en200:.3e} / {en320:.3e} (bound {bound(g['neck200'], TOL):.3e}), the two widths "
           f"are {float(g['d'].min()):.3e} apart")
-    assert e200 < _bound(ref200) and e320 < _bound(ref320)
-    assert en200 < _bound(g["neck200"]) and en320 < _bound(g["neck320"])
+    assert e200 < bound(ref200, TOL) and e320 < bound(ref320, TOL)
+    assert en200 < bound(g["neck200"], TOL) and en320 < bound(g["neck320"], TOL)
     assert not eng.range_overflow()
 
 
@@ -247,20 +209,19 @@ def test_both_depthwise_routes_are_invariant_and_agree_within_the_bound(golden_d
         assert bool(got[route]["same"]) and bool(got[route]["same50"]) and not bool(got[route]["overflow"]), route
     a, b = got["0"]["tokens"], got["1"]["tokens"]
     e = float(np.abs(a - b).max())
-    print(f"\n[mv1e routes] direct against strip: max-abs difference of the tokens {e:.3e} (bound {_bound(a):.3e}, max |tokens| {float(np.abs(a).max()):.2f})")
-    assert e < _bound(a)
+    print(f"\n[mv1e routes] direct against strip: max-abs difference of the tokens {e:.3e} (bound {bound(a, TOL):.3e}, max |tokens| {float(np.abs(a).max()):.2f})")
+    assert e < bound(a, TOL)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. session
 def test_session_from_cfg_chunk_of_six_eager_and_lazy(tmp_path, golden_dir):
     from rapiddoc_amd.session import LazySoftmax, Mi355RecSession
     st = _state(golden_dir)
-    p = tmp_path / "korean_PP-OCRv4_rec_mobile.safetensors"
-    p.write_bytes(W.to_safetensors_bytes({"model." + k: v for k, v in st.items()}))
+    p = write_weights(tmp_path, "korean_PP-OCRv4_rec_mobile", st)
     sess = Mi355RecSession.from_cfg({"model_path": str(p)})
     assert sess.kind == KIND and sess.engine.num_classes == 3690
     g = np.load(golden_dir / "recmv1e_korean_seed0_b6_w1088.npz")
-    x = _golden_x(g)                                                   # a chunk of six at full width
+    x = golden_x(g)                                                   # a chunk of six at full width
     sess.lazy_softmax = False
     eager = sess(x)
     assert type(eager) is np.ndarray and eager.shape == (6, 136, 3690) and float(np.abs(eager.sum(axis=2) - 1.0).max()) < 1e-4
@@ -325,22 +286,6 @@ def test_page_pipeline_strict_equals_the_reference_chunk_loop_through_the_sessio
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5. the strip kernel alone
-def _hswish64(v):
-    return v * torch.clamp(v + 3.0, 0.0, 6.0) / 6.0
-
-
-def _dw_lib():
-    from rapiddoc_amd import _lib
-    lib = _lib.load()
-    lib.rd_debug_dw5_strip.restype = C.c_float
-    lib.rd_debug_dw5_strip.argtypes = [C.c_int] * 11 + [C.c_void_p] * 7
-    lib.rd_debug_lcv3_dw.restype = C.c_float
-    lib.rd_debug_lcv3_dw.argtypes = [C.c_int] * 9 + [C.c_void_p] * 8
-    lib.rd_debug_mv1e_pool.restype = C.c_int
-    lib.rd_debug_mv1e_pool.argtypes = [C.c_int] * 4 + [C.c_void_p] * 3
-    return lib
-
-
 @pytest.mark.parametrize("sh,sw", [(1, 1), (2, 1), (1, 2)])
 @pytest.mark.parametrize("pre_act,post_act", [(1, 1), (0, 1), (1, 0), (0, 0)])
 @pytest.mark.parametrize("H,W_,Cn", [(6, 37, 48), (3, 70, 16), (2, 37, 16), (1, 1, 48), (6, 70, 16)])
@@ -352,7 +297,7 @@ def test_strip_kernel_alone_matches_float64(sh, sw, pre_act, post_act, H, W_, Cn
     all three branches of the hardswish are taken.  Compared inside each line's output width; beyond it zeros; a NaN guard band around
     and between the pixels (the padding channels of y) stays NaN.  Bound 2e-5 * max(1, max |ref|) (25 fp32 multiply-adds of O(1) terms, two
     hardswishes, two affines).  Where post_act = 1 also against `lcv3_dw_kernel` on the same operands, within twice the bound."""
-    lib = _dw_lib()
+    lib = _lib.load()
     N, xld, yld = 3, Cn + 8, Cn + 4
     g = torch.Generator(device="cuda").manual_seed(1000 * H + 10 * W_ + 100 * sh + sw + pre_act + 2 * post_act + Cn)
     xbuf = torch.full((N, H, W_, xld), float("nan"), device="cuda")
@@ -380,11 +325,11 @@ def test_strip_kernel_alone_matches_float64(sh, sw, pre_act, post_act, H, W_, Cn
     for n in range(N):
         xin = x[n, :, : lin[n]].double().cpu().permute(2, 0, 1)[None]                 # the line alone, at its own width
         if pre_act:
-            xin = float(aff[0]) * _hswish64(xin) + float(aff[1])
+            xin = float(aff[0]) * hswish64(xin) + float(aff[1])
         wd = w.double().cpu().t().reshape(Cn, 1, 5, 5)
         ref = torch.nn.functional.conv2d(xin, wd, b.double().cpu(), stride=(sh, sw), padding=2, groups=Cn)
         if post_act:
-            ref = float(aff[2]) * _hswish64(ref) + float(aff[3])
+            ref = float(aff[2]) * hswish64(ref) + float(aff[3])
         ref = ref[0].permute(1, 2, 0)                                                 # [OH][lout][C]
         assert ref.shape[:2] == (OH, lout[n])
         worst = max(worst, float((yd[n, :, : lout[n]] - ref).abs().max()))
@@ -404,7 +349,7 @@ def test_strip_kernel_alone_matches_float64(sh, sw, pre_act, post_act, H, W_, Cn
 
 
 def test_strip_kernel_declines_what_it_does_not_cover():
-    lib = _dw_lib()
+    lib = _lib.load()
     aff = np.array([1, 0, 1, 0], np.float32)
     z = torch.zeros(8 * 7 * 40 * 32, device="cuda")
     args = (aff.ctypes.data, z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), None, None)
@@ -420,11 +365,11 @@ def test_strip_kernel_declines_what_it_does_not_cover():
 # ---------------------------------------------------------------------------------------------------------------- 6. the pool kernel alone
 def test_pool_kernel_alone_ignores_row_2_and_follows_the_line_table():
     from rapiddoc_amd.engine import rec_line_table
-    lib = _dw_lib()
+    lib = _lib.load()
     N, H, W4, Cn = 3, 3, 21, 32
     g = torch.Generator(device="cuda").manual_seed(5)
     x = (torch.rand((N, H, W4, Cn), device="cuda", generator=g) - 0.5) * 8
-    ref = _hswish64(x[:, :2, :20].double()).reshape(N, 2, 10, 2, Cn).mean(dim=(1, 3))            # [N][10][C]
+    ref = hswish64(x[:, :2, :20].double()).reshape(N, 2, 10, 2, Cn).mean(dim=(1, 3))            # [N][10][C]
     y = torch.full((N, W4 // 2, Cn), 7.0, device="cuda")
     assert lib.rd_debug_mv1e_pool(N, H, W4, Cn, x.data_ptr(), y.data_ptr(), None) == 0
     e = float((y.double() - ref).abs().max())

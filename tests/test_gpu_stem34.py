@@ -9,8 +9,6 @@ odd map sizes (tile edges in both directions: 4 x 32 / 2 x 64 output tiles, odd 
 column is or is not read), row strides wider than the channel count on both sides (channel slices of concat buffers), images smaller than
 a tile, many tiles per workgroup of the persistent grid, activations; bit-exactness of an image's rows whatever the launch holds; the
 range flag."""
-import ctypes as C
-
 import pytest
 import torch
 
@@ -19,10 +17,7 @@ pytestmark = pytest.mark.gpu
 
 def _lib():
     from rapiddoc_amd import _lib
-    lib = _lib.load()
-    lib.rd_debug_stem34.restype = C.c_float
-    lib.rd_debug_stem34.argtypes = [C.c_int] * 11 + [C.c_void_p] * 7
-    return lib
+    return _lib.load()
 
 
 def _run(x, w3, b3, w4, b4, act3=1, act4=1, xld=None, yld=None, iters=0, flag=None):

@@ -13,7 +13,6 @@ LayerNorm at C = 768 through `rd_debug_layernorm` against fp64.
 The encoder against the four reference-minted fixtures in the `auto` and `fp32` precisions: every tap (patch embedding, layers 0 and 11,
 memory) within 1e-3 max(1, max|ref|), the project's fixture bound; image 1 of the B = 2 fixture equal to that image alone, bit for bit;
 repeated forwards (the hipGraph replay) equal to the first; shapes outside the kernel's limits declined with a message."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -25,19 +24,9 @@ import unitable_reference as R
 pytestmark = pytest.mark.gpu
 
 HD = 64
-_LIB = {}
-
-
 def _lib():
-    if not _LIB:
-        from rapiddoc_amd import _lib
-        lib = _lib.load()
-        lib.rd_debug_vit_attention.restype = C.c_int
-        lib.rd_debug_vit_attention.argtypes = [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p]
-        lib.rd_debug_layernorm.restype = C.c_int
-        lib.rd_debug_layernorm.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float]
-        _LIB["lib"] = lib
-    return _LIB["lib"]
+    from rapiddoc_amd import _lib
+    return _lib.load()
 
 
 # ---------------------------------------------------------------------------------------------------------------- attention alone

@@ -4,14 +4,13 @@ lines launched alone, its stages against each other, the range guard, and the se
 
 Bound of the numeric comparisons against the fixtures: 1e-3 * max(1, max |reference|), the rule tests/test_gpu_det_server.py uses for the
 neck output.  Everything that compares the engine with itself is bit for bit.  Figures are printed before they are asserted (-s)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
+from kind_helpers import bound, engine_cache, golden_x, hswish64, line_launch, rand_lines, synth_state, write_weights
+from rapiddoc_amd import _lib
 from rapiddoc_amd import ocr_host
-from rapiddoc_amd import weights as W
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -19,38 +18,12 @@ KIND = "ppocrv5_rec_mobile"
 TAGS = ["b2_w320", "b1_w96", "b3_w640", "b6_w1088"]
 
 
-def _bound(ref):
-    return TOL * max(1.0, float(np.abs(ref).max()))
-
-
 def _state(golden_dir, kind=KIND):
-    return W.synth_state_dict(W.load_manifest(golden_dir / f"manifest_{kind}.json"), 0)
+    return synth_state(golden_dir, kind)
 
 
-_ENGINES = {}
-
-
-def _engine(golden_dir, precision="auto", kind=KIND):
-    """One engine per (kind, precision) for the module (RD_PRECISION is read when the handle is created)."""
-    from rapiddoc_amd.engine import RdEngine
-    if (kind, precision) not in _ENGINES:
-        old = os.environ.get("RD_PRECISION")
-        os.environ["RD_PRECISION"] = precision
-        try:
-            _ENGINES[(kind, precision)] = RdEngine(kind, guard="off").load_weights(_state(golden_dir, kind))
-        finally:
-            if old is None:
-                del os.environ["RD_PRECISION"]
-            else:
-                os.environ["RD_PRECISION"] = old
-    return _ENGINES[(kind, precision)]
-
-
-def _golden_x(g):
-    if "x" in g.files:
-        return g["x"]
-    assert str(g["x_kind"]) == "pm1"
-    return np.random.default_rng(int(g["x_seed"])).uniform(-1.0, 1.0, tuple(int(v) for v in g["x_shape"])).astype(np.float32)
+_engine = engine_cache(KIND)
+_server_engine = engine_cache("ppocrv5_rec_server")
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. parity
@@ -60,7 +33,7 @@ def test_whole_network_matches_the_reference_fixtures(golden_dir, tag, precision
     from rapiddoc_amd.engine import REC_WANT_NECK
     eng = _engine(golden_dir, precision)
     g = np.load(golden_dir / f"rec5m_seed0_{tag}.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     cs = int(g["backbone_cs"])
     tok = eng.rec_backbone_forward(x).cpu().numpy()                                   # [B, T, 480]
     ref_tok = g["backbone"][:, :, 0, :].transpose(0, 2, 1)                            # [B, 480 / cs, 1, T] -> [B, T, 480 / cs]
@@ -72,11 +45,11 @@ def test_whole_network_matches_the_reference_fixtures(golden_dir, tag, precision
     e_prob = float(np.abs(prob - g["prob"]).max())
     safe = g["top2gap"] > 1e-2
     masked = float(1.0 - safe.mean())
-    print(f"\n[v5 mobile {tag} {precision}] max-abs errors: tokens {e_tok:.3e} (bound {_bound(ref_tok):.3e}) neck {e_neck:.3e} "
-          f"(bound {_bound(g['neck']):.3e}) prob {e_prob:.3e}; masked share {masked:.4f}; "
+    print(f"\n[v5 mobile {tag} {precision}] max-abs errors: tokens {e_tok:.3e} (bound {bound(ref_tok, TOL):.3e}) neck {e_neck:.3e} "
+          f"(bound {bound(g['neck'], TOL):.3e}) prob {e_prob:.3e}; masked share {masked:.4f}; "
           f"idx mismatches at safe positions {int((idx != g['idx'])[safe].sum())}")
     assert not eng.range_overflow()
-    assert e_tok < _bound(ref_tok) and e_neck < _bound(g["neck"]) and e_prob < TOL
+    assert e_tok < bound(ref_tok, TOL) and e_neck < bound(g["neck"], TOL) and e_prob < TOL
     assert masked <= 0.01
     assert (idx == g["idx"])[safe].all()
 
@@ -85,54 +58,37 @@ def test_whole_network_matches_the_reference_fixtures(golden_dir, tag, precision
 LINE_W = [96, 322, 330, 200, 640]            # w2 / w4 odd for some (161 / 81, 165 / 83), one line far narrower than the launch
 
 
-def _line_launch(lines, W_launch):
-    """Lines [1,3,48,w] -> one zero-padded [n,3,48,W_launch] tensor, the line table on the device, the token offsets."""
-    from rapiddoc_amd.engine import rec_line_table
-    x = torch.zeros((len(lines), 3, 48, W_launch), device="cuda")
-    for i, ln in enumerate(lines):
-        x[i, :, :, : ln.shape[3]] = ln[0]
-    T = [ocr_host.rec_seq_len(ln.shape[3]) for ln in lines]
-    first = np.concatenate([[0], np.cumsum(T)[:-1]])
-    tab = torch.from_numpy(rec_line_table([ln.shape[3] for ln in lines], first)).cuda()
-    return x, tab, T, first
-
-
-def _rand_lines(widths, seed):
-    g = torch.Generator().manual_seed(seed)
-    return [(torch.rand((1, 3, 48, w), generator=g) * 2 - 1).cuda() for w in widths]
-
-
 @pytest.mark.parametrize("precision", ["auto", "fp32"])
 def test_lines_of_different_widths_in_one_launch_equal_each_line_alone(golden_dir, precision):
     eng = _engine(golden_dir, precision)
     g = np.load(golden_dir / "rec5m_width_pair.npz")
-    lines = _rand_lines(LINE_W, seed=31)
+    lines = rand_lines(LINE_W, seed=31)
     lines[3] = torch.from_numpy(g["x200"]).cuda()                                     # the 200-px line of the width-pair fixture
     alone = [eng.rec_backbone_forward(ln)[0].clone() for ln in lines]
-    x, tab, T, first = _line_launch(lines, 640)
+    x, tab, T, first = line_launch(lines, 640)
     tokens = torch.full((sum(T) + 3, eng.rec_token_dim), 7.0, device="cuda")
     eng.rec_backbone_forward_lines(x, tab, tokens)
     assert float((tokens[sum(T):] - 7.0).abs().max()) == 0.0                          # nothing past the last line's tokens
     for i, (a, t, f) in enumerate(zip(alone, T, first)):
         assert torch.equal(tokens[f: f + t], a), (precision, LINE_W[i], float((tokens[f: f + t] - a).abs().max()))
     # line 0 among other neighbours of other widths
-    others = [lines[0]] + _rand_lines([640, 100, 402], seed=32)
-    x2, tab2, T2, _f2 = _line_launch(others, 640)
+    others = [lines[0]] + rand_lines([640, 100, 402], seed=32)
+    x2, tab2, T2, _f2 = line_launch(others, 640)
     tokens2 = torch.zeros((sum(T2), eng.rec_token_dim), device="cuda")
     eng.rec_backbone_forward_lines(x2, tab2, tokens2)
     assert torch.equal(tokens2[: T2[0]], alone[0])
     # against the reference: the 200-px line at its own width and at table width 320
     ref200 = g["backbone200"][0, :, 0, :].T
     e200 = float(np.abs(tokens[first[3]: first[3] + T[3]].cpu().numpy() - ref200).max())
-    x3, tab3, T3, _f3 = _line_launch([torch.nn.functional.pad(lines[3], (0, 120))] + [lines[4]], 640)
+    x3, tab3, T3, _f3 = line_launch([torch.nn.functional.pad(lines[3], (0, 120))] + [lines[4]], 640)
     assert T3[0] == 40
     tokens3 = torch.zeros((sum(T3), eng.rec_token_dim), device="cuda")
     eng.rec_backbone_forward_lines(x3, tab3, tokens3)
     ref320 = g["backbone320"][0, :, 0, :].T
     e320 = float(np.abs(tokens3[:40].cpu().numpy() - ref320).max())
-    print(f"\n[v5 mobile lines {precision}] 200-px line in a 640 launch: at width 200 {e200:.3e} (bound {_bound(ref200):.3e}), at table width 320 "
-          f"{e320:.3e} (bound {_bound(ref320):.3e})")
-    assert e200 < _bound(ref200) and e320 < _bound(ref320)
+    print(f"\n[v5 mobile lines {precision}] 200-px line in a 640 launch: at width 200 {e200:.3e} (bound {bound(ref200, TOL):.3e}), at table width 320 "
+          f"{e320:.3e} (bound {bound(ref320, TOL):.3e})")
+    assert e200 < bound(ref200, TOL) and e320 < bound(ref320, TOL)
     assert not eng.range_overflow()
 
 
@@ -181,10 +137,6 @@ def test_two_stages_equal_the_whole_network_bit_for_bit(golden_dir, precision):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. the depthwise kernel alone
-def _hswish64(v):
-    return v * torch.clamp(v + 3.0, 0.0, 6.0) / 6.0
-
-
 @pytest.mark.parametrize("k,sh,sw", [(3, 1, 1), (3, 2, 1), (3, 1, 2), (5, 1, 1), (5, 2, 1)])
 @pytest.mark.parametrize("pre_act", [0, 1])
 @pytest.mark.parametrize("Cn", [32, 240])
@@ -195,11 +147,7 @@ def test_depthwise_layer_alone_matches_float64(k, sh, sw, pre_act, Cn):
     taken on load and in the epilogue.  Compared inside each line's output width; beyond it the kernel writes zeros.  Bound
     2e-5 * max(1, max |ref|): at most 25 fp32 multiply-adds of O(1) terms, two hardswishes and two affines per output - a few 2^-24
     relative roundings of values up to max |ref| - as the bound of the 9x9 and local-tail kernels' tests."""
-    import ctypes as C
-    from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_lcv3_dw.restype = C.c_float
-    lib.rd_debug_lcv3_dw.argtypes = [C.c_int] * 9 + [C.c_void_p] * 8
     N, H, W_ = 3, 24, 37
     g = torch.Generator(device="cuda").manual_seed(100 * k + 10 * sh + sw + pre_act + Cn)
     x = (torch.rand((N, H, W_, Cn), device="cuda", generator=g) - 0.5) * 8
@@ -222,10 +170,10 @@ def test_depthwise_layer_alone_matches_float64(k, sh, sw, pre_act, Cn):
     for n in range(N):
         xin = x[n, :, : lin[n]].double().cpu().permute(2, 0, 1)[None]                 # the line alone, at its own width
         if pre_act:
-            xin = float(aff[0]) * _hswish64(xin) + float(aff[1])
+            xin = float(aff[0]) * hswish64(xin) + float(aff[1])
         wd = w.double().cpu().t().reshape(Cn, 1, k, k)
         ref = torch.nn.functional.conv2d(xin, wd, b.double().cpu(), stride=(sh, sw), padding=k // 2, groups=Cn)
-        ref = (float(aff[2]) * _hswish64(ref) + float(aff[3]))[0].permute(1, 2, 0)     # [OH][lout][C]
+        ref = (float(aff[2]) * hswish64(ref) + float(aff[3]))[0].permute(1, 2, 0)     # [OH][lout][C]
         assert ref.shape[1] == lout[n]
         worst = max(worst, float((y[n, :, : lout[n]] - ref).abs().max()))
         scale = max(scale, float(ref.abs().max()))
@@ -238,19 +186,6 @@ def test_depthwise_layer_alone_matches_float64(k, sh, sw, pre_act, Cn):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4b. the fused block kernel alone
-def _lcv3_block_lib():
-    import ctypes as C
-    from rapiddoc_amd import _lib
-    lib = _lib.load()
-    lib.rd_debug_lcv3_block.restype = C.c_float
-    lib.rd_debug_lcv3_block.argtypes = [C.c_int] * 9 + [C.c_void_p] * 9
-    lib.rd_debug_lcv3_dw.restype = C.c_float
-    lib.rd_debug_lcv3_dw.argtypes = [C.c_int] * 9 + [C.c_void_p] * 8
-    lib.rd_debug_conv.restype = C.c_float
-    lib.rd_debug_conv.argtypes = [C.c_int] * 14 + [C.c_void_p] * 8
-    return lib
-
-
 @pytest.mark.parametrize("split", [1, 0])
 @pytest.mark.parametrize("pre_act", [0, 1])
 @pytest.mark.parametrize("cin,cout", [(16, 32), (32, 64), (64, 64)])
@@ -264,7 +199,7 @@ def test_fused_block_alone_matches_float64_and_the_separate_operators(cin, cout,
     Bound 2e-5 * max(1, max |ref|), as the 9x9 and local-tail kernels' tests: 9 + cin <= 73 fp32 multiply-adds of O(1) terms and three
     hardswishes per output; the split product drops the lo x lo term, 2^-22 of a product.  The range flag stays down in both routes; one
     input element of 1e5 raises it on the split route only."""
-    lib = _lcv3_block_lib()
+    lib = _lib.load()
     N, H, W_ = 3, 24, 37
     g = torch.Generator(device="cuda").manual_seed(1000 + cin + cout + 2 * pre_act + split)
     x = (torch.rand((N, H, W_, cin), device="cuda", generator=g) - 0.5) * 8
@@ -302,11 +237,11 @@ def test_fused_block_alone_matches_float64_and_the_separate_operators(cin, cout,
     for n in range(N):
         xin = x[n, :, : lin[n]].double().cpu().permute(2, 0, 1)[None]                 # the line alone, at its own width
         if pre_act:
-            xin = float(aff[0]) * _hswish64(xin) + float(aff[1])
+            xin = float(aff[0]) * hswish64(xin) + float(aff[1])
         a = torch.nn.functional.conv2d(xin, dw.double().cpu().t().reshape(cin, 1, 3, 3), db.double().cpu(), padding=1, groups=cin)
-        a = float(aff[2]) * _hswish64(a) + float(aff[3])
+        a = float(aff[2]) * hswish64(a) + float(aff[3])
         ref = torch.nn.functional.conv2d(a, pw.double().cpu().reshape(cout, cin, 1, 1), pb.double().cpu())
-        ref = (float(aff[4]) * _hswish64(ref) + float(aff[5]))[0].permute(1, 2, 0)     # [H][lw][cout]
+        ref = (float(aff[4]) * hswish64(ref) + float(aff[5]))[0].permute(1, 2, 0)     # [H][lw][cout]
         worst = max(worst, float((y_act[n, :, : lin[n]] - ref).abs().max()))
         scale = max(scale, float(ref.abs().max()))
         s_n = sep[n, :, : lin[n]].double().cpu()
@@ -329,7 +264,7 @@ def test_range_guard_falls_back_to_the_fp32_mode_bit_for_bit(golden_dir, monkeyp
     monkeypatch.setenv("RD_PRECISION", "auto")
     big = dict(_state(golden_dir))
     big["backbone.conv1.conv.weight"] = big["backbone.conv1.conv.weight"] * 3e5
-    x = torch.from_numpy(_golden_x(np.load(golden_dir / "rec5m_seed0_b2_w320.npz"))).cuda()
+    x = torch.from_numpy(golden_x(np.load(golden_dir / "rec5m_seed0_b2_w320.npz"))).cuda()
     ref = RdEngine(KIND, guard="off").load_weights(big).set_precision("fp32").rec_forward(x)
     raw = RdEngine(KIND, guard="off").load_weights(big)
     raw.rec_forward(x)
@@ -341,19 +276,13 @@ def test_range_guard_falls_back_to_the_fp32_mode_bit_for_bit(golden_dir, monkeyp
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6. session
-def _write(tmp_path, state):
-    p = tmp_path / "ch_PP-OCRv5_rec_mobile.safetensors"
-    p.write_bytes(W.to_safetensors_bytes({"model." + k: v for k, v in state.items()}))
-    return p
-
-
 def test_session_from_cfg_chunk_of_six_eager_and_lazy(tmp_path, golden_dir):
     from rapiddoc_amd.session import LazySoftmax, Mi355RecSession
     st = _state(golden_dir)
-    sess = Mi355RecSession.from_cfg({"model_path": str(_write(tmp_path, st))})
+    sess = Mi355RecSession.from_cfg({"model_path": str(write_weights(tmp_path, "ch_PP-OCRv5_rec_mobile", st))})
     assert sess.kind == KIND and sess.engine.num_classes == 18385
     g = np.load(golden_dir / "rec5m_seed0_b6_w1088.npz")
-    x = _golden_x(g)                                                   # a chunk of six at full width
+    x = golden_x(g)                                                   # a chunk of six at full width
     sess.lazy_softmax = False
     eager = sess(x)
     assert type(eager) is np.ndarray and eager.shape == (6, 136, 18385) and float(np.abs(eager.sum(axis=2) - 1.0).max()) < 1e-4
@@ -399,7 +328,7 @@ def test_page_pipeline_strict_equals_the_reference_chunk_loop_through_the_sessio
     assert len(pipe.last_rec_batches) < len(set(line_w.values()))       # fewer launches than distinct widths
     cw, ch, rot, _keep = pipe.last_rec_crop_sizes
     crop_hw = [(int(cw[i]), int(ch[i])) if rot[i] else (int(ch[i]), int(cw[i])) for i in range(n)]
-    sess = Mi355RecSession.from_cfg({"model_path": str(_write(tmp_path, states[KIND]))})
+    sess = Mi355RecSession.from_cfg({"model_path": str(write_weights(tmp_path, "ch_PP-OCRv5_rec_mobile", states[KIND]))})
     ratios = np.array([w / float(h) for h, w in crop_hw])
     indices = np.argsort(ratios)
     out = [None] * n
@@ -418,7 +347,7 @@ def test_page_pipeline_strict_equals_the_reference_chunk_loop_through_the_sessio
 # ---------------------------------------------------------------------------------------------------------------- 8. refusals
 def test_the_server_kind_still_refuses_per_line_widths(golden_dir):
     from rapiddoc_amd.engine import EngineError, rec_line_table
-    eng = _engine(golden_dir, "auto", "ppocrv5_rec_server")
+    eng = _server_engine(golden_dir, "auto")
     x = torch.zeros((2, 3, 48, 320), device="cuda")
     tab = torch.from_numpy(rec_line_table([320, 200], [0, 40])).cuda()
     tokens = torch.zeros((65, eng.rec_token_dim), device="cuda")

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from kind_helpers import engine_cache, golden_x, synth_state, write_weights
+from rapiddoc_amd import _lib
 from rapiddoc_amd import ocr_host
 from rapiddoc_amd import weights as W
 
@@ -23,33 +25,10 @@ TAGS = ["b2_w320", "b1_w96", "b3_w640", "b6_w1088"]
 
 
 def _state(golden_dir, kind=KIND):
-    return W.synth_state_dict(W.load_manifest(golden_dir / f"manifest_{kind}.json"), 0)
+    return synth_state(golden_dir, kind)
 
 
-_ENGINES = {}
-
-
-def _engine(golden_dir, precision="auto"):
-    """One engine per precision for the module (RD_PRECISION is read when the handle is created)."""
-    from rapiddoc_amd.engine import RdEngine
-    if precision not in _ENGINES:
-        old = os.environ.get("RD_PRECISION")
-        os.environ["RD_PRECISION"] = precision
-        try:
-            _ENGINES[precision] = RdEngine(KIND).load_weights(_state(golden_dir))
-        finally:
-            if old is None:
-                del os.environ["RD_PRECISION"]
-            else:
-                os.environ["RD_PRECISION"] = old
-    return _ENGINES[precision]
-
-
-def _golden_x(g):
-    if "x" in g.files:
-        return g["x"]
-    assert str(g["x_kind"]) == "pm1"
-    return np.random.default_rng(int(g["x_seed"])).uniform(-1.0, 1.0, tuple(int(v) for v in g["x_shape"])).astype(np.float32)
+_engine = engine_cache(KIND, guard="sync")
 
 
 @pytest.mark.parametrize("precision", ["auto", "fp32"])
@@ -58,7 +37,7 @@ def test_whole_network_matches_the_reference_fixtures(golden_dir, tag, precision
     from rapiddoc_amd.engine import REC_WANT_LOGITS, REC_WANT_NECK, REC_WANT_SOFTMAX
     eng = _engine(golden_dir, precision)
     g = np.load(golden_dir / f"rec5s_seed0_{tag}.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     cs = int(g["backbone_cs"])
     tok = eng.rec_backbone_forward(x).cpu().numpy()                                   # [B, T, 2048]
     ref_tok = g["backbone"][:, :, 0, :].transpose(0, 2, 1)                            # [B, 2048 / cs, 1, T] -> [B, T, 2048 / cs]
@@ -97,7 +76,7 @@ def test_ctc_flags_agree_with_the_fused_head(golden_dir, precision):
     from rapiddoc_amd.engine import REC_UNFUSED_CTC, REC_WANT_LOGITS, REC_WANT_SOFTMAX
     eng = _engine(golden_dir, precision)
     g = np.load(golden_dir / "rec5s_seed0_b3_w640.npz")
-    x = torch.from_numpy(_golden_x(g)).cuda()
+    x = torch.from_numpy(golden_x(g)).cuda()
     safe = g["top2gap"] > 1e-2
     i0, p0, _ = eng.rec_forward(x)
     i0, p0 = i0.cpu().numpy(), p0.cpu().numpy()
@@ -196,11 +175,7 @@ def test_a_line_does_not_depend_on_the_launch_it_rides_in(golden_dir, precision)
 
 
 def _seqconv(x0, x1, w, b, lens, split, act=3, T=0):
-    from rapiddoc_amd import _lib
     lib = _lib.load()
-    lib.rd_debug_seqconv.restype = C.c_float
-    lib.rd_debug_seqconv.argtypes = [C.c_int] * 8 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                     C.c_void_p]
     M, C0 = x0.shape
     C1 = x1.shape[1] if x1 is not None else 0
     N = w.shape[0]
@@ -290,19 +265,13 @@ def test_per_line_widths_inside_a_launch_are_refused(golden_dir):
         eng.rec_backbone_forward_lines(x, tab, tokens)
 
 
-def _write(tmp_path, state):
-    p = tmp_path / "ch_PP-OCRv5_rec_server.safetensors"
-    p.write_bytes(W.to_safetensors_bytes({"model." + k: v for k, v in state.items()}))
-    return p
-
-
 def test_session_from_cfg_chunk_of_six_eager_and_lazy(tmp_path, golden_dir):
     from rapiddoc_amd.session import LazySoftmax, Mi355RecSession
     st = _state(golden_dir)
-    sess = Mi355RecSession.from_cfg({"model_path": str(_write(tmp_path, st))})
+    sess = Mi355RecSession.from_cfg({"model_path": str(write_weights(tmp_path, "ch_PP-OCRv5_rec_server", st))})
     assert sess.kind == KIND and sess.engine.num_classes == 18385
     g = np.load(golden_dir / "rec5s_seed0_b6_w1088.npz")
-    x = _golden_x(g)                                                   # a chunk of six at full width
+    x = golden_x(g)                                                   # a chunk of six at full width
     sess.lazy_softmax = False
     eager = sess(x)
     assert type(eager) is np.ndarray and eager.shape == (6, 136, 18385) and float(np.abs(eager.sum(axis=2) - 1.0).max()) < 1e-4
@@ -347,7 +316,7 @@ def test_page_pipeline_strict_equals_the_reference_chunk_loop_through_the_sessio
             line_x[int(i)], line_w[int(i)] = x[j].cpu().numpy(), int(lw[j])
     cw, ch, rot, _keep = pipe.last_rec_crop_sizes
     crop_hw = [(int(cw[i]), int(ch[i])) if rot[i] else (int(ch[i]), int(cw[i])) for i in range(n)]
-    sess = Mi355RecSession.from_cfg({"model_path": str(_write(tmp_path, states[KIND]))})
+    sess = Mi355RecSession.from_cfg({"model_path": str(write_weights(tmp_path, "ch_PP-OCRv5_rec_server", states[KIND]))})
     ratios = np.array([w / float(h) for h, w in crop_hw])
     indices = np.argsort(ratios)
     out = [None] * n

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from kind_helpers import golden_x, hswish64
 from rapiddoc_amd import ocr_host
 from rapiddoc_amd import weights as W
 
@@ -169,10 +170,6 @@ def _fold(st, conv, bn):
     return w * sc.reshape(-1, 1, 1, 1), _t(st[bn + ".bias"]) - _t(st[bn + ".running_mean"]) * sc
 
 
-def _hswish(v):
-    return v * torch.clamp(v + 3.0, 0.0, 6.0) / 6.0
-
-
 def _swish(v):
     return v * torch.sigmoid(v)
 
@@ -186,7 +183,7 @@ def folded_graph_float64(st, x):
     for i, (k, sh, sw, se) in enumerate(_BLOCKS):
         p = f"backbone.block_list.{i}"
         w, b = _fold(st, p + "._depthwise_conv._conv.weight", p + "._depthwise_conv._batch_norm")
-        t = _hswish(F.conv2d(_hswish(h), w, b, stride=(sh, sw), padding=k // 2, groups=w.shape[0]))     # on-load hardswish, then zero padding
+        t = hswish64(F.conv2d(hswish64(h), w, b, stride=(sh, sw), padding=k // 2, groups=w.shape[0]))     # on-load hardswish, then zero padding
         if se:
             m = t.mean(dim=(2, 3), keepdim=True)
             m = torch.relu(F.conv2d(m, _t(st[p + "._se.conv1.weight"]), _t(st[p + "._se.conv1.bias"])))
@@ -195,7 +192,7 @@ def folded_graph_float64(st, x):
         w, b = _fold(st, p + "._pointwise_conv._conv.weight", p + "._pointwise_conv._batch_norm")
         h = F.conv2d(t, w, b)
     assert h.shape[2] == 3
-    a = _hswish(h[:, :, :2, : h.shape[3] // 2 * 2])                                  # AvgPool2d(2, 2) of a 3-row map: rows 0 and 1 only
+    a = hswish64(h[:, :, :2, : h.shape[3] // 2 * 2])                                  # AvgPool2d(2, 2) of a 3-row map: rows 0 and 1 only
     tok = (a[:, :, 0, 0::2] + a[:, :, 0, 1::2] + a[:, :, 1, 0::2] + a[:, :, 1, 1::2]) / 4.0       # [B, 512, T]
     e = "neck.encoder"
 
@@ -233,7 +230,7 @@ def test_float64_restatement_of_the_folded_graph_reproduces_the_fixtures(golden_
     agree within the engine's bound 1e-3 max(1, max |ref|) - in fact far inside it (fp32 rounding of the reference only)."""
     st = W.synth_state_dict(_manifest(golden_dir, lang), 0, kind=KIND)
     g = np.load(golden_dir / f"recmv1e_{lang}_seed0_{tag}.npz")
-    x = g["x"] if "x" in g.files else np.random.default_rng(int(g["x_seed"])).uniform(-1.0, 1.0, tuple(int(v) for v in g["x_shape"])).astype(np.float32)
+    x = golden_x(g)
     tok, neck, logits = folded_graph_float64(st, x)
     cs, step = int(g["backbone_cs"]), _summary(golden_dir)["files"][lang]["logits_step"]
     ref_tok = g["backbone"][:, :, 0, :].transpose(0, 2, 1)

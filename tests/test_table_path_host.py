@@ -68,7 +68,6 @@ def test_library_tables_equal_the_restatement(n_in, n_out):
     from rapiddoc_amd import _lib
     lib = _lib.load()
     fn = lib.rd_debug_resize_aa_coeffs
-    fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
     bounds, kk, ksize = TP.aa_coeffs(n_in, n_out)
     b = np.full((n_out, 2), -1, dtype=np.int32)
     k = np.full((n_out, ksize), -1, dtype=np.int32)

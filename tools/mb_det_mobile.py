@@ -14,7 +14,6 @@
     python tools/mb_det_mobile.py [--steps 7] [--warmup 3] [--pages 32] > profiles/mb_det_mobile.txt
 """
 import argparse
-import ctypes as C
 import os
 import sys
 from pathlib import Path
@@ -81,8 +80,6 @@ def forward_section(kind, st, x, precision, steps, warmup, table=True, label="")
 def dw_section(pages, iters, reps):
     lib = _lib.load()
     fn = lib.rd_debug_lcv3_dw_det
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 10 + [C.c_void_p] * 5
     g = torch.Generator(device="cuda").manual_seed(0)
     aff = np.asarray([1.05, 0.02, 0.95, -0.03], np.float32)
     print(f"\n== the depthwise layers alone, {pages} pages, pre-activation on load as in the network: direct (lcv3_dw_kernel) vs LDS-staged (lcv3_dw2d_kernel), "

@@ -75,8 +75,6 @@ def forward_section(st, x, precision, steps, warmup):
 
 def conv_section(pages, iters):
     lib = _lib.load()
-    lib.rd_debug_conv.restype = C.c_float
-    lib.rd_debug_conv.argtypes = [C.c_int] * 14 + [C.c_void_p] * 7 + [C.c_void_p]
     g = torch.Generator(device="cuda").manual_seed(0)
     print(f"\n== the 9x9 layers alone, {pages} pages: direct kernel (conv9x9_h1) vs the generic k x k split implicit GEMM, alternating, {iters} timed launches each")
     print(f"{'layer':16s} {'shape':24s} {'GFLOP':>7s} {'direct ms':>10s} {'TFLOP/s':>8s} {'of peak':>8s} {'generic ms':>11s} {'TFLOP/s':>8s} {'ratio':>6s} {'max |d|':>9s}")
@@ -107,8 +105,6 @@ def conv_section(pages, iters):
 def tail_section(pages, iters):
     lib = _lib.load()
     fn = lib.rd_debug_det_local
-    fn.restype = C.c_float
-    fn.argtypes = [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.POINTER(C.c_int)]
     g = torch.Generator(device="cuda").manual_seed(1)
     f = torch.rand((pages, H // 2, W_ // 2, 64), device="cuda", generator=g)
     shrink = torch.rand((pages, H, W_), device="cuda", generator=g)

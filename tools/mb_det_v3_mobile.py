@@ -18,7 +18,6 @@
     python tools/mb_det_v3_mobile.py [--routes] [--steps 7] [--warmup 3] [--pages 32] > profiles/mb_det_v3_mobile.txt
 """
 import argparse
-import ctypes as C
 import os
 import sys
 from pathlib import Path
@@ -151,9 +150,6 @@ DW_LAYERS = [("2.2-3", 3, 96, 1, 4), ("2.4", 3, 240, 1, 4), ("2.5", 3, 336, 1, 4
 def dw_section(pages, iters, reps):
     lib = _lib.load()
     direct, staged = lib.rd_debug_mbv3_dw, lib.rd_debug_lcv3_dw_det
-    direct.restype = staged.restype = C.c_float
-    direct.argtypes = [C.c_int] * 12 + [C.c_void_p] * 4
-    staged.argtypes = [C.c_int] * 10 + [C.c_void_p] * 5
     g = torch.Generator(device="cuda").manual_seed(0)
     aff = np.asarray([1.0, 0.0, 1.0, 0.0], np.float32)
     print(f"\n== the hardswish depthwise layers with C % 16 == 0 alone, {pages} pages, hardswish on load and in the epilogue: direct (mbv3_dw_kernel) vs LDS-staged "

@@ -12,8 +12,6 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from rapiddoc_amd import _lib
 
 lib = _lib.load()
-lib.rd_debug_dwconv.restype = C.c_float
-lib.rd_debug_dwconv.argtypes = [C.c_int] * 8 + [C.c_void_p] * 8
 
 for (N, H, W, Cn, gap_on) in ((128, 6, 132, 192, True), (128, 6, 132, 192, False), (128, 12, 132, 96, False), (128, 3, 132, 384, True),
                               (64, 6, 400, 192, True), (24, 6, 800, 192, True), (512, 6, 40, 192, True)):

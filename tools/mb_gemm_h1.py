@@ -19,12 +19,7 @@ SHAPES = ((131072, 768, 384, 0), (65536, 768, 384, 0), (131072, 384, 768, 2), (6
 
 def _lib():
     from rapiddoc_amd import _lib
-    lib = _lib.load()
-    lib.rd_debug_time_gemm.restype = C.c_float
-    lib.rd_debug_time_gemm.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6
-    lib.rd_debug_gemm_h1.restype = C.c_float
-    lib.rd_debug_gemm_h1.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    return lib
+    return _lib.load()
 
 
 def act_ref(v, act):

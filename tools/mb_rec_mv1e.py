@@ -16,7 +16,6 @@ width the strict planner gives it, GPU-sized backbone launches with a line table
     python tools/mb_rec_mv1e.py [--steps 5] [--warmup 2] [--pages 32] > profiles/mb_rec_mv1e.txt
 """
 import argparse
-import ctypes as C
 import os
 import sys
 from pathlib import Path
@@ -109,10 +108,6 @@ def dw5_ops(eng, step):
 
 def kernel_ab(rounds):
     lib = _lib.load()
-    lib.rd_debug_dw5_strip.restype = C.c_float
-    lib.rd_debug_dw5_strip.argtypes = [C.c_int] * 11 + [C.c_void_p] * 7
-    lib.rd_debug_lcv3_dw.restype = C.c_float
-    lib.rd_debug_lcv3_dw.argtypes = [C.c_int] * 9 + [C.c_void_p] * 8
     aff = np.array([1, 0, 1, 0], np.float32)
     print(f"\nstrip kernel (dw5_strip_kernel) against the direct kernel (lcv3_dw_kernel<5, SW, 4>), same operands, {rounds} rounds of 20 launches, "
           "alternating; pre_act and post_act on; GB/s on input + output bytes")

@@ -104,10 +104,6 @@ def main():
 
     # ---- the sequence convolution alone, uniform lines, against the general route
     lib = _lib.load()
-    lib.rd_debug_seqconv.restype = C.c_float
-    lib.rd_debug_seqconv.argtypes = [C.c_int] * 8 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.rd_debug_conv.restype = C.c_float
-    lib.rd_debug_conv.argtypes = [C.c_int] * 14 + [C.c_void_p] * 7 + [C.c_void_p]
     T, B = 40, n_tok // 40
     M, C0, C1, N = B * T, 2048, 2048, 256
     K = 3 * (C0 + C1)

@@ -10,10 +10,6 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from rapiddoc_amd import _lib
 
 lib = _lib.load()
-lib.rd_debug_time_mixer.restype = C.c_float
-lib.rd_debug_time_mixer.argtypes = [C.c_int] * 4 + [C.c_void_p] * 6
-lib.rd_debug_time_gemm.restype = C.c_float
-lib.rd_debug_time_gemm.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6
 
 
 def mixer(C_, M, variant, iters=20, check=False):
@@ -37,8 +33,6 @@ def mixer(C_, M, variant, iters=20, check=False):
 
 def ctc(M, Ccls=18385, K=120, nsplit=0, iters=20, split=True):
     """Fused CTC head in isolation (weights prepared here the way Builder::ctc_head (csrc/builder.cpp) does: bias in column K, hi/lo fp16 split)."""
-    lib.rd_debug_time_ctc.restype = C.c_float
-    lib.rd_debug_time_ctc.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
     g = torch.Generator(device="cuda").manual_seed(0)
     x = torch.rand((M, K), device="cuda", generator=g) - 0.5
     wp = torch.zeros((Ccls, 128), device="cuda")
