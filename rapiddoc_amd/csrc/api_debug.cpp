@@ -1,6 +1,7 @@
 // The developer entries of librapiddoc_mi355.so (rd_debug_*): single kernels and plan variants with taps, for the tests, tools/ and the
 // micro-benchmarks.  None of them is part of the public header; the product C surface is api.cpp.
 #include <algorithm>
+#include <cstring>
 #include <functional>
 #include <string>
 #include <vector>
@@ -314,6 +315,37 @@ float rd_debug_det_local(int N, int H, int W, int split, int iters, float* f, fl
     return ms;
 }
 
+// what rd_debug_conv reports in *used_direct for a route
+static int debug_conv_code(rd::ConvRoute r) {
+    return r == rd::CONV_DIRECT ? 1 : r == rd::CONV_STREAM ? 2 : r == rd::CONV_C3H1 ? 3 : r == rd::CONV_C9H1 ? 4 : 0;
+}
+static void debug_copy_name(const char* s, char* name, int name_len) {
+    if (name && name_len > 0) { std::strncpy(name, s, (size_t)name_len - 1); name[name_len - 1] = 0; }
+}
+
+// developer entry, host only (no HIP call): the route of a dense convolution as the planner decides it.  Geometry as rd_debug_conv with a dense
+// input (xld = Cin), N images; images: bit 0 the (hi, lo) split weights, 1 the one-accumulator GEMM image, 2 the 3x3 image, 3 the 9x9 image
+// (only bits are looked at: the images themselves are not); split = 0 asks conv_f32_route, with allow_skinny.  The route's name goes to
+// name[name_len]; returns the code rd_debug_conv reports for the route in *used_direct, -1 on a bad argument.
+int rd_debug_conv_route(int N, int H, int W, int Cin, int Cout, int KH, int KW, int S, int PT, int PL, int PB, int PR, int act, int images,
+                        int has_ascale, int allow_skinny, int split, char* name, int name_len) {
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || S <= 0) return -1;
+    static const uint16_t image[8] = {};       // something for the image pointers to point at
+    rd::ConvParams p{};
+    p.xld = Cin; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.yld = Cout;
+    p.OH = (H + PT + PB - KH) / S + 1; p.OW = (W + PL + PR - KW) / S + 1; p.Cout = Cout;
+    p.KH = KH; p.KW = KW; p.SH = p.SW = S; p.PT = PT; p.PL = PL; p.act = act; p.out_mode = rd::OUT_NHWC; p.rld = Cout;
+    p.M = N * p.OH * p.OW; p.K = KH * KW * Cin; p.Ng = Cout;
+    p.allow_skinny = allow_skinny;
+    if (images & 1) p.wh = p.wl = image;
+    if (images & 2) { p.w1 = image; p.w1_inv = 1.f; }
+    if (images & 4) { p.w3 = image; p.w3_inv = 1.f; }
+    if (images & 8) { p.w9 = image; p.w9_inv = 1.f; }
+    const rd::ConvRoute r = split ? rd::conv_split_route(p, has_ascale != 0) : rd::conv_f32_route(p);
+    debug_copy_name(rd::conv_route_name(r), name, name_len);
+    return debug_conv_code(r);
+}
+
 // developer entry: one dense convolution on prepared operands (x NHWC fp32 [N][H][W][Cin]; w folded [Cout][K], k = (kh*KW+kw)*Cin+ci;
 // wh / wl its fp16 split with rows padded to Kp = ceil32(K), or null for the fp32 MFMA kernels; y NHWC [N][OH][OW][Cout]).
 // Returns ms per launch (iters timed launches after one untimed).  *used_direct: in = 1 forces the direct k x k kernel when it
@@ -356,19 +388,11 @@ float rd_debug_conv(int N, int H, int W, int Cin, int Cout, int KH, int KW, int 
             }
         }
     }
-    const bool c9 = wh && rd::conv9x9_h1_applies(p);
-    const bool c3 = wh && rd::conv3x3_h1_applies(p);
-    const bool force = used_direct && *used_direct == 1 && wh && rd::conv_direct_h3_supported(p);
-    const bool force_stream = used_direct && *used_direct == 2 && wh && rd::conv_stream_h3_supported(p);
-    if (used_direct) *used_direct = c9 ? 4 : c3 ? 3 : force_stream ? 2 : (force || (wh && !rd::conv_stream_h3_applies(p) && rd::conv_direct_h3_applies(p))) ? 1
-                                    : (wh && rd::conv_stream_h3_applies(p)) ? 2 : 0;
-    auto go = [&] {
-        if (force_stream) rd::launch_conv_stream_h3(p, nullptr);
-        else if (force) rd::launch_conv_direct_h3(p, nullptr);
-        else if (wh) rd::launch_conv_igemm_h3(p, nullptr);
-        else rd::launch_conv_igemm(p, nullptr);
-    };
-    const float ms = rd_debug_time(iters, go);
+    rd::ConvRoute route = wh ? rd::conv_split_route(p, false) : rd::conv_f32_route(p);
+    if (used_direct && *used_direct == 2 && wh && rd::conv_stream_h3_supported(p)) route = rd::CONV_STREAM;
+    else if (used_direct && *used_direct == 1 && wh && rd::conv_direct_h3_supported(p)) route = rd::CONV_DIRECT;
+    if (used_direct) *used_direct = debug_conv_code(route);
+    const float ms = rd_debug_time(iters, [&] { rd::launch_conv_route(route, p, nullptr); });
     if (img3) (void)hipFree(img3);
     if (img9) (void)hipFree(img9);
     return ms;
@@ -412,12 +436,33 @@ float rd_debug_dwconv(int N, int H, int W, int C, int K, int SH, int act, int it
     p.x = x; p.xld = C; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = C;
     p.KH = p.KW = K; p.SH = SH; p.SW = 1; p.PT = p.PL = K / 2;
     p.OH = (H + 2 * p.PT - K) / SH + 1; p.OW = W; p.act = act; p.res = res; p.rld = C;
-    const int chunks = rd::dwconv_gap_chunks(p);
-    if (gap_chunks) *gap_chunks = chunks;
-    p.gap_partial = chunks > 0 ? gap : nullptr; p.gap_chunks = chunks;
     p.line_w = line_w; p.line_w_stride = 1;
-    if (gap_chunks && rd::dwconv_kxk_lds_applies(p)) *gap_chunks = -1;      // (tests: the one-channel-per-lane 5x5 / 7x7 kernel takes this call)
+    p.gap_chunks = rd::dwconv_gap_chunks(p);
+    p.gap_partial = p.gap_chunks > 0 ? gap : nullptr;
+    // (tests: -1 = the one-channel-per-lane 5x5 / 7x7 kernel takes this call)
+    if (gap_chunks) *gap_chunks = rd::dw_route(p, p.gap_partial != nullptr).kernel == rd::DW_KXK_LDS ? -1 : p.gap_chunks;
     return rd_debug_time(iters, [&] { rd::launch_dwconv(p, nullptr); });
+}
+
+// developer entry, host only (no HIP call): the route of a depthwise convolution.  Geometry as rd_debug_dwconv (K = 1 with ragged: the
+// recogniser's 1 x 3 over one token row).  The kernel's name goes to name[name_len] ("lds1" .. "lds5" = dwconv_lds_variant, "kxk_lds5" / "7",
+// "tiled4" / "8", "col", "pixel"), *gap_chunks (optional) receives the route's chunk count.  Returns the count the planner sizes the partial-sum
+// buffer with (dwconv_gap_chunks on the unbound geometry), -1 on a bad argument.
+int rd_debug_dw_route(int N, int H, int W, int C, int K, int SH, int ragged, int has_line_w, int wants_gap, char* name, int name_len, int* gap_chunks) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || SH <= 0) return -1;
+    static const int32_t table[1] = {};        // something for the ragged / line-table pointers to point at
+    rd::DwParams p{};
+    p.xld = p.yld = p.rld = C; p.N = N; p.H = H; p.W = W; p.C = C;
+    p.KH = ragged ? 1 : K; p.KW = ragged ? 3 : K; p.SH = SH; p.SW = 1; p.PT = p.KH / 2; p.PL = p.KW / 2;
+    p.OH = (H + 2 * p.PT - p.KH) / SH + 1; p.OW = W;
+    const int planned = rd::dwconv_gap_chunks(p);
+    if (ragged) p.tokinfo = table;
+    if (has_line_w) { p.line_w = table; p.line_w_stride = 1; }
+    const rd::DwRoute r = rd::dw_route(p, wants_gap != 0);
+    static const char* const kernels[] = {"pixel", "lds", "kxk_lds", "col", "tiled"};
+    debug_copy_name((std::string(kernels[r.kernel]) + (r.kernel == rd::DW_PIXEL || r.kernel == rd::DW_COL ? "" : std::to_string(r.variant))).c_str(), name, name_len);
+    if (gap_chunks) *gap_chunks = r.gap_chunks;
+    return planned;
 }
 
 // developer entry: one PPLCNetV3 depthwise layer through launch_lcv3_dw (kernels_lcv3.hip; x NHWC fp32 [N][H][W][C], w [K*K][C], bias [C],

@@ -130,9 +130,8 @@ static inline bool auto_split_conv(int kh, int kw, int K, int cout) {
     static const int kxk_n = std::getenv("RD_H3_KXK_MIN_N") ? std::atoi(std::getenv("RD_H3_KXK_MIN_N")) : 24;
     static const int pw_k = std::getenv("RD_H3_1X1_MIN_K") ? std::atoi(std::getenv("RD_H3_1X1_MIN_K")) : 96;
     static const int pw_n = std::getenv("RD_H3_1X1_MIN_N") ? std::atoi(std::getenv("RD_H3_1X1_MIN_N")) : 96;
-    static const bool stream_off = std::getenv("RD_CONV_STREAM") && std::getenv("RD_CONV_STREAM")[0] == '0';
     // small-K layers: the streaming split kernel (kernels_conv_stream_h3.hip) takes them whatever the thresholds below say
-    if (!stream_off && cout >= 12 && conv_stream_h3_shape_ok(kh, kw, K / (kh * kw), cout)) return true;
+    if (conv_stream_h3_enabled() && cout >= 12 && conv_stream_h3_shape_ok(kh, kw, K / (kh * kw), cout)) return true;
     return (kh == 1 && kw == 1) ? (K >= pw_k && cout >= pw_n) : (K >= kxk_k && cout >= kxk_n);
 }
 
@@ -173,7 +172,6 @@ TView Builder::conv(const std::string& wname, const std::string& bname, const st
     OpRecord r;
     r.name = wname;
     r.kind = (kh == 1 && kw == 1) ? "conv1x1" : "conv" + std::to_string(kh) + "x" + std::to_string(kw);
-    r.cfg = conv_igemm_config_name(p);
     r.shape = "M" + std::to_string(p.M) + "_K" + std::to_string(K) + "_N" + std::to_string(cout);
     r.flops = 2.0 * p.M * (double)K * cout;
     r.bytes = 4.0 * ((double)x.pixels() * cin + (double)p.M * cout * (res ? 2 : 1) + (double)cout * K);
@@ -199,17 +197,16 @@ TView Builder::conv(const std::string& wname, const std::string& bname, const st
             p.w9_inv = *pb_->host_ptr(key + "#w9s");
         }
         p.range_flag = range_flag_;
-        r.cfg = std::string(conv_stream_h3_applies(p) ? "stream" : conv3x3_h1_applies(p) ? "c3h1" : conv9x9_h1_applies(p) ? "c9h1" : conv_direct_h3_applies(p) ? "direct" : gemm_h1_applies(p) ? "h1w256x128" : gemm_h3_dma_applies(p) ? (gemm_h3_dma_uses16(p) ? "dma16w256x128" : "dma256x128") : cout > 96 ? "256x128" : cout > 64 ? "128x96"
-                            : (cout > 32 && p.M >= 65536) ? "256x64" : K <= 256 || cout <= 32 ? "128x32" : "128x64") + "/h3";
     }
-    r.run = [p, xv, yv, rv, av, has_res, has_as, h3](const Plan& pl, const RunCtx& c) mutable {
+    const ConvRoute route = h3 ? conv_split_route(p, has_as) : conv_f32_route(p);
+    r.cfg = std::string(conv_route_name(route)) + (h3 ? "/h3" : "");
+    r.run = [p, xv, yv, rv, av, has_res, has_as, route](const Plan& pl, const RunCtx& c) mutable {
         ConvParams q = p;
         q.x = pl.vptr(xv, c);
         q.y = pl.vptr(yv, c);
         q.res = has_res ? pl.vptr(rv, c) : nullptr;
         q.ascale = has_as ? pl.vptr(av, c) : nullptr;
-        if (h3) launch_conv_igemm_h3(q, c.stream);
-        else launch_conv_igemm(q, c.stream);
+        launch_conv_route(route, q, c.stream);
     };
     emit(std::move(r));
     return y;
@@ -267,13 +264,17 @@ void Builder::fold_conv(const std::string& wname, const std::string& bname, cons
     }
 }
 
-bool Builder::mixer_takes_dw(const std::string& prefix, int C) const {
-    if (!planning() || !(h3_ || mixer_h3_) || !mixer_res_fuses_dw(C)) return false;
-    const std::string hkey = prefix + ".mixer#h3";
+// which mixer kernel serves the block: the weight images the preparation left in the parameter block, and RD_MIXER_WS=0 (A/B switch)
+Builder::MixerRoute Builder::mixer_route(const std::string& prefix, int C) const {
     static const bool ws_off = std::getenv("RD_MIXER_WS") && std::string(std::getenv("RD_MIXER_WS")) == "0";
-    const bool split = pb_->has(hkey + ".w1h");
-    const bool ws = split && !ws_off && pb_->has(hkey + ".ws");
-    return split && !ws && pb_->has(hkey + ".res");       // the route Builder::mixer_fused takes to the resident-weights kernel
+    const std::string hkey = prefix + ".mixer#h3";
+    if (!(h3_ || mixer_h3_) || !pb_->has(hkey + ".w1h")) return MIXER_F32;
+    if (!ws_off && pb_->has(hkey + ".ws")) return MIXER_WS;
+    return mixer_res_supported(C) && pb_->has(hkey + ".res") ? MIXER_RES : MIXER_H3;
+}
+
+bool Builder::mixer_takes_dw(const std::string& prefix, int C) const {
+    return planning() && mixer_res_fuses_dw(C) && mixer_route(prefix, C) == MIXER_RES;
 }
 
 TView Builder::mixer_fused(const std::string& prefix, const TView& x, const TView* gate, const std::string* dw_key) {
@@ -314,23 +315,21 @@ TView Builder::mixer_fused(const std::string& prefix, const TView& x, const TVie
         }
         return y;
     }
-    const bool split = (h3_ || mixer_h3_) && pb_->has(hkey + ".w1h");
-    static const bool ws_off = std::getenv("RD_MIXER_WS") && std::string(std::getenv("RD_MIXER_WS")) == "0";   // A/B switch
-    const bool ws = split && !ws_off && pb_->has(hkey + ".ws");
-    const bool res_k = split && !ws && mixer_res_supported(C) && pb_->has(hkey + ".res");
+    const MixerRoute route = mixer_route(prefix, C);
+    const bool res_k = route == MIXER_RES;
     MixerParams p{};
     if (res_k) {
         p.w1h = reinterpret_cast<const uint16_t*>(pb_->ptr(hkey + ".res"));
         p.ws_inv1 = pb_->host_ptr(hkey + ".resinv")[0];
         p.ws_inv2 = pb_->host_ptr(hkey + ".resinv")[1];
         p.range_flag = range_flag_;
-    } else if (ws) {
+    } else if (route == MIXER_WS) {
         p.w1h = reinterpret_cast<const uint16_t*>(pb_->ptr(hkey + ".ws"));
         p.ws_inv1 = pb_->host_ptr(hkey + ".wsinv")[0];
         p.ws_inv2 = pb_->host_ptr(hkey + ".wsinv")[1];
         p.ws_pf = mixer_ws_prefetch() && C == 192;
         p.range_flag = range_flag_;
-    } else if (split) {
+    } else if (route == MIXER_H3) {
         p.w1h = reinterpret_cast<const uint16_t*>(pb_->ptr(hkey + ".w1h")); p.w1l = reinterpret_cast<const uint16_t*>(pb_->ptr(hkey + ".w1l"));
         p.w2h = reinterpret_cast<const uint16_t*>(pb_->ptr(hkey + ".w2h")); p.w2l = reinterpret_cast<const uint16_t*>(pb_->ptr(hkey + ".w2l"));
         p.range_flag = range_flag_;
@@ -350,7 +349,8 @@ TView Builder::mixer_fused(const std::string& prefix, const TView& x, const TVie
     p.w2 = pb_->ptr(w2 + "|" + bn2 + "#w"); p.b2 = pb_->ptr(w2 + "|" + bn2 + "#b");
     OpRecord r;
     r.name = prefix + ".mixer";
-    r.kind = res_k ? (with_dw ? "mixer_fused_res_dw" : "mixer_fused_res") : ws ? "mixer_fused_ws" : split ? "mixer_fused_h3" : "mixer_fused";
+    static const char* const kinds[] = {"mixer_fused", "mixer_fused_h3", "mixer_fused_ws", "mixer_fused_res"};   // by MixerRoute
+    r.kind = with_dw ? "mixer_fused_res_dw" : kinds[route];
     r.cfg = "C" + std::to_string(C);
     r.shape = "M" + std::to_string(p.M) + "_C" + std::to_string(C);
     r.flops = 8.0 * p.M * (double)C * C + (with_dw ? 18.0 * p.M * C : 0.0);
@@ -360,7 +360,7 @@ TView Builder::mixer_fused(const std::string& prefix, const TView& x, const TVie
     const TView gv = gate ? *gate : TView{};
     const bool has_lt = with_dw && has_lt_;
     const TView ltv = lt_;
-    r.run = [p, xv, yv, gv, has_gate, split, ws, res_k, has_lt, ltv](const Plan& pl, const RunCtx& c) {
+    r.run = [p, xv, yv, gv, has_gate, route, has_lt, ltv](const Plan& pl, const RunCtx& c) {
         MixerParams q = p;
         q.x = pl.vptr(xv, c);
         q.y = pl.vptr(yv, c);
@@ -369,10 +369,12 @@ TView Builder::mixer_fused(const std::string& prefix, const TView& x, const TVie
             q.dw_line_w = reinterpret_cast<const int32_t*>(pl.vptr(ltv, c)) + 2;
             q.dw_line_w_stride = kLineTabStride;
         }
-        if (res_k) launch_mixer_fused_res(q, c.stream);
-        else if (ws) launch_mixer_fused_ws(q, c.stream);
-        else if (split) launch_mixer_fused_h3(q, c.stream);
-        else launch_mixer_fused(q, c.stream);
+        switch (route) {
+            case MIXER_RES: launch_mixer_fused_res(q, c.stream); break;
+            case MIXER_WS: launch_mixer_fused_ws(q, c.stream); break;
+            case MIXER_H3: launch_mixer_fused_h3(q, c.stream); break;
+            case MIXER_F32: launch_mixer_fused(q, c.stream); break;
+        }
     };
     emit(std::move(r));
     return y;
@@ -496,17 +498,17 @@ TView Builder::deconv2x2(const std::string& wname, const std::string& bname, con
     OpRecord r;
     r.name = wname;
     r.kind = "deconv2x2";
-    r.cfg = conv_igemm_config_name(p);
+    const bool h3 = h3_ && p.wh != nullptr;
+    const ConvRoute route = h3 ? conv_split_route(p, false) : conv_f32_route(p);
+    r.cfg = std::string(conv_route_name(route)) + (h3 ? "/h3" : "");
     r.flops = 2.0 * p.M * (double)cin * 4 * cout;
     r.bytes = 4.0 * ((double)p.M * cin + (double)p.M * 4 * cout);
     const TView xv = x, yv = y;
-    const bool h3 = h3_ && p.wh != nullptr;
-    r.run = [p, xv, yv, h3](const Plan& pl, const RunCtx& c) {
+    r.run = [p, xv, yv, route](const Plan& pl, const RunCtx& c) {
         ConvParams q = p;
         q.x = pl.vptr(xv, c);
         q.y = pl.vptr(yv, c);
-        if (h3) launch_conv_igemm_h3(q, c.stream);
-        else launch_conv_igemm(q, c.stream);
+        launch_conv_route(route, q, c.stream);
     };
     emit(std::move(r));
     return y;
@@ -841,6 +843,7 @@ TView Builder::dwconv(const std::string& wname, const std::string& bname, const 
     p.OH = oh; p.OW = ow; p.KH = kh; p.KW = kw; p.SH = g.sh; p.SW = g.sw; p.PT = g.pt; p.PL = g.pl;
     p.act = act;
     p.rld = res ? plan_->ld(*res) : 0;
+    p.gap_chunks = gap ? gap->chunks : 0;
     OpRecord r;
     r.name = wname;
     r.kind = "dwconv" + std::to_string(kh) + "x" + std::to_string(kw);

@@ -293,6 +293,9 @@ class Builder {
    private:
     void emit(OpRecord&& r) { plan_->ops.push_back(std::move(r)); }
     std::vector<float> bn_scale_shift(const std::string& bn, int c, std::vector<float>& shift) const;
+    // the kernel the channel mixer of `prefix` runs on in this plan (mixer_fused launches it, mixer_takes_dw asks about it)
+    enum MixerRoute { MIXER_F32, MIXER_H3, MIXER_WS, MIXER_RES };
+    MixerRoute mixer_route(const std::string& prefix, int C) const;
     Mode mode_;
     bool h3_ = false;        // every dense layer on the fp16 matrix cores with hi/lo operand splitting (fp32-accurate)
     bool mixer_h3_ = false;  // only the fused channel mixers (the default "auto" precision)

@@ -828,16 +828,7 @@ void FormulaDecoder::load(const WeightStore& ws) {
 void FormulaDecoder::gemm(const float* x, int M, int K, const std::string& key, int N, float* y, int act, const float* res, hipStream_t s,
                           const std::string& ln_key, float* ln_tmp) {
     ConvParams p{};
-    if (!ln_key.empty()) {
-        if (skinny_gemm_applies(M, K) && N <= 4096) {   // every workgroup re-normalises X: only worth it for few workgroups
-            p.ln_g = params_.ptr(ln_key + ".weight");
-            p.ln_b = params_.ptr(ln_key + ".bias");
-        } else {
-            ln(x, ln_key, ln_tmp, M, s);
-            x = ln_tmp;
-        }
-    }
-    p.x = x; p.xld = K; p.N = 1; p.H = 1; p.W = M; p.Cin = K;
+    p.xld = K; p.N = 1; p.H = 1; p.W = M; p.Cin = K;
     p.w = params_.ptr(key + "#w");
     p.bias = params_.has(key + "#b") ? params_.ptr(key + "#b") : nullptr;
     p.y = y; p.yld = N; p.OH = 1; p.OW = M; p.Cout = N;
@@ -846,6 +837,16 @@ void FormulaDecoder::gemm(const float* x, int M, int K, const std::string& key, 
     p.act = act; p.out_mode = OUT_NHWC;
     p.M = M; p.K = K; p.Ng = N;
     p.allow_skinny = 1;      // M is the decode batch
+    if (!ln_key.empty()) {
+        p.ln_g = params_.ptr(ln_key + ".weight");
+        p.ln_b = params_.ptr(ln_key + ".bias");
+        if (conv_f32_route(p) != CONV_SKINNY || N > 4096) {   // every workgroup re-normalises X: only worth it for few workgroups
+            p.ln_g = p.ln_b = nullptr;
+            ln(x, ln_key, ln_tmp, M, s);
+            x = ln_tmp;
+        }
+    }
+    p.x = x;
     launch_conv_igemm(p, s);
 }
 

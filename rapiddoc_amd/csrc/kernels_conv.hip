@@ -18,6 +18,7 @@
 #include "rd_device.h"
 
 #include <cstdlib>
+#include <stdexcept>
 
 namespace rd {
 
@@ -208,24 +209,29 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_igemm_kernel(ConvParams p, i
     }
 }
 
-struct TileCfg { int bn; const char* name; };
-
-static inline TileCfg pick_cfg(const ConvParams& p) {
-    const int n = p.Ng;
-    if (n <= 32) return {32, "128x32"};
-    if (n <= 64) return {64, "128x64"};
-    if (n <= 96) return {96, "128x96"};
-    // fewest padded columns; ties go to the wider tile
-    const int w128 = (n + 127) / 128 * 128, w96 = (n + 95) / 96 * 96;
-    if (w96 < w128) return {96, "128x96"};
-    return {128, "128x128"};
-}
-
 static inline bool is_1x1(const ConvParams& p) {
     return p.KH == 1 && p.KW == 1 && p.SH == 1 && p.SW == 1 && p.PT == 0 && p.PL == 0 && p.OH == p.H && p.OW == p.W;
 }
 
-const char* conv_igemm_config_name(const ConvParams& p) { return pick_cfg(p).name; }
+ConvRoute conv_f32_route(const ConvParams& p) {
+    // (ln_g is only honoured by the skinny path: a caller that wants it fused asks here first, with ln_g set)
+    if (p.allow_skinny && p.M <= 32 && p.out_mode == OUT_NHWC && is_1x1(p) && p.K % 4 == 0 && p.K >= 64 && (!p.ln_g || p.K <= 512)) return CONV_SKINNY;
+    const int n = p.Ng;
+    if (n <= 32) return CONV_F32_128x32;
+    if (n <= 64) return CONV_F32_128x64;
+    if (n <= 96) return CONV_F32_128x96;
+    // fewest padded columns; ties go to the wider tile
+    const int w128 = (n + 127) / 128 * 128, w96 = (n + 95) / 96 * 96;
+    return w96 < w128 ? CONV_F32_128x96 : CONV_F32_128x128;
+}
+
+const char* conv_route_name(ConvRoute r) {
+    static const char* const names[] = {"stream", "c3h1", "c9h1", "direct", "h1w256x128", "dma16w256x128", "dma256x128",
+                                        "256x128", "128x96", "256x64", "128x32", "128x64", "f32",
+                                        "skinny", "128x32", "128x64", "128x96", "128x128"};
+    static_assert(sizeof(names) / sizeof(names[0]) == CONV_F32_128x128 + 1, "one name per ConvRoute");
+    return names[r];
+}
 
 template <int BM, int BN, int WM, int WN>
 static void launch_cfg(const ConvParams& p, hipStream_t s) {
@@ -487,22 +493,18 @@ static void launch_skinny(const ConvParams& p, hipStream_t s) {
     else hipLaunchKernelGGL(skinny_gemm_kernel<32>, dim3(blocks), dim3(256), 0, s, p, cpw);
 }
 
-bool skinny_gemm_applies(int M, int K) { return M <= 32 && K % 4 == 0 && K >= 64 && K <= 512; }
-
-void launch_conv_igemm(const ConvParams& p, hipStream_t s) {
-    if (p.M <= 0) return;
-    if (p.allow_skinny && p.M <= 32 && p.out_mode == OUT_NHWC && is_1x1(p) && p.K % 4 == 0 && p.K >= 64 && (!p.ln_g || p.K <= 512)) {
-        launch_skinny(p, s);
-        return;
-    }
-    // (ln_g is only honoured by the skinny path; callers check skinny_gemm_applies() before relying on it)
-    switch (pick_cfg(p).bn) {
-        case 32: launch_cfg<128, 32, 4, 1>(p, s); break;
-        case 64: launch_cfg<128, 64, 4, 1>(p, s); break;
-        case 96: launch_cfg<128, 96, 4, 1>(p, s); break;
-        default: launch_cfg<128, 128, 2, 2>(p, s); break;
+void launch_conv_f32_route(ConvRoute r, const ConvParams& p, hipStream_t s) {
+    switch (r) {
+        case CONV_SKINNY: launch_skinny(p, s); break;
+        case CONV_F32_128x32: launch_cfg<128, 32, 4, 1>(p, s); break;
+        case CONV_F32_128x64: launch_cfg<128, 64, 4, 1>(p, s); break;
+        case CONV_F32_128x96: launch_cfg<128, 96, 4, 1>(p, s); break;
+        case CONV_F32_128x128: launch_cfg<128, 128, 2, 2>(p, s); break;
+        default: throw std::runtime_error("launch_conv_f32_route: not an fp32 route");
     }
 }
+
+void launch_conv_igemm(const ConvParams& p, hipStream_t s) { launch_conv_route(conv_f32_route(p), p, s); }
 
 // --------------------------------------------------------------------------------------------------
 // Stem: 3x3 stride-2 pad-1 conv on the caller's NCHW fp32 image (Cin = 3), BN folded, ReLU.

@@ -370,9 +370,9 @@ __global__ void __launch_bounds__(WM* WN * 64, (WM * WN == 4 && BM * BN >= 128 *
     if (emax >= 0x7f800000u && p.range_flag) rd_raise_flag(p.range_flag);
 }
 
-static inline int h3_pick_bn(const ConvParams& p) {
-    static const int forced = [] { const char* e = getenv("RD_H3_BN"); return e ? atoi(e) : 0; }();
-    if (forced) return forced;
+static inline ConvRoute h3_pick_tile(const ConvParams& p) {
+    static const int forced = [] { const char* e = getenv("RD_H3_BN"); return e ? atoi(e) : 0; }();   // 32 / 64 / 96 / 258 (256x128), anything else 256x64
+    if (forced) return forced == 32 ? CONV_H3_128x32 : forced == 64 ? CONV_H3_128x64 : forced == 96 ? CONV_H3_128x96 : forced == 258 ? CONV_H3_256x128 : CONV_H3_256x64;
     // Measured on MI355X (TF/s of fp32-equivalent work, M = 131072; fp32 MFMA kernel in brackets):
     //   K192/N384  K384/N768  K768/N384  K2176/N512  4096^2
     //     102        150        204        253        288     256x128 tile, 8 wavefronts (4x2), two LDS stages
@@ -381,11 +381,11 @@ static inline int h3_pick_bn(const ConvParams& p) {
     // The A tile is split once per K step whatever the tile width, so wide tiles amortise the split; narrow tiles are
     // for narrow layers only.
     const int n = p.Ng;
-    if (n > 96) return 258;
-    if (n > 32 && n <= 64 && p.M >= 65536) return 260;
-    if (n > 64) return 96;
-    if (n <= 32 || p.K <= 256) return 32;
-    return 64;
+    if (n > 96) return CONV_H3_256x128;
+    if (n > 32 && n <= 64 && p.M >= 65536) return CONV_H3_256x64;
+    if (n > 64) return CONV_H3_128x96;
+    if (n <= 32 || p.K <= 256) return CONV_H3_128x32;
+    return CONV_H3_128x64;
 }
 static inline bool h3_is_1x1(const ConvParams& p) {
     return p.KH == 1 && p.KW == 1 && p.SH == 1 && p.SW == 1 && p.PT == 0 && p.PL == 0 && p.OH == p.H && p.OW == p.W;
@@ -411,47 +411,44 @@ static void h3_launch_cfg(const ConvParams& p_in, hipStream_t s) {
         hipLaunchKernelGGL((conv_igemm_h3_kernel<BM, BN, WM, WN, false>), grid, block, 0, s, p, ntn, ntiles);
 }
 
-void launch_conv_igemm_h3(const ConvParams& p, hipStream_t s) {
-    if (p.M <= 0) return;
-    if (conv_stream_h3_applies(p)) {   // small K (stems): HBM-bound, operands streamed from global memory at high occupancy
-        launch_conv_stream_h3(p, s);
-        return;
-    }
-    if (conv3x3_h1_applies(p)) {       // 3x3 stride 1 pad 1, <= 96 output channels: one accumulator set, two workgroups per CU (round 6)
-        launch_conv3x3_h1(p, s);
-        return;
-    }
-    if (conv9x9_h1_applies(p)) {       // 9x9 stride 1 pad 4 to 33 .. 64 output channels (LKPAN): the same scheme with a 16 x 40 patch
-        launch_conv9x9_h1(p, s);
-        return;
-    }
-    if (conv_direct_h3_applies(p)) {   // 2x2 / 3x3 stride 1, <= 96 output channels: patch in LDS, taps as address offsets
-        launch_conv_direct_h3(p, s);
-        return;
-    }
-    if (gemm_h1_applies(p)) {       // pointwise, K % 32 == 0, wide: single-accumulator split, two workgroups per CU (kernels_gemm_h1.hip)
-        launch_gemm_h1(p, s);
-        return;
-    }
-    if (gemm_h3_dma_applies(p)) {   // pointwise, other K: the round-3 LDS-DMA pipeline (kernels_gemm_h3_dma.hip)
-        launch_gemm_h3_dma(p, s);
-        return;
+ConvRoute conv_split_route(const ConvParams& p, bool has_ascale) {
+    if (!has_ascale) {      // none of the specialised kernels scales its rows on load: a gated layer goes to the tiles below
+        if (conv_stream_h3_applies(p)) return CONV_STREAM;    // small K (stems): HBM-bound, operands streamed from global memory at high occupancy
+        if (conv3x3_h1_applies(p)) return CONV_C3H1;          // 3x3 stride 1 pad 1, <= 96 output channels: one accumulator set, two workgroups per CU (round 6)
+        if (conv9x9_h1_applies(p)) return CONV_C9H1;          // 9x9 stride 1 pad 4 to 33 .. 64 output channels (LKPAN): the same scheme with a 16 x 40 patch
+        if (conv_direct_h3_applies(p)) return CONV_DIRECT;    // 2x2 / 3x3 stride 1, <= 96 output channels: patch in LDS, taps as address offsets
+        if (gemm_h1_applies(p)) return CONV_GEMM_H1;          // pointwise, K % 32 == 0, wide: single-accumulator split, two workgroups per CU (kernels_gemm_h1.hip)
+        if (gemm_h3_dma_applies(p)) return gemm_h3_dma_uses16(p) ? CONV_DMA16 : CONV_DMA8;   // pointwise, other K: the round-3 LDS-DMA pipeline (kernels_gemm_h3_dma.hip)
     }
     // the staged kernels address X and the split weights with 32-bit element offsets; a tensor beyond 2^32 elements (16 GB of
     // fp32 activations in one layer) takes the fp32 MFMA kernel, which uses 64-bit addresses
     if ((unsigned long long)p.N * p.H * p.W * (unsigned long long)p.xld >= (1ull << 32) ||
-        (unsigned long long)p.Ng * (unsigned long long)((p.K + 31) & ~31) >= (1ull << 32)) {
-        launch_conv_igemm(p, s);
-        return;
-    }
-    switch (h3_pick_bn(p)) {
-        case 32: h3_launch_cfg<128, 32, 4, 1>(p, s); break;
-        case 64: h3_launch_cfg<128, 64, 4, 1>(p, s); break;
-        case 96: h3_launch_cfg<128, 96, 4, 1>(p, s); break;
-        case 258: h3_launch_cfg<256, 128, 4, 2>(p, s); break;
-        default: h3_launch_cfg<256, 64, 4, 2>(p, s); break;   // 260
+        (unsigned long long)p.Ng * (unsigned long long)((p.K + 31) & ~31) >= (1ull << 32))
+        return CONV_H3_TO_F32;
+    return h3_pick_tile(p);
+}
+
+void launch_conv_route(ConvRoute r, const ConvParams& p, hipStream_t s) {
+    if (p.M <= 0) return;
+    switch (r) {
+        case CONV_STREAM: launch_conv_stream_h3(p, s); break;
+        case CONV_C3H1: launch_conv3x3_h1(p, s); break;
+        case CONV_C9H1: launch_conv9x9_h1(p, s); break;
+        case CONV_DIRECT: launch_conv_direct_h3(p, s); break;
+        case CONV_GEMM_H1: launch_gemm_h1(p, s); break;
+        case CONV_DMA16: launch_gemm_h3_dma(p, true, s); break;
+        case CONV_DMA8: launch_gemm_h3_dma(p, false, s); break;
+        case CONV_H3_128x32: h3_launch_cfg<128, 32, 4, 1>(p, s); break;
+        case CONV_H3_128x64: h3_launch_cfg<128, 64, 4, 1>(p, s); break;
+        case CONV_H3_128x96: h3_launch_cfg<128, 96, 4, 1>(p, s); break;
+        case CONV_H3_256x128: h3_launch_cfg<256, 128, 4, 2>(p, s); break;
+        case CONV_H3_256x64: h3_launch_cfg<256, 64, 4, 2>(p, s); break;
+        case CONV_H3_TO_F32: launch_conv_f32_route(conv_f32_route(p), p, s); break;
+        default: launch_conv_f32_route(r, p, s); break;
     }
 }
+
+void launch_conv_igemm_h3(const ConvParams& p, hipStream_t s) { launch_conv_route(conv_split_route(p, p.ascale != nullptr), p, s); }
 
 // host helper: split a weight matrix [rows][K] fp32 into hi/lo fp16 matrices [rows][Kp] (Kp = K rounded up to 32, zero filled:
 // the LDS-DMA GEMM reads whole 32-wide K tiles of the weights and relies on the zeros past K)

@@ -179,11 +179,12 @@ bool conv_stream_h3_supported(const ConvParams& p) {
     StreamGeom g;
     return stream_geom(p, g);
 }
-// routing policy (launch_conv_igemm_h3): every layer it supports, unless RD_CONV_STREAM=0
-bool conv_stream_h3_applies(const ConvParams& p) {
+// routing policy (conv_split_route): every layer it supports, unless RD_CONV_STREAM=0
+bool conv_stream_h3_enabled() {
     static const bool off = [] { const char* e = getenv("RD_CONV_STREAM"); return e && e[0] == '0'; }();
-    return !off && conv_stream_h3_supported(p);
+    return !off;
 }
+bool conv_stream_h3_applies(const ConvParams& p) { return conv_stream_h3_enabled() && conv_stream_h3_supported(p); }
 
 void launch_conv_stream_h3(const ConvParams& p, hipStream_t s) {
     StreamGeom g;

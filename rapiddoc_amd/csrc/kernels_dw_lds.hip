@@ -244,16 +244,18 @@ __global__ void __launch_bounds__(256) dwconv_kxk_lds_kernel(DwParams p, int tx_
     }
 }
 
-static inline int dw_kxk_lds_k(const DwParams& p) {
+// RD_DW_LDS=0: neither kernel of this file is routed to
+static inline bool dw_lds_off() {
     static const bool off = std::getenv("RD_DW_LDS") && std::string(std::getenv("RD_DW_LDS")) == "0";
-    if (off || p.tokinfo || p.line_w || p.gap_partial) return 0;       // (gap_partial: the planner sized its buffer for the register kernel)
-    if (p.KH != p.KW || (p.KH != 5 && p.KH != 7) || p.SH != 1 || p.SW != 1 || p.PT != p.KH / 2 || p.PL != p.KH / 2) return 0;
-    if (p.OH != p.H || p.OW != p.W || p.C % 32 != 0 || p.xld % 4 != 0) return 0;
-    return p.KH;
+    return off;
 }
-bool dwconv_kxk_lds_applies(const DwParams& p) { return dw_kxk_lds_k(p) != 0; }
-void launch_dwconv_kxk_lds(const DwParams& p, hipStream_t s) {
-    const int k = dw_kxk_lds_k(p);
+// the kernel knows no line ends, no line table and no SE partial sums: dw_route asks for ops without them only
+bool dwconv_kxk_lds_applies(const DwParams& p) {
+    if (dw_lds_off()) return false;
+    if (p.KH != p.KW || (p.KH != 5 && p.KH != 7) || p.SH != 1 || p.SW != 1 || p.PT != p.KH / 2 || p.PL != p.KH / 2) return false;
+    return p.OH == p.H && p.OW == p.W && p.C % 32 == 0 && p.xld % 4 == 0;
+}
+void launch_dwconv_kxk_lds(const DwParams& p, int k, hipStream_t s) {
     const int tx_n = (p.W + 15) / 16, ty_n = (p.H + 7) / 8, ns = p.C / 32;
     const int ntiles = p.N * ty_n * tx_n * ns, per_xcd = (ntiles + 7) / 8;
     dim3 grid(per_xcd * 8), block(256);
@@ -263,9 +265,8 @@ void launch_dwconv_kxk_lds(const DwParams& p, hipStream_t s) {
 }
 
 // which instantiation serves this geometry: 0 = none
-static inline int dw_lds_variant(const DwParams& p) {
-    static const bool off = std::getenv("RD_DW_LDS") && std::string(std::getenv("RD_DW_LDS")) == "0";
-    if (off || p.tokinfo) return 0;
+int dwconv_lds_variant(const DwParams& p) {
+    if (dw_lds_off()) return 0;
     if (!(p.KH == 3 && p.KW == 3 && p.SW == 1 && p.PT == 1 && p.PL == 1 && p.OW == p.W)) return 0;
     if (p.SH == 2) {                                      // the stride-(2, 1) layer in front of a stage (H even: OH = H / 2)
         if (p.OH * 2 != p.H || p.C % 4 != 0) return 0;
@@ -274,18 +275,15 @@ static inline int dw_lds_variant(const DwParams& p) {
         return 0;
     }
     if (p.SH != 1 || p.OH != p.H) return 0;
-    // geometry only - no pointer or leading dimension may enter: the planner asks with an unbound DwParams (dwconv_gap_chunks)
-    // and must get the answer the launch gets.  The SE partial buffer is one value per 16 x H outputs, ~1 % of the map.
+    // geometry only (dw_route's rule).  The SE partial buffer is one value per 16 x H outputs, ~1 % of the map.
     if (p.H == 6 && p.C % 64 == 0) return 1;              // <16, 6>
     if (p.H == 12 && p.C % 32 == 0) return 2;             // <8, 6>: two row groups
     if (p.H == 3 && p.C % 64 == 0) return 3;              // <16, 3>
     return 0;
 }
-bool dwconv_lds_applies(const DwParams& p) { return dw_lds_variant(p) != 0; }
 int dwconv_lds_gap_chunks(const DwParams& p) { return (p.W + kDwTileCols - 1) / kDwTileCols; }
 
-void launch_dwconv_lds(const DwParams& p, hipStream_t s) {
-    const int v = dw_lds_variant(p);
+void launch_dwconv_lds(const DwParams& p, int v, hipStream_t s) {
     const int ct_n = (p.W + kDwTileCols - 1) / kDwTileCols;
     const int ns = p.C / ((v == 2 || v == 4) ? 32 : 64);
     const int ntiles = p.N * ct_n * ns;

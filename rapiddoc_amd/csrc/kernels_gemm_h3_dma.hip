@@ -519,7 +519,7 @@ bool gemm_h3_dma_applies(const ConvParams& p) {
            p.out_mode == OUT_NHWC && !p.ascale && p.K % 4 == 0 && p.K >= 2 * DK && p.Ng >= 96 && (p.xld % 4) == 0;
 }
 
-// which of the two kernels launch_gemm_h3_dma runs for p (the per-op profile names it)
+// which of the two kernels serves p (conv_split_route: CONV_DMA16 / CONV_DMA8)
 bool gemm_h3_dma_uses16(const ConvParams& p) {
     static const int force16 = [] { const char* e = getenv("RD_H3_DMA16"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
     // the 8-wavefront kernel addresses its operands with 32-bit element offsets from p.x / p.wh
@@ -530,7 +530,7 @@ bool gemm_h3_dma_uses16(const ConvParams& p) {
     return !fits32 || (force16 >= 0 ? force16 == 1 : (p.K <= 192 && p.act == ACT_GELU));
 }
 
-void launch_gemm_h3_dma(const ConvParams& p, hipStream_t s) {
+void launch_gemm_h3_dma(const ConvParams& p, bool use16, hipStream_t s) {
     const int ntm = (p.M + DM - 1) / DM, ntn = (p.Ng + DN - 1) / DN, ntiles = ntm * ntn;
     static const int n_cu = [] {
         int dev = 0, n = 256;
@@ -548,7 +548,6 @@ void launch_gemm_h3_dma(const ConvParams& p, hipStream_t s) {
     // 113-124 / 128-136; K96 N96 100 / 112; only the short-K GELU layers keep the 16-wavefront tile: K192 N384 GELU 145 / 139, 183 / 169
     // (their epilogue is a third of the tile's time and drains faster from 64 accumulator registers per wavefront).  Round 3 routed every
     // K <= 384 to the 16-wavefront kernel on measurements at M = 26112-52224, where it led by 5 %.
-    const bool use16 = gemm_h3_dma_uses16(p);
     if (use16) {
         static const int dbg = [] { const char* e = getenv("RD_GEMM_DBG"); return e ? atoi(e) : 0; }();
 #define RD_DMA16(A)                                                                                                  \

@@ -3,6 +3,7 @@
 // conversion at the C-ABI boundary and the image resize+normalise pre-processing.
 // Everything is NHWC fp32 with the channel dimension innermost => 16-byte coalesced accesses.
 #include <cstdlib>
+#include <stdexcept>
 #include <string>
 
 #include "rd_device.h"
@@ -280,45 +281,45 @@ static inline int dw_tiled_tw(const DwParams& p) {
     if (p.KH == 7 && p.KW == 7 && p.SW == 1) return dw7_tw();
     return 0;
 }
-int dwconv_gap_chunks(const DwParams& p) {
-    if (dwconv_lds_applies(p)) return dwconv_lds_gap_chunks(p);
+DwRoute dw_route(const DwParams& p, bool wants_gap) {
+    if (p.tokinfo) return {DW_PIXEL, 0, 0};      // ragged rows: only the per-pixel kernel knows about line ends
+    if (const int v = dwconv_lds_variant(p)) return {DW_LDS, v, dwconv_lds_gap_chunks(p)};
+    // (the one-channel-per-lane kernel writes no partial sums: an op with the SE pooling stays on the register kernels below)
+    if (!wants_gap && !p.line_w && dwconv_kxk_lds_applies(p)) return {DW_KXK_LDS, p.KH, 0};
+    int c4n, threads, gw, g, gpb, chunks;
     if (dw_col_applies(p)) {
-        int c4n, threads, gw, gpb, chunks;
         dw_col_geom(p, c4n, threads, gw, gpb, chunks);
-        return chunks;
+        return {DW_COL, 4, chunks};
     }
     const int tw = dw_tiled_tw(p);
-    if (!tw) return 0;
-    int c4n, threads, gw, g, gpb, chunks;
+    if (!tw) return {DW_PIXEL, 0, 0};
     dw_tiled_geom(p, tw, c4n, threads, gw, g, gpb, chunks);
-    return chunks;
+    return {DW_TILED, tw, chunks};
 }
 
 void launch_dwconv(const DwParams& p_in, hipStream_t s) {
     static const int dbg_env = [] { const char* e = std::getenv("RD_DW_DBG"); return e ? atoi(e) : 0; }();
     DwParams p = p_in;
     p.dbg = dbg_env;
-    if (p.tokinfo) {      // ragged rows: only the per-pixel kernel knows about line ends
-        const long total = (long)p.N * p.OH * p.OW * (p.C >> 2);
-        hipLaunchKernelGGL(dwconv_kernel, dim3(grid_for(total)), dim3(256), 0, s, p);
+    const DwRoute r = dw_route(p, p.gap_partial != nullptr);
+    // the kernels write gridDim-many chunks per image: the buffer must have been sized (dwconv_gap_chunks) for this very route
+    if (p.gap_partial && p.gap_chunks != r.gap_chunks) throw std::runtime_error("launch_dwconv: gap_partial was sized for another kernel");
+    if (r.kernel == DW_LDS) {
+        launch_dwconv_lds(p, r.variant, s);
         return;
     }
-    if (dwconv_lds_applies(p)) {
-        launch_dwconv_lds(p, s);
+    if (r.kernel == DW_KXK_LDS) {
+        launch_dwconv_kxk_lds(p, r.variant, s);
         return;
     }
-    if (dwconv_kxk_lds_applies(p)) {
-        launch_dwconv_kxk_lds(p, s);
-        return;
-    }
-    if (dw_col_applies(p)) {
+    if (r.kernel == DW_COL) {
         int c4n, threads, gw, gpb, chunks;
         dw_col_geom(p, c4n, threads, gw, gpb, chunks);
         hipLaunchKernelGGL((dwconv3x3_col_kernel<4>), dim3(chunks, p.N), dim3(threads), 0, s, p, c4n, gw, gpb);
         return;
     }
-    const int tw = dw_tiled_tw(p);
-    if (tw) {
+    if (r.kernel == DW_TILED) {
+        const int tw = r.variant;
         int c4n, threads, gw, g, gpb, chunks;
         dw_tiled_geom(p, tw, c4n, threads, gw, g, gpb, chunks);
         dim3 grid(chunks, p.N), block(threads);

@@ -68,12 +68,29 @@ struct ConvParams {
     float w9_inv = 0.f;
     int fast_epi = 1;               // interior tiles of the split implicit-GEMM kernels store through buffer accesses (round 5; RD_CONV_FAST_EPI=0: A/B)
 };
+// The kernel a dense convolution runs on.  The route of an op is decided ONCE - by conv_split_route (ops that carry p.wh / p.wl) or
+// conv_f32_route - from the geometry, the weight-image pointers, the mode fields (act, out_mode, allow_skinny, ln_g) and the RD_* switches;
+// x, y, res and ascale are never read, so a planner asks with unbound ConvParams and gets the answer of the launch.  Whether the op
+// multiplies its rows by `ascale` is passed in.  The builder names the op with conv_route_name and launches with launch_conv_route.
+enum ConvRoute : int {
+    // split-fp16 path, in the order conv_split_route asks (the *_applies predicate next to each kernel)
+    CONV_STREAM, CONV_C3H1, CONV_C9H1, CONV_DIRECT, CONV_GEMM_H1, CONV_DMA16, CONV_DMA8,
+    CONV_H3_256x128, CONV_H3_128x96, CONV_H3_256x64, CONV_H3_128x32, CONV_H3_128x64,   // the staged implicit-GEMM tiles (kernels_conv_h3.hip)
+    CONV_H3_TO_F32,       // a tensor beyond the staged kernels' 32-bit offsets: whatever conv_f32_route says, at launch
+    // fp32 MFMA path (kernels_conv.hip)
+    CONV_SKINNY, CONV_F32_128x32, CONV_F32_128x64, CONV_F32_128x96, CONV_F32_128x128
+};
+ConvRoute conv_split_route(const ConvParams& p, bool has_ascale);
+ConvRoute conv_f32_route(const ConvParams& p);      // CONV_SKINNY is the one route that honours ln_g / ln_b (K <= 512 then)
+const char* conv_route_name(ConvRoute r);           // the per-op profile's tag (the builder appends "/h3" on the split path)
+void launch_conv_route(ConvRoute r, const ConvParams& p, hipStream_t s);
+void launch_conv_f32_route(ConvRoute r, const ConvParams& p, hipStream_t s);   // its fp32 half (kernels_conv.hip)
+// callers without a plan: the route, then launch_conv_route
 void launch_conv_igemm(const ConvParams& p, hipStream_t s);
-bool skinny_gemm_applies(int M, int K);   // true when launch_conv_igemm will take the small-M path that can fuse ln_g / ln_b
 // fp32-accurate variant on the fp16 matrix cores (3 MFMAs per product, see kernels_conv_h3.hip); needs p.wh / p.wl
 bool gemm_h3_dma_applies(const ConvParams& p);
 bool gemm_h3_dma_uses16(const ConvParams& p);   // the 16-wavefront kernel (short-K GELU layers, > 2^32-element tensors) or the 8-wavefront one
-void launch_gemm_h3_dma(const ConvParams& p, hipStream_t s);
+void launch_gemm_h3_dma(const ConvParams& p, bool use16, hipStream_t s);
 // single-accumulator split GEMM, 64 x 128 per wavefront, two 4-wavefront workgroups per CU (kernels_gemm_h1.hip); needs p.w1 / p.w1s
 bool gemm_h1_shape_ok(int K, int cout);       // host-side: which layers get a weight image
 bool gemm_h1_applies(const ConvParams& p);
@@ -117,6 +134,7 @@ bool conv_direct_h3_supported(const ConvParams& p);   // geometry
 bool conv_direct_h3_applies(const ConvParams& p);     // geometry + routing policy
 void launch_conv_direct_h3(const ConvParams& p, hipStream_t s);
 // small-K layers (padded K <= 256, <= 96 output channels), operands streamed from global memory (kernels_conv_stream_h3.hip)
+bool conv_stream_h3_enabled();                        // RD_CONV_STREAM != 0 (read once)
 bool conv_stream_h3_supported(const ConvParams& p);
 bool conv_stream_h3_applies(const ConvParams& p);
 void launch_conv_stream_h3(const ConvParams& p, hipStream_t s);
@@ -142,8 +160,6 @@ struct SeqConvParams {
 };
 bool seqconv_shape_ok(int C0, int C1, int N);
 void launch_seqconv(const SeqConvParams& p, hipStream_t s);
-// a short human-readable tag of the tile configuration chosen for p (for the per-op profile)
-const char* conv_igemm_config_name(const ConvParams& p);
 
 // First conv of a network: 3x3 stride 2 pad 1, Cin = 3, reads the caller's NCHW (or NHWC u8/f32) image.
 struct StemParams {
@@ -183,7 +199,7 @@ struct DwParams {
     int act;
     const float* res; int rld;  // added after activation
     float* gap_partial;         // optional [N][gap_chunks][C] partial sums of the OUTPUT (SE fusion), or nullptr
-    int gap_chunks;
+    int gap_chunks;             // host only: the chunk count the buffer was sized for (dwconv_gap_chunks); launch_dwconv checks it
     // ragged rows (the recogniser's batched tail): the tensor is [1][1][W = all tokens][C], token i sits at position
     // tokinfo[i] & 0xffff of a text line of tokinfo[i] >> 16 tokens and the kernel's horizontal taps stop at the line's ends
     const int32_t* tokinfo = nullptr;
@@ -192,17 +208,25 @@ struct DwParams {
     const int32_t* line_w = nullptr; int line_w_stride = 0;
     int dbg = 0;                // developer (RD_DW_DBG): 1 no stores, 2 no loads - timing only
 };
+// The kernel a depthwise convolution runs on and the partial-sum chunks per image it writes when the SE pooling rides along (0: the fused
+// pooling is not available on that kernel).  variant: the LDS kernels' instantiation (dwconv_lds_variant / kernel size), the tiled kernel's width.
+enum DwKernel : int { DW_PIXEL, DW_LDS, DW_KXK_LDS, DW_COL, DW_TILED };
+struct DwRoute { DwKernel kernel; int variant; int gap_chunks; };
+// launch_dwconv and the planner (dwconv_gap_chunks, which sizes the partial-sum buffer) both ask here.  Ragged rows (p.tokinfo) and the line
+// table (p.line_w) are read from p as the launch sees it; wants_gap = the launch will carry gap_partial.  The rule that lets the planner ask
+// with wants_gap = true and an UNBOUND DwParams: the only kernel that looks at a pointer or a leading dimension is DW_KXK_LDS, and it is
+// never taken when the gap is wanted; ragged ops (1 x k) have no pooled kernel.  Everything else is geometry and switches.
+DwRoute dw_route(const DwParams& p, bool wants_gap);
+// throws std::runtime_error when p.gap_partial is set and p.gap_chunks (the planner's count) is not the route's
 void launch_dwconv(const DwParams& p, hipStream_t s);
-// number of per-image partial-sum chunks launch_dwconv writes to p.gap_partial for this geometry (0 = the fused
-// global-average-pool is not available for it)
-int dwconv_gap_chunks(const DwParams& p);
-// kernels_dw_lds.hip: the LDS-DMA-staged 3x3 / stride 1 for the recogniser's 3 / 6 / 12-row maps; launch_dwconv routes to it
-bool dwconv_lds_applies(const DwParams& p);
+inline int dwconv_gap_chunks(const DwParams& p) { return dw_route(p, true).gap_chunks; }
+// kernels_dw_lds.hip: the LDS-DMA-staged 3x3 / stride 1 for the recogniser's 3 / 6 / 12-row maps (geometry only; 0 = none) ...
+int dwconv_lds_variant(const DwParams& p);
 int dwconv_lds_gap_chunks(const DwParams& p);
-void launch_dwconv_lds(const DwParams& p, hipStream_t s);
-// ... and the 5x5 / 7x7 stride-1 kernel with one channel per lane (needs gap_partial == nullptr: checked at the launch, not by the planner)
+void launch_dwconv_lds(const DwParams& p, int variant, hipStream_t s);
+// ... and the 5x5 / 7x7 stride-1 kernel with one channel per lane (no ragged rows, line table or SE pooling: dw_route)
 bool dwconv_kxk_lds_applies(const DwParams& p);
-void launch_dwconv_kxk_lds(const DwParams& p, hipStream_t s);
+void launch_dwconv_kxk_lds(const DwParams& p, int k, hipStream_t s);
 
 // PPLCNetV3 depthwise layer (kernels_lcv3.hip): y = post_act ? post_s hardswish(dw(x') + bias) + post_b : dw(x') + bias, x' = pre_act ? pre_s hardswish(x) + pre_b : x,
 // k = 3 / 5, strides (1,1), (2,1), (1,2), (2,2), 'same' padding of ZEROS around the pre-affined map; per-image valid widths of the input / output (LineTab columns) or nullptr
