@@ -95,6 +95,7 @@ DEBUG_SYMBOLS = {
     "rd_debug_stem34": (_F, [_I] * 11 + [_P] * 7),
     "rd_debug_dwconv": (_F, [_I] * 8 + [_P] * 8),
     "rd_debug_dw_route": (_I, [_I] * 9 + [_P, _I, _P]),
+    "rd_debug_weight_split": (_I, [_P, _I, _I, _P, _P]),
     "rd_debug_lcv3_dw": (_F, [_I] * 9 + [_P] * 8),
     "rd_debug_dw5_strip": (_F, [_I] * 11 + [_P] * 7),
     "rd_debug_mv1e_pool": (_I, [_I] * 4 + [_P] * 3),

@@ -465,6 +465,19 @@ int rd_debug_dw_route(int N, int H, int W, int C, int K, int SH, int ragged, int
     return planned;
 }
 
+// developer entry, host only (no HIP call): the weight rules of rd_host.h on w[n].  Returns rd_pow2_exp(w, n, clamp) (clamp <= 0: not
+// clamped) and writes, per element i, the fp16 bits (hi, lo) of rd_split_scaled at that exponent to scaled[2 i], scaled[2 i + 1] and of
+// rd_split_2048 to h3[2 i], h3[2 i + 1].  Returns -1000 (no exponent) on a bad argument.
+int rd_debug_weight_split(const float* w, int n, int clamp, uint16_t* scaled, uint16_t* h3) {
+    if (!w || n <= 0 || !scaled || !h3) return -1000;
+    const int ex = rd::rd_pow2_exp(w, (size_t)n, clamp);
+    for (int i = 0; i < n; ++i) {
+        rd::rd_split_scaled(w[i], ex, scaled[2 * i], scaled[2 * i + 1]);
+        rd::rd_split_2048(w[i], h3[2 * i], h3[2 * i + 1]);
+    }
+    return ex;
+}
+
 // developer entry: one PPLCNetV3 depthwise layer through launch_lcv3_dw (kernels_lcv3.hip; x NHWC fp32 [N][H][W][C], w [K*K][C], bias [C],
 // y [N][OH][OW][C]; aff = {pre_s, pre_b, post_s, post_b}, pre_act: hardswish + (pre_s, pre_b) on load; line_in / line_out int32 [N] valid
 // widths or null; gap: [N][OH][C] row sums of y over the output width, or null).  Returns ms per launch, < 0: geometry not served.

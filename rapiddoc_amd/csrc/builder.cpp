@@ -126,10 +126,10 @@ std::vector<float> Builder::bn_scale_shift(const std::string& bn, int c, std::ve
 // "auto" precision: wide pointwise convolutions also run on the split-fp16 matrix-core path (256x128 tile; measured
 // 1.2x the fp32 MFMA kernel at K = 192, 2x at K >= 768 - table in kernels_conv_h3.hip)
 static inline bool auto_split_conv(int kh, int kw, int K, int cout) {
-    static const int kxk_k = std::getenv("RD_H3_KXK_MIN_K") ? std::atoi(std::getenv("RD_H3_KXK_MIN_K")) : 96;   // round 2: 96 / 24 (round 1: 288 / 48) measured +2.8 % pages/s
-    static const int kxk_n = std::getenv("RD_H3_KXK_MIN_N") ? std::atoi(std::getenv("RD_H3_KXK_MIN_N")) : 24;
-    static const int pw_k = std::getenv("RD_H3_1X1_MIN_K") ? std::atoi(std::getenv("RD_H3_1X1_MIN_K")) : 96;
-    static const int pw_n = std::getenv("RD_H3_1X1_MIN_N") ? std::atoi(std::getenv("RD_H3_1X1_MIN_N")) : 96;
+    static const int kxk_k = rd_env_int("RD_H3_KXK_MIN_K", 96);   // round 2: 96 / 24 (round 1: 288 / 48) measured +2.8 % pages/s
+    static const int kxk_n = rd_env_int("RD_H3_KXK_MIN_N", 24);
+    static const int pw_k = rd_env_int("RD_H3_1X1_MIN_K", 96);
+    static const int pw_n = rd_env_int("RD_H3_1X1_MIN_N", 96);
     // small-K layers: the streaming split kernel (kernels_conv_stream_h3.hip) takes them whatever the thresholds below say
     if (conv_stream_h3_enabled() && cout >= 12 && conv_stream_h3_shape_ok(kh, kw, K / (kh * kw), cout)) return true;
     return (kh == 1 && kw == 1) ? (K >= pw_k && cout >= pw_n) : (K >= kxk_k && cout >= kxk_n);
@@ -266,7 +266,7 @@ void Builder::fold_conv(const std::string& wname, const std::string& bname, cons
 
 // which mixer kernel serves the block: the weight images the preparation left in the parameter block, and RD_MIXER_WS=0 (A/B switch)
 Builder::MixerRoute Builder::mixer_route(const std::string& prefix, int C) const {
-    static const bool ws_off = std::getenv("RD_MIXER_WS") && std::string(std::getenv("RD_MIXER_WS")) == "0";
+    static const bool ws_off = rd_env_off("RD_MIXER_WS");
     const std::string hkey = prefix + ".mixer#h3";
     if (!(h3_ || mixer_h3_) || !pb_->has(hkey + ".w1h")) return MIXER_F32;
     if (!ws_off && pb_->has(hkey + ".ws")) return MIXER_WS;
@@ -386,7 +386,7 @@ TView Builder::linear(const std::string& prefix, const TView& x, int act, const 
 
 bool Builder::deconv_pair_to_prob(const std::string& w1n, const std::string& b1n, const std::string& bn1, const std::string& w2n,
                                   const std::string& b2n, const TView& x, const TView& out) {
-    static const bool off = [] { const char* e = getenv("RD_DET_HEAD_FUSED"); return e && e[0] == '0'; }();
+    static const bool off = rd_env_off("RD_DET_HEAD_FUSED");
     const HostTensor& w1 = ws_->get(w1n);
     const HostTensor& w2 = ws_->get(w2n);
     if (off || w1.shape.size() != 4 || w2.shape.size() != 4 || w1.shape[2] != 2 || w1.shape[3] != 2 || w2.shape[2] != 2 || w2.shape[3] != 2)
@@ -569,7 +569,7 @@ TView Builder::stem_front(const std::string& w1, const std::string& bn1, const s
     g2.kh = g2.kw = 2;
     g2.pb = g2.pr = 1;
     const std::string fkey = w1 + "|" + bn1 + "|stemfront";
-    const bool off = std::getenv("RD_STEM_FUSED") && std::getenv("RD_STEM_FUSED")[0] == '0';   // A/B switch, read per plan
+    const bool off = rd_env_off("RD_STEM_FUSED");   // A/B switch, read per plan
     const bool fused = planning() && !off && (h3_ || mixer_h3_) && pb_->has(fkey + "#img");
     if (!fused) {
         // the four separate kernels (fp32 precision mode, unsupported widths, and - in PREPARE mode - the weight folding of both forms)

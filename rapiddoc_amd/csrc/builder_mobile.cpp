@@ -429,7 +429,7 @@ bool Builder::lcv3_block(const std::string& dw_w, const std::string& pw_w, const
         prepare_lcv3_block(key, w, pw_b);   // parameters this kernel shares
         return false;
     }
-    const bool on = std::getenv("RD_LCV3_FUSED") && std::getenv("RD_LCV3_FUSED")[0] == '1';   // A/B switch, read per plan
+    const bool on = rd_env_on("RD_LCV3_FUSED");   // A/B switch, read per plan
     if (!on || !(h3_ || mixer_h3_) || !pb_->has(key + "#w") || !pb_->has(dkey + "#w") || plan_->ld(x) % 4 != 0 || x.coff % 4 != 0) return false;
     TView y = alloc(x.n, x.h, x.w, cout);
     Lcv3BlockParams p{};

@@ -40,8 +40,7 @@ static inline std::string shape_str(const TView& x, std::initializer_list<int> c
 // A/B switch of a route, read per plan: the variable's first character '0' / '1' forces the route off / on for every layer the kernel
 // serves; unset or anything else leaves the per-layer default
 static inline bool route_switch(const char* env, bool dflt) {
-    const char* sw = std::getenv(env);
-    return sw && (sw[0] == '0' || sw[0] == '1') ? sw[0] == '1' : dflt;
+    return rd_env_on(env) || (dflt && !rd_env_off(env));
 }
 
 // OpRecord::run of a one-input one-output kernel: the plan-time parameters with x / y taken from the plan's buffers at run time

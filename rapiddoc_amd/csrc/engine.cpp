@@ -213,8 +213,8 @@ Plan::~Plan() {
 // =================================================================================================
 extern bool g_disable_fused_mixer;
 Engine::Engine(int device, const std::string& kind) : device_(device), kind_(kind), model_(find_model(kind)) {
-    if (const char* e = getenv("RD_DISABLE_FUSED_MIXER")) g_disable_fused_mixer = e[0] == '1';
-    if (const char* e = getenv("RD_GRAPHS")) graphs_ = e[0] != '0';
+    if (const char* e = getenv("RD_DISABLE_FUSED_MIXER")) g_disable_fused_mixer = e[0] == '1';   // (a process-wide flag: unset leaves it as it is)
+    if (rd_env_off("RD_GRAPHS")) graphs_ = false;
     if (const char* e = getenv("RD_PRECISION")) {
         const std::string v(e);
         RD_CHECK(v == "auto" || v == "fp32" || v == "h3", "RD_PRECISION must be auto, fp32 or h3");
@@ -344,7 +344,7 @@ void Engine::run(int B, int H, int W, int flags, const std::vector<void*>& ext, 
             arena_bytes_ = plan.arena_bytes;
             // developer check (RD_POISON_ARENA=1): fresh workspace filled with NaN bit patterns - no kernel may let workspace bytes
             // it did not write reach a result or the range guard
-            static const bool poison = std::getenv("RD_POISON_ARENA") && std::getenv("RD_POISON_ARENA")[0] == '1';
+            static const bool poison = rd_env_on("RD_POISON_ARENA");
             if (poison) {     // on the launch stream: a null-stream memset is not ordered against a non-blocking stream
                 RD_HIP(hipMemsetAsync(arena_, 0xFF, arena_bytes_, s));
                 RD_HIP(hipStreamSynchronize(s));
@@ -356,7 +356,7 @@ void Engine::run(int B, int H, int W, int flags, const std::vector<void*>& ext, 
         if (b.external >= 0) RD_CHECK(b.external < (int)ext.size() && ext[b.external], "missing external buffer");
     if (!profiling_) {
         // developer trace (RD_RANGE_TRACE=1): which op raises the split-fp16 range flag (synchronises after every op)
-        static const bool range_trace = std::getenv("RD_RANGE_TRACE") && std::getenv("RD_RANGE_TRACE")[0] == '1';
+        static const bool range_trace = rd_env_on("RD_RANGE_TRACE");
         if (range_trace && range_flag_) {
             for (const OpRecord& op : plan.ops) {
                 op.run(plan, ctx);

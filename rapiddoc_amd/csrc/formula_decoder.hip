@@ -869,10 +869,10 @@ static int route_gemv(const GemvParams& p, int max_wgs, hipStream_t s) {
     return MT * 10000 + CW * 1000 + KPL * 100 + (DB ? 10 : 0) + (DX ? 1 : 0);
 }
 int dec_gemv_route(const GemvParams& p, hipStream_t s) {
-    static const bool on = [] { const char* e = getenv("RD_DEC_GEMV"); return !(e && e[0] == '0'); }();
+    static const bool on = !rd_env_off("RD_DEC_GEMV");
     // developer knobs (tools/bench_formula.py sweeps): workgroups of a wide layer's loop, columns per wavefront of a wide layer
-    static const int wide_wgs = [] { const char* e = getenv("RD_DEC_GEMV_WGS"); return e ? atoi(e) : 512; }();
-    static const bool dx = [] { const char* e = getenv("RD_DEC_GEMV_DX"); return !(e && e[0] == '0'); }();     // A/B
+    static const int wide_wgs = rd_env_int("RD_DEC_GEMV_WGS", 512);
+    static const bool dx = !rd_env_off("RD_DEC_GEMV_DX");     // A/B
     const int M = p.M, K = p.K;
     const bool has_ln = p.ln_g != nullptr;
     if (!on || M < 1 || p.N < 1 || M > 32 || (K != 512 && K != 2048) || (K == 2048 && (M > 16 || has_ln))) return 0;
@@ -982,9 +982,9 @@ int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long lon
         gemm(enc_d, B * S, D, "l" + std::to_string(l) + ".ckv", 2 * D, ckv + (size_t)l * B * S * 2 * D, ACT_NONE, nullptr, s);
 
     // fused projection + attention launches (dec_attn_fused_kernel): RD_DEC_FUSED=0 keeps the round-3 form (A/B, parity tests)
-    static const bool fused_env = [] { const char* e = getenv("RD_DEC_FUSED"); return !(e && e[0] == '0'); }();
+    static const bool fused_env = !rd_env_off("RD_DEC_FUSED");
     const bool fused = fused_env && B <= 32;
-    static const bool attn2 = [] { const char* e = getenv("RD_DEC_ATTN2"); return !(e && e[0] == '0'); }();
+    static const bool attn2 = !rd_env_off("RD_DEC_ATTN2");
     // One decode step = ~70 dependent launches whose arguments never change (the step index lives in device memory), so
     // the step is captured once into a hipGraph and replayed: the host cost per step drops from ~70 launches to one.
     // a linear of the step: the weight-streaming GEMV where it covers the shape, the round-3 skinny GEMM otherwise
@@ -994,7 +994,7 @@ int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long lon
     };
     // the embedding of step t + 1 rides in step t's select launch (RD_DEC_EMBED_IN_SELECT=0: its own launch, as rounds 1-5); the first
     // step's is enqueued once, ahead of the loop
-    static const bool embed_in_select = [] { const char* e = getenv("RD_DEC_EMBED_IN_SELECT"); return !(e && e[0] == '0'); }();
+    static const bool embed_in_select = !rd_env_off("RD_DEC_EMBED_IN_SELECT");
     auto enqueue_embed = [&]() {
         hipLaunchKernelGGL(dec_embed_ln_kernel, dim3(B), dim3(64), 0, s, params_.ptr("emb"), params_.ptr("pos"), ids_out, ids_ld, st,
                            params_.ptr("ln_emb.weight"), params_.ptr("ln_emb.bias"), x);
@@ -1065,7 +1065,7 @@ int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long lon
     if (embed_in_select) enqueue_embed();
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
-    static const bool use_graph = [] { const char* e = getenv("RD_DECODE_GRAPH"); return !(e && e[0] == '0'); }();
+    static const bool use_graph = !rd_env_off("RD_DECODE_GRAPH");
     if (use_graph && max_new > 2) {
         if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
             enqueue_step();

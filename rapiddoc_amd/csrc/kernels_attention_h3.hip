@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256) attention_h3_kernel(const float* __restri
 }
 
 bool attention_h3_applies(int T, int hd) {
-    static const bool off = [] { const char* e = getenv("RD_ATTN_MFMA"); return e && e[0] == '0'; }();
+    static const bool off = rd_env_off("RD_ATTN_MFMA");
     return !off && (hd == 15 || hd == 16) && T >= 1 && T <= ATT_MAX_T;
 }
 int attention_h3_max_t() { return ATT_MAX_T; }

@@ -477,7 +477,7 @@ static void launch_skinny2(const ConvParams& p, hipStream_t s) {
 }
 
 static void launch_skinny(const ConvParams& p, hipStream_t s) {
-    static const bool v2 = [] { const char* e = getenv("RD_SKINNY2"); return !(e && e[0] == '0'); }();
+    static const bool v2 = !rd_env_off("RD_SKINNY2");
     if (v2 && p.K <= 2048 && (!p.ln_g || p.K <= 512)) {
         const bool wide = p.K > 512;        // K passes of 1024 (fc2: K = 2048) instead of 512
         if (p.M <= 8) { if (wide) launch_skinny2<8, 4, 4>(p, s); else launch_skinny2<8, 4, 2>(p, s); return; }

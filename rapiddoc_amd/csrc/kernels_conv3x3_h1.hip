@@ -326,7 +326,7 @@ bool conv3x3_h1_shape_ok(int kh, int kw, int cin, int cout) {
 }
 
 bool conv3x3_h1_applies(const ConvParams& p) {
-    static const bool off = [] { const char* e = getenv("RD_CONV3X3_H1"); return e && e[0] == '0'; }();
+    static const bool off = rd_env_off("RD_CONV3X3_H1");
     return !off && p.w3 && p.w3_inv > 0.f && conv3x3_h1_shape_ok(p.KH, p.KW, p.Cin, p.Ng) && p.SH == 1 && p.SW == 1 && p.PT == 1 && p.PL == 1 &&
            p.OH == p.H && p.OW == p.W && p.out_mode == OUT_NHWC && !p.ascale && !p.ln_g && (p.xld % 4) == 0;
 }
@@ -336,12 +336,7 @@ void launch_conv3x3_h1(const ConvParams& p, hipStream_t s) {
     const int tiles_r = (p.OH + C3_TR - 1) / C3_TR, tiles_c = (p.OW + C3_TC - 1) / C3_TC;
     const int ntiles = p.N * tiles_r * tiles_c;
     const int nstep = 9 * (p.Cin / 16);
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return rd_cu_budget(n > 0 ? n : 256);
-    }();
+    const int n_cu = rd_cu_budget(rd_cu_count());
     const int nb = (p.Ng + 31) / 32;
     const size_t lds = (size_t)2 * C3_PLANE + (size_t)C3_D * nb * 2048;
     const dim3 grid((unsigned)std::min(ntiles, 2 * n_cu)), block(256);
@@ -369,15 +364,7 @@ void launch_conv3x3_h1(const ConvParams& p, hipStream_t s) {
 float prepare_conv3x3_h1_weights(const float* w, int N, int Cin, std::vector<uint16_t>& img) {
     const int K = 9 * Cin, nb_n = (N + 31) / 32, nstep = 9 * (Cin / 16);
     img.assign((size_t)nstep * nb_n * 2 * 512, 0);
-    float mx = 0.f;
-    for (size_t i = 0; i < (size_t)N * K; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-    int ex = 0;
-    if (mx > 0.f && std::isfinite(mx)) {
-        int x = 0;
-        (void)std::frexp(mx, &x);
-        ex = 14 - x;
-        ex = ex > 100 ? 100 : ex < -100 ? -100 : ex;
-    }
+    const int ex = rd_pow2_exp(w, (size_t)N * K, RD_EXP_CLAMP);
     const int full = Cin / 32, tail16 = (Cin % 32) / 16;
     size_t slab = 0;
     for (int pass = 0; pass < full + tail16; ++pass) {
@@ -390,15 +377,8 @@ float prepare_conv3x3_h1_weights(const float* w, int N, int Cin, std::vector<uin
                         if (n >= N) continue;
                         for (int e = 0; e < 8; ++e) {
                             const int k = tap * Cin + pass * 32 + ks * 16 + 8 * (lane >> 5) + e;
-                            const float vs = std::ldexp(w[(size_t)n * K + k], ex);
-                            const _Float16 hh = (_Float16)vs;
-                            const _Float16 ll = (_Float16)(vs - (float)hh);
-                            uint16_t hb, lb;
-                            __builtin_memcpy(&hb, &hh, 2);
-                            __builtin_memcpy(&lb, &ll, 2);
                             const size_t base = ((slab * nb_n + nb) * 2) * 512 + (size_t)lane * 8 + e;
-                            img[base] = hb;
-                            img[base + 512] = lb;
+                            rd_split_scaled(w[(size_t)n * K + k], ex, img[base], img[base + 512]);
                         }
                     }
     }

@@ -264,7 +264,7 @@ bool conv9x9_h1_shape_ok(int kh, int kw, int cin, int cout) {
 }
 
 bool conv9x9_h1_applies(const ConvParams& p) {
-    static const bool off = [] { const char* e = getenv("RD_CONV9X9_H1"); return e && e[0] == '0'; }();
+    static const bool off = rd_env_off("RD_CONV9X9_H1");
     // (the patch loads address an image with 32-bit byte offsets)
     return !off && p.w9 && p.w9_inv > 0.f && conv9x9_h1_shape_ok(p.KH, p.KW, p.Cin, p.Ng) && p.SH == 1 && p.SW == 1 && p.PT == C9_HALO && p.PL == C9_HALO &&
            p.OH == p.H && p.OW == p.W && p.out_mode == OUT_NHWC && !p.ascale && !p.ln_g && (p.xld % 4) == 0 &&
@@ -276,12 +276,7 @@ void launch_conv9x9_h1(const ConvParams& p, hipStream_t s) {
     const int tiles_r = (p.OH + C9_TR - 1) / C9_TR, tiles_c = (p.OW + C9_TC - 1) / C9_TC;
     const int ntiles = p.N * tiles_r * tiles_c;
     const int nstep = C9_NS * (p.Cin / C9_CC);
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return rd_cu_budget(n > 0 ? n : 256);
-    }();
+    const int n_cu = rd_cu_budget(rd_cu_count());
     const size_t lds = (size_t)2 * C9_PLANE + (size_t)C9_D * C9_SLAB;
     const dim3 grid((unsigned)std::min(ntiles, 2 * n_cu)), block(256);
     static unsigned long long ok = 0;
@@ -296,15 +291,7 @@ void launch_conv9x9_h1(const ConvParams& p, hipStream_t s) {
 float prepare_conv9x9_h1_weights(const float* w, int N, int Cin, std::vector<uint16_t>& img) {
     const int K = C9_NS * Cin, passes = Cin / C9_CC, nstep = C9_NS * passes;
     img.assign((size_t)nstep * C9_NB * 2 * 512, 0);
-    float mx = 0.f;
-    for (size_t i = 0; i < (size_t)N * K; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-    int ex = 0;
-    if (mx > 0.f && std::isfinite(mx)) {
-        int x = 0;
-        (void)std::frexp(mx, &x);
-        ex = 14 - x;
-        ex = ex > 100 ? 100 : ex < -100 ? -100 : ex;
-    }
+    const int ex = rd_pow2_exp(w, (size_t)N * K, RD_EXP_CLAMP);
     size_t slab = 0;
     for (int pass = 0; pass < passes; ++pass)
         for (int tap = 0; tap < C9_NS; ++tap, ++slab)
@@ -314,15 +301,8 @@ float prepare_conv9x9_h1_weights(const float* w, int N, int Cin, std::vector<uin
                     if (n >= N) continue;
                     for (int e = 0; e < 8; ++e) {
                         const int k = tap * Cin + pass * C9_CC + 8 * (lane >> 5) + e;
-                        const float vs = std::ldexp(w[(size_t)n * K + k], ex);
-                        const _Float16 hh = (_Float16)vs;
-                        const _Float16 ll = (_Float16)(vs - (float)hh);
-                        uint16_t hb, lb;
-                        __builtin_memcpy(&hb, &hh, 2);
-                        __builtin_memcpy(&lb, &ll, 2);
                         const size_t base = ((slab * C9_NB + nb) * 2) * 512 + (size_t)lane * 8 + e;
-                        img[base] = hb;
-                        img[base + 512] = lb;
+                        rd_split_scaled(w[(size_t)n * K + k], ex, img[base], img[base + 512]);
                     }
                 }
     return std::ldexp(1.f, -ex);

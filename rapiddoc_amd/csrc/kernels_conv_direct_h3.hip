@@ -369,7 +369,7 @@ bool conv_direct_h3_supported(const ConvParams& p) {
 // ... and where launch_conv_igemm_h3 routes to it: 3x3 layers.  The 2x2 stem layers (4 taps, K = 96 / 192) measured level with
 // the implicit GEMM (58 / 62 vs 54 / 63 us) and stay there (RD_CONV_DIRECT=2 routes them here too, =0 nothing).
 bool conv_direct_h3_applies(const ConvParams& p) {
-    static const int mode = [] { const char* e = getenv("RD_CONV_DIRECT"); return e ? atoi(e) : 1; }();
+    static const int mode = rd_env_int("RD_CONV_DIRECT", 1);
     if (mode == 0) return false;
     if (p.KH * p.KW < 9 && mode != 2) return false;
     return conv_direct_h3_supported(p);
@@ -380,13 +380,8 @@ void launch_conv_direct_h3(const ConvParams& p, hipStream_t s) {
     if (!direct_geom(p, g)) return;
     const int nb = g.N32 / 32, ks = ((g.CC + 15) / 16 * 16) / 16;
     const size_t lds = (size_t)2 * g.PP * g.S + (size_t)6 * g.N32 * g.S;
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    static const int fast_epi = [] { const char* e = getenv("RD_DIRECT_FAST_EPI"); return e && e[0] == '0' ? 0 : 1; }();
+    const int n_cu = rd_cu_count();
+    static const int fast_epi = rd_env_off("RD_DIRECT_FAST_EPI") ? 0 : 1;
     g.fast_epi = fast_epi;
     const long ntiles = (long)p.N * g.tiles_r * g.tiles_c;
     // persistent workgroups: as many as fit the chip at once (two per CU when LDS and the 128-VGPR single-block kernels allow)

@@ -371,7 +371,7 @@ __global__ void __launch_bounds__(WM* WN * 64, (WM * WN == 4 && BM * BN >= 128 *
 }
 
 static inline ConvRoute h3_pick_tile(const ConvParams& p) {
-    static const int forced = [] { const char* e = getenv("RD_H3_BN"); return e ? atoi(e) : 0; }();   // 32 / 64 / 96 / 258 (256x128), anything else 256x64
+    static const int forced = rd_env_int("RD_H3_BN", 0);   // 32 / 64 / 96 / 258 (256x128), anything else 256x64
     if (forced) return forced == 32 ? CONV_H3_128x32 : forced == 64 ? CONV_H3_128x64 : forced == 96 ? CONV_H3_128x96 : forced == 258 ? CONV_H3_256x128 : CONV_H3_256x64;
     // Measured on MI355X (TF/s of fp32-equivalent work, M = 131072; fp32 MFMA kernel in brackets):
     //   K192/N384  K384/N768  K768/N384  K2176/N512  4096^2
@@ -392,17 +392,12 @@ static inline bool h3_is_1x1(const ConvParams& p) {
 }
 template <int BM, int BN, int WM, int WN>
 static void h3_launch_cfg(const ConvParams& p_in, hipStream_t s) {
-    static const int fast_epi = [] { const char* e = getenv("RD_CONV_FAST_EPI"); return e && e[0] == '0' ? 0 : 1; }();
+    static const int fast_epi = rd_env_off("RD_CONV_FAST_EPI") ? 0 : 1;
     ConvParams p = p_in;
     p.fast_epi = fast_epi;
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.Ng + BN - 1) / BN, ntiles = ntm * ntn;
     // 8-wavefront tiles: persistent workgroups, one per CU (their two LDS stages leave room for one only)
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = rd_cu_count();
     const bool persistent = WM * WN == 8;
     dim3 grid(persistent ? (ntiles < n_cu ? ntiles : n_cu) : ntiles), block(WM * WN * 64);
     if (h3_is_1x1(p))
@@ -457,16 +452,7 @@ void split_weights_h3(const float* w, int rows, int K, std::vector<uint16_t>& hi
     hi.assign((size_t)rows * Kp, 0);
     lo.assign((size_t)rows * Kp, 0);
     for (int r = 0; r < rows; ++r)
-        for (int k = 0; k < K; ++k) {
-            const float v = w[(size_t)r * K + k];
-            const _Float16 h = (_Float16)v;
-            const _Float16 l = (_Float16)((v - (float)h) * 2048.f);
-            uint16_t hb, lb;
-            __builtin_memcpy(&hb, &h, 2);
-            __builtin_memcpy(&lb, &l, 2);
-            hi[(size_t)r * Kp + k] = hb;
-            lo[(size_t)r * Kp + k] = lb;
-        }
+        for (int k = 0; k < K; ++k) rd_split_2048(w[(size_t)r * K + k], hi[(size_t)r * Kp + k], lo[(size_t)r * Kp + k]);
 }
 
 }  // namespace rd

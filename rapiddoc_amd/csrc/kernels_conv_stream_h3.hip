@@ -181,7 +181,7 @@ bool conv_stream_h3_supported(const ConvParams& p) {
 }
 // routing policy (conv_split_route): every layer it supports, unless RD_CONV_STREAM=0
 bool conv_stream_h3_enabled() {
-    static const bool off = [] { const char* e = getenv("RD_CONV_STREAM"); return e && e[0] == '0'; }();
+    static const bool off = rd_env_off("RD_CONV_STREAM");
     return !off;
 }
 bool conv_stream_h3_applies(const ConvParams& p) { return conv_stream_h3_enabled() && conv_stream_h3_supported(p); }

@@ -385,7 +385,7 @@ void launch_ctc_head(const CtcParams& p, hipStream_t s) {
         const int tiles = (p.M + CH_TOK - 1) / CH_TOK;
         const size_t sh3 = (size_t)(2 * 2 * CH_CLS * CT_K) * sizeof(_Float16);   // two (hi, lo) class tiles
         const int per_xcd = (tiles * p.nsplit + 7) / 8;
-        static const int mode = std::getenv("RD_CTC_MODE") ? atoi(std::getenv("RD_CTC_MODE")) : 0;
+        static const int mode = rd_env_int("RD_CTC_MODE", 0);
         static unsigned long long okm[4] = {};
 #define RD_CTC_CASE(A) case A: rd_allow_dynamic_lds((const void*)ctc_head_h3_kernel<A>, sh3, okm[A]); \
         hipLaunchKernelGGL(ctc_head_h3_kernel<A>, dim3(per_xcd * 8), dim3(512), sh3, s, p, cps, tiles, per_xcd); break;

@@ -248,15 +248,7 @@ float prepare_det_local_weights(const float* w3, std::vector<float>& img32, std:
             for (int tp = 0; tp < 9; ++tp) row[4 * DL_C + tp] = w3[((size_t)co * 65) * 9 + tp];
         }
     }
-    float mx = 0.f;
-    for (float v : m) mx = std::fmax(mx, std::fabs(v));
-    int ex = 0;
-    if (mx > 0.f && std::isfinite(mx)) {
-        int x = 0;
-        (void)std::frexp(mx, &x);
-        ex = 14 - x;
-        ex = ex > 100 ? 100 : ex < -100 ? -100 : ex;
-    }
+    const int ex = rd_pow2_exp(m.data(), m.size(), RD_EXP_CLAMP);
     const size_t nfrag = (size_t)4 * DL_STEPS * 2;
     img32.assign(nfrag * 512, 0.f);
     img16.assign(nfrag * 1024, 0);
@@ -269,14 +261,7 @@ float prepare_det_local_weights(const float* w3, std::vector<float>& img32, std:
                         const float v = m[((size_t)par * DL_C + co) * KP + k];
                         const size_t frag = ((size_t)par * DL_STEPS + s) * 2 + cb;
                         img32[frag * 512 + (size_t)lane * 8 + e] = v;
-                        const float vs = std::ldexp(v, ex);
-                        const _Float16 hh = (_Float16)vs;
-                        const _Float16 ll = (_Float16)(vs - (float)hh);
-                        uint16_t hb, lb;
-                        __builtin_memcpy(&hb, &hh, 2);
-                        __builtin_memcpy(&lb, &ll, 2);
-                        img16[frag * 1024 + (size_t)lane * 8 + e] = hb;
-                        img16[frag * 1024 + 512 + (size_t)lane * 8 + e] = lb;
+                        rd_split_scaled(v, ex, img16[frag * 1024 + (size_t)lane * 8 + e], img16[frag * 1024 + 512 + (size_t)lane * 8 + e]);
                     }
     return std::ldexp(1.f, -ex);
 }

@@ -246,7 +246,7 @@ __global__ void __launch_bounds__(256) dwconv_kxk_lds_kernel(DwParams p, int tx_
 
 // RD_DW_LDS=0: neither kernel of this file is routed to
 static inline bool dw_lds_off() {
-    static const bool off = std::getenv("RD_DW_LDS") && std::string(std::getenv("RD_DW_LDS")) == "0";
+    static const bool off = rd_env_off("RD_DW_LDS");
     return off;
 }
 // the kernel knows no line ends, no line table and no SE partial sums: dw_route asks for ops without them only

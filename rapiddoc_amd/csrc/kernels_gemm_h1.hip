@@ -447,15 +447,7 @@ __global__ void __launch_bounds__(256, 2) gemm_h1_kernel(ConvParams p, int ntn, 
 float prepare_gemm_h1_weights(const float* w, int N, int K, std::vector<uint16_t>& img) {
     const int KS = K / 16, ntn = (N + HN - 1) / HN;
     img.assign((size_t)ntn * KS * (H_BH / 2), 0);
-    float mx = 0.f;
-    for (size_t i = 0; i < (size_t)N * K; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-    int ex = 0;
-    if (mx > 0.f && std::isfinite(mx)) {
-        int x = 0;
-        (void)std::frexp(mx, &x);           // mx = m * 2^x, m in [0.5, 1)
-        ex = 14 - x;
-        ex = ex > 100 ? 100 : ex < -100 ? -100 : ex;
-    }
+    const int ex = rd_pow2_exp(w, (size_t)N * K, RD_EXP_CLAMP);
     for (int nt = 0; nt < ntn; ++nt)
         for (int s = 0; s < KS; ++s)
             for (int j = 0; j < 4; ++j)
@@ -464,15 +456,8 @@ float prepare_gemm_h1_weights(const float* w, int N, int K, std::vector<uint16_t
                     if (n >= N) continue;
                     for (int e8 = 0; e8 < 8; ++e8) {
                         const int k = 16 * s + 8 * (lane >> 5) + e8;
-                        const float vs = std::ldexp(w[(size_t)n * K + k], ex);
-                        const _Float16 hh = (_Float16)vs;
-                        const _Float16 ll = (_Float16)(vs - (float)hh);
-                        uint16_t hb, lb;
-                        __builtin_memcpy(&hb, &hh, 2);
-                        __builtin_memcpy(&lb, &ll, 2);
                         const size_t base = (((size_t)nt * KS + s) * 8 + 2 * j) * 512 + (size_t)lane * 8 + e8;
-                        img[base] = hb;
-                        img[base + 512] = lb;
+                        rd_split_scaled(w[(size_t)n * K + k], ex, img[base], img[base + 512]);
                     }
                 }
     return std::ldexp(1.f, -ex);
@@ -481,7 +466,7 @@ float prepare_gemm_h1_weights(const float* w, int N, int K, std::vector<uint16_t
 bool gemm_h1_shape_ok(int K, int cout) { return K % HK == 0 && K >= 2 * HK && cout >= 96; }
 
 bool gemm_h1_applies(const ConvParams& p) {
-    static const bool off = [] { const char* e = getenv("RD_GEMM_H1"); return e && e[0] == '0'; }();
+    static const bool off = rd_env_off("RD_GEMM_H1");
     return !off && p.w1 && p.w1_inv > 0.f && p.KH == 1 && p.KW == 1 && p.SH == 1 && p.SW == 1 && p.PT == 0 && p.PL == 0 && p.OH == p.H && p.OW == p.W &&
            p.out_mode == OUT_NHWC && !p.ascale && gemm_h1_shape_ok(p.K, p.Ng) && (p.xld % 4) == 0 &&
            (unsigned long long)HM * (unsigned long long)p.xld * 4ull + (unsigned long long)p.K * 4ull < (1ull << 31);
@@ -489,17 +474,12 @@ bool gemm_h1_applies(const ConvParams& p) {
 
 void launch_gemm_h1(const ConvParams& p, hipStream_t s) {
     const int ntm = (p.M + HM - 1) / HM, ntn = (p.Ng + HN - 1) / HN, ntiles = ntm * ntn;
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return rd_cu_budget(n > 0 ? n : 256);
-    }();
-    static const int per_cu = [] { const char* e = getenv("RD_GEMM1_WGS"); return e ? atoi(e) : 2; }();     // developer A/B: 1 = one workgroup per CU
-    static const int dbg = [] { const char* e = getenv("RD_GEMM1_DBG"); return e ? atoi(e) : 0; }();
+    const int n_cu = rd_cu_budget(rd_cu_count());
+    static const int per_cu = rd_env_int("RD_GEMM1_WGS", 2);     // developer A/B: 1 = one workgroup per CU
+    static const int dbg = rd_env_int("RD_GEMM1_DBG", 0);
     // IL (the DMA pieces between the MFMA groups instead of in front of them): level within +-3 % at the step's shapes, ahead at M = 131072 /
     // K = 768 (283 vs 291 us), behind at M = 65536 (118 vs 111), K = 384 / N = 384 (136 vs 129), K = 192 (99 vs 92); off by default
-    static const int il = [] { const char* e = getenv("RD_GEMM1_IL"); return e ? atoi(e) : 0; }();
+    static const int il = rd_env_int("RD_GEMM1_IL", 0);
     const int grid = ntiles < per_cu * n_cu ? ntiles : per_cu * n_cu;
 #define RD_H1(A, I)                                                                                                   \
     do {                                                                                                              \

@@ -514,7 +514,7 @@ __global__ void __launch_bounds__(1024) gemm_h3_dma16_kernel(ConvParams p, int n
 }
 
 bool gemm_h3_dma_applies(const ConvParams& p) {
-    static const bool off = [] { const char* e = getenv("RD_H3_DMA"); return e && e[0] == '0'; }();
+    static const bool off = rd_env_off("RD_H3_DMA");
     return !off && p.wh && p.KH == 1 && p.KW == 1 && p.SH == 1 && p.SW == 1 && p.PT == 0 && p.PL == 0 && p.OH == p.H && p.OW == p.W &&
            p.out_mode == OUT_NHWC && !p.ascale && p.K % 4 == 0 && p.K >= 2 * DK && p.Ng >= 96 && (p.xld % 4) == 0;
 }
@@ -532,14 +532,9 @@ bool gemm_h3_dma_uses16(const ConvParams& p) {
 
 void launch_gemm_h3_dma(const ConvParams& p, bool use16, hipStream_t s) {
     const int ntm = (p.M + DM - 1) / DM, ntn = (p.Ng + DN - 1) / DN, ntiles = ntm * ntn;
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = rd_cu_count();
     const size_t sh = (size_t)D_NSTAGE * D_STAGE;
-    static const int order_env = [] { const char* e = getenv("RD_GEMM_ORDER"); return e ? atoi(e) : 0; }();
+    static const int order_env = rd_env_int("RD_GEMM_ORDER", 0);
     const int order = order_env;
     static unsigned long long lds_ok = 0, lds_ok16 = 0;
     rd_allow_dynamic_lds((const void*)gemm_h3_dma_kernel<false, false>, sh, lds_ok);
@@ -549,7 +544,7 @@ void launch_gemm_h3_dma(const ConvParams& p, bool use16, hipStream_t s) {
     // (their epilogue is a third of the tile's time and drains faster from 64 accumulator registers per wavefront).  Round 3 routed every
     // K <= 384 to the 16-wavefront kernel on measurements at M = 26112-52224, where it led by 5 %.
     if (use16) {
-        static const int dbg = [] { const char* e = getenv("RD_GEMM_DBG"); return e ? atoi(e) : 0; }();
+        static const int dbg = rd_env_int("RD_GEMM_DBG", 0);
 #define RD_DMA16(A)                                                                                                  \
     do {                                                                                                             \
         static unsigned long long ok_ = 0;                                                                           \
@@ -568,7 +563,7 @@ void launch_gemm_h3_dma(const ConvParams& p, bool use16, hipStream_t s) {
         (void)lds_ok16;
         return;
     }
-    static const bool trace_on = [] { const char* e = getenv("RD_GEMM_TRACE"); return e && e[0] == '1'; }();
+    static const bool trace_on = rd_env_on("RD_GEMM_TRACE");
     if (trace_on) {      // developer: phase stamps of workgroup 0 (one launch, synchronous; prints cycles per phase to stderr)
         static unsigned long long* tbuf = nullptr;
         static unsigned long long tok = 0;
@@ -592,7 +587,7 @@ void launch_gemm_h3_dma(const ConvParams& p, bool use16, hipStream_t s) {
         }
         return;
     }
-    static const int il_env = [] { const char* e = getenv("RD_GEMM_IL"); return e ? atoi(e) : 1; }();
+    static const int il_env = rd_env_int("RD_GEMM_IL", 1);
     if (il_env) {
         static unsigned long long ok_il = 0;
         rd_allow_dynamic_lds((const void*)gemm_h3_dma_kernel<false, true>, sh, ok_il);

@@ -227,9 +227,8 @@ __global__ void __launch_bounds__(256) dwconv3x3_col_kernel(DwParams p, int c4n,
 }
 // column-strip geometry: groups are the W / TW column strips of one image
 static inline bool dw_col_applies(const DwParams& p) {
-    static const bool off = std::getenv("RD_DW_COL") && std::string(std::getenv("RD_DW_COL")) == "0";
-    static const bool on = std::getenv("RD_DW_COL") && std::string(std::getenv("RD_DW_COL")) == "1";   // measured 17.6 vs 16.5 ms per step: OFF by default
-    return on && !off && p.KH == 3 && p.KW == 3 && p.SH == 1 && p.SW == 1 && p.PT == 1 && p.PL == 1 && p.OH == p.H && p.OW == p.W &&
+    static const bool on = rd_env_on("RD_DW_COL");   // measured 17.6 vs 16.5 ms per step: OFF by default
+    return on && p.KH == 3 && p.KW == 3 && p.SH == 1 && p.SW == 1 && p.PT == 1 && p.PL == 1 && p.OH == p.H && p.OW == p.W &&
            p.C % 4 == 0 && (p.C >> 2) <= 256;
 }
 static inline void dw_col_geom(const DwParams& p, int& c4n, int& threads, int& groups_w, int& gpb, int& chunks) {
@@ -252,7 +251,7 @@ static inline void dw_tiled_geom(const DwParams& p, int TW, int& c4n, int& threa
     // groups per pixel lane: 4 on the large maps (fewer, longer blocks), down to 1 when that would leave the chip under-filled:
     // the recogniser's 6 x 68 x 192 maps gave 192 blocks of 4 wavefronts (under one wavefront per SIMD) with a fixed 4, and the
     // kernel ran latency-bound at 2.3 TB/s
-    static const int k_env = std::getenv("RD_DW_GPL") ? atoi(std::getenv("RD_DW_GPL")) : 0;
+    static const int k_env = rd_env_int("RD_DW_GPL", 0);
     int k = 4;
     while (k > 1 && (long)((groups + lanes_p * k - 1) / (lanes_p * k)) * p.N < 4096) --k;
     if (k_env > 0) k = k_env;
@@ -262,16 +261,12 @@ static inline void dw_tiled_geom(const DwParams& p, int TW, int& c4n, int& threa
     chunks = (groups + gpb - 1) / gpb;
 }
 static inline int dw_env_tw(const char* name, int dflt) {
-    const char* e = std::getenv(name);
-    const int v = e ? atoi(e) : 0;
+    const int v = rd_env_int(name, 0);
     return (v == 4 || v == 8) ? v : dflt;
 }
 static inline int dw3_tw() { static const int v = dw_env_tw("RD_DW3_TW", 8); return v; }
 static inline int dw5_tw() { static const int v = dw_env_tw("RD_DW5_TW", 8); return v; }
-static inline int dw7_tw() {
-    static const int v = [] { const char* e = std::getenv("RD_DW7_TW"); return e && atoi(e) == 8 ? 8 : 4; }();
-    return v;
-}
+static inline int dw7_tw() { static const int v = rd_env_int("RD_DW7_TW", 4) == 8 ? 8 : 4; return v; }
 static inline int dw_tiled_tw(const DwParams& p) {
     if (p.C % 4 != 0 || (p.C >> 2) > 256) return 0;
     if (p.KH == 3 && p.KW == 3 && (p.SW == 1 || p.SW == 2)) return p.SW == 1 ? dw3_tw() : 4;
@@ -298,7 +293,7 @@ DwRoute dw_route(const DwParams& p, bool wants_gap) {
 }
 
 void launch_dwconv(const DwParams& p_in, hipStream_t s) {
-    static const int dbg_env = [] { const char* e = std::getenv("RD_DW_DBG"); return e ? atoi(e) : 0; }();
+    static const int dbg_env = rd_env_int("RD_DW_DBG", 0);
     DwParams p = p_in;
     p.dbg = dbg_env;
     const DwRoute r = dw_route(p, p.gap_partial != nullptr);

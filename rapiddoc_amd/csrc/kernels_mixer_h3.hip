@@ -325,22 +325,16 @@ void launch_mixer_fused_h3(const MixerParams& p, hipStream_t s) {
 // host: split (and for W2 permute) the mixer weights.  w1 [2C][C], w2 [C][2C] fp32 (BN folded)
 void prepare_mixer_weights_h3(const float* w1, const float* w2, int C, std::vector<uint16_t>& w1h, std::vector<uint16_t>& w1l,
                               std::vector<uint16_t>& w2h, std::vector<uint16_t>& w2l) {
-    auto put = [](float v, uint16_t& hb, uint16_t& lb) {
-        const _Float16 h = (_Float16)v;
-        const _Float16 l = (_Float16)((v - (float)h) * 2048.f);
-        __builtin_memcpy(&hb, &h, 2);
-        __builtin_memcpy(&lb, &l, 2);
-    };
     const int H2 = 2 * C;
     w1h.assign((size_t)H2 * C, 0); w1l.assign((size_t)H2 * C, 0);
     w2h.assign((size_t)C * H2, 0); w2l.assign((size_t)C * H2, 0);
-    for (size_t i = 0; i < (size_t)H2 * C; ++i) put(w1[i], w1h[i], w1l[i]);
+    for (size_t i = 0; i < (size_t)H2 * C; ++i) rd_split_2048(w1[i], w1h[i], w1l[i]);
     for (int n = 0; n < C; ++n)
         for (int hid = 0; hid < H2; ++hid) {
             const int chunk = hid / 32, q = hid % 32;
             const int a = q >> 3, b = (q >> 2) & 1, c = q & 3;
             const int pos = 16 * (a >> 1) + 8 * b + 4 * (a & 1) + c;
-            put(w2[(size_t)n * H2 + hid], w2h[(size_t)n * H2 + chunk * 32 + pos], w2l[(size_t)n * H2 + chunk * 32 + pos]);
+            rd_split_2048(w2[(size_t)n * H2 + hid], w2h[(size_t)n * H2 + chunk * 32 + pos], w2l[(size_t)n * H2 + chunk * 32 + pos]);
         }
 }
 

@@ -263,12 +263,12 @@ __global__ void __launch_bounds__(1024) lc_mixer_res_kernel(MixerParams p, const
 // lane and tile cost the mixer more (31 launches: 3.36 -> 5.44 ms per 32-page step) than the depthwise launches they replace (1.59 ms);
 // profiles/r6_mixer_dw.txt
 bool mixer_res_fuses_dw(int C) {
-    static const bool on = [] { const char* e = getenv("RD_MIXER_DW"); return e && e[0] == '1'; }();
+    static const bool on = rd_env_on("RD_MIXER_DW");
     return on && mixer_res_supported(C);
 }
 
 bool mixer_res_supported(int C) {
-    static const bool off = [] { const char* e = getenv("RD_MIXER_RES"); return e && e[0] == '0'; }();
+    static const bool off = rd_env_off("RD_MIXER_RES");
     return !off && (C == 64 || C == 96);       // multiples of 32 whose image fits in LDS (C = 128: 256 KB)
 }
 
@@ -281,25 +281,9 @@ void prepare_mixer_weights_res(const float* w1, const float* w2, int C, std::vec
     const int H2 = 2 * C, KS1 = C / 32, HB = H2 / 16, NQ = H2 / 32, OB = C / 16;
     const int F1 = HB * KS1, F2 = OB * NQ;
     img.assign((size_t)2 * (F1 + F2) * 512, 0);
-    auto scale_of = [](const float* w, size_t n) {
-        float mx = 0.f;
-        for (size_t i = 0; i < n; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-        if (!(mx > 0.f) || !(mx < INFINITY)) return 1.f;
-        int e = 0;
-        (void)std::frexp(mx, &e);
-        return std::ldexp(1.f, 14 - e);
-    };
-    const float s1 = scale_of(w1, (size_t)H2 * C), s2 = scale_of(w2, (size_t)H2 * C);
-    inv[0] = 1.f / s1;
-    inv[1] = 1.f / s2;
-    float sc = s1;
-    auto put = [&sc](float v, uint16_t& hb, uint16_t& lb) {
-        const float vs = v * sc;
-        const _Float16 h = (_Float16)vs;
-        const _Float16 l = (_Float16)(vs - (float)h);
-        __builtin_memcpy(&hb, &h, 2);
-        __builtin_memcpy(&lb, &l, 2);
-    };
+    const int ex1 = rd_pow2_exp(w1, (size_t)H2 * C, RD_EXP_NO_CLAMP), ex2 = rd_pow2_exp(w2, (size_t)H2 * C, RD_EXP_NO_CLAMP);   // (as prepare_mixer_weights_ws)
+    inv[0] = 1.f / std::ldexp(1.f, ex1);
+    inv[1] = 1.f / std::ldexp(1.f, ex2);
     uint16_t* w1h = img.data();
     uint16_t* w1l = w1h + (size_t)F1 * 512;
     uint16_t* w2h = w1l + (size_t)F1 * 512;
@@ -311,9 +295,8 @@ void prepare_mixer_weights_res(const float* w1, const float* w2, int C, std::vec
                     // k-slot e of lane group g = l / 16: channel 16 (2 ks + e / 4) + 4 g + e % 4 (see the kernel's tile load)
                     const int row = 16 * hb + (l & 15), k = 16 * (2 * ks + (e >> 2)) + 4 * (l >> 4) + (e & 3);
                     const size_t o = ((size_t)(hb * KS1 + ks) * 64 + l) * 8 + e;
-                    put(w1[(size_t)row * C + k], w1h[o], w1l[o]);
+                    rd_split_scaled(w1[(size_t)row * C + k], ex1, w1h[o], w1l[o]);
                 }
-    sc = s2;
     for (int ob = 0; ob < OB; ++ob)
         for (int q = 0; q < NQ; ++q)
             for (int l = 0; l < 64; ++l)
@@ -321,25 +304,20 @@ void prepare_mixer_weights_res(const float* w1, const float* w2, int C, std::vec
                     const int row = 16 * ob + (l & 15);
                     const int hid = 16 * (2 * q + (e >> 2)) + 4 * (l >> 4) + (e & 3);
                     const size_t o = ((size_t)(ob * NQ + q) * 64 + l) * 8 + e;
-                    put(w2[(size_t)row * H2 + hid], w2h[o], w2l[o]);
+                    rd_split_scaled(w2[(size_t)row * H2 + hid], ex2, w2h[o], w2l[o]);
                 }
 }
 
 template <int C>
 static void launch_res(const MixerParams& p, hipStream_t s) {
     using G = ResGeom<C>;
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return rd_cu_budget(n > 0 ? n : 256);
-    }();
+    const int n_cu = rd_cu_budget(rd_cu_count());
     const int n_tiles = (p.M + 15) / 16;
     const int n_wg = (n_tiles + MR_WAVES - 1) / MR_WAVES;
     const int grid = n_wg < n_cu ? n_wg : n_cu;
     const unsigned char* img = reinterpret_cast<const unsigned char*>(p.w1h);
     static unsigned long long ok0 = 0, ok1 = 0, ok2 = 0, ok3 = 0;
-    static const bool rs = [] { const char* e = getenv("RD_RES_RS"); return !(e && e[0] == '0'); }();     // A/B switch: RD_RES_RS=0 = residual re-read (round 2-4)
+    static const bool rs = !rd_env_off("RD_RES_RS");     // A/B switch: RD_RES_RS=0 = residual re-read (round 2-4)
     if (p.dw_w) {            // (the builder only asks for it without a gate; the residual then always comes from the fragments)
         static unsigned long long okd = 0;
         rd_allow_dynamic_lds((const void*)lc_mixer_res_kernel<C, false, true, true>, G::LDS_BYTES_DW, okd);

@@ -747,20 +747,10 @@ __global__ void __launch_bounds__(512, 2) lc_mixer_ws_kernel(MixerParams p, cons
 // engine only routes C = 192 here
 bool mixer_ws_supported(int C) { return C == 96 || C == 192; }
 bool mixer_ws_prefetch() {
-    static const bool on = [] { const char* e = getenv("RD_WS_PF"); return e ? e[0] == '1' : true; }();
+    static const bool on = [] { const char* e = getenv("RD_WS_PF"); return e ? e[0] == '1' : true; }();     // (set to anything but 1: off)
     return on;
 }
 bool mixer_ws_preferred(int C) { return C == 192; }
-
-// largest power of two s with max|w| * s < 2^14 (1 for an all-zero matrix)
-static float ws_weight_scale(const float* w, size_t n) {
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-    if (!(mx > 0.f) || !(mx < INFINITY)) return 1.f;
-    int e = 0;
-    (void)std::frexp(mx, &e);            // mx = f * 2^e, f in [0.5, 1)  ->  mx * 2^(14 - e) in [2^13, 2^14)
-    return std::ldexp(1.f, 14 - e);
-}
 
 // host: the weight stream image.  w1 [2C][C], w2 [C][2C] fp32 (BN folded).  img: NC stages of STAGE_BYTES;
 // inv[0] = 1 / scale(W1), inv[1] = 1 / (scale(W2) * WS_SH) - what the kernel multiplies its accumulators by.
@@ -768,16 +758,10 @@ void prepare_mixer_weights_ws(const float* w1, const float* w2, int C, std::vect
     const int KS = C / 32, NB = C / 16, NC = 2 * C / WS_HC, H2 = 2 * C;
     const int w1_frags = 2 * KS * 2, w2_frags = NB * 2, stage_halfs = (w1_frags + w2_frags) * 512;
     img.assign((size_t)NC * stage_halfs, 0);
-    const float s1 = ws_weight_scale(w1, (size_t)H2 * C), s2 = ws_weight_scale(w2, (size_t)H2 * C);
-    inv[0] = 1.f / s1;
-    inv[1] = 1.f / (s2 * WS_SH);
-    auto put = [](float v, float sc, uint16_t& hb, uint16_t& lb) {
-        const float vs = v * sc;
-        const _Float16 h = (_Float16)vs;
-        const _Float16 l = (_Float16)(vs - (float)h);
-        __builtin_memcpy(&hb, &h, 2);
-        __builtin_memcpy(&lb, &l, 2);
-    };
+    // the two mixer images leave the exponent unclamped (it matters below max |w| = 2^-86 only; beyond 2^-113 the scale is no float)
+    const int ex1 = rd_pow2_exp(w1, (size_t)H2 * C, RD_EXP_NO_CLAMP), ex2 = rd_pow2_exp(w2, (size_t)H2 * C, RD_EXP_NO_CLAMP);
+    inv[0] = 1.f / std::ldexp(1.f, ex1);
+    inv[1] = 1.f / (std::ldexp(1.f, ex2) * WS_SH);
     for (int q = 0; q < NC; ++q) {
         uint16_t* st = img.data() + (size_t)q * stage_halfs;
         const int c1 = (q + 1) % NC;   // W1 chunk of this stage
@@ -788,7 +772,7 @@ void prepare_mixer_weights_ws(const float* w1, const float* w2, int C, std::vect
                         const int m = l & 15, g = l >> 4;
                         const int hid = 32 * c1 + 16 * b + m, ch = 16 * (2 * s + e / 4) + 4 * g + (e & 3);
                         const size_t f = (size_t)((s * 2 + b) * 2) * 512 + l * 8 + e;   // unit s = [b0 hi, b0 lo, b1 hi, b1 lo]
-                        put(w1[(size_t)hid * C + ch], s1, st[f], st[f + 512]);
+                        rd_split_scaled(w1[(size_t)hid * C + ch], ex1, st[f], st[f + 512]);
                     }
         uint16_t* st2 = st + (size_t)w1_frags * 512;
         const int c2 = q;              // W2 chunk of this stage
@@ -798,7 +782,7 @@ void prepare_mixer_weights_ws(const float* w1, const float* w2, int C, std::vect
                     const int m = l & 15, g = l >> 4;
                     const int out = 16 * n + m, hid = 32 * c2 + 16 * (e / 4) + 4 * g + (e & 3);
                     const size_t f = (size_t)(2 * n) * 512 + l * 8 + e;
-                    put(w2[(size_t)out * H2 + hid], s2, st2[f], st2[f + 512]);
+                    rd_split_scaled(w2[(size_t)out * H2 + hid], ex2, st2[f], st2[f + 512]);
                 }
     }
 }
@@ -830,13 +814,7 @@ static void launch_ws(const MixerParams& p, const unsigned char* wimg, int n_til
 // (default: kept in registers at C = 96, re-read at C = 192 where keeping it spills); bits 8.. ablations (C = 192, garbage)
 void launch_mixer_fused_ws(const MixerParams& p, hipStream_t s) {
     if (p.M <= 0) return;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        (void)hipGetDevice(&dev);
-        n_cu = rd_cu_budget((hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256);
-    }
+    const int n_cu = rd_cu_budget(rd_cu_count());
     const int n_tiles = (p.M + WS_PX - 1) / WS_PX;
     const int n_wg = (n_tiles + WS_WAVES - 1) / WS_WAVES;
     // persistent grid: as many rounds as a full machine needs, on the FEWEST workgroups that still manage in that many
@@ -890,9 +868,9 @@ void launch_mixer_fused_ws(const MixerParams& p, hipStream_t s) {
         return;
     }
     if (pf) {
-        static const bool il = [] { const char* e = getenv("RD_WS_IL"); return !(e && e[0] == '0'); }();     // A/B switch: RD_WS_IL=0 = the round-3 form
-        static const bool go = [] { const char* e = getenv("RD_WS_GO"); return !(e && e[0] == '0'); }();    // A/B switch: RD_WS_GO=0 = GELU first (round 3)
-        static const bool rs = [] { const char* e = getenv("RD_WS_RS"); return !(e && e[0] == '0'); }();    // A/B switch: RD_WS_RS=0 = residual re-read (rounds 3-4)
+        static const bool il = !rd_env_off("RD_WS_IL");     // A/B switch: RD_WS_IL=0 = the round-3 form
+        static const bool go = !rd_env_off("RD_WS_GO");     // A/B switch: RD_WS_GO=0 = GELU first (round 3)
+        static const bool rs = !rd_env_off("RD_WS_RS");     // A/B switch: RD_WS_RS=0 = residual re-read (rounds 3-4)
         if (il && go && rs) {
             if (gated) launch_ws<192, true, false, 896, true>(p, img, n_tiles, grid, ph_mul, ph_unit, s);
             else launch_ws<192, false, false, 896, true>(p, img, n_tiles, grid, ph_mul, ph_unit, s);

@@ -360,7 +360,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3s2_pw_h1_kernel(Stem34Params p,
 // 79.15 ms, profiles/r6_stem34.txt) - its phases (patch requests at the HBM limit, split + LDS write, MFMAs, epilogue) add up instead of
 // overlapping; RD_STEM34=1 switches it on (parity and launch-invariance tests run it through rd_debug_stem34 either way).
 bool stem34_enabled() {
-    static const bool on = [] { const char* e = getenv("RD_STEM34"); return e && e[0] == '1'; }();
+    static const bool on = rd_env_on("RD_STEM34");
     return on;
 }
 bool stem34_shape_ok(int cin, int n1, int n2) {
@@ -368,7 +368,7 @@ bool stem34_shape_ok(int cin, int n1, int n2) {
 }
 
 static int wgs_per_cu() {
-    static const int n = [] { const char* e = getenv("RD_STEM34_WGS"); return e ? atoi(e) : 2; }();     // developer A/B
+    static const int n = rd_env_int("RD_STEM34_WGS", 2);     // developer A/B
     return n;
 }
 template <int NB, int MB, int TR, bool HALF>
@@ -384,20 +384,15 @@ static void launch_stem34_t(const Stem34Params& p, hipStream_t s, int n_cu) {
 
 void launch_stem34(const Stem34Params& p_in, hipStream_t s) {
     if (p_in.N <= 0 || p_in.OH <= 0 || p_in.OW <= 0) return;
-    static const int abl = [] { const char* e = getenv("RD_STEM34_ABL"); return e ? atoi(e) : 0; }();
+    static const int abl = rd_env_int("RD_STEM34_ABL", 0);
     Stem34Params p = p_in;
     p.abl = abl;
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = rd_cu_count();
     const int nb = (p.N1 + 31) / 32, mb = (p.N2 + 31) / 32;
     // tile shape: 4 x 32 or 2 x 64 outputs - by the MAP (never by the batch: an image's tiling, hence nothing about its arithmetic, which is
     // per output element anyway, depends on N), whichever covers it with fewer wasted outputs; ties -> 4 x 32
     auto covered = [&](int tr, int tc) { return (long)((p.OH + tr - 1) / tr * tr) * ((p.OW + tc - 1) / tc * tc); };
-    static const int force_tr = [] { const char* e = getenv("RD_STEM34_TR"); return e ? atoi(e) : 0; }();
+    static const int force_tr = rd_env_int("RD_STEM34_TR", 0);
     const bool tr2 = force_tr ? force_tr == 2 : covered(2, 64) < covered(4, 32);
     const bool half = p.N1 <= 32 * nb - 16;          // the last 32-wide block of stem3's channels is at most half full
 #define RD_S34_CASE(NBv, MBv, FULL)                                             \
@@ -416,26 +411,6 @@ void launch_stem34(const Stem34Params& p_in, hipStream_t s) {
 #undef RD_S34_CASE
 }
 
-static float s34_scale_exp(const float* w, size_t n, int& ex) {
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-    ex = 0;
-    if (mx > 0.f && std::isfinite(mx)) {
-        int x = 0;
-        (void)std::frexp(mx, &x);
-        ex = 14 - x;
-        ex = ex > 100 ? 100 : ex < -100 ? -100 : ex;
-    }
-    return std::ldexp(1.f, -ex);
-}
-static void s34_put(float v, int ex, uint16_t& hb, uint16_t& lb) {
-    const float vs = std::ldexp(v, ex);
-    const _Float16 hh = (_Float16)vs;
-    const _Float16 ll = (_Float16)(vs - (float)hh);
-    __builtin_memcpy(&hb, &hh, 2);
-    __builtin_memcpy(&lb, &ll, 2);
-}
-
 // Host: the two weight images.  w3 = folded weights [N1][9 Cin], k = (kh * 3 + kw) * Cin + ci; w4 = [N2][N1].
 // img3: slab (pass, tap) = 16 input channels of one tap; per 32-wide output block the hi and the lo fragment (1 KB each): lane (l31, lhi)
 // carries w3[32 nb + l31][tap * Cin + 16 pass + 8 lhi + e].  img4: fragment (mb, j, plane): lane (l31, lhi) carries
@@ -444,9 +419,9 @@ static void s34_put(float v, int ex, uint16_t& hb, uint16_t& lb) {
 void prepare_stem34_weights(const float* w3, const float* w4, int Cin, int N1, int N2, std::vector<uint16_t>& img3, std::vector<uint16_t>& img4,
                             float inv[2]) {
     const int K = 9 * Cin, nb_n = (N1 + 31) / 32, mb_n = (N2 + 31) / 32, passes = Cin / 16, K2 = 2 * nb_n - (N1 <= 32 * nb_n - 16 ? 1 : 0);
-    int ex3 = 0, ex4 = 0;
-    inv[0] = s34_scale_exp(w3, (size_t)N1 * K, ex3);
-    inv[1] = s34_scale_exp(w4, (size_t)N2 * N1, ex4);
+    const int ex3 = rd_pow2_exp(w3, (size_t)N1 * K, RD_EXP_CLAMP), ex4 = rd_pow2_exp(w4, (size_t)N2 * N1, RD_EXP_CLAMP);
+    inv[0] = std::ldexp(1.f, -ex3);
+    inv[1] = std::ldexp(1.f, -ex4);
     img3.assign((size_t)passes * 9 * nb_n * 2 * 512, 0);
     size_t slab = 0;
     for (int pass = 0; pass < passes; ++pass)
@@ -458,7 +433,7 @@ void prepare_stem34_weights(const float* w3, const float* w4, int Cin, int N1, i
                     for (int e = 0; e < 8; ++e) {
                         const int k = tap * Cin + pass * 16 + 8 * (lane >> 5) + e;
                         const size_t base = ((slab * nb_n + nb) * 2) * 512 + (size_t)lane * 8 + e;
-                        s34_put(w3[(size_t)n * K + k], ex3, img3[base], img3[base + 512]);
+                        rd_split_scaled(w3[(size_t)n * K + k], ex3, img3[base], img3[base + 512]);
                     }
                 }
     img4.assign((size_t)mb_n * K2 * 2 * 512, 0);
@@ -471,7 +446,7 @@ void prepare_stem34_weights(const float* w3, const float* w4, int Cin, int N1, i
                     const int c = 16 * j + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
                     if (c >= N1) continue;
                     const size_t base = ((size_t)(mb * K2 + j) * 2) * 512 + (size_t)lane * 8 + e;
-                    s34_put(w4[(size_t)n * N1 + c], ex4, img4[base], img4[base + 512]);
+                    rd_split_scaled(w4[(size_t)n * N1 + c], ex4, img4[base], img4[base + 512]);
                 }
             }
 }

@@ -437,29 +437,14 @@ __global__ void __launch_bounds__(SF_NT, 2) stem_fused_kernel(StemFusedParams p)
 
 bool stem_fused_supported(int c1) { return c1 == 24 || c1 == 32 || c1 == 48; }
 
-// power-of-two scale of one weight matrix: max |w| s in [2^13, 2^14) (prepare_gemm_h1_weights) -> exponent
-static int sf_scale_exp(const float* w, size_t n) {
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 0;
-    int x = 0;
-    (void)std::frexp(mx, &x);
-    const int ex = 14 - x;
-    return ex > 100 ? 100 : ex < -100 ? -100 : ex;
-}
-
 template <int C1>
 static void sf_prepare(const float* w1, const float* w2a, const float* w2b, std::vector<uint16_t>& img) {
     using G = SfGeom<C1>;
     img.assign(G::IMG_HALFS, 0);
-    const int ex[3] = {sf_scale_exp(w1, (size_t)27 * C1), sf_scale_exp(w2a, (size_t)G::NA * G::K2A), sf_scale_exp(w2b, (size_t)C1 * 4 * G::NA)};
-    auto put = [&](size_t hi_at, size_t lo_at, float v, int e) {
-        const float vs = std::ldexp(v, e);
-        const _Float16 h = (_Float16)vs;
-        const _Float16 l = (_Float16)(vs - (float)h);
-        __builtin_memcpy(&img[hi_at], &h, 2);
-        __builtin_memcpy(&img[lo_at], &l, 2);
-    };
+    // one power-of-two scale per weight matrix
+    const int ex[3] = {rd_pow2_exp(w1, (size_t)27 * C1, RD_EXP_CLAMP), rd_pow2_exp(w2a, (size_t)G::NA * G::K2A, RD_EXP_CLAMP),
+                       rd_pow2_exp(w2b, (size_t)C1 * 4 * G::NA, RD_EXP_CLAMP)};
+    auto put = [&](size_t hi_at, size_t lo_at, float v, int e) { rd_split_scaled(v, e, img[hi_at], img[lo_at]); };
     // stem1: w1 [27][C1] with row (kh * 3 + kw) * 3 + ci  ->  [co][kh * 16 + kw * 3 + ci]
     for (int co = 0; co < C1; ++co)
         for (int kh = 0; kh < 3; ++kh)
@@ -499,12 +484,7 @@ static void sf_launch(StemFusedParams& p, hipStream_t s, int n_cu) {
 // x NCHW [N][in_ch][H][W] -> cat NHWC [N][H2][W2][2 c1] (row stride yld floats)
 void launch_stem_fused(int c1, const float* x, int N, int H, int W, int in_ch, const uint16_t* wimg, const float* bias, float* y, int yld,
                        unsigned* range_flag, hipStream_t s, const int32_t* line_tab) {
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = rd_cu_count();
     StemFusedParams p{};
     p.x = x; p.N = N; p.H = H; p.W = W; p.in_ch = in_ch;
     p.wimg = wimg; p.bias = bias; p.y = y; p.yld = yld;
@@ -514,7 +494,7 @@ void launch_stem_fused(int c1, const float* x, int N, int H, int W, int in_ch, c
     p.tiles_x = (p.W2 + SF_TW - 1) / SF_TW;
     p.range_flag = range_flag;
     p.line_tab = line_tab;
-    static const int dbg = [] { const char* e = getenv("RD_STEM_DBG"); return e ? atoi(e) : 0; }();
+    static const int dbg = rd_env_int("RD_STEM_DBG", 0);
     p.dbg = dbg;
     if (c1 == 24) sf_launch<24>(p, s, n_cu);
     else if (c1 == 32) sf_launch<32>(p, s, n_cu);

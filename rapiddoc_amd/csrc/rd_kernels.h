@@ -8,28 +8,9 @@
 #include <string>
 #include <vector>
 
+#include "rd_host.h"
+
 namespace rd {
-
-// Kernels that need more than 64 KB of dynamic LDS opt in once per (kernel, device): the attribute belongs to the device
-// the call is made on, and one process may drive several GPUs.  `mask` is a static of the launcher, one bit per device.
-inline void rd_allow_dynamic_lds(const void* kernel, size_t bytes, unsigned long long& mask) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(mask & bit)) {
-        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        mask |= bit;
-    }
-}
-
-// CUs the persistent matrix kernels size their grids for.  Their workgroups book a CU's LDS and registers completely (gemm_h1 2 x 80 KB,
-// the mixers 146 - 148 KB), so while one of them covers all 256 CUs nothing of another stream - not even a bandwidth-bound depthwise
-// launch that needs no matrix pipe - can start: RD_PERSISTENT_CUS=n leaves 256 - n CUs (spread over the XCDs by the dispatcher's round robin)
-// to whatever else is in flight.  Default: all of them.
-inline int rd_cu_budget(int n_cu) {
-    static const int env = [] { const char* e = std::getenv("RD_PERSISTENT_CUS"); return e ? std::atoi(e) : 0; }();
-    return env > 0 && env < n_cu ? env : n_cu;
-}
 
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_SILU = 3, ACT_SIGMOID = 4, ACT_HSIG = 5, ACT_HSIG_PADDLE = 6 };
 enum OutMode : int { OUT_NHWC = 0, OUT_DECONV2X2 = 1 };
