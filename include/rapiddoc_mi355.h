@@ -14,6 +14,8 @@
  *   rd_preproc_resize_norm <- PPPreProcess: .../model_handler/pp_doclayout/pre_process.py:22-42
  *   rd_preproc_resize_aa_norm <- UniTable's TablePreprocess (PIL Resize + ToTensor + Normalize):
  *                           rapid_doc/model/table/rapid_table_self/table_structure/unitable/pre_process.py
+ *   rd_formula_margin_boxes, rd_formula_preproc_plan, rd_formula_preproc_batch <- UniMERNetImgDecode + UniMERNetTestTransform +
+ *                           LatexImageFormat: .../model_handler/pp_formulanet_plus/pre_process.py:39-246
  *   rd_load_weights      <- `_load_state_dict` + `load_state_dict`: rapid_doc/model/ocr/torch.py:82-110
  *
  * Conventions: every pointer named *_dev is a DEVICE pointer on the handle's GPU (PyTorch-ROCm
@@ -156,6 +158,47 @@ int rd_preproc_resize_norm_batch(int device_id, const uint8_t* pages_u8_dev, int
 #define RD_RESIZE_AA_MAX_SIDE 16384
 int rd_preproc_resize_aa_norm(int device_id, const uint8_t* hwc_u8_dev, int H, int W, int OH, int OW, const float mean[3],
                               const float std[3], int swap_rb, float* out_chw_dev, uint8_t* out_u8_hwc_dev, void* stream);
+
+/* The formula pre-process of PP-FormulaNet_plus on the device, bit for bit as the reference runs it with Pillow
+ * (pp_formulanet_plus/pre_process.py:39-246: margin crop, Image.resize(BILINEAR) to a short side of 384, Image.thumbnail((384, 384)) =
+ * reduce + BICUBIC over a float32 box, centre pad with 0, (v / 255 - 0.7931) / 0.1738, grey = .114 c0 + .587 c1 + .299 c2).  Three calls:
+ *   1. rd_formula_margin_boxes: one launch for n crops.  descs_dev: n device-resident crop descriptors, each a 3-channel uint8 HWC view
+ *      (any base, any row pitch: a window of a page); boxes_dev int32 [n][4] = (x0, y0, x1, y1) of the pixels whose normalised grey
+ *      (L - min) * 255 < 200 * (max - min), L = Pillow's convert("L"); the whole crop when it is uniform.
+ *   2. the caller copies the boxes to the host (the ONE device-to-host copy of a batch: every later size follows from the box) and may
+ *      ask rd_formula_preproc_plan, host only, what follows from a box of w x h pixels.  served = 0: a side of a stage lies outside
+ *      1 .. RD_RESIZE_AA_MAX_SIDE and the crop has to take the host path.
+ *   3. rd_formula_preproc_batch: descs_host / boxes_host are the same n descriptors and their boxes in HOST memory; out_dev float32
+ *      [n][384][384] (= [n, 1, 384, 384]); out_u8_dev (may be NULL) uint8 [n][384][384][3], the padded image in front of the normalisation.
+ *      Enqueues everything on `stream` and returns; a crop's bits do not depend on the batch it rides in (crops are processed one after
+ *      the other).  The workspace is the library's, per (device, stream) and grown on demand, as that of rd_preproc_resize_aa_norm
+ *      (no caller-given workspace, no size query): intermediates, and the batch's coefficient tables, which are computed on the host and
+ *      uploaded with one asynchronous copy from a pinned staging buffer.  A first call with larger crops allocates (not capturable
+ *      into a hipGraph); calls on one stream are ordered, calls on different streams use different workspaces.
+ * Bad arguments (NULL, n < 1, a box outside its crop, a crop whose plan is not served) return non-zero WITHOUT a launch; the message is
+ * in rd_create_error(). */
+#define RD_RESAMPLE_BILINEAR 2 /* Pillow's Image.BILINEAR / Image.BICUBIC */
+#define RD_RESAMPLE_BICUBIC 3
+#define RD_FORMULA_SIDE 384
+typedef struct rd_formula_crop {
+    const uint8_t* base; /* device address of pixel (0, 0), channel 0 */
+    int64_t pitch;       /* bytes from one row to the next */
+    int32_t w, h;
+} rd_formula_crop;
+typedef struct rd_formula_plan {
+    int32_t served;           /* 1: every stage fits the device bound */
+    int32_t resize_w, resize_h; /* Image.resize(BILINEAR) target: short side 384, long side int(384 * long / short) */
+    int32_t thumb;            /* 1: thumbnail resamples (a side above 384) */
+    int32_t final_w, final_h; /* size in front of the pad */
+    int32_t fx, fy;           /* reduce factors (1, 1: reduce does not run) */
+    int32_t reduced_w, reduced_h;
+    float box_w, box_h;       /* the bicubic resample's box (0, 0, box_w, box_h), float32 as Pillow's C side takes it */
+    int32_t pad_x, pad_y;     /* paste offsets: (384 - final) / 2, floored */
+} rd_formula_plan;
+int rd_formula_margin_boxes(int device_id, const rd_formula_crop* descs_dev, int n, int32_t* boxes_dev, void* stream);
+int rd_formula_preproc_plan(int w, int h, rd_formula_plan* plan);
+int rd_formula_preproc_batch(int device_id, const rd_formula_crop* descs_host, const int32_t* boxes_host, int n, float* out_dev,
+                             uint8_t* out_u8_dev, void* stream);
 
 /* Text-line crops for one rec batch (replaces per-line cv2.warpPerspective + rapidocr resize_norm_img:
  * rapid_doc/utils/ocr_utils.py:494-536, rapid_doc/model/ocr/rapid_ocr.py:436-440).  pages_u8_dev: [P][H][W][3];

@@ -34,6 +34,9 @@ SYMBOLS = {
     "rd_preproc_resize_norm": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rd_preproc_resize_norm_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rd_preproc_resize_aa_norm": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rd_formula_margin_boxes": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rd_formula_preproc_plan": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
+    "rd_formula_preproc_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rd_crop_resize_norm_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "rd_line_crops_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rd_line_warp_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -85,6 +88,7 @@ DEBUG_SYMBOLS = {
     "rd_debug_table_encoder_taps": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "rd_debug_formula_decode": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(C.c_int32), _P, _P, _P]),
     "rd_debug_resize_aa_coeffs": (_I, [_I, _I, _P, _P, C.c_int64]),
+    "rd_debug_resample_coeffs": (_I, [_I, _I, C.c_double, C.c_double, _I, _P, _P, C.c_int64]),
     "rd_debug_time_mixer": (_F, [_I] * 4 + [_P] * 6),
     "rd_debug_time_gemm": (_F, [_I] * 5 + [_P] * 6),
     "rd_debug_gemm_h1": (_F, [_I] * 5 + [_P, _I, _P, _P, _P, _I, _P, _I, _P]),

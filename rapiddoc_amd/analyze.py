@@ -120,9 +120,15 @@ def recognise_formulas(pages: torch.Tensor, layout_dets_per_page: Sequence[Seque
     """Formula branch of BatchAnalyze (batch_analyze.py:258-283): every formula region (category 8 / 13 / 14) is cropped
     - grown by `bbox_expand_px` where no neighbouring layout box is in the way - and handed to
     `formula_model.batch_predict(images, batch_size=...)` (a `formula_host.FormulaRecognizer` or any CustomBaseModel-shaped
-    object); a non-empty result is written to the detection's `latex` field IN PLACE.  Returns the number of formulas."""
+    object); a non-empty result is written to the detection's `latex` field IN PLACE.  Returns the number of formulas.
+
+    A model that declares `accepts_device_images` (FormulaRecognizer) gets the crops as device views of `pages`, no copy, unless
+    RD_FORMULA_PREPROC keeps the pre-process on the host; every other model, and every region with `polygon_points` (the white-out is
+    a host mask), gets numpy crops as before."""
+    from . import formula_host
     P, H, W, _ = pages.shape
     targets, crops = [], []
+    on_device = bool(getattr(formula_model, "accepts_device_images", False)) and pages.is_cuda and formula_host.device_preproc_enabled()
     for p, dets in enumerate(layout_dets_per_page):
         for d in dets:
             if int(d["category_id"]) not in layout_host.FORMULA_CATEGORY_IDS:
@@ -133,6 +139,9 @@ def recognise_formulas(pages: torch.Tensor, layout_dets_per_page: Sequence[Seque
             if x1 <= x0 or y1 <= y0:
                 continue
             targets.append(d)
+            if on_device and not c.get("polygon_points"):                # the window itself: pre-processed on the device with its chunk
+                crops.append(pages[p, y0:y1, x0:x1])
+                continue
             crop = pages[p, y0:y1, x0:x1].cpu().numpy()                  # RGB crop, no margin (crop_img with paste 0)
             if c.get("polygon_points"):                                  # crop_img whites out what lies outside the polygon
                 crop = crop.copy()

@@ -241,6 +241,27 @@ int rd_preproc_resize_aa_norm(int device_id, const uint8_t* src, int H, int W, i
     return rc;
 }
 
+int rd_formula_margin_boxes(int device_id, const rd_formula_crop* descs_dev, int n, int32_t* boxes_dev, void* stream) {
+    std::string err;
+    const int rc = rd::launch_formula_margin_boxes(device_id, descs_dev, n, boxes_dev, (hipStream_t)stream, err);
+    if (rc != 0) g_create_err = err;
+    return rc;
+}
+
+int rd_formula_preproc_plan(int w, int h, rd_formula_plan* plan) {
+    if (!plan) { g_create_err = "rd_formula_preproc_plan: plan is NULL"; return 1; }
+    rd::formula_preproc_plan(w, h, plan);
+    return 0;
+}
+
+int rd_formula_preproc_batch(int device_id, const rd_formula_crop* descs_host, const int32_t* boxes_host, int n, float* out, uint8_t* out_u8,
+                             void* stream) {
+    std::string err;
+    const int rc = rd::launch_formula_preproc_batch(device_id, descs_host, boxes_host, n, out, out_u8, (hipStream_t)stream, err);
+    if (rc != 0) g_create_err = err;
+    return rc;
+}
+
 int rd_crop_resize_norm_batch(int device_id, const uint8_t* pages, int P, int H, int W, const rd_crop_desc* descs, int n,
                               int out_h, int out_w_padded, const float mean[3], const float std[3], float scale, int swap_rb,
                               float* out, void* stream) {

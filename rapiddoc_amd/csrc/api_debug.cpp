@@ -118,6 +118,20 @@ int rd_debug_resize_aa_coeffs(int in, int out, int32_t* bounds_out, int32_t* kk_
     return ksize;
 }
 
+// developer entry (host only): the same for a filter (RD_RESAMPLE_BILINEAR / RD_RESAMPLE_BICUBIC) sampled over the box [box0, box1) of the
+// `in` source pixels: the tables of the formula pre-process (rd_formula_preproc_batch hands over box0 = 0 and a float32 box1).
+int rd_debug_resample_coeffs(int filter, int in, double box0, double box1, int out, int32_t* bounds_out, int32_t* kk_out, int64_t kk_cap) {
+    if ((filter != RD_RESAMPLE_BILINEAR && filter != RD_RESAMPLE_BICUBIC) || in < 1 || out < 1 || in > RD_RESIZE_AA_MAX_SIDE ||
+        out > RD_RESIZE_AA_MAX_SIDE || !(box0 >= 0.0) || !(box1 > box0) || !(box1 <= (double)in) || !bounds_out || !kk_out)
+        return -1;
+    std::vector<int32_t> bounds, kk;
+    const int ksize = rd::resample_coeffs(filter, in, box0, box1, out, bounds, kk);
+    if ((int64_t)kk.size() > kk_cap) return -1;
+    std::copy(bounds.begin(), bounds.end(), bounds_out);
+    std::copy(kk.begin(), kk.end(), kk_out);
+    return ksize;
+}
+
 // ---- developer micro-benchmarks (not part of the public header): time one kernel on caller-provided buffers
 float rd_debug_time_mixer(int C, int M, int variant, int iters, float* x, float* y, float* w1, float* b1, float* w2, float* b2) {
     rd::MixerParams p{};

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/rapiddoc_mi355.h"      // rd_formula_crop, rd_formula_plan
 #include "rd_host.h"
 
 namespace rd {
@@ -478,7 +479,15 @@ void launch_preproc_resize_norm(const PreprocParams& p, hipStream_t s);
 
 // Pillow's antialiased bilinear resample + ToTensor / Normalize (kernels_resize_aa.hip; rd_preproc_resize_aa_norm).  Returns 0, or 1 with
 // the message in `err` (a size outside 1 .. RD_RESIZE_AA_MAX_SIDE never launches).  resize_aa_coeffs: the per-axis tables on the host.
+// resample_coeffs: the same for a filter (RD_RESAMPLE_*) over the box [box0, box1) of the `in` source pixels.
 int resize_aa_coeffs(int in, int out, std::vector<int32_t>& bounds, std::vector<int32_t>& kk);
+int resample_coeffs(int filter, int in, double box0, double box1, int out, std::vector<int32_t>& bounds, std::vector<int32_t>& kk);
+// The formula pre-process (kernels_resize_aa.hip; rd_formula_margin_boxes / _preproc_plan / _preproc_batch).  The launchers return 0, or 1
+// with the message in `err` and nothing launched.
+void formula_preproc_plan(int w, int h, rd_formula_plan* plan);
+int launch_formula_margin_boxes(int device, const rd_formula_crop* descs_dev, int n, int32_t* boxes_dev, hipStream_t s, std::string& err);
+int launch_formula_preproc_batch(int device, const rd_formula_crop* descs, const int32_t* boxes, int n, float* out, uint8_t* out_u8, hipStream_t s,
+                                 std::string& err);
 int launch_resize_aa_norm(int device, const uint8_t* src, int H, int W, int OH, int OW, const float mean[3], const float std[3], int swap_rb,
                           float* out, uint8_t* out_u8, hipStream_t s, std::string& err);
 

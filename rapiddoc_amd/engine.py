@@ -595,3 +595,109 @@ def preproc_resize_aa_norm(img_u8_hwc: torch.Tensor, out_hw: Tuple[int, int], me
     if rc != 0:
         raise EngineError(lib.rd_create_error().decode())
     return (out, u8) if return_u8 else out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the formula pre-process
+FORMULA_SIDE = 384
+FORMULA_CROP_DTYPE = np.dtype([("base", "<u8"), ("pitch", "<i8"), ("w", "<i4"), ("h", "<i4")])            # rd_formula_crop
+
+
+class FormulaPlan(C.Structure):
+    """rd_formula_plan (include/rapiddoc_mi355.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("served", "resize_w", "resize_h", "thumb", "final_w", "final_h", "fx", "fy", "reduced_w", "reduced_h")] + \
+               [("box_w", C.c_float), ("box_h", C.c_float), ("pad_x", C.c_int32), ("pad_y", C.c_int32)]
+
+
+def formula_preproc_plan(w: int, h: int) -> FormulaPlan:
+    """What follows from a margin box of w x h pixels (rd_formula_preproc_plan: host only, needs no GPU)."""
+    p = FormulaPlan()
+    if _lib.load().rd_formula_preproc_plan(int(w), int(h), C.byref(p)) != 0:
+        raise EngineError("rd_formula_preproc_plan failed")
+    return p
+
+
+def _formula_view(t: torch.Tensor) -> Optional[torch.Tensor]:
+    """the tensor as the kernels read it (a [H, W, 3] uint8 device window: channels and pixels packed, any row pitch), or None when the
+    device path does not take it (grey-level, empty, beyond the bound)"""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3):
+        return None
+    H, W_ = int(t.shape[0]), int(t.shape[1])
+    if not (1 <= H <= 16384 and 1 <= W_ <= 16384):
+        return None
+    if t.stride(2) != 1 or t.stride(1) != 3 or (H > 1 and t.stride(0) < 3 * W_):
+        t = t.contiguous()
+    return t
+
+
+def formula_margin_boxes(crops: List[torch.Tensor]) -> torch.Tensor:
+    """[n] device uint8 [H, W, 3] windows -> int32 [n, 4] (x0, y0, x1, y1) ON THE DEVICE: the margin box of every crop
+    (rd_formula_margin_boxes, one launch).  The windows must be what `_formula_view` returns."""
+    lib = _lib.load()
+    dev = crops[0].device
+    descs = _formula_descs(crops)
+    boxes = torch.empty((len(crops), 4), dtype=torch.int32, device=dev)
+    d_dev = torch.from_numpy(descs.view(np.uint8)).to(dev)
+    if lib.rd_formula_margin_boxes(dev.index or 0, d_dev.data_ptr(), len(crops), boxes.data_ptr(), _stream_ptr()) != 0:
+        raise EngineError(lib.rd_create_error().decode())
+    return boxes
+
+
+def _formula_descs(crops: List[torch.Tensor]) -> np.ndarray:
+    descs = np.zeros(len(crops), dtype=FORMULA_CROP_DTYPE)
+    for i, t in enumerate(crops):
+        descs[i] = (t.data_ptr(), t.stride(0) if t.shape[0] > 1 else 3 * int(t.shape[1]), int(t.shape[1]), int(t.shape[0]))
+    return descs
+
+
+def formula_preprocess(crops: list, return_u8: bool = False):
+    """The pre-process of PP-FormulaNet_plus for a list of device uint8 [H, W, 3] RGB crops (windows of a page batch are taken as they
+    are, no copy) -> (x [n, 1, 384, 384] float32 on the device, routes): bit for bit what `formula_host.preprocess` gives.
+
+    One launch finds every margin box, ONE device-to-host copy brings the [n, 4] boxes back (every later size follows from the box),
+    then everything up to `x` is enqueued without another synchronisation.  routes[i]: "device", or "host" for a crop the device path
+    declines - an intermediate beyond 16384 pixels, a grey-level or empty tensor, a numpy array: it is copied to the host, goes through
+    `formula_host.preprocess` and its row is uploaded; "empty" when that returns None (the row is zero).  `return_u8`: also returns the
+    padded uint8 images [n, 384, 384, 3] (rows of host-routed crops included)."""
+    lib = _lib.load()
+    n = len(crops)
+    dev = next((c.device for c in crops if isinstance(c, torch.Tensor) and c.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    x = torch.zeros((n, 1, FORMULA_SIDE, FORMULA_SIDE), dtype=torch.float32, device=dev)
+    u8 = torch.zeros((n, FORMULA_SIDE, FORMULA_SIDE, 3), dtype=torch.uint8, device=dev) if return_u8 else None
+    routes = ["host"] * n
+    views = [_formula_view(c) for c in crops]
+    cand = [i for i, v in enumerate(views) if v is not None]
+    if cand:
+        boxes = formula_margin_boxes([views[i] for i in cand]).cpu().numpy()                 # the one device-to-host copy
+        served = [k for k, b in enumerate(boxes) if formula_preproc_plan(int(b[2] - b[0]), int(b[3] - b[1])).served]
+        if served:
+            idx = [cand[k] for k in served]
+            descs = _formula_descs([views[i] for i in idx])
+            b = np.ascontiguousarray(boxes[served], dtype=np.int32)
+            whole = len(idx) == n
+            xo = x if whole else torch.empty((len(idx), 1, FORMULA_SIDE, FORMULA_SIDE), dtype=torch.float32, device=dev)
+            uo = None if u8 is None else (u8 if whole else torch.empty((len(idx), FORMULA_SIDE, FORMULA_SIDE, 3), dtype=torch.uint8, device=dev))
+            rc = lib.rd_formula_preproc_batch(dev.index or 0, descs.ctypes.data, b.ctypes.data, len(idx), xo.data_ptr(),
+                                              uo.data_ptr() if uo is not None else None, _stream_ptr())
+            if rc != 0:
+                raise EngineError(lib.rd_create_error().decode())
+            if not whole:
+                at = torch.tensor(idx, dtype=torch.long, device=dev)
+                x.index_copy_(0, at, xo)
+                if u8 is not None:
+                    u8.index_copy_(0, at, uo)
+            for i in idx:
+                routes[i] = "device"
+    if any(r == "host" for r in routes):
+        from . import formula_host
+        for i, r in enumerate(routes):
+            if r != "host":
+                continue
+            img = crops[i].cpu().numpy() if isinstance(crops[i], torch.Tensor) else np.asarray(crops[i])
+            d = formula_host.decode_image(img) if img.size else None
+            if d is None:
+                routes[i] = "empty"
+                continue
+            x[i].copy_(torch.from_numpy(formula_host.to_network_input(d)[0]))
+            if u8 is not None:
+                u8[i].copy_(torch.from_numpy(d))
+    return (x, routes, u8) if return_u8 else (x, routes)

@@ -14,6 +14,7 @@ chunks of `batch_size`, one [B,1,384,384] tensor per chunk -> encoder -> greedy 
 from __future__ import annotations
 
 import math
+import os
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -21,6 +22,18 @@ from PIL import Image, ImageOps
 
 INPUT_SIZE = (384, 384)
 MEAN, STD = 0.7931, 0.1738
+# RD_FORMULA_PREPROC (read once): "host" = every crop is pre-processed on the host with Pillow, device tensors are copied first (the path
+# before the device pre-process, kept for A/B); "device" = device tensors take `engine.formula_preprocess`; unset = DEVICE_BY_DEFAULT.
+PREPROC_SWITCH = os.environ.get("RD_FORMULA_PREPROC", "").strip().lower()
+DEVICE_BY_DEFAULT = True
+
+
+def device_preproc_enabled() -> bool:
+    """whether device tensors handed to `FormulaRecognizer.batch_predict` stay on the device (and `analyze.recognise_formulas` hands
+    device views over at all)"""
+    if PREPROC_SWITCH in ("host", "device"):
+        return PREPROC_SWITCH == "device"
+    return DEVICE_BY_DEFAULT
 
 
 def _crop_margin(img: Image.Image) -> Image.Image:
@@ -137,18 +150,51 @@ class FormulaRecognizer:
                 return _fix(text) if _fix else text
         self.token_decoder = token_decoder
 
-    def batch_predict(self, image_list: Sequence[np.ndarray], batch_size: int = 16, **kwargs) -> list:
+    accepts_device_images = True      # batch_predict takes device uint8 [H, W, 3] RGB tensors (page windows) next to numpy images
+
+    def batch_predict(self, image_list: Sequence, batch_size: int = 16, **kwargs) -> list:
+        """numpy images are pre-processed on the host exactly as before.  Device tensors take `engine.formula_preprocess` per chunk (one
+        device-to-host copy of the margin boxes per chunk; a crop it declines is copied and pre-processed on the host: the same bits),
+        unless RD_FORMULA_PREPROC says "host".  `self.last_routes[i]`: "numpy", "device", "host" or "empty" for image i."""
         import torch
+        from .engine import formula_preprocess
         results: list = [None] * len(image_list)
-        inputs = preprocess(image_list)
+        on_device = device_preproc_enabled()
+        inputs: list = [None] * len(image_list)
+        routes = ["numpy"] * len(image_list)
+        for i, im in enumerate(image_list):
+            if isinstance(im, torch.Tensor) and on_device and im.is_cuda and im.numel() > 0:
+                inputs[i] = im                                            # pre-processed with its chunk
+                routes[i] = "device"
+            else:
+                if isinstance(im, torch.Tensor):
+                    im, routes[i] = im.cpu().numpy(), "host"
+                inputs[i] = preprocess([im])[0]
+                if inputs[i] is None:
+                    routes[i] = "empty"
         valid = [i for i, x in enumerate(inputs) if x is not None]
         for beg in range(0, len(valid), batch_size):
             chunk = valid[beg: beg + batch_size]
-            x = torch.from_numpy(np.concatenate([inputs[i] for i in chunk], axis=0)).cuda(self.encoder.device)
+            dev_rows = [k for k, i in enumerate(chunk) if routes[i] == "device"]
+            if dev_rows:
+                xd, got = formula_preprocess([inputs[chunk[k]] for k in dev_rows])
+                for k, r in zip(dev_rows, got):
+                    routes[chunk[k]] = r                                  # "device", or "host" where the plan declined
+            host_rows = [k for k in range(len(chunk)) if routes[chunk[k]] in ("numpy", "host") and k not in dev_rows]
+            xh = torch.from_numpy(np.concatenate([inputs[chunk[k]] for k in host_rows], axis=0)).cuda(self.encoder.device) if host_rows else None
+            if not dev_rows:
+                x = xh
+            elif not host_rows:
+                x = xd
+            else:                                                         # a chunk of both kinds: every row goes to its place
+                x = torch.empty((len(chunk), 1) + tuple(INPUT_SIZE), dtype=torch.float32, device=xd.device)
+                x[host_rows] = xh
+                x[dev_rows] = xd
             ids = self.decoder.formula_decode(self.encoder.formula_encoder_forward(x), self.max_new_tokens).cpu().numpy()
             for row, i in zip(ids, chunk):
                 toks = row[1:].tolist()
                 if 2 in toks:
                     toks = toks[: toks.index(2)]          # UniMERNetDecode cuts at EOS (post_process.py:277-296)
                 results[i] = self.token_decoder(toks) if self.token_decoder else toks
+        self.last_routes = routes
         return [r if r is not None else ([] if self.token_decoder is None else "") for r in results]
