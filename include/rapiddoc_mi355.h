@@ -398,6 +398,57 @@ double rd_polygon_area(const double* a, int na);
 double rd_polygon_intersection_area(const double* a, int na, const double* b, int nb);
 int rd_fill_poly(uint8_t* img, int h, int w, const int32_t* pts, int n, int value);
 
+/* cv2.findContours(mask, RETR_EXTERNAL, CHAIN_APPROX_NONE): the same components in the same order as rd_find_external_contours, every
+ * border-following point written (a pixel the walk passes twice appears twice).  Same arguments and return values. */
+int rd_find_external_contours_none(const uint8_t* mask, int h, int w, int32_t* pts_out, int max_pts, int32_t* counts_out, int max_contours,
+                                   int32_t* n_contours, int32_t* n_pts);
+
+/* Checkbox detection, rapid_doc/utils/checkbox_det_cls.py checkbox_predict (called at batch_analyze.py:207-219), on the device
+ * (csrc/kernels_checkbox.hip, csrc/checkbox_host.cpp; docs/notebook/checkbox.md).  OpenCV is restated from its published algorithms,
+ * PARITY UNPINNED as for the polygon primitives above; tests/checkbox_reference.py is the yardstick.
+ *   1. rd_checkbox_workspace: bytes of device scratch for a batch, 0 on bad arguments.  offsets (may be NULL) receives the byte offset of
+ *      every part, in this order: threshold bits, line mask, dilated line mask (each [P][H][ceil(W / 64)] 64-bit words, bit i of word j =
+ *      pixel 64 j + i), row counts [P][H], row offsets [P][H + 1], runs [P][max_runs] of int16 (y, x0, x1, 0), then six int32
+ *      [P][max_runs] arrays: parent (a run whose parent is itself is a component's root), and at the roots block key, min x, max x,
+ *      min y, max y; last the staged candidates.
+ *   2. rd_checkbox_detect_device: every kernel of the stage on `stream`, nothing copied.  pages_dev: [P][H][W][3] u8, `bgr` non-zero
+ *      when the channel order is B, G, R.  hdr_dev [P] and cands_dev [P * max_cand] are DEVICE memory.  The caller then copies hdr_dev
+ *      (32 bytes a page) and, knowing the counts, the first sum(min(n_cand, max_cand)) records of cands_dev (584 bytes a candidate):
+ *      two device-to-host copies per batch, neither proportional to the page area.  A page's records start at its cand_off.  A page
+ *      whose flags are non-zero holds no usable records: repeat it with max_runs = H * ceil(W / 2) (RD_CHECKBOX_RUNS_OVERFLOW) or
+ *      max_cand = its n_cand (RD_CHECKBOX_CANDS_OVERFLOW).
+ *   3. rd_checkbox_finish (HOST pointers, one page): re-checks every record against the size filter and the ROI rectangle in double,
+ *      orders the records by label order (`key`), applies the contour rule to the ROI and classifies by the tick count.  out [max_out].
+ * Return 0 = ok, 1 = bad arguments (nothing launched; the message is rd_create_error()'s), 2 = max_out too small (*n_out holds the
+ * need), 3 = a record disagrees with the host's arithmetic. */
+#define RD_CHECKBOX_MAX_SIDE 16384
+#define RD_CHECKBOX_MAX_PAGES 1024
+#define RD_CHECKBOX_ROI_ROWS 70
+#define RD_CHECKBOX_WS_PARTS 13
+#define RD_CHECKBOX_RUNS_OVERFLOW 1
+#define RD_CHECKBOX_CANDS_OVERFLOW 2
+typedef struct rd_checkbox_page {
+    int32_t n_runs;       /* runs of the complement of the dilated line mask */
+    int32_t flags;        /* RD_CHECKBOX_*_OVERFLOW */
+    int32_t n_comp;       /* 8-connected components of that complement */
+    int32_t n_cand;       /* components that pass the size filter, the first in label order left out */
+    int32_t first_key;    /* key of the first component in label order (the one stats[2:] drops), -1 without components */
+    int32_t cand_off;     /* index of the page's first record */
+    int32_t reserved[2];
+} rd_checkbox_page;
+typedef struct rd_checkbox_cand {
+    int32_t key;                          /* label order: (min y / 2) << 16 | x / 2 of the component's first 2 x 2 block */
+    int32_t tick;                         /* countNonZero of the opened adaptive threshold of image[y : y + h, x : x + w] */
+    int16_t x, y, w, h;                   /* the component's bounding box */
+    int16_t rx, ry, rw, rh;               /* the ROI of the contour rule */
+    uint64_t roi[RD_CHECKBOX_ROI_ROWS];   /* its rows of the dilated line mask, bit i = column rx + i; rows >= rh are zero */
+} rd_checkbox_cand;
+typedef struct rd_checkbox_box { int32_t x, y, w, h, ticked; } rd_checkbox_box;
+size_t rd_checkbox_workspace(int P, int H, int W, int max_runs, int max_cand, size_t* offsets);
+int rd_checkbox_detect_device(int device_id, const uint8_t* pages_dev, int P, int H, int W, int bgr, int max_runs, int max_cand, void* ws_dev,
+                              size_t ws_bytes, rd_checkbox_page* hdr_dev, rd_checkbox_cand* cands_dev, void* stream);
+int rd_checkbox_finish(const rd_checkbox_cand* cands, int n, int H, int W, rd_checkbox_box* out, int max_out, int32_t* n_out);
+
 /* Host: chunk sizes of the recogniser's THROUGHPUT mode (the engine's own scheduling; rapidocr's fixed rec_batch_num chunks,
  * rapid_doc/model/ocr/rapid_ocr.py:430-440, are the `strict` mode of rapiddoc_amd.pipeline.PagePipeline).  wpad_sorted[i] = padded
  * width of the i-th line of the aspect-sorted list (int(48 * max(320/48, w/h)) rounded up to the width multiple); a chunk is a run of

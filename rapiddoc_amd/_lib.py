@@ -60,6 +60,11 @@ SYMBOLS = {
     "rd_layout_postprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rd_layout_postprocess_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rd_find_external_contours": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rd_find_external_contours_none": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rd_checkbox_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rd_checkbox_detect_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+    "rd_checkbox_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "rd_contour_area": (C.c_double, [C.c_void_p, C.c_int]),
     "rd_arc_length": (C.c_double, [C.c_void_p, C.c_int, C.c_int]),
     "rd_approx_poly_dp": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
@@ -112,6 +117,7 @@ DEBUG_SYMBOLS = {
     "rd_debug_lcv3_dw_det": (_F, [_I] * 10 + [_P] * 5),
     "rd_debug_lcv3_block": (_F, [_I] * 9 + [_P] * 9),
     "rd_debug_time_ctc": (_F, [_I] * 4 + [_P] * 7 + [_I, _P]),
+    "rd_debug_time_checkbox_mask": (_F, [_I] * 4 + [_P, _P]),
     "rd_debug_attention": (_I, [_I] * 4 + [_F, _P, _P, _P, _I, _P]),
     "rd_debug_vit_attention": (_I, [_I] * 4 + [_F, _P, _P]),
     "rd_debug_attention_limits": (_I, [_I, _P, _P]),

@@ -578,12 +578,14 @@ class PageAnalyzer:
         #    Its seal detector is ONNX-only (not built): pages WITH a seal region and no model to read it fail loudly.
         self.seal_model, self.seal_enable = seal_model, seal_enable
         # checkbox detection (checkbox_config["checkbox_enable"], default False, batch_analyze.py:51,207-219): `checkbox_fn(bgr page) ->
-        # [{'bbox': [x0, y0, x1, y1], 'text': ...}]` = utils/checkbox_det_cls.py checkbox_predict (OpenCV morphology on the host; not
-        # built - a caller that enables the stage supplies it).  Every hit becomes a CheckBox detection of the page and masks the OCR
-        # detector's input like a formula box.
+        # [{'bbox': [x0, y0, x1, y1], 'text': ...}]` = utils/checkbox_det_cls.py checkbox_predict.  rapiddoc_amd.checkbox.Mi355Checkbox is
+        # that function on the GPU; a `checkbox_fn` that declares `accepts_device_pages` (as it does) is handed the page TENSOR, once
+        # per batch (`detect_pages(pages) -> one list per page`), any other callable one BGR numpy page at a time.  Every hit becomes a
+        # CheckBox detection of the page and masks the OCR detector's input like a formula box.
         self.checkbox_fn, self.checkbox_enable = checkbox_fn, checkbox_enable
         if checkbox_enable and checkbox_fn is None:
-            raise ValueError("checkbox_enable needs a checkbox_fn (the reference's checkbox_predict is host OpenCV code, not part of this build)")
+            raise ValueError("checkbox_enable needs a checkbox_fn: rapiddoc_amd.checkbox.Mi355Checkbox(device) runs the reference's "
+                             "checkbox_predict on the GPU, or hand in any callable that takes a BGR page")
         # page orientation (USE_DOC_ORIENTATION_CLASSIFY, default off, batch_analyze.py:66-67,113-125,153-161): `orientation_model.predict(
         # rgb page) -> "0" | "90" | "180" | "270"` (the ONNX-only ImgOrientationCls model); pages labelled 90 / 270 are turned upright
         # before the layout model sees them and every detection's `poly` is mapped back afterwards
@@ -627,13 +629,17 @@ class PageAnalyzer:
         # 2. region collection: writes the integer `bbox` into the formula detections before anything else touches them, so that the
         #    fields of a detection also appear in the reference's ORDER (bbox, then latex) when the result is serialised
         checkbox_res: Optional[List[List[dict]]] = None
+        checkbox_found = None
+        if self.checkbox_enable and getattr(self.checkbox_fn, "accepts_device_pages", False):
+            checkbox_found = [list(found) for found in self.checkbox_fn.detect_pages(pages)]      # the tensor itself: nothing leaves the device
         for p, page in enumerate(dets):
             layout_host.split_regions(page)
             attach_table_images(pages, p, page)
             if self.checkbox_enable:          # after the regions were collected: a checkbox is never an OCR region itself
                 if checkbox_res is None:
                     checkbox_res = []
-                found = list(self.checkbox_fn(np.ascontiguousarray(pages[p].cpu().numpy()[:, :, ::-1])))
+                found = checkbox_found[p] if checkbox_found is not None else \
+                    list(self.checkbox_fn(np.ascontiguousarray(pages[p].cpu().numpy()[:, :, ::-1])))
                 checkbox_res.append(found)
                 for res in found:
                     b = res["bbox"]

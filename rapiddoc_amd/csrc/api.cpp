@@ -262,6 +262,26 @@ int rd_formula_preproc_batch(int device_id, const rd_formula_crop* descs_host, c
     return rc;
 }
 
+size_t rd_checkbox_workspace(int P, int H, int W, int max_runs, int max_cand, size_t* offsets) {
+    return rd::checkbox_workspace_bytes(P, H, W, max_runs, max_cand, offsets);
+}
+
+int rd_checkbox_detect_device(int device_id, const uint8_t* pages_dev, int P, int H, int W, int bgr, int max_runs, int max_cand, void* ws_dev,
+                              size_t ws_bytes, rd_checkbox_page* hdr_dev, rd_checkbox_cand* cands_dev, void* stream) {
+    std::string err;
+    const int rc = rd::launch_checkbox_detect(device_id, pages_dev, P, H, W, bgr, max_runs, max_cand, ws_dev, ws_bytes, hdr_dev, cands_dev,
+                                              (hipStream_t)stream, err);
+    if (rc != 0) g_create_err = err;
+    return rc;
+}
+
+int rd_checkbox_finish(const rd_checkbox_cand* cands, int n, int H, int W, rd_checkbox_box* out, int max_out, int32_t* n_out) {
+    std::string err;
+    const int rc = rd::checkbox_finish(cands, n, H, W, out, max_out, n_out, err);
+    if (rc != 0) g_create_err = err;
+    return rc;
+}
+
 int rd_crop_resize_norm_batch(int device_id, const uint8_t* pages, int P, int H, int W, const rd_crop_desc* descs, int n,
                               int out_h, int out_w_padded, const float mean[3], const float std[3], float scale, int swap_rb,
                               float* out, void* stream) {

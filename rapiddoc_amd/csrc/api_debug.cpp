@@ -719,6 +719,13 @@ float rd_debug_time_ctc(int M, int K, int Ccls, int iters, float* x, float* wp, 
     return rd_debug_time(iters, [&] { rd::launch_ctc_head(p, nullptr); });
 }
 
+// developer timing of the checkbox stage's threshold kernel alone (cb_bin_kernel, the one pass over the 3 B / pixel pages): pages
+// [P][H][W][3] u8, bin = room for P * H * ceil(W / 64) 64-bit words.  Returns ms per launch, -1 outside the stage's bounds.
+float rd_debug_time_checkbox_mask(int P, int H, int W, int iters, void* pages, void* bin) {
+    if (!pages || !bin || P < 1 || P > RD_CHECKBOX_MAX_PAGES || H < 1 || W < 1 || H > RD_CHECKBOX_MAX_SIDE || W > RD_CHECKBOX_MAX_SIDE) return -1.f;
+    return rd_debug_time(iters, [&] { rd::launch_checkbox_bin((const uint8_t*)pages, P, H, W, 0, (uint64_t*)bin, nullptr); });
+}
+
 // A range-flag word for the developer entries below: pinned, device-mapped host memory, as the engine's own (engine.cpp load_weights).
 static unsigned* debug_flag_new() {
     unsigned* flag = nullptr;

@@ -31,8 +31,8 @@ static const int DY[8] = {0, -1, -1, -1, 0, 1, 1, 1};
 // Suzuki-Abe border following of ONE outer border starting at (x0, y0) (the component's first pixel in raster order, so its
 // west neighbour is background), as OpenCV's contour fetcher walks it: first non-zero neighbour clockwise from west, then
 // counter-clockwise search from the direction after the one we came from; stop when the first step is about to repeat.
-// CHAIN_APPROX_SIMPLE: a point is written only where the direction changes.
-static void trace_outer_border(const uint8_t* img, int H, int W, int x0, int y0, std::vector<Pt>& out) {
+// CHAIN_APPROX_SIMPLE: a point is written only where the direction changes; CHAIN_APPROX_NONE (`none`): at every step.
+static void trace_outer_border(const uint8_t* img, int H, int W, int x0, int y0, bool none, std::vector<Pt>& out) {
     auto at = [&](int x, int y) -> int { return (x >= 0 && y >= 0 && x < W && y < H) ? img[(size_t)y * W + x] != 0 : 0; };
     int s = 4;
     const int s_stop = 4;
@@ -57,7 +57,7 @@ static void trace_outer_border(const uint8_t* img, int H, int W, int x0, int y0,
             if (at(x4, y4)) break;
         }
         s &= 7;
-        if (s != prev_s) {
+        if (none || s != prev_s) {
             out.push_back({px, py});
             prev_s = s;
         }
@@ -153,11 +153,10 @@ static void slab_xs(const double* a, int na, const double* b, int nb, std::vecto
 // cv2.findContours(mask, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE): the outer border of every 8-connected component that does not lie
 // inside a hole of another one (its first pixel's west neighbour belongs to background that is 4-connected to the image frame).
 // Returned last-found first, the order OpenCV's list has (it only matters to which of several equal-area contours a caller's
-// `max(...)` picks).  pts_out: [max_pts][2] (x, y); counts_out[c] = points of contour c.
-// Returns 0, 1 (bad arguments) or 2 (capacity: *n_contours / *n_pts hold what is needed).
-extern "C" int rd_find_external_contours(const uint8_t* mask, int h, int w, int32_t* pts_out, int max_pts, int32_t* counts_out,
-                                         int max_contours, int32_t* n_contours, int32_t* n_pts) {
-    if (!mask || h <= 0 || w <= 0 || !n_contours || !n_pts || max_pts < 0 || max_contours < 0) return 1;
+// `max(...)` picks).  `none`: CHAIN_APPROX_NONE, the same search and the same walk with every point kept.
+// The C entries below write pts_out: [max_pts][2] (x, y); counts_out[c] = points of contour c, and
+// return 0, 1 (bad arguments) or 2 (capacity: *n_contours / *n_pts hold what is needed).
+static void external_contours(const uint8_t* mask, int h, int w, bool none, std::vector<std::vector<Pt>>& found) {
     // One raster pass over row RUNS instead of per-pixel flood fills: foreground runs are joined with the runs of the previous row
     // they touch (8-connected: x ranges may differ by one), background runs with those they overlap (4-connected); node 0 of the
     // background forest is "outside the image".  A component is external iff the background run left of its first pixel is outside.
@@ -208,16 +207,22 @@ extern "C" int rd_find_external_contours(const uint8_t* mask, int h, int w, int3
     }
     // the first run (raster order) of every component is its start pixel; later runs of the same component are dropped
     std::vector<char> taken(fg_parent.size(), 0);
-    std::vector<std::vector<Pt>> found;
     for (const Start& st : starts) {
         const int root = find(fg_parent, st.fg);
         if (taken[root]) continue;
         taken[root] = 1;
         if (find(bg_parent, st.bg_left) != 0) continue;      // inside a hole of another component
         found.emplace_back();
-        trace_outer_border(mask, h, w, st.x, st.y, found.back());
+        trace_outer_border(mask, h, w, st.x, st.y, none, found.back());
     }
     std::reverse(found.begin(), found.end());
+}
+
+static int contours_out(const uint8_t* mask, int h, int w, bool none, int32_t* pts_out, int max_pts, int32_t* counts_out, int max_contours,
+                        int32_t* n_contours, int32_t* n_pts) {
+    if (!mask || h <= 0 || w <= 0 || !n_contours || !n_pts || max_pts < 0 || max_contours < 0) return 1;
+    std::vector<std::vector<Pt>> found;
+    external_contours(mask, h, w, none, found);
     size_t total = 0;
     for (const auto& c : found) total += c.size();
     *n_contours = (int32_t)found.size();
@@ -230,6 +235,29 @@ extern "C" int rd_find_external_contours(const uint8_t* mask, int h, int w, int3
     }
     return 0;
 }
+
+extern "C" int rd_find_external_contours(const uint8_t* mask, int h, int w, int32_t* pts_out, int max_pts, int32_t* counts_out,
+                                         int max_contours, int32_t* n_contours, int32_t* n_pts) {
+    return contours_out(mask, h, w, false, pts_out, max_pts, counts_out, max_contours, n_contours, n_pts);
+}
+
+// cv2.findContours(mask, RETR_EXTERNAL, CHAIN_APPROX_NONE): the same walk, every point kept (utils/checkbox_det_cls.py:53)
+extern "C" int rd_find_external_contours_none(const uint8_t* mask, int h, int w, int32_t* pts_out, int max_pts, int32_t* counts_out,
+                                              int max_contours, int32_t* n_contours, int32_t* n_pts) {
+    return contours_out(mask, h, w, true, pts_out, max_pts, counts_out, max_contours, n_contours, n_pts);
+}
+
+namespace rd {
+void find_external_contours(const uint8_t* mask, int h, int w, bool none, std::vector<std::vector<int32_t>>& xy_out) {
+    std::vector<std::vector<Pt>> found;
+    if (mask && h > 0 && w > 0) external_contours(mask, h, w, none, found);
+    xy_out.clear();
+    for (const auto& c : found) {
+        xy_out.emplace_back();
+        for (const Pt& p : c) { xy_out.back().push_back(p.x); xy_out.back().push_back(p.y); }
+    }
+}
+}  // namespace rd
 
 // cv2.contourArea(contour) of integer points: |shoelace| / 2, products and sum in double
 extern "C" double rd_contour_area(const int32_t* pts, int n) {

@@ -537,6 +537,17 @@ int launch_line_resize_norm(const LineCropParams& p, hipStream_t s);   // stage 
 // bytes (length, then the entry's UTF-8 bytes).
 // box_score_fast of the DB post-process candidates (kernels_image.hip), used by launch_db_boxes
 int launch_db_scores(const float* prob, int B, int H, int W, const void* cand, const int32_t* n_cand, int max_cand, double* scores, hipStream_t s);
+// checkbox detection on the device (kernels_checkbox.hip): include/rapiddoc_mi355.h rd_checkbox_workspace / rd_checkbox_detect_device.
+// The launcher returns 0, or 1 with the message in `err` and nothing launched.
+size_t checkbox_workspace_bytes(int P, int H, int W, int max_runs, int max_cand, size_t* offsets);
+int launch_checkbox_detect(int device, const uint8_t* pages, int P, int H, int W, int bgr, int max_runs, int max_cand, void* ws, size_t ws_bytes,
+                           rd_checkbox_page* hdr, rd_checkbox_cand* cands, hipStream_t s, std::string& err);
+void launch_checkbox_bin(const uint8_t* pages, int P, int H, int W, int bgr, uint64_t* bin, hipStream_t s);      // the threshold kernel alone
+// its host half (checkbox_host.cpp): 0, or 1 / 2 / 3 as rd_checkbox_finish documents, the message in `err`
+int checkbox_finish(const rd_checkbox_cand* cands, int n, int H, int W, rd_checkbox_box* out, int max_out, int32_t* n_out, std::string& err);
+// polygon_ops.cpp: the external contours of a u8 mask, last found first; `none` = CHAIN_APPROX_NONE, else CHAIN_APPROX_SIMPLE
+void find_external_contours(const uint8_t* mask, int h, int w, bool none, std::vector<std::vector<int32_t>>& xy_out);
+
 // the whole DB post-process on the device (kernels_dbpost.hip): include/rapiddoc_mi355.h rd_db_boxes_device
 size_t db_boxes_workspace_bytes(int B, int H, int max_runs, int max_cand);
 int launch_db_boxes(const float* prob, int B, int H, int W, const int32_t* src_hw_dev, float thresh, float box_thresh, float unclip_ratio,

@@ -34,9 +34,11 @@ def _pts_i32(pts) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(pts).reshape(-1, 2), dtype=np.int32)
 
 
-def find_external_contours(mask: np.ndarray) -> List[np.ndarray]:
-    """cv2.findContours(mask, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE)[0] as a list of int32 [n, 2] arrays."""
+def find_external_contours(mask: np.ndarray, approx_none: bool = False) -> List[np.ndarray]:
+    """cv2.findContours(mask, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE)[0] as a list of int32 [n, 2] arrays; `approx_none`:
+    CHAIN_APPROX_NONE, every border-following point."""
     lib = _lib.load()
+    entry = lib.rd_find_external_contours_none if approx_none else lib.rd_find_external_contours
     m = np.ascontiguousarray(mask, dtype=np.uint8)
     assert m.ndim == 2
     h, w = m.shape
@@ -47,7 +49,7 @@ def find_external_contours(mask: np.ndarray) -> List[np.ndarray]:
     while True:
         pts = np.empty((cap_p, 2), np.int32)
         counts = np.empty(cap_c, np.int32)
-        rc = lib.rd_find_external_contours(m.ctypes.data, h, w, pts.ctypes.data, cap_p, counts.ctypes.data, cap_c, C.byref(n_c), C.byref(n_p))
+        rc = entry(m.ctypes.data, h, w, pts.ctypes.data, cap_p, counts.ctypes.data, cap_c, C.byref(n_c), C.byref(n_p))
         if rc == 0:
             break
         if rc != 2:
