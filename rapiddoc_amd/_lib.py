@@ -102,6 +102,7 @@ DEBUG_SYMBOLS = {
     "rd_debug_conv_route": (_I, [_I] * 17 + [_P, _I]),
     "rd_debug_conv": (_F, [_I] * 14 + [_P] * 8),
     "rd_debug_stem34": (_F, [_I] * 11 + [_P] * 7),
+    "rd_debug_dwconv_ex": (_F, [_I] * 17 + [_P] * 10 + [_I]),
     "rd_debug_dwconv": (_F, [_I] * 8 + [_P] * 8),
     "rd_debug_dw_route": (_I, [_I] * 9 + [_P, _I, _P]),
     "rd_debug_weight_split": (_I, [_P, _I, _I, _P, _P]),
@@ -122,6 +123,13 @@ DEBUG_SYMBOLS = {
     "rd_debug_vit_attention": (_I, [_I] * 4 + [_F, _P, _P]),
     "rd_debug_attention_limits": (_I, [_I, _P, _P]),
     "rd_debug_layernorm": (_I, [_I, _I, _P, _I, _P, _I, _P, _P, _F]),
+    "rd_debug_se_chain": (_I, [_I] * 7 + [_F] + [_I] * 3 + [_P] * 9),
+    "rd_debug_maxpool2x2s1": (_I, [_I] * 6 + [_P] * 2),
+    "rd_debug_avgpool3x2": (_I, [_I] * 6 + [_P] * 3),
+    "rd_debug_mask_cols": (_I, [_I] * 5 + [_P, _P, _I]),
+    "rd_debug_upsample": (_I, [_I] * 8 + [_P] * 2),
+    "rd_debug_add": (_I, [_I] * 5 + [_P] * 3),
+    "rd_debug_det_head_tail": (_I, [_I] * 4 + [_P] * 6),
     "rd_debug_ctc_head": (_I, [_I] * 3 + [_P, _I] + [_P] * 6 + [_I, _P, _P]),
     "rd_debug_dec_gemv": (_I, [_I] * 4 + [_P] * 7),
     "rd_debug_dec_attention": (_I, [_I] * 4 + [_P, _P, _I, C.c_longlong] + [_P] * 5 + [_P, _I, _P, _P, _I, _P, _I]),

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "api_handle.h"
+#include "builder_util.h"
 
 extern "C" {
 
@@ -441,21 +442,44 @@ float rd_debug_stem34(int N, int H, int W, int Cin, int xld, int N1, int N2, int
     return ms;
 }
 
-// developer entry: one depthwise convolution through launch_dwconv (x NHWC fp32 [N][H][W][C], w [KH*KW][C], bias [C] or null,
-// res NHWC or null, line_w int32 [N] valid widths or null, gap = [N][chunks][C] partial sums of the output or null).
+// "lds1" .. "lds5" = dwconv_lds_variant, "kxk_lds5" / "7", "tiled4" / "8", "col", "pixel": what rd_debug_dw_route and rd_debug_dwconv_ex report
+static std::string debug_dw_route_name(const rd::DwRoute& r) {
+    static const char* const kernels[] = {"pixel", "lds", "kxk_lds", "col", "tiled"};
+    return std::string(kernels[r.kernel]) + (r.kernel == rd::DW_PIXEL || r.kernel == rd::DW_COL ? "" : std::to_string(r.variant));
+}
+
+// developer entry: one depthwise convolution through launch_dwconv with every field of DwParams the engine sets open to the caller: x NHWC
+// fp32 [N][H][W][xld >= C], w [KH*KW][C], bias [C] or null, res [N][OH][OW][rld >= C] or null, y [N][OH][OW][yld >= C] with OH / OW from
+// out_dim as Builder::dwconv has them, line_w int32 [N] valid widths or null (stride-1 'same' widths only), tokinfo int32 [W] or null (ragged
+// rows: N = H = KH = 1), gap = [N][chunks][C] partial sums of the output or null.  *gap_chunks as rd_debug_dwconv; name[name_len] receives the
+// route's name (debug_dw_route_name) from the dw_route call the launch makes.  Returns ms per launch, -1 on a bad argument (nothing launched).
+float rd_debug_dwconv_ex(int N, int H, int W, int C, int KH, int KW, int SH, int SW, int PT, int PL, int PB, int PR, int act, int xld, int yld, int rld,
+                         int iters, float* x, float* w, float* bias, float* res, float* y, const int32_t* line_w, const int32_t* tokinfo, float* gap,
+                         int* gap_chunks, char* name, int name_len) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 != 0 || KH <= 0 || KW <= 0 || SH <= 0 || SW <= 0 || PT < 0 || PL < 0 || PB < 0 || PR < 0) return -1.f;
+    if (!x || !w || !y || xld < C || xld % 4 != 0 || yld < C || yld % 4 != 0 || (res && (rld < C || rld % 4 != 0))) return -1.f;
+    if (H + PT + PB < KH || W + PL + PR < KW) return -1.f;
+    rd::DwParams p = rd::dw_geometry(N, H, W, C, KH, KW, SH, SW, PT, PL, PB, PR);
+    if (tokinfo && !(N == 1 && H == 1 && KH == 1 && SW == 1 && p.OW == W)) return -1.f;          // (Builder::dwconv's rules for the two tables)
+    if (line_w && !(SW == 1 && p.OW == W)) return -1.f;
+    p.x = x; p.xld = xld; p.w = w; p.bias = bias; p.y = y; p.yld = yld; p.act = act; p.res = res; p.rld = res ? rld : 0;
+    p.tokinfo = tokinfo;
+    if (line_w) { p.line_w = line_w; p.line_w_stride = 1; }
+    p.gap_chunks = rd::dwconv_gap_chunks(p);
+    p.gap_partial = p.gap_chunks > 0 ? gap : nullptr;
+    const rd::DwRoute r = rd::dw_route(p, p.gap_partial != nullptr);
+    // (tests: -1 = the one-channel-per-lane 5x5 / 7x7 kernel takes this call)
+    if (gap_chunks) *gap_chunks = r.kernel == rd::DW_KXK_LDS ? -1 : p.gap_chunks;
+    debug_copy_name(debug_dw_route_name(r).c_str(), name, name_len);
+    return rd_debug_time(iters, [&] { rd::launch_dwconv(p, nullptr); });
+}
+
+// developer entry: rd_debug_dwconv_ex on dense maps (xld = yld = rld = C) with a square K x K kernel, stride (SH, 1), padding K / 2 and OW = W.
 // *gap_chunks receives the chunk count the launcher uses for this geometry.  Returns ms per launch.
 float rd_debug_dwconv(int N, int H, int W, int C, int K, int SH, int act, int iters, float* x, float* w, float* bias, float* res, float* y,
                       const int32_t* line_w, float* gap, int* gap_chunks) {
-    rd::DwParams p{};
-    p.x = x; p.xld = C; p.N = N; p.H = H; p.W = W; p.C = C; p.w = w; p.bias = bias; p.y = y; p.yld = C;
-    p.KH = p.KW = K; p.SH = SH; p.SW = 1; p.PT = p.PL = K / 2;
-    p.OH = (H + 2 * p.PT - K) / SH + 1; p.OW = W; p.act = act; p.res = res; p.rld = C;
-    p.line_w = line_w; p.line_w_stride = 1;
-    p.gap_chunks = rd::dwconv_gap_chunks(p);
-    p.gap_partial = p.gap_chunks > 0 ? gap : nullptr;
-    // (tests: -1 = the one-channel-per-lane 5x5 / 7x7 kernel takes this call)
-    if (gap_chunks) *gap_chunks = rd::dw_route(p, p.gap_partial != nullptr).kernel == rd::DW_KXK_LDS ? -1 : p.gap_chunks;
-    return rd_debug_time(iters, [&] { rd::launch_dwconv(p, nullptr); });
+    return rd_debug_dwconv_ex(N, H, W, C, K, K, SH, 1, K / 2, K / 2, K / 2, K - 1 - K / 2, act, C, C, C, iters, x, w, bias, res, y, line_w, nullptr, gap,
+                              gap_chunks, nullptr, 0);
 }
 
 // developer entry, host only (no HIP call): the route of a depthwise convolution.  Geometry as rd_debug_dwconv (K = 1 with ragged: the
@@ -473,8 +497,7 @@ int rd_debug_dw_route(int N, int H, int W, int C, int K, int SH, int ragged, int
     if (ragged) p.tokinfo = table;
     if (has_line_w) { p.line_w = table; p.line_w_stride = 1; }
     const rd::DwRoute r = rd::dw_route(p, wants_gap != 0);
-    static const char* const kernels[] = {"pixel", "lds", "kxk_lds", "col", "tiled"};
-    debug_copy_name((std::string(kernels[r.kernel]) + (r.kernel == rd::DW_PIXEL || r.kernel == rd::DW_COL ? "" : std::to_string(r.variant))).c_str(), name, name_len);
+    debug_copy_name(debug_dw_route_name(r).c_str(), name, name_len);
     if (gap_chunks) *gap_chunks = r.gap_chunks;
     return planned;
 }
@@ -784,6 +807,89 @@ int rd_debug_layernorm(int M, int C, float* x, int xld, float* y, int yld, float
     if (C > 512) return -1;
     rd::launch_layernorm(x, xld, y, yld, g, b, M, C, eps, nullptr);
     return debug_finish(nullptr, nullptr);
+}
+
+// developer entry: the squeeze-excite chain launch_gap_partial -> launch_se_fc -> launch_scale_channels on caller-owned buffers, synchronised.
+// x NHWC fp32 [N][H][W][xld >= C], w1 [Cr][C], b1 [Cr], w2 [C][Cr], b2 [C], partial [N][chunks][C], gate_out [N][C], y [N][H][W][yld >= C] or
+// null (no scaling pass: y = x (gate + alpha) otherwise).  fill_partial != 0: the entry fills `partial` from x; 0: the caller has (a
+// depthwise launch's SE sums).  line_w int32 [N] or null: image n pools over H x line_w[n] - only with caller-filled sums, as in the engine
+// (launch_gap_partial knows no line ends).  Returns 0, -1 on a bad argument or a width se_fc_shape_ok declines (nothing launched).
+int rd_debug_se_chain(int N, int H, int W, int C, int Cr, int chunks, int gate_act, float alpha, int xld, int yld, int fill_partial, float* x,
+                      float* w1, float* b1, float* w2, float* b2, const int32_t* line_w, float* partial, float* gate_out, float* y) {
+    if (N <= 0 || H <= 0 || W <= 0 || !rd::se_fc_shape_ok(C) || Cr <= 0 || Cr > 4096 || chunks <= 0) return -1;
+    if (!w1 || !b1 || !w2 || !b2 || !partial || !gate_out || (fill_partial && line_w)) return -1;
+    if ((fill_partial || y) && (!x || xld < C || xld % 4 != 0)) return -1;
+    if (y && (yld < C || yld % 4 != 0)) return -1;
+    const int hw = H * W;
+    if (fill_partial) rd::launch_gap_partial(x, xld, N, hw, C, partial, chunks, nullptr);
+    rd::SeFcParams f{};
+    f.partial = partial; f.chunks = chunks; f.N = N; f.C = C; f.Cr = Cr; f.inv_hw = 1.f / (float)hw;
+    f.w1 = w1; f.b1 = b1; f.w2 = w2; f.b2 = b2; f.gate = gate_act; f.scale = gate_out; f.H = H;
+    if (line_w) { f.line_w = line_w; f.line_w_stride = 1; }
+    rd::launch_se_fc(f, nullptr);
+    if (y) rd::launch_scale_channels(x, xld, y, yld, gate_out, alpha, N, hw, C, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
+
+// developer entries: the small NHWC operators of kernels_misc.hip, one synchronised launch each on caller-owned buffers with explicit leading
+// dimensions (multiples of 4, >= C).  Each returns 0, -1 on a bad argument (nothing launched).
+// y [N][H][W] = max over the 2 x 2 window at (h, w) of x zero-padded by one row / column
+int rd_debug_maxpool2x2s1(int N, int H, int W, int C, int xld, int yld, float* x, float* y) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 || !x || !y || xld < C || xld % 4 || yld < C || yld % 4) return -1;
+    rd::launch_maxpool2x2s1(x, xld, y, yld, N, H, W, C, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
+// y [N][H / 3][W / 2] = avg_pool2d((3, 2)) of x [N][H][W]; with line_tab (int32 [N][kLineTabStride], H / 3 == 1) image n writes its
+// line_tab[n][2] / 2 tokens at row line_tab[n][3] of y instead
+int rd_debug_avgpool3x2(int N, int H, int W, int C, int xld, int yld, float* x, float* y, const int32_t* line_tab) {
+    if (N <= 0 || H < 3 || W < 2 || C <= 0 || C % 4 || !x || !y || xld < C || xld % 4 || yld < C || yld % 4 || (line_tab && H / 3 != 1)) return -1;
+    rd::launch_avgpool3x2(x, xld, y, yld, N, H, W, C, nullptr, line_tab);
+    return debug_finish(nullptr, nullptr);
+}
+// y [n][:][w >= line_w[n * stride]] = 0
+int rd_debug_mask_cols(int N, int H, int W, int C, int yld, float* y, const int32_t* line_w, int stride) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 || !y || yld < C || yld % 4 || !line_w || stride < 1) return -1;
+    rd::launch_mask_cols(y, yld, N, H, W, C, line_w, stride, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
+// y [N][H][W] (+)= x [N][H / f][W / f] nearest; H and W are the output's and multiples of f
+int rd_debug_upsample(int N, int H, int W, int C, int f, int accumulate, int xld, int yld, float* x, float* y) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 || f < 1 || H % f || W % f || !x || !y || xld < C || xld % 4 || yld < C || yld % 4) return -1;
+    rd::launch_upsample(x, xld, y, yld, N, H, W, C, f, accumulate, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
+// y [M][yld] = a [M][ald] + b [M][bld] on the first C columns
+int rd_debug_add(int M, int C, int ald, int bld, int yld, float* a, float* b, float* y) {
+    if (M <= 0 || C <= 0 || C % 4 || !a || !b || !y || ald < C || ald % 4 || bld < C || bld % 4 || yld < C || yld % 4) return -1;
+    rd::launch_add(a, ald, b, bld, y, yld, M, C, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
+
+// developer entry: the DB head's tail ConvTranspose2d(24, 24, 2, 2) -> ReLU -> ConvTranspose2d(24, 1, 2, 2) -> sigmoid through
+// launch_det_head_tail, on the weights in their checkpoint layouts (device pointers: w1 [24][24][2][2], b1 [24], w2 [24][1][2][2], b2 [1]),
+// repacked by the engine's own pack_det_head_tail with the identity for the BatchNorm.  x [N][H][W][xld >= 24], y [N][4 H][4 W].  Synchronised;
+// returns 0, -1 on a bad argument or no memory.
+int rd_debug_det_head_tail(int N, int H, int W, int xld, float* x, float* w1, float* b1, float* w2, float* b2, float* y) {
+    constexpr int kC = 24;
+    if (N <= 0 || H <= 0 || W <= 0 || !x || !w1 || !b1 || !w2 || !b2 || !y || xld < kC || xld % 4 || !rd::det_head_tail_supported(kC, kC, 1)) return -1;
+    std::vector<float> h1((size_t)kC * kC * 4), hb1(kC), h2((size_t)kC * 4), hb2(1);
+    if (hipMemcpy(h1.data(), w1, h1.size() * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hb1.data(), b1, hb1.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(h2.data(), w2, h2.size() * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hb2.data(), b2, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+    const std::vector<float> one(kC, 1.f), zero(kC, 0.f);
+    std::vector<float> wa, ba, wb;
+    rd::pack_det_head_tail(h1.data(), hb1.data(), h2.data(), kC, kC, one.data(), zero.data(), wa, ba, wb);
+    std::vector<float> img(wa);                 // one upload: wa | ba | wb | b2 (every part a multiple of 4 floats long before b2)
+    img.insert(img.end(), ba.begin(), ba.end());
+    img.insert(img.end(), wb.begin(), wb.end());
+    img.push_back(hb2[0]);
+    float* d = nullptr;
+    if (hipMalloc((void**)&d, img.size() * 4) != hipSuccess) return -1;
+    (void)hipMemcpy(d, img.data(), img.size() * 4, hipMemcpyHostToDevice);
+    rd::launch_det_head_tail(x, xld, N, H, W, d, d + wa.size(), d + wa.size() + ba.size(), d + wa.size() + ba.size() + wb.size(), y, nullptr);
+    const int rc = debug_finish(nullptr, nullptr);
+    (void)hipFree(d);
+    return rc;
 }
 
 // developer entry: ONE launch of the fused CTC head on prepared weights (as rd_debug_time_ctc), synchronised, with a free row stride of x

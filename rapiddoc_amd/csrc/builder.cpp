@@ -399,20 +399,8 @@ bool Builder::deconv_pair_to_prob(const std::string& w1n, const std::string& b1n
         if (!pb_->has(key + "#w1")) {
             std::vector<float> shift;
             std::vector<float> scale = bn_scale_shift(bn1, cmid, shift);
-            std::vector<float> wa((size_t)4 * cmid * cin), ba(cmid, 0.f), wb((size_t)4 * cmid), bb(1, 0.f);
-            const float* s1 = w1.f32();          // [cin][cmid][2][2]
-            for (int ci = 0; ci < cin; ++ci)
-                for (int co = 0; co < cmid; ++co)
-                    for (int tap = 0; tap < 4; ++tap)
-                        wa[((size_t)tap * cmid + co) * cin + ci] = s1[((size_t)ci * cmid + co) * 4 + tap] * scale[co];
-            if (!b1n.empty()) {
-                const float* bs = ws_->get(b1n).f32();
-                for (int co = 0; co < cmid; ++co) ba[co] = bs[co] * scale[co];
-            }
-            for (int co = 0; co < cmid; ++co) ba[co] += shift[co];
-            const float* s2 = w2.f32();          // [cmid][1][2][2]
-            for (int co = 0; co < cmid; ++co)
-                for (int tap = 0; tap < 4; ++tap) wb[(size_t)tap * cmid + co] = s2[(size_t)co * 4 + tap];
+            std::vector<float> wa, ba, wb, bb(1, 0.f);
+            pack_det_head_tail(w1.f32(), b1n.empty() ? nullptr : ws_->get(b1n).f32(), w2.f32(), cin, cmid, scale.data(), shift.data(), wa, ba, wb);
             if (!b2n.empty()) bb[0] = ws_->get(b2n).f32()[0];
             pb_->add(key + "#w1", wa);
             pb_->add(key + "#b1", ba);
@@ -808,15 +796,13 @@ TView Builder::dwconv(const std::string& wname, const std::string& bname, const 
     const int c = (int)w.shape[0], kh = (int)w.shape[2], kw = (int)w.shape[3];
     RD_CHECK(c == x.c && c % 4 == 0, "depthwise channel mismatch: " + wname);
     RD_CHECK(kh == g.kh && kw == g.kw, "depthwise kernel mismatch: " + wname);
-    const int oh = out_dim(x.h, kh, g.sh, g.pt, g.pb), ow = out_dim(x.w, kw, g.sw, g.pl, g.pr);
+    DwParams p = dw_geometry(x.n, x.h, x.w, c, kh, kw, g.sh, g.sw, g.pt, g.pl, g.pb, g.pr);
+    const int oh = p.OH, ow = p.OW;
     TView y = out ? *out : alloc(x.n, oh, ow, c);
     RD_CHECK(y.h == oh && y.w == ow && y.c == c, "depthwise output view mismatch: " + wname);
     const std::string key = wname + "|" + bn + "|dw";
     if (gap) {
-        DwParams gp{};
-        gp.N = x.n; gp.H = x.h; gp.W = x.w; gp.C = c; gp.OH = oh; gp.OW = ow;
-        gp.KH = kh; gp.KW = kw; gp.SH = g.sh; gp.SW = g.sw; gp.PT = g.pt; gp.PL = g.pl;
-        gap->chunks = dwconv_gap_chunks(gp);
+        gap->chunks = dwconv_gap_chunks(p);        // (asked on the unbound geometry: dw_route's rule)
         if (gap->chunks > 0) gap->partial = alloc_raw((size_t)x.n * gap->chunks * c);
     }
     if (!planning()) {
@@ -834,13 +820,10 @@ TView Builder::dwconv(const std::string& wname, const std::string& bname, const 
         }
         return y;
     }
-    DwParams p{};
     p.xld = plan_->ld(x);
-    p.N = x.n; p.H = x.h; p.W = x.w; p.C = c;
     p.w = pb_->ptr(key + "#w");
     p.bias = pb_->ptr(key + "#b");
     p.yld = plan_->ld(y);
-    p.OH = oh; p.OW = ow; p.KH = kh; p.KW = kw; p.SH = g.sh; p.SW = g.sw; p.PT = g.pt; p.PL = g.pl;
     p.act = act;
     p.rld = res ? plan_->ld(*res) : 0;
     p.gap_chunks = gap ? gap->chunks : 0;
@@ -980,7 +963,7 @@ TView Builder::se_gate(const std::string& w1n, const std::string& b1n, const std
     const HostTensor& w1 = ws_->get(w1n);
     const int cr = (int)w1.shape[0], c = (int)w1.shape[1];
     RD_CHECK(c == x.c && c % 4 == 0, "SE channel mismatch: " + w1n);
-    RD_CHECK(c <= 512, "SE width above 512 channels (se_fc_kernel reads a row of W1 with two 16-byte loads per lane): " + w1n);
+    RD_CHECK(se_fc_shape_ok(c), "SE width above 512 channels (se_fc_kernel reads a row of W1 with two 16-byte loads per lane): " + w1n);
     const int hw = x.h * x.w;
     const bool fused_gap = pre && pre->chunks > 0;  // the producing depthwise conv already wrote the partial sums
     RD_CHECK(!has_lt_ || fused_gap, "line table: the SE pooling sums must come from the depthwise kernel (it leaves out the columns beyond a line)");

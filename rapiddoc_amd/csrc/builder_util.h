@@ -1,4 +1,5 @@
-// Helpers shared by builder.cpp and builder_mobile.cpp only (everything here is file-local to the including source).
+// Helpers shared by builder.cpp, builder_mobile.cpp and the developer entries of api_debug.cpp (everything here is file-local to the
+// including source).
 #pragma once
 #include <cmath>
 #include <cstdlib>
@@ -24,6 +25,36 @@ static inline std::vector<float> fold_dw_taps(const float* w, int c, int taps, c
     for (int ch = 0; ch < c; ++ch)
         for (int t = 0; t < taps; ++t) wf[(size_t)t * c + ch] = w[(size_t)ch * taps + t] * (scale ? scale[ch] : 1.f);
     return wf;
+}
+
+// the geometry of a depthwise convolution as launch_dwconv, dw_route and the planner's dwconv_gap_chunks read it (pointers, leading
+// dimensions, epilogue and line tables stay with the caller): Builder::dwconv and the developer entries fill DwParams here only
+static inline DwParams dw_geometry(int n, int h, int w, int c, int kh, int kw, int sh, int sw, int pt, int pl, int pb, int pr) {
+    DwParams p{};
+    p.N = n; p.H = h; p.W = w; p.C = c;
+    p.OH = out_dim(h, kh, sh, pt, pb); p.OW = out_dim(w, kw, sw, pl, pr);
+    p.KH = kh; p.KW = kw; p.SH = sh; p.SW = sw; p.PT = pt; p.PL = pl;
+    return p;
+}
+
+// The DB head's two ConvTranspose2d(.., 2, stride 2) weights in their checkpoint layouts - w1 [cin][cmid][2][2], b1 [cmid] or null,
+// w2 [cmid][1][2][2] - as det_head_tail_kernel reads them: tap = 2 dy + dx major, wa [4][cmid][cin] and ba [cmid] with the middle
+// channel's affine (a folded BatchNorm: scale, shift per channel) applied, wb [4][cmid]
+static inline void pack_det_head_tail(const float* w1, const float* b1, const float* w2, int cin, int cmid, const float* scale, const float* shift,
+                                      std::vector<float>& wa, std::vector<float>& ba, std::vector<float>& wb) {
+    wa.assign((size_t)4 * cmid * cin, 0.f);
+    ba.assign(cmid, 0.f);
+    wb.assign((size_t)4 * cmid, 0.f);
+    for (int tap = 0; tap < 4; ++tap) {
+        const int dy = tap >> 1, dx = tap & 1;
+        for (int co = 0; co < cmid; ++co) {
+            for (int ci = 0; ci < cin; ++ci) wa[((size_t)tap * cmid + co) * cin + ci] = w1[(((size_t)ci * cmid + co) * 2 + dy) * 2 + dx] * scale[co];
+            wb[(size_t)tap * cmid + co] = w2[((size_t)co * 2 + dy) * 2 + dx];
+        }
+    }
+    if (b1)
+        for (int co = 0; co < cmid; ++co) ba[co] = b1[co] * scale[co];
+    for (int co = 0; co < cmid; ++co) ba[co] += shift[co];
 }
 
 // OpRecord::shape of a layer over the map x: "N<n>_<h>x<w>", then "_C<c>" per channel count given

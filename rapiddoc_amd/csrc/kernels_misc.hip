@@ -549,6 +549,7 @@ __global__ void __launch_bounds__(256) se_fc_kernel(SeFcParams p) {
         p.scale[(size_t)n * p.C + c] = rd_act(s, p.gate);
     }
 }
+bool se_fc_shape_ok(int c) { return c > 0 && c % 4 == 0 && c <= 512; }
 void launch_se_fc(const SeFcParams& p, hipStream_t s) {
     const int ks = std::max(1, std::min(8, 256 / (p.C >> 2)));
     const size_t sh = ((size_t)p.C + ((p.Cr + 3) & ~3) + (size_t)ks * p.C) * sizeof(float);

@@ -384,6 +384,8 @@ struct SeFcParams {
     float* scale;                      // [N][C]
     const int32_t* line_w = nullptr; int line_w_stride = 0; int H = 0;   // per-image pooling extent H x line_w[n * stride] instead of 1 / inv_hw
 };
+// the widths se_fc_kernel serves: float4 channel quads, a row of W1 in two 16-byte loads per lane (Builder::se_gate and rd_debug_se_chain ask here)
+bool se_fc_shape_ok(int c);
 void launch_se_fc(const SeFcParams& p, hipStream_t s);
 bool det_head_tail_supported(int cin, int cmid, int cout);
 void launch_det_head_tail(const float* x, int xld, int N, int H, int W, const float* w1, const float* b1, const float* w2, const float* b2,
