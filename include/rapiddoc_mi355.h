@@ -130,6 +130,26 @@ int rd_formula_encoder_forward(rd_handle* h, const float* x_nchw_dev, int B, int
  * *n_cols = number of leading columns the reference would return (it stops when every sequence has produced EOS). */
 int rd_formula_decode(rd_handle* h, const float* enc_dev, int B, int S, int max_new_tokens, int64_t* ids_dev, int32_t* n_cols,
                       void* stream);
+/* The same decode through refilled slots (model_kind "ppformulanet_head"): the N formulas of enc_dev [N,S,2048] run through `slots` decode
+ * rows; a row whose formula ends (EOS, or max_new_tokens reached) takes the next waiting formula on the device, inside the captured step, so
+ * no row waits for the longest formula of a batch.  Row i of ids_dev [N][max_new_tokens+1] is what rd_formula_decode writes for formula i
+ * in a batch of `slots` formulas: start token 0, the tokens, EOS 2, pad 1 behind it; lens_dev[i] = the columns that count, EOS included
+ * (max_new_tokens + 1 for a formula that reached the limit: it has no EOS).
+ * Limits: 1 <= slots <= RD_FORMULA_STREAM_MAX_SLOTS (the decode rows of the fused step kernels), N >= 1, and
+ * N * S <= RD_FORMULA_STREAM_MAX_TOKENS: every encoder token keeps its projection and its cross-attention K | V of every layer on the
+ * device for the whole call, 6 layers x 2 x 512 x 4 B + 512 x 4 B = 26 KiB per token, 1.6 GiB at the limit.  Outside the limits the call
+ * returns non-zero with a message in rd_last_error, launches nothing and leaves the outputs untouched.
+ * stats (host, may be NULL) is filled before the call returns; the call synchronises `stream`. */
+#define RD_FORMULA_STREAM_MAX_SLOTS 32
+#define RD_FORMULA_STREAM_MAX_TOKENS 65536
+typedef struct rd_formula_stream_stats {
+    int32_t steps;           /* step launches, the host loop's run-ahead included (it looks at the device state every 8 steps) */
+    int32_t live_slot_steps; /* slot-steps that produced a token = sum over the formulas of lens - 1 */
+    int32_t slots;
+    int32_t admitted;        /* formulas that were given a slot (= N) */
+} rd_formula_stream_stats;
+int rd_formula_decode_stream(rd_handle* h, const float* enc_dev, int N, int S, int max_new_tokens, int slots, int64_t* ids_dev,
+                             int32_t* lens_dev, rd_formula_stream_stats* stats, void* stream);
 /* largest max_new_tokens the loaded positional table supports (2560 for the shipped PP-FormulaNet_plus-M) */
 int rd_formula_max_new_tokens(rd_handle* h);
 

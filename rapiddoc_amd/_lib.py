@@ -30,6 +30,7 @@ SYMBOLS = {
     "rd_backbone_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p]),
     "rd_formula_encoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rd_formula_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "rd_formula_decode_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rd_formula_max_new_tokens": (C.c_int, [C.c_void_p]),
     "rd_preproc_resize_norm": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rd_preproc_resize_norm_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -92,6 +93,7 @@ DEBUG_SYMBOLS = {
     "rd_debug_table_decode": (_I, [_P, _P, _I, _I, _I, _P] + [_P] * 7),
     "rd_debug_table_encoder_taps": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "rd_debug_formula_decode": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(C.c_int32), _P, _P, _P]),
+    "rd_debug_formula_decode_stream": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I]),
     "rd_debug_resize_aa_coeffs": (_I, [_I, _I, _P, _P, C.c_int64]),
     "rd_debug_resample_coeffs": (_I, [_I, _I, C.c_double, C.c_double, _I, _P, _P, C.c_int64]),
     "rd_debug_time_mixer": (_F, [_I] * 4 + [_P] * 6),

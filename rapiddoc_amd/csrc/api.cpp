@@ -206,6 +206,15 @@ int rd_formula_decode(rd_handle* h, const float* enc, int B, int S, int max_new_
                                              nullptr);
     });
 }
+int rd_formula_decode_stream(rd_handle* h, const float* enc, int N, int S, int max_new_tokens, int slots, int64_t* ids, int32_t* lens,
+                             rd_formula_stream_stats* stats, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->kind == "ppformulanet_head" && h->dec, "handle is not a loaded ppformulanet_head model");
+        RD_CHECK(enc && ids && lens, "null input/output");
+        rd::formula_decoder_decode_stream(h->dec, enc, N, S, max_new_tokens, slots, reinterpret_cast<long long*>(ids), (int*)lens, stats,
+                                          (hipStream_t)stream, nullptr, nullptr, nullptr, 0);
+    });
+}
 int rd_formula_max_new_tokens(rd_handle* h) { return (h && h->dec) ? rd::formula_decoder_max_new(h->dec) : -1; }
 
 int rd_preproc_resize_norm(int device_id, const uint8_t* src, int H, int W, int OH, int OW, const float mean[3],

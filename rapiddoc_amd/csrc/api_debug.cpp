@@ -107,6 +107,22 @@ int rd_debug_formula_decode(rd_handle* h, const float* enc, int B, int S, int ma
     });
 }
 
+// developer entry: rd_formula_decode_stream plus optional traces written inside the step (graph replay included), indexed by what the slot
+// holds: trace_logits [N][max_new_tokens][V] and trace_hidden [N][max_new_tokens][512] by (formula, position), and trace_sched int32
+// [sched_steps][slots][2] = the (formula or -1, position) of every slot at the start of every step (steps past sched_steps are not recorded).
+// With all three null it enqueues exactly what rd_formula_decode_stream enqueues.
+int rd_debug_formula_decode_stream(rd_handle* h, const float* enc, int N, int S, int max_new_tokens, int slots, int64_t* ids, int32_t* lens,
+                                   rd_formula_stream_stats* stats, void* stream, float* trace_logits, float* trace_hidden, int32_t* trace_sched,
+                                   int sched_steps) {
+    return guarded(h, [&] {
+        RD_CHECK(h->kind == "ppformulanet_head" && h->dec, "handle is not a loaded ppformulanet_head model");
+        RD_CHECK(enc && ids && lens, "null input/output");
+        RD_CHECK(!trace_sched || sched_steps > 0, "trace_sched needs sched_steps > 0");
+        rd::formula_decoder_decode_stream(h->dec, enc, N, S, max_new_tokens, slots, reinterpret_cast<long long*>(ids), (int*)lens, stats,
+                                          (hipStream_t)stream, trace_logits, trace_hidden, (int*)trace_sched, sched_steps);
+    });
+}
+
 // developer entry (host only): the per-axis tables rd_preproc_resize_aa_norm uploads.  bounds_out int32 [out][2], kk_out int32 [out][ksize]
 // with kk_cap entries of room; returns ksize, or -1 on bad arguments / too little room.
 int rd_debug_resize_aa_coeffs(int in, int out, int32_t* bounds_out, int32_t* kk_out, int64_t kk_cap) {

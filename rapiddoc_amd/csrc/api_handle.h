@@ -13,6 +13,10 @@ FormulaDecoder* formula_decoder_create(int device, const void* blob, size_t nbyt
 void formula_decoder_destroy(FormulaDecoder* d);
 int formula_decoder_decode(FormulaDecoder* d, const float* enc, int B, int S, int max_new, long long* ids, hipStream_t s, float* trace_logits,
                            float* trace_hidden);
+// the decode through refilled slots (rd_formula_decode_stream); the traces (rd_debug_formula_decode_stream) may each be null
+void formula_decoder_decode_stream(FormulaDecoder* d, const float* enc, int N, int S, int max_new, int slots, long long* ids, int* lens,
+                                   rd_formula_stream_stats* stats, hipStream_t s, float* trace_logits, float* trace_hidden, int* trace_sched,
+                                   int sched_steps);
 int debug_dec_gemv(int M, int K, int N, int act, const float* x, const float* w, const float* bias, const float* ln_g, const float* ln_b,
                    const float* res, float* y);
 int debug_dec_attention(int route, int self, int B, int T, float* kc, float* vc, int ldkv, long long seq_stride, const float* x, const float* ln_g,

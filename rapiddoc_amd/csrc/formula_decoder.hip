@@ -433,6 +433,166 @@ __global__ void __launch_bounds__(SELF ? 768 : 256) dec_attn_fused2_kernel(AttnF
     if (tid < 32) p.out[(size_t)b * p.ldo + h * HD + tid] = (red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid]) * inv;
 }
 
+// rd_formula_decode_stream's form of dec_attn_fused2_kernel: row b is a decode SLOT with a state of its own - the formula it holds
+// (ss->src[b], -1 = idle: the workgroup returns at once) and that formula's position (ss->pos[b] = its cached length).  The self cache is the
+// slot's (rows 0 .. pos - 1 were all written by the formula that holds the slot now: a refilled slot starts at length 0 and never reads its
+// predecessor's rows), the cross K | V block is the formula's.  Everything else is dec_attn_fused2_kernel's code, statement for statement,
+// so a slot's row is a batch row bit for bit.  It is a copy and not a shared __device__ body on purpose: inlining the body into
+// dec_attn_fused2_kernel through a function changed that kernel's register allocation and schedule (docs/notebook/formula_stream.md s2),
+// and the batch path's kernels are to stay the code they were.
+static constexpr int MAX_SLOTS = 32;   // RD_FORMULA_STREAM_MAX_SLOTS
+struct StreamState {  // device-resident; written by one lane with plain stores, read by later launches (a kernel boundary in between)
+    int next;              // first formula not yet admitted
+    int n_live;            // slots that hold a formula
+    int steps;             // step launches so far
+    int live_slot_steps;   // slot-steps that produced a token
+    int src[MAX_SLOTS];    // formula of the slot, -1 = idle
+    int pos[MAX_SLOTS];    // tokens generated so far for that formula
+    int done[MAX_SLOTS];   // the select launch of this step ended the slot's formula (cleared by the admission launch)
+};
+template <bool SELF>
+__global__ void __launch_bounds__(SELF ? 768 : 256) dec_stream_attn_kernel(AttnFusedParams p, const StreamState* ss) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    extern __shared__ __attribute__((aligned(16))) float smf[];
+    float* xn = smf;                   // [512] normalised row
+    float* qs = smf + D;               // [32] q | [32] k | [32] v of this step
+    float* red = qs + 3 * HD;          // [256]
+    float* sc = red + 256;             // [T] scores
+    const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    static_assert(D == 512 && HD == 32, "two values per thread, eight float4 per head row");
+    const bool att = !SELF || tid < 256;                  // the 256 threads of LayerNorm and of the attention
+    const int t256 = SELF ? (tid & 255) : tid, pm = SELF ? (tid >> 8) : 0;       // projection: matrix pm, output o, part
+    const int o = t256 >> 3, part = t256 & 7;
+    // ---- requested first: this thread's weight row (its eighth of it), its first cached K row
+    const int row = pm * D + h * HD + o;
+    f4 wv[16];
+    {
+        const f4* wr = reinterpret_cast<const f4*>(p.w + (size_t)row * D);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) wv[i] = wr[8 * i + part];
+    }
+    const int src = ss->src[b];
+    if (src < 0) return;               // an idle slot (uniform over the block)
+    const int Tc = SELF ? ss->pos[b] : p.fixed_T;    // cached keys: the slot's own length
+    const int kvb = SELF ? b : src;    // the block of the K / V buffers this row reads (and, SELF, appends to)
+    const bool kpre = att && tid < Tc;
+    f4 k0[8];
+    {
+        const f4* kr = reinterpret_cast<const f4*>(p.kc + (size_t)kvb * p.seq_stride + (size_t)(kpre ? tid : 0) * p.ldkv + h * HD);
+#pragma unroll
+        for (int d = 0; d < 8; ++d) k0[d] = kr[d];       // (row 0 of the cache buffer exists for every step; unused when !kpre)
+    }
+    // ---- LayerNorm of row b (threads 0 .. 255)
+    {
+        float v0 = 0.f, v1 = 0.f;
+        if (att) { v0 = p.x[(size_t)b * D + tid]; v1 = p.x[(size_t)b * D + 256 + tid]; }
+        float s = wsum(v0 + v1);
+        if (att && lane == 0) red[wave] = s;
+        __syncthreads();
+        const float mean = (red[0] + red[1] + red[2] + red[3]) / D;
+        const float d0 = v0 - mean, d1 = v1 - mean;
+        float q = wsum(d0 * d0 + d1 * d1);
+        if (att && lane == 0) red[4 + wave] = q;
+        __syncthreads();
+        const float rstd = rsqrtf((red[4] + red[5] + red[6] + red[7]) / D + 1e-5f);
+        if (att) {
+            xn[tid] = d0 * rstd * p.ln_g[tid] + p.ln_b[tid];
+            xn[256 + tid] = d1 * rstd * p.ln_g[256 + tid] + p.ln_b[256 + tid];
+        }
+    }
+    __syncthreads();
+    // ---- this head's projections
+    {
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const f4 xr = reinterpret_cast<const f4*>(xn)[8 * i + part];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = fmaf(xr[e], wv[i][e], acc);
+        }
+        acc += __shfl_xor(acc, 1, 64);
+        acc += __shfl_xor(acc, 2, 64);
+        acc += __shfl_xor(acc, 4, 64);
+        if (part == 0) {
+            const float v = acc + p.bias[row];
+            qs[pm * HD + o] = v;
+            if (SELF && pm == 1) p.kw[(size_t)kvb * p.seq_stride + (size_t)Tc * p.ldkv + h * HD + o] = v;
+            if (SELF && pm == 2) p.vw[(size_t)kvb * p.seq_stride + (size_t)Tc * p.ldkv + h * HD + o] = v;
+        }
+    }
+    __syncthreads();
+    // ---- single-query attention (threads 0 .. 255; this step's k, v come from LDS)
+    const int T = Tc + (SELF ? 1 : 0);
+    f4 q[8];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) q[d] = reinterpret_cast<const f4*>(qs)[d];
+    auto krow = [&](int j) -> const float* { return (!SELF || j < Tc) ? p.kc + (size_t)kvb * p.seq_stride + (size_t)j * p.ldkv + h * HD : qs + HD; };
+    auto vrow = [&](int j) -> const float* { return (!SELF || j < Tc) ? p.vc + (size_t)kvb * p.seq_stride + (size_t)j * p.ldkv + h * HD : qs + 2 * HD; };
+    float mx = -INFINITY;
+    if (att) {
+        for (int j = tid; j < T; j += 256) {
+            f4 k[8];
+            if (j == tid && kpre) {
+#pragma unroll
+                for (int d = 0; d < 8; ++d) k[d] = k0[d];
+            } else {
+                const f4* kr = reinterpret_cast<const f4*>(krow(j));
+#pragma unroll
+                for (int d = 0; d < 8; ++d) k[d] = kr[d];
+            }
+            float s = 0.f;
+#pragma unroll
+            for (int d = 0; d < 8; ++d)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s = fmaf(q[d][e], k[d][e], s);
+            sc[j] = s;
+            mx = fmaxf(mx, s);
+        }
+    }
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o2, 64));
+    if (att && lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float sum = 0.f;
+    if (att) {
+        for (int j = tid; j < T; j += 256) {
+            const float e = __expf(sc[j] - mx);
+            sc[j] = e;
+            sum += e;
+        }
+    }
+    sum = wsum(sum);
+    __syncthreads();                       // (red[0..3] read by everybody; sc[] complete)
+    if (att && lane == 0) red[4 + wave] = sum;
+    __syncthreads();
+    const float inv = 1.f / (red[4] + red[5] + red[6] + red[7]);
+    // output: thread (g = tid / 8: one of 32 key groups, dq = tid % 8: dims 4 dq .. + 3), four rows in flight
+    const int dq = tid & 7, g = tid >> 3;
+    f4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (att) {
+        int j = g;
+        for (; j + 96 < T; j += 128) {
+            const f4 v0 = reinterpret_cast<const f4*>(vrow(j))[dq], v1 = reinterpret_cast<const f4*>(vrow(j + 32))[dq];
+            const f4 v2 = reinterpret_cast<const f4*>(vrow(j + 64))[dq], v3 = reinterpret_cast<const f4*>(vrow(j + 96))[dq];
+            acc += v0 * sc[j];
+            acc += v1 * sc[j + 32];
+            acc += v2 * sc[j + 64];
+            acc += v3 * sc[j + 96];
+        }
+        for (; j < T; j += 32) acc += reinterpret_cast<const f4*>(vrow(j))[dq] * sc[j];
+    }
+    __syncthreads();                       // red[] is reused below
+#pragma unroll
+    for (int o2 = 8; o2 < 64; o2 <<= 1) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] += __shfl_xor(acc[e], o2, 64);
+    }
+    if (att && lane < 8) *reinterpret_cast<f4*>(&red[wave * 32 + 4 * lane]) = acc;
+    __syncthreads();
+    if (tid < 32) p.out[(size_t)b * p.ldo + h * HD + tid] = (red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid]) * inv;
+}
+
 // Round 6: the decode step's linears (M = the decode batch, K = 512 / 2048) as weight-streaming GEMVs.  profiles/r4_formula_decode.txt: 25 of a
 // step's 39 launches were skinny2_gemm_kernel at 5 - 35 us each for 1 - 4 MB of weights (fc2: 4 MB in 15 us = 0.28 TB/s) - 32 workgroups of
 // four wavefronts, every wavefront four columns x two serial K passes.  The guide's price list puts a dependent kernel boundary at 1.2 - 1.9 us
@@ -707,6 +867,174 @@ __global__ void __launch_bounds__(1024) dec_select_kernel(const float* logits, i
         }
     }
 }
+// dec_select_kernel's argmax and embedding as functions, for the stream launches below (dec_select_kernel keeps its own text: see
+// dec_stream_attn_kernel).  argmax of the logits row z [V] over the 1024 threads of the block; the result is thread 0's
+__device__ __forceinline__ int dec_argmax_block(const float* z, int V) {
+    const int tid = threadIdx.x;
+    // numpy / torch argmax: a NaN counts as the greatest value, the lowest index among equals wins.  Every thread that owns an element starts
+    // on its FIRST one's index, so a row of nothing but -inf (nothing ever compares greater) still names a real column: the token is in [0, V).
+    auto above = [](float c, float a) { return c > a || (c != c && a == a); };
+    float mx = -INFINITY;
+    int mi = 0x7fffffff;            // (a thread without elements: loses every tie)
+    if ((V & 3) == 0 && V <= 65536) {
+        // 16-byte loads, every load of the thread requested before the first compare (the scalar loop below ran its 49 loads per
+        // thread through a compare-and-select chain: 18 us for 200 KB); indices still visited in increasing order per thread
+        constexpr int MAXQ = 16;                     // V <= 65536
+        const int nq = V >> 2;
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        f4 q[MAXQ];
+#pragma unroll
+        for (int it = 0; it < MAXQ; ++it) q[it] = *reinterpret_cast<const f4*>(z + 4 * (size_t)min(tid + 1024 * it, nq - 1));
+#pragma unroll
+        for (int it = 0; it < MAXQ; ++it) {
+            const int c0 = 4 * (tid + 1024 * it);
+            if (tid + 1024 * it < nq) {
+                if (it == 0) mi = c0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (above(q[it][e], mx)) { mx = q[it][e]; mi = c0 + e; }
+            }
+        }
+    } else {
+        if (tid < V) mi = tid;
+        for (int c = tid; c < V; c += 1024) {
+            const float v = z[c];
+            if (above(v, mx)) { mx = v; mi = c; }
+        }
+    }
+    // (value, index) pairs are totally ordered - larger value first, then smaller index - so any reduction tree gives the pair the ten-level
+    // LDS tree of rounds 1-5 gave: butterfly inside the wavefront, one exchange between the sixteen (round 6: two barriers instead of eleven)
+    __shared__ float smx[16];
+    __shared__ int smi[16];
+    auto better = [&](float c, int ic, float a, int ia) { return above(c, a) || ((c == a || (c != c && a != a)) && ic < ia); };
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float c = __shfl_xor(mx, o, 64);
+        const int ic = __shfl_xor(mi, o, 64);
+        if (better(c, ic, mx, mi)) { mx = c; mi = ic; }
+    }
+    if ((tid & 63) == 0) { smx[tid >> 6] = mx; smi[tid >> 6] = mi; }
+    __syncthreads();
+    if (tid == 0) {
+        float a = smx[0];
+        int ia = smi[0];
+        for (int w = 1; w < 16; ++w)
+            if (better(smx[w], smi[w], a, ia)) { a = smx[w]; ia = smi[w]; }
+        mi = ia;
+    }
+    return mi;
+}
+// x = LayerNorm(emb[tok] + pos[position]) by one wavefront: the input row of a decode step (dec_embed_ln_kernel's arithmetic)
+__device__ __forceinline__ void dec_embed_ln_row(const float* emb, const float* pos, const float* g, const float* b, long long tok, int position,
+                                                 int lane, float* x) {
+    float v[8];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = emb[(size_t)tok * D + c] + pos[(size_t)position * D + c];
+        s += v[i];
+    }
+    const float mean = wsum(s) / D;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) q += (v[i] - mean) * (v[i] - mean);
+    const float rstd = rsqrtf(wsum(q) / D + 1e-5f);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int c = lane + 64 * i;
+        x[c] = (v[i] - mean) * rstd * g[c] + b[c];
+    }
+}
+// ---- the step of rd_formula_decode_stream: the launches of a step that read per-row state (the linears in between are dec_gemv_route with
+// M = slots, unchanged: a row's sums never see another row, so an idle slot's row is computed, finite, and never looked at)
+// next token of every live slot: ids[src][pos + 1]; EOS (or the formula's last column) ends the formula: lens[src], done[slot]; otherwise the
+// position advances and the next step's input row is embedded.  Block `slot` is the only one that touches slot's words in this launch.
+__global__ void __launch_bounds__(1024) dec_stream_select_kernel(const float* logits, int V, long long* ids, int ids_ld, int* lens,
+                                                                 StreamState* ss, NextEmbed ne) {
+    const int slot = blockIdx.x, tid = threadIdx.x, src = ss->src[slot];
+    if (src < 0) return;                 // idle (uniform over the block)
+    const int t = ss->pos[slot];
+    const int ia = dec_argmax_block(logits + (size_t)slot * V, V);
+    __shared__ int s_tok;
+    if (tid == 0) {
+        int tok = ia;
+        if (t + 1 == FORCED_EOS_LEN - 1) tok = EOS_ID;          // per formula: its own input length
+        ids[(size_t)src * ids_ld + t + 1] = tok;
+        const bool end = tok == EOS_ID || t + 1 == ne.max_new;
+        if (end) {
+            lens[src] = t + 2;
+            ss->done[slot] = 1;
+        } else {
+            ss->pos[slot] = t + 1;
+        }
+        s_tok = end ? -1 : tok;
+    }
+    __syncthreads();
+    if (s_tok < 0) return;               // the admission launch behind this one writes the row of whatever takes the slot
+    if (tid < 64) dec_embed_ln_row(ne.emb, ne.pos, ne.g, ne.b, s_tok, t + 1 + 2, tid, ne.x + (size_t)slot * D);
+}
+// Admission, one workgroup, in the launch behind the select launch (the kernel boundary is what makes every select block's stores visible
+// here: blocks of one launch may sit on different XCDs, whose L2s are not coherent).  In slot order every finished slot takes the first
+// waiting formula - position 0, input row = the start token's (x0) - or goes idle: which slot a formula lands in follows from the lengths alone.
+__global__ void __launch_bounds__(256) dec_stream_admit_kernel(StreamState* ss, int N, int slots, const float* x0, float* x) {
+    __shared__ int reset[MAX_SLOTS];
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        int next = ss->next, n_live = ss->n_live, live = 0;
+        for (int s = 0; s < slots; ++s) {
+            reset[s] = 0;
+            if (ss->src[s] < 0) continue;
+            ++live;
+            if (!ss->done[s]) continue;
+            ss->done[s] = 0;
+            ss->pos[s] = 0;
+            reset[s] = 1;
+            if (next < N) {
+                ss->src[s] = next++;
+            } else {
+                ss->src[s] = -1;
+                --n_live;
+            }
+        }
+        ss->next = next;
+        ss->n_live = n_live;
+        ss->steps += 1;
+        ss->live_slot_steps += live;
+    }
+    __syncthreads();
+    for (int s = 0; s < slots; ++s)
+        if (reset[s]) {
+            x[(size_t)s * D + tid] = x0[tid];
+            x[(size_t)s * D + 256 + tid] = x0[256 + tid];
+        }
+}
+// Once per call: the state (formulas 0 .. min(N, slots) - 1 sit in the slots of their number), ids = start token | PAD, and the start token's
+// input row LayerNorm(emb[START] + pos[2]) into x0 and into every slot's row (block 0, one wavefront per row)
+__global__ void __launch_bounds__(256) dec_stream_init_kernel(StreamState* ss, long long* ids, int ids_ld, int N, int slots, NextEmbed ne, float* x0) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) { ss->next = min(N, slots); ss->n_live = min(N, slots); ss->steps = 0; ss->live_slot_steps = 0; }
+    if (i < MAX_SLOTS) { ss->src[i] = (i < slots && i < N) ? i : -1; ss->pos[i] = 0; ss->done[i] = 0; }
+    for (long long k = i; k < (long long)N * ids_ld; k += (long long)gridDim.x * blockDim.x) ids[k] = (k % ids_ld == 0) ? START_ID : PAD_ID;
+    if (blockIdx.x == 0)
+        for (int r = threadIdx.x >> 6; r <= slots; r += 4)
+            dec_embed_ln_row(ne.emb, ne.pos, ne.g, ne.b, START_ID, 2, threadIdx.x & 63, r < slots ? ne.x + (size_t)r * D : x0);
+}
+// developer traces (rd_debug_formula_decode_stream): row (src, pos) of dst [N][max_new][n] = row `slot` of src_rows [slots][n]
+__global__ void __launch_bounds__(256) dec_stream_trace_kernel(const float* src_rows, float* dst, int n, int max_new, const StreamState* ss) {
+    const int slot = blockIdx.x, src = ss->src[slot];
+    if (src < 0) return;
+    float* d = dst + ((size_t)src * max_new + ss->pos[slot]) * n;
+    const float* r = src_rows + (size_t)slot * n;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) d[i] = r[i];
+}
+// sched [sched_steps][slots][2] = (src, pos) of every slot at the start of step ss->steps
+__global__ void dec_stream_sched_kernel(const StreamState* ss, int* sched, int sched_steps, int slots) {
+    const int s = threadIdx.x, t = ss->steps;
+    if (s >= slots || t >= sched_steps) return;
+    sched[((size_t)t * slots + s) * 2] = ss->src[s];
+    sched[((size_t)t * slots + s) * 2 + 1] = ss->pos[s];
+}
 __global__ void dec_advance_kernel(DecState* st) { st->step += 1; }
 __global__ void dec_init_kernel(DecState* st, int* unfinished, long long* ids, int ids_ld, int B) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -728,11 +1056,15 @@ class FormulaDecoder {
     // trace_logits [max_new][B][V] / trace_hidden [max_new][B][512] (the row in front of ln_out), or null: developer traces of every step
     int decode(const float* enc, int B, int S, int max_new, long long* ids_out, hipStream_t s, float* trace_logits = nullptr,
                float* trace_hidden = nullptr);
+    // enc [N,S,2048] through `slots` refilled decode rows -> ids [N][max_new+1], lens [N] (device); stats (host) may be null.  Traces (each
+    // may be null): logits [N][max_new][V], hidden [N][max_new][512], sched int [sched_steps][slots][2]
+    void decode_stream(const float* enc, int N, int S, int max_new, int slots, long long* ids_out, int* lens_out, rd_formula_stream_stats* stats,
+                       hipStream_t s, float* trace_logits, float* trace_hidden, int* trace_sched, int sched_steps);
     int max_positions() const { return n_pos_ - 2; }
 
    private:
     void gemm(const float* x, int M, int K, const std::string& key, int N, float* y, int act, const float* res, hipStream_t s,
-              const std::string& ln_key = "", float* ln_tmp = nullptr);
+              const std::string& ln_key = "", float* ln_tmp = nullptr, bool allow_skinny = true);
     // the decode step's linears (M <= 32 rows, K = 512 / 2048) through dec_gemv_kernel; false = shape not covered, nothing launched
     bool gemv(const float* x, int M, int K, const std::string& key, int N, float* y, int act, const float* res, hipStream_t s,
               const std::string& ln_key = "");
@@ -826,7 +1158,7 @@ void FormulaDecoder::load(const WeightStore& ws) {
 // y = act(LN?(x) . W^T + b) (+ res).  With `ln_key` the pre-LayerNorm is fused into the small-M GEMM when it applies, otherwise
 // it runs as its own kernel through `ln_tmp`.
 void FormulaDecoder::gemm(const float* x, int M, int K, const std::string& key, int N, float* y, int act, const float* res, hipStream_t s,
-                          const std::string& ln_key, float* ln_tmp) {
+                          const std::string& ln_key, float* ln_tmp, bool allow_skinny) {
     ConvParams p{};
     p.xld = K; p.N = 1; p.H = 1; p.W = M; p.Cin = K;
     p.w = params_.ptr(key + "#w");
@@ -836,7 +1168,7 @@ void FormulaDecoder::gemm(const float* x, int M, int K, const std::string& key, 
     p.res = res; p.rld = N;
     p.act = act; p.out_mode = OUT_NHWC;
     p.M = M; p.K = K; p.Ng = N;
-    p.allow_skinny = 1;      // M is the decode batch
+    p.allow_skinny = allow_skinny ? 1 : 0;      // M is the decode batch (decode_stream: the route of a batch of `slots`, whatever M is)
     if (!ln_key.empty()) {
         p.ln_g = params_.ptr(ln_key + ".weight");
         p.ln_b = params_.ptr(ln_key + ".bias");
@@ -1112,6 +1444,159 @@ int FormulaDecoder::decode(const float* enc, int B, int S, int max_new, long lon
     return steps + 1;
 }
 
+static void launch_dec_stream_attn(const AttnFusedParams& p, const StreamState* ss, bool self, int slots, int keys, hipStream_t s) {
+    const size_t sh = (size_t)(D + 3 * HD + 256 + ((keys + 3) & ~3)) * sizeof(float);      // as launch_dec_attn_fused
+    if (self) hipLaunchKernelGGL((dec_stream_attn_kernel<true>), dim3(slots, HEADS), dim3(768), sh, s, p, ss);
+    else hipLaunchKernelGGL((dec_stream_attn_kernel<false>), dim3(slots, HEADS), dim3(256), sh, s, p, ss);
+}
+
+// rd_formula_decode_stream.  decode() above is batch-synchronous: the rows of a batch share one step counter and the loop runs until the
+// longest formula has ended, so on a page batch of mixed lengths most slot-steps compute PAD.  Here the step is the same launch sequence at
+// M = slots, but every row carries its own (formula, position) in device memory (StreamState) and a one-workgroup admission launch at the end
+// of the captured step hands a finished row the next waiting formula.  The host only replays the graph and looks at the state every 8 steps.
+void FormulaDecoder::decode_stream(const float* enc, int N, int S, int max_new, int slots, long long* ids_out, int* lens_out,
+                                   rd_formula_stream_stats* stats, hipStream_t s, float* trace_logits, float* trace_hidden, int* trace_sched,
+                                   int sched_steps) {
+    // refusals first: nothing is launched and the outputs stay as they are
+    RD_CHECK(slots >= 1 && slots <= MAX_SLOTS, "formula decode stream: slots must be 1 .. " + std::to_string(MAX_SLOTS) + ", got " + std::to_string(slots));
+    RD_CHECK(N >= 1 && S >= 1 && max_new >= 1, "formula decode stream: N, S and max_new_tokens must be at least 1");
+    RD_CHECK((long long)N * S <= RD_FORMULA_STREAM_MAX_TOKENS, "formula decode stream: N * S = " + std::to_string((long long)N * S) +
+                                                                   " encoder tokens exceed RD_FORMULA_STREAM_MAX_TOKENS (" +
+                                                                   std::to_string(RD_FORMULA_STREAM_MAX_TOKENS) + "): decode in windows");
+    RD_CHECK(max_new + 2 <= n_pos_, "formula decode stream: max_new_tokens exceeds the positional table of these weights");
+    RD_HIP(hipSetDevice(device_));
+    const int Tmax = max_new + 1, ids_ld = max_new + 1, M = slots;
+    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t f = sizeof(float);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    const size_t o_state = take(sizeof(StreamState));
+    const size_t o_encp = take((size_t)N * S * D * f);
+    const size_t o_ckv = take((size_t)n_layers_ * N * S * 2 * D * f);                        // [layer][N][S][2 D]
+    const size_t o_kc = take((size_t)n_layers_ * M * Tmax * D * f), o_vc = take((size_t)n_layers_ * M * Tmax * D * f);   // [layer][slots][Tmax][D]
+    const size_t o_x = take((size_t)M * D * f), o_x2 = take((size_t)M * D * f), o_x0 = take((size_t)D * f), o_h = take((size_t)M * D * f);
+    const size_t o_a = take((size_t)M * D * f), o_f = take((size_t)M * FFN * f), o_lg = take((size_t)M * vocab_ * f);
+    if (off > buf_bytes_) {
+        RD_HIP(hipStreamSynchronize(s));
+        if (buf_) RD_HIP(hipFree(buf_));
+        buf_ = nullptr;
+        buf_bytes_ = 0;
+        RD_HIP(hipMalloc((void**)&buf_, off));
+        buf_bytes_ = off;
+    }
+    StreamState* ss = reinterpret_cast<StreamState*>(buf_ + o_state);
+    float* encp = reinterpret_cast<float*>(buf_ + o_encp);
+    float* ckv = reinterpret_cast<float*>(buf_ + o_ckv);
+    float* kc = reinterpret_cast<float*>(buf_ + o_kc);
+    float* vc = reinterpret_cast<float*>(buf_ + o_vc);
+    float* x = reinterpret_cast<float*>(buf_ + o_x);
+    float* x2 = reinterpret_cast<float*>(buf_ + o_x2);
+    float* x0 = reinterpret_cast<float*>(buf_ + o_x0);
+    float* h = reinterpret_cast<float*>(buf_ + o_h);      // LayerNorm scratch of a linear that takes the GEMM route
+    float* a = reinterpret_cast<float*>(buf_ + o_a);
+    float* ff = reinterpret_cast<float*>(buf_ + o_f);
+    float* lg = reinterpret_cast<float*>(buf_ + o_lg);
+
+    const NextEmbed ne{params_.ptr("emb"), params_.ptr("pos"), params_.ptr("ln_emb.weight"), params_.ptr("ln_emb.bias"), x, max_new};
+    hipLaunchKernelGGL(dec_stream_init_kernel, dim3(64), dim3(256), 0, s, ss, ids_out, ids_ld, N, slots, ne, x0);
+    // once per call: the encoder projection and every layer's cross-attention K | V of all N formulas.  The large-M GEMMs go out in groups of
+    // `slots` formulas on the route decode() takes for a batch of `slots`, so a formula's K | V do not depend on N or on its place in the queue
+    const bool skinny = (long long)slots * S <= 32;
+    for (int g0 = 0; g0 < N; g0 += slots) {
+        const int rows = std::min(slots, N - g0) * S;
+        const float* enc_g = enc + (size_t)g0 * S * enc_dim_;
+        if (params_.has("encp#w")) {
+            gemm(enc_g, rows, enc_dim_, "encp", D, encp + (size_t)g0 * S * D, ACT_NONE, nullptr, s, "", nullptr, skinny);
+            enc_g = encp + (size_t)g0 * S * D;
+        }
+        for (int l = 0; l < n_layers_; ++l)
+            gemm(enc_g, rows, D, "l" + std::to_string(l) + ".ckv", 2 * D, ckv + ((size_t)l * N + g0) * S * 2 * D, ACT_NONE, nullptr, s, "", nullptr, skinny);
+    }
+    // a linear of the step, exactly as decode() routes it at B = slots: the weight-streaming GEMV where it covers the shape, the skinny GEMM otherwise
+    auto lin = [&](const float* xin, int K, const std::string& key, int Nn, float* y, int act, const float* res, const std::string& ln_key = "") {
+        if (!gemv(xin, M, K, key, Nn, y, act, res, s, ln_key)) gemm(xin, M, K, key, Nn, y, act, res, s, ln_key, h);
+    };
+    auto enqueue_step = [&]() {
+        if (trace_sched) hipLaunchKernelGGL(dec_stream_sched_kernel, dim3(1), dim3(64), 0, s, ss, trace_sched, sched_steps, slots);
+        float* cur = x;
+        float* nxt = x2;
+        for (int l = 0; l < n_layers_; ++l) {
+            const std::string K = "l" + std::to_string(l) + ".";
+            AttnFusedParams sp{};
+            sp.x = cur; sp.ln_g = params_.ptr(K + "ln1.weight"); sp.ln_b = params_.ptr(K + "ln1.bias");
+            sp.w = params_.ptr(K + "qkv#w"); sp.bias = params_.ptr(K + "qkv#b");
+            sp.kw = kc + (size_t)l * M * Tmax * D; sp.vw = vc + (size_t)l * M * Tmax * D;
+            sp.kc = sp.kw; sp.vc = sp.vw; sp.ldkv = D; sp.seq_stride = (long long)Tmax * D;
+            sp.fixed_T = 0; sp.out = a; sp.ldo = D;
+            launch_dec_stream_attn(sp, ss, true, slots, Tmax, s);
+            lin(a, D, K + "so", D, nxt, ACT_NONE, cur);
+            std::swap(cur, nxt);
+            AttnFusedParams xp{};
+            xp.x = cur; xp.ln_g = params_.ptr(K + "ln2.weight"); xp.ln_b = params_.ptr(K + "ln2.bias");
+            xp.w = params_.ptr(K + "cq#w"); xp.bias = params_.ptr(K + "cq#b");
+            xp.kc = ckv + (size_t)l * N * S * 2 * D; xp.vc = xp.kc + D; xp.ldkv = 2 * D; xp.seq_stride = (long long)S * 2 * D;
+            xp.fixed_T = S; xp.out = a; xp.ldo = D;
+            launch_dec_stream_attn(xp, ss, false, slots, S, s);
+            lin(a, D, K + "co", D, nxt, ACT_NONE, cur);
+            std::swap(cur, nxt);
+            lin(cur, D, K + "fc1", FFN, ff, ACT_GELU, nullptr, K + "ln3");
+            lin(ff, FFN, K + "fc2", D, nxt, ACT_NONE, cur);
+            std::swap(cur, nxt);
+        }
+        if (trace_hidden) hipLaunchKernelGGL(dec_stream_trace_kernel, dim3(slots, 2), dim3(256), 0, s, cur, trace_hidden, D, max_new, ss);
+        lin(cur, D, "lm", vocab_, lg, ACT_NONE, nullptr, "ln_out");
+        if (trace_logits) hipLaunchKernelGGL(dec_stream_trace_kernel, dim3(slots, 16), dim3(256), 0, s, lg, trace_logits, vocab_, max_new, ss);
+        hipLaunchKernelGGL(dec_stream_select_kernel, dim3(slots), dim3(1024), 0, s, lg, vocab_, ids_out, ids_ld, lens_out, ss, ne);
+        hipLaunchKernelGGL(dec_stream_admit_kernel, dim3(1), dim3(256), 0, s, ss, N, slots, x0, x);
+    };
+    RD_CHECK(n_layers_ % 2 == 0 /* three buffer swaps per layer */, "formula decode stream: the layer stack must end in the buffer the next embedding is written to");
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t gexec = nullptr;
+    static const bool use_graph = !rd_env_off("RD_DECODE_GRAPH");
+    if (use_graph) {      // one stream, no parallel branches
+        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            bool ok = true;
+            try {
+                enqueue_step();
+            } catch (...) {
+                ok = false;
+            }
+            if (hipStreamEndCapture(s, &graph) != hipSuccess || !ok || hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess) {
+                if (graph) (void)hipGraphDestroy(graph);
+                graph = nullptr;
+                gexec = nullptr;
+                (void)hipGetLastError();
+            }
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    // every live slot advances by one token per step and a formula ends after max_new at the latest: N * max_new steps would decode the
+    // formulas one after the other in a single slot
+    const long long cap = (long long)N * max_new + 8;
+    StreamState hs{};
+    hipError_t err = hipSuccess;
+    bool ended = false;
+    for (long long t = 0; t < cap && err == hipSuccess && !ended; ++t) {
+        if (gexec) err = hipGraphLaunch(gexec, s);
+        else enqueue_step();
+        if (err == hipSuccess && (t & 7) == 7) {        // one small D2H + sync every 8 steps
+            err = hipMemcpyAsync(&hs, ss, sizeof(StreamState), hipMemcpyDeviceToHost, s);
+            if (err == hipSuccess) err = hipStreamSynchronize(s);
+            ended = hs.next >= N && hs.n_live == 0;
+        }
+    }
+    if (gexec) {
+        (void)hipStreamSynchronize(s);
+        (void)hipGraphExecDestroy(gexec);
+        (void)hipGraphDestroy(graph);
+    }
+    RD_HIP(err);
+    RD_HIP(hipGetLastError());
+    RD_CHECK(ended, "formula decode stream: the device state never reported the end of the queue");
+    if (stats) *stats = rd_formula_stream_stats{hs.steps, hs.live_slot_steps, slots, hs.next};
+}
+
 // ---- C++ side of the C-ABI handle (api.cpp) -----------------------------------------------------------------------
 FormulaDecoder* formula_decoder_create(int device, const void* blob, size_t nbytes) {
     RD_HIP(hipSetDevice(device));
@@ -1130,6 +1615,11 @@ void formula_decoder_destroy(FormulaDecoder* d) { delete d; }
 int formula_decoder_decode(FormulaDecoder* d, const float* enc, int B, int S, int max_new, long long* ids, hipStream_t s, float* trace_logits,
                            float* trace_hidden) {
     return d->decode(enc, B, S, max_new, ids, s, trace_logits, trace_hidden);
+}
+void formula_decoder_decode_stream(FormulaDecoder* d, const float* enc, int N, int S, int max_new, int slots, long long* ids, int* lens,
+                                   rd_formula_stream_stats* stats, hipStream_t s, float* trace_logits, float* trace_hidden, int* trace_sched,
+                                   int sched_steps) {
+    d->decode_stream(enc, N, S, max_new, slots, ids, lens, stats, s, trace_logits, trace_hidden, trace_sched, sched_steps);
 }
 int formula_decoder_max_new(FormulaDecoder* d) { return d->max_positions(); }
 

@@ -20,6 +20,15 @@ DET_NECK_CHANNELS = {"ppocrv5_det_server": 256, "ppocrv5_det_mobile": 96}
 DET_NECK_CHANNELS_V3_MOBILE = {"ppocrv3_det_mobile": 96}    # the PP-OCRv3 multilingual detector: the same RSEFPN
 CLS_WANT_AUX = 1            # ppocr_cls_mobile: also hand out [B, 2 logits | 200 pooled features]
 CLS_FEATURES = 200          # channels of the classifier's pooled features (conv2 of MobileNetV3 small scale 0.35)
+FORMULA_STREAM_MAX_TOKENS = 65536      # RD_FORMULA_STREAM_MAX_TOKENS: N * S of one rd_formula_decode_stream call
+FORMULA_STREAM_MAX_SLOTS = 32          # RD_FORMULA_STREAM_MAX_SLOTS
+
+
+class FormulaStreamStats(C.Structure):
+    """rd_formula_stream_stats (include/rapiddoc_mi355.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("steps", "live_slot_steps", "slots", "admitted")]
+
+
 KINDS = ("ppocrv6_det", "ppocrv5_det_server", "ppocrv5_det_mobile", "ppocrv3_det_mobile", "ppocr_cls_mobile", "unitable_encoder", "unitable_decoder", "ppocrv6_rec", "ppocrv5_rec_server", "ppocrv5_rec_mobile", "ppocr_rec_mv1e", "pphgnetv2_b4", "pphgnetv2_b6_formula", "ppformulanet_head")
 
 
@@ -474,6 +483,29 @@ class RdEngine:
         n = C.c_int32(0)
         self._chk(self._l.rd_formula_decode(self._h, enc.data_ptr(), B, S, max_new_tokens, ids.data_ptr(), C.byref(n), _stream_ptr()))
         return ids[:, : n.value]
+
+    def formula_decode_stream(self, enc: torch.Tensor, max_new_tokens: int, slots: int = 16, trace: Optional[dict] = None):
+        """enc [N,S,2048] -> (ids [N, max_new_tokens + 1] int64, lens [N] int32, stats): the N formulas run through `slots` decode rows,
+        a row whose formula ends takes the next one (rd_formula_decode_stream).  Row i is what `formula_decode` gives formula i - start
+        token, tokens, EOS, PAD behind it - and lens[i] the columns that count.  N * S may be at most FORMULA_STREAM_MAX_TOKENS.
+        `trace` (developer, rd_debug_formula_decode_stream): a dict with any of "logits" [N, max_new, V], "hidden" [N, max_new, 512]
+        (float32) and "sched" [max_steps, slots, 2] (int32) device tensors, written inside the step."""
+        enc = self._prep(enc)
+        N, S, _ = enc.shape
+        ids = torch.empty((N, max_new_tokens + 1), dtype=torch.int64, device=enc.device)
+        lens = torch.empty((N,), dtype=torch.int32, device=enc.device)
+        st = FormulaStreamStats()
+        if trace is None:
+            rc = self._l.rd_formula_decode_stream(self._h, enc.data_ptr(), N, S, max_new_tokens, slots, ids.data_ptr(), lens.data_ptr(),
+                                                  C.byref(st), _stream_ptr())
+        else:
+            ptr = lambda k: trace[k].data_ptr() if trace.get(k) is not None else None
+            sched = trace.get("sched")
+            rc = self._l.rd_debug_formula_decode_stream(self._h, enc.data_ptr(), N, S, max_new_tokens, slots, ids.data_ptr(), lens.data_ptr(),
+                                                        C.byref(st), _stream_ptr(), ptr("logits"), ptr("hidden"), ptr("sched"),
+                                                        int(sched.shape[0]) if sched is not None else 0)
+        self._chk(rc)
+        return ids, lens, {"steps": st.steps, "live_slot_steps": st.live_slot_steps, "slots": st.slots, "admitted": st.admitted}
 
     @property
     def formula_max_new_tokens(self) -> int:

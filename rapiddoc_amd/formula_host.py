@@ -128,10 +128,16 @@ class FormulaRecognizer:
     def __init__(self, weights, device: int = 0, max_new_tokens: Optional[int] = None,
                  token_decoder: Optional[Callable[[List[int]], str]] = None,
                  bpe_decode: Optional[Callable[[List[int]], str]] = None,
-                 fix_text: Optional[Callable[[str], str]] = None, tokenizer_json=None):
+                 fix_text: Optional[Callable[[str], str]] = None, tokenizer_json=None, batching: str = "chunk", slots: int = 16):
+        """`batching`: "chunk" decodes every chunk of `batch_size` formulas as one batch, which runs until its longest formula has ended;
+        "stream" encodes the chunks, then decodes all formulas through `slots` decode rows that take the next waiting formula as soon as
+        theirs ends (`RdEngine.formula_decode_stream`).  Both return the same strings in the caller's order."""
         import torch  # noqa: F401  (device memory + stream only)
         from . import weights as W
         from .engine import RdEngine
+        if batching not in ("chunk", "stream"):
+            raise ValueError("batching must be 'chunk' or 'stream'")
+        self.batching, self.slots = batching, int(slots)
         if isinstance(weights, (str, bytes)):
             blob = weights if isinstance(weights, bytes) else open(weights, "rb").read()
             state = W.strip_model_prefix(W.from_safetensors_bytes(blob))
@@ -173,6 +179,9 @@ class FormulaRecognizer:
                 if inputs[i] is None:
                     routes[i] = "empty"
         valid = [i for i, x in enumerate(inputs) if x is not None]
+        if self.batching == "stream":
+            self._predict_stream(valid, inputs, routes, results, batch_size)
+            valid = []
         for beg in range(0, len(valid), batch_size):
             chunk = valid[beg: beg + batch_size]
             dev_rows = [k for k, i in enumerate(chunk) if routes[i] == "device"]
@@ -198,3 +207,48 @@ class FormulaRecognizer:
                 results[i] = self.token_decoder(toks) if self.token_decoder else toks
         self.last_routes = routes
         return [r if r is not None else ([] if self.token_decoder is None else "") for r in results]
+
+    def _predict_stream(self, valid: list, inputs: list, routes: list, results: list, batch_size: int) -> None:
+        """batching="stream": pre-process and encode the valid crops in chunks of `batch_size` (the chunk path's routes), decode every
+        window of formulas that fits the token limit with one `formula_decode_stream`, cut the rows by `lens`."""
+        import torch
+        from .engine import FORMULA_STREAM_MAX_TOKENS, formula_preprocess
+        encs = []
+        for beg in range(0, len(valid), batch_size):
+            chunk = valid[beg: beg + batch_size]
+            dev_rows = [k for k, i in enumerate(chunk) if routes[i] == "device"]
+            x = torch.empty((len(chunk), 1) + tuple(INPUT_SIZE), dtype=torch.float32, device=torch.device("cuda", self.encoder.device))
+            if dev_rows:
+                xd, got = formula_preprocess([inputs[chunk[k]] for k in dev_rows])
+                x[dev_rows] = xd
+                for k, r in zip(dev_rows, got):
+                    routes[chunk[k]] = r
+            host_rows = [k for k in range(len(chunk)) if k not in dev_rows]
+            if host_rows:
+                x[host_rows] = torch.from_numpy(np.concatenate([inputs[chunk[k]] for k in host_rows], axis=0)).to(x.device)
+            encs.append(self.encoder.formula_encoder_forward(x))
+        if not encs:
+            self.last_stream_stats = []
+            return
+        enc = torch.cat(encs, dim=0)                                      # [n, S, 2048]
+        self.last_stream_stats = []
+        for beg, end in stream_windows(enc.shape[0], enc.shape[1], FORMULA_STREAM_MAX_TOKENS):
+            ids, lens, stats = self.decoder.formula_decode_stream(enc[beg:end], self.max_new_tokens, self.slots)
+            self.last_stream_stats.append(stats)
+            ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
+            for row, n, i in zip(ids, lens, valid[beg:end]):
+                toks = row[1:int(n)].tolist()
+                if toks and toks[-1] == 2:
+                    toks = toks[:-1]                      # UniMERNetDecode cuts at EOS (post_process.py:277-296)
+                results[i] = self.token_decoder(toks) if self.token_decoder else toks
+
+
+def stream_windows(n: int, S: int, max_tokens: int) -> list:
+    """(begin, end) windows over n formulas of S encoder tokens each: as many formulas per `formula_decode_stream` call as its token limit
+    takes (N * S <= max_tokens).  One formula alone must fit."""
+    if n <= 0:
+        return []
+    per = max_tokens // S
+    if per < 1:
+        raise ValueError(f"one formula has {S} encoder tokens, the stream decode takes {max_tokens} per call")
+    return [(b, min(n, b + per)) for b in range(0, n, per)]
