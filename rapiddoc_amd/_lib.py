@@ -102,6 +102,7 @@ DEBUG_SYMBOLS = {
     "rd_debug_seqconv": (_F, [_I] * 8 + [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
     "rd_debug_det_local": (_F, [_I] * 5 + [_P] * 5 + [_F, _P, C.POINTER(C.c_int)]),
     "rd_debug_conv_route": (_I, [_I] * 17 + [_P, _I]),
+    "rd_debug_conv_ex": (_F, [_I] * 22 + [_P] * 10 + [C.c_char_p, _P, _I, _P]),
     "rd_debug_conv": (_F, [_I] * 14 + [_P] * 8),
     "rd_debug_stem34": (_F, [_I] * 11 + [_P] * 7),
     "rd_debug_dwconv_ex": (_F, [_I] * 17 + [_P] * 10 + [_I]),

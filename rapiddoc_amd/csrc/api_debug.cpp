@@ -377,55 +377,179 @@ int rd_debug_conv_route(int N, int H, int W, int Cin, int Cout, int KH, int KW, 
     return debug_conv_code(r);
 }
 
-// developer entry: one dense convolution on prepared operands (x NHWC fp32 [N][H][W][Cin]; w folded [Cout][K], k = (kh*KW+kw)*Cin+ci;
-// wh / wl its fp16 split with rows padded to Kp = ceil32(K), or null for the fp32 MFMA kernels; y NHWC [N][OH][OW][Cout]).
-// Returns ms per launch (iters timed launches after one untimed).  *used_direct: in = 1 forces the direct k x k kernel when it
+// a host array as a fresh device buffer (freed by the entry that made it)
+static bool debug_upload(const void* src, size_t bytes, void** dev) {
+    if (hipMalloc(dev, bytes) != hipSuccess) return false;
+    return hipMemcpy(*dev, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// `force` of rd_debug_conv_ex: the staged tile of that name in the precision asked for
+static bool debug_conv_tile(const char* force, int split, rd::ConvRoute* r) {
+    static const rd::ConvRoute h3[] = {rd::CONV_H3_256x128, rd::CONV_H3_128x96, rd::CONV_H3_256x64, rd::CONV_H3_128x32, rd::CONV_H3_128x64};
+    static const rd::ConvRoute f32[] = {rd::CONV_F32_128x32, rd::CONV_F32_128x64, rd::CONV_F32_128x96, rd::CONV_F32_128x128};
+    const rd::ConvRoute* t = split ? h3 : f32;
+    for (int i = 0, n = split ? 5 : 4; i < n; ++i)
+        if (std::strcmp(force, rd::conv_route_name(t[i])) == 0) { *r = t[i]; return true; }
+    return false;
+}
+
+// what rd_debug_conv hands to the body it shares with rd_debug_conv_ex: the caller's own split planes instead of the ones prepared here, and
+// its route code (*used_direct on entry: 1 the direct k x k kernel, 2 the streaming one, 4 the 9x9 one, where they support the geometry)
+struct DebugConvOld {
+    const void* wh; const void* wl;
+    int code;
+};
+
+// the body of rd_debug_conv_ex (its comment says what the arguments mean); *route_out receives the route launched
+static float debug_conv_run(int N, int H, int W, int Cin, int Cout, int KH, int KW, int SH, int SW, int PT, int PL, int PB, int PR, int act, int xld,
+                            int yld, int rld, int out_mode, int split, int images, int allow_skinny, int iters, float* x, float* w, float* bias,
+                            float* res, float* y, const float* dscale, const float* dshift, const float* ln_g, const float* ln_b, const float* ascale,
+                            const char* force, const DebugConvOld* old, rd::ConvRoute* route_out, int* range_out) {
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || SH <= 0 || SW <= 0 || PT < 0 || PL < 0 || PB < 0 || PR < 0) return -1.f;
+    if (!x || !w || !y || H + PT + PB < KH || W + PL + PR < KW) return -1.f;
+    if (Cin % 4 != 0 || xld % 4 != 0 || xld < Cin || yld < Cout || (res && rld < Cout)) return -1.f;     // (Cin % 4: as Builder::conv)
+    const bool deconv = out_mode == rd::OUT_DECONV2X2;
+    if (out_mode != rd::OUT_NHWC && !deconv) return -1.f;
+    if (deconv && (res || KH != 1 || KW != 1 || SH != 1 || SW != 1 || PT || PL || PB || PR)) return -1.f;
+    if ((ln_g != nullptr) != (ln_b != nullptr)) return -1.f;
+    rd::ConvParams p{};
+    p.x = x; p.xld = xld; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.w = w; p.bias = bias; p.y = y; p.yld = yld;
+    p.OH = rd::out_dim(H, KH, SH, PT, PB); p.OW = rd::out_dim(W, KW, SW, PL, PR); p.Cout = Cout;
+    p.KH = KH; p.KW = KW; p.SH = SH; p.SW = SW; p.PT = PT; p.PL = PL; p.act = act; p.out_mode = out_mode;
+    p.res = res; p.rld = rld; p.ascale = ascale; p.ln_g = ln_g; p.ln_b = ln_b; p.allow_skinny = allow_skinny;
+    p.M = N * p.OH * p.OW; p.K = KH * KW * Cin; p.Ng = deconv ? 4 * Cout : Cout;
+    std::vector<void*> owned;                  // device buffers of this call
+    unsigned* flag = nullptr;
+    auto done = [&](float ms) {
+        (void)hipDeviceSynchronize();
+        if (flag) {
+            if (range_out) *range_out = (int)*flag;
+            (void)hipHostFree(flag);
+        }
+        for (void* b : owned) (void)hipFree(b);
+        return ms;
+    };
+    auto upload = [&](const auto& v, void** dev) {
+        const bool ok = debug_upload(v.data(), v.size() * sizeof(v[0]), dev);
+        if (*dev) owned.push_back(*dev);
+        return ok;
+    };
+    // the weights as the engine holds them: [Ng][K] on the host for the images, the deconvolution's repacked from its checkpoint layout
+    const bool want_images = split && !(old && old->wh);
+    std::vector<float> hw;
+    if (deconv) {
+        std::vector<float> ck((size_t)Cin * Cout * 4), hb(Cout), sc(Cout, 1.f), sh(Cout, 0.f), bf;
+        if (hipMemcpy(ck.data(), w, ck.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(-1.f);
+        if (bias && hipMemcpy(hb.data(), bias, hb.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(-1.f);
+        if (dscale && hipMemcpy(sc.data(), dscale, sc.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(-1.f);
+        if (dshift && hipMemcpy(sh.data(), dshift, sh.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(-1.f);
+        rd::pack_deconv2x2(ck.data(), bias ? hb.data() : nullptr, Cin, Cout, sc.data(), sh.data(), hw, bf);
+        void *dw = nullptr, *db = nullptr;
+        if (!upload(hw, &dw) || !upload(bf, &db)) return done(-1.f);
+        p.w = (const float*)dw; p.bias = (const float*)db;
+    } else if (want_images || (split && old && (images & 12))) {
+        hw.resize((size_t)p.Ng * p.K);
+        if (hipMemcpy(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(-1.f);
+    }
+    if (split) {
+        if (old && old->wh) {
+            p.wh = (const uint16_t*)old->wh; p.wl = (const uint16_t*)old->wl;
+        } else {
+            if (!rd::fits_fp16_range(hw)) return done(-1.f);
+            std::vector<uint16_t> hi, lo;
+            rd::split_weights_h3(hw.data(), p.Ng, p.K, hi, lo);
+            void *dh = nullptr, *dl = nullptr;
+            if (!upload(hi, &dh) || !upload(lo, &dl)) return done(-1.f);
+            p.wh = (const uint16_t*)dh; p.wl = (const uint16_t*)dl;
+        }
+        // the one-accumulator images, prepared the way the engine prepares them for the layers that get one
+        std::vector<uint16_t> img;
+        void* d = nullptr;
+        if ((images & 2) && !deconv && rd::gemm_h1_shape_ok(p.K, p.Ng)) {
+            p.w1_inv = rd::prepare_gemm_h1_weights(hw.data(), p.Ng, p.K, img);
+            if (!upload(img, &d)) return done(-1.f);
+            p.w1 = (const uint16_t*)d;
+        }
+        if ((images & 4) && !deconv && rd::conv3x3_h1_shape_ok(KH, KW, Cin, Cout)) {
+            p.w3_inv = rd::prepare_conv3x3_h1_weights(hw.data(), Cout, Cin, img);
+            d = nullptr;
+            if (!upload(img, &d)) return done(-1.f);
+            p.w3 = (const uint16_t*)d;
+        }
+        if ((images & 8) && !deconv && rd::conv9x9_h1_shape_ok(KH, KW, Cin, Cout)) {
+            p.w9_inv = rd::prepare_conv9x9_h1_weights(hw.data(), Cout, Cin, img);
+            d = nullptr;
+            if (!upload(img, &d)) return done(-1.f);
+            p.w9 = (const uint16_t*)d;
+        }
+        if (range_out) {
+            if (hipHostMalloc((void**)&flag, sizeof(unsigned), hipHostMallocMapped) != hipSuccess) { flag = nullptr; return done(-1.f); }
+            *flag = 0;
+            p.range_flag = flag;
+        }
+    } else if (range_out) {
+        *range_out = 0;
+    }
+    rd::ConvRoute route = split ? rd::conv_split_route(p, ascale != nullptr) : rd::conv_f32_route(p);
+    if (force) {
+        // the staged tiles take any geometry below their 32-bit offsets (the rule of conv_split_route)
+        if (!debug_conv_tile(force, split, &route)) return done(-1.f);
+        if (split && ((unsigned long long)N * H * W * (unsigned long long)xld >= (1ull << 32) ||
+                      (unsigned long long)p.Ng * (unsigned long long)((p.K + 31) & ~31) >= (1ull << 32)))
+            return done(-1.f);
+    }
+    if (old && split && old->code == 2 && rd::conv_stream_h3_supported(p)) route = rd::CONV_STREAM;
+    else if (old && split && old->code == 1 && rd::conv_direct_h3_supported(p)) route = rd::CONV_DIRECT;
+    if (ln_g && route != rd::CONV_SKINNY) return done(-1.f);        // every other route would drop the LayerNorm
+    if (route_out) *route_out = route;
+    float ms = -2.f;
+    try {
+        ms = rd_debug_time(iters, [&] { rd::launch_conv_route(route, p, nullptr); });
+    } catch (const std::exception&) {
+        ms = -2.f;
+    }
+    return done(ms);
+}
+
+// developer entry: one dense convolution through launch_conv_route on operands prepared the way the engine prepares them, with every field
+// of ConvParams the builder sets open to the caller.  x NHWC fp32 [N][H][W][xld >= Cin]; w folded [Cout][K], k = (kh * KW + kw) * Cin + ci;
+// bias [Cout] or null; res [N][OH][OW][rld >= Cout] or null; y [N][OH][OW][yld >= Cout] with OH / OW from out_dim.  out_mode = OUT_DECONV2X2
+// (1 x 1 geometry, no res): w is the checkpoint's [Cin][Cout][2][2], bias its [Cout] or null, dscale / dshift [Cout] (device, or null: 1 / 0)
+// the channel affine of a folded BatchNorm - repacked here by pack_deconv2x2 as Builder::deconv2x2 does - and y is [N][2 H][2 W][yld].
+// split = 1: the split-fp16 path, the (hi, lo) planes made here by split_weights_h3; 0: the fp32 MFMA path.  images (split only): bit 1 the
+// one-accumulator GEMM image, bit 2 the 3x3 image, bit 3 the 9x9 image, each for the layers that get one in the engine (the bits of
+// rd_debug_conv_route).  ln_g / ln_b [K] (the skinny route's fused LayerNorm) or null.  force: null = the natural route (conv_split_route /
+// conv_f32_route), else the name of a staged tile of the precision ("256x128", "128x96", "256x64", "128x32", "128x64" split; "128x32" ..
+// "128x128" fp32).  name[name_len] receives conv_route_name of the route launched, *range_out (optional) the range flag (0 on the fp32 path).
+// Returns ms per launch (iters timed launches after one untimed); -1 with nothing launched: Cin % 4 or xld % 4 != 0, a view narrower than its
+// channels, res or a geometry other than 1 x 1 with OUT_DECONV2X2, ln_g on a route that is not "skinny", a `force` that names no tile of the
+// precision; -2: the launcher threw (a non-null ascale: no kernel applies it).
+float rd_debug_conv_ex(int N, int H, int W, int Cin, int Cout, int KH, int KW, int SH, int SW, int PT, int PL, int PB, int PR, int act, int xld, int yld,
+                       int rld, int out_mode, int split, int images, int allow_skinny, int iters, float* x, float* w, float* bias, float* res, float* y,
+                       const float* dscale, const float* dshift, const float* ln_g, const float* ln_b, const float* ascale, const char* force,
+                       char* name, int name_len, int* range_out) {
+    rd::ConvRoute route = rd::CONV_F32_128x128;
+    debug_copy_name("", name, name_len);
+    const float ms = debug_conv_run(N, H, W, Cin, Cout, KH, KW, SH, SW, PT, PL, PB, PR, act, xld, yld, rld, out_mode, split, images, allow_skinny, iters,
+                                    x, w, bias, res, y, dscale, dshift, ln_g, ln_b, ascale, force, nullptr, &route, range_out);
+    if (ms != -1.f) debug_copy_name(rd::conv_route_name(route), name, name_len);
+    return ms;
+}
+
+// developer entry: rd_debug_conv_ex's convolution on dense maps (xld = Cin, yld = rld = Cout) with one stride S, NHWC output, no range flag,
+// and the CALLER's split planes wh / wl (rows padded to Kp = ceil32(K)), or null for the fp32 MFMA kernels.  The one-accumulator 3x3 image is
+// prepared when *used_direct is 0 or absent, the 9x9 image when it is 4.  *used_direct: in = 1 forces the direct k x k kernel when it
 // supports the geometry, in = 2 the small-K streaming kernel, in = 4 the direct 9x9 kernel (kernels_conv9x9_h1.hip; in = 0 leaves a 9x9 layer
 // on the generic k x k implicit GEMM it displaces); out = 1 / 2 / 4 when the direct / streaming / 9x9 kernel ran (3: the one-accumulator 3x3).
+// Returns ms per launch (iters timed launches after one untimed).
 float rd_debug_conv(int N, int H, int W, int Cin, int Cout, int KH, int KW, int S, int PT, int PL, int PB, int PR, int act, int iters,
                     float* x, float* w, void* wh, void* wl, float* bias, float* res, float* y, int* used_direct) {
-    rd::ConvParams p{};
-    p.x = x; p.xld = Cin; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.w = w; p.bias = bias; p.y = y; p.yld = Cout;
-    p.wh = (const uint16_t*)wh; p.wl = (const uint16_t*)wl;
-    p.OH = (H + PT + PB - KH) / S + 1; p.OW = (W + PL + PR - KW) / S + 1; p.Cout = Cout;
-    p.KH = KH; p.KW = KW; p.SH = p.SW = S; p.PT = PT; p.PL = PL; p.act = act; p.out_mode = rd::OUT_NHWC;
-    p.res = res; p.rld = Cout;
-    p.M = N * p.OH * p.OW; p.K = KH * KW * Cin; p.Ng = Cout;
-    // the one-accumulator 3x3 kernel needs its own weight image, prepared here the way the engine prepares it (RD_CONV3X3_H1=0 or
-    // *used_direct = 1 / 2 on entry: the older kernels).  Reported as *used_direct = 3.
-    void* img3 = nullptr;
-    if (wh && !(used_direct && *used_direct) && rd::conv3x3_h1_shape_ok(KH, KW, Cin, Cout)) {
-        std::vector<float> hw((size_t)Cout * p.K);
-        if (hipMemcpy(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
-            std::vector<uint16_t> img;
-            const float inv = rd::prepare_conv3x3_h1_weights(hw.data(), Cout, Cin, img);
-            if (hipMalloc(&img3, img.size() * 2) == hipSuccess) {
-                (void)hipMemcpy(img3, img.data(), img.size() * 2, hipMemcpyHostToDevice);
-                p.w3 = (const uint16_t*)img3;
-                p.w3_inv = inv;
-            }
-        }
-    }
-    void* img9 = nullptr;
-    if (wh && used_direct && *used_direct == 4 && rd::conv9x9_h1_shape_ok(KH, KW, Cin, Cout)) {
-        std::vector<float> hw((size_t)Cout * p.K);
-        if (hipMemcpy(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
-            std::vector<uint16_t> img;
-            const float inv = rd::prepare_conv9x9_h1_weights(hw.data(), Cout, Cin, img);
-            if (hipMalloc(&img9, img.size() * 2) == hipSuccess) {
-                (void)hipMemcpy(img9, img.data(), img.size() * 2, hipMemcpyHostToDevice);
-                p.w9 = (const uint16_t*)img9;
-                p.w9_inv = inv;
-            }
-        }
-    }
-    rd::ConvRoute route = wh ? rd::conv_split_route(p, false) : rd::conv_f32_route(p);
-    if (used_direct && *used_direct == 2 && wh && rd::conv_stream_h3_supported(p)) route = rd::CONV_STREAM;
-    else if (used_direct && *used_direct == 1 && wh && rd::conv_direct_h3_supported(p)) route = rd::CONV_DIRECT;
-    if (used_direct) *used_direct = debug_conv_code(route);
-    const float ms = rd_debug_time(iters, [&] { rd::launch_conv_route(route, p, nullptr); });
-    if (img3) (void)hipFree(img3);
-    if (img9) (void)hipFree(img9);
+    const DebugConvOld old{wh, wl, used_direct ? *used_direct : 0};
+    const int images = old.code == 0 ? 4 : old.code == 4 ? 8 : 0;
+    rd::ConvRoute route = rd::CONV_F32_128x128;
+    const float ms = debug_conv_run(N, H, W, Cin, Cout, KH, KW, S, S, PT, PL, PB, PR, act, Cin, Cout, Cout, rd::OUT_NHWC, wh != nullptr, images, 0, iters, x,
+                                    w, bias, res, y, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &old, &route, nullptr);
+    if (used_direct && ms != -1.f) *used_direct = debug_conv_code(route);
     return ms;
 }
 

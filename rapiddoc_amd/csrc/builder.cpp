@@ -147,6 +147,9 @@ TView Builder::conv(const std::string& wname, const std::string& bname, const st
     RD_CHECK(kh == g.kh && kw == g.kw, "conv kernel size mismatch: " + wname);
     RD_CHECK(cin == x.c, "conv Cin mismatch: " + wname + " expects " + std::to_string(cin) + " got " + std::to_string(x.c));
     RD_CHECK(cin % 4 == 0, "conv_igemm needs Cin % 4 == 0: " + wname);
+    // (no dense-conv kernel multiplies its rows by a gate: a layer planned with one would run ungated.  Gates go through Builder::scale or
+    //  the fused mixer)
+    RD_CHECK(!ascale, "conv: a row gate (ascale) is applied by no kernel: " + wname);
     const int oh = out_dim(x.h, kh, g.sh, g.pt, g.pb), ow = out_dim(x.w, kw, g.sw, g.pl, g.pr);
     TView y = out ? *out : alloc(x.n, oh, ow, cout);
     RD_CHECK(y.n == x.n && y.h == oh && y.w == ow && y.c == cout, "conv output view mismatch: " + wname);
@@ -442,20 +445,8 @@ TView Builder::deconv2x2(const std::string& wname, const std::string& bname, con
         if (!pb_->has(key + "#w")) {
             std::vector<float> shift;
             std::vector<float> scale = bn_scale_shift(bn, cout, shift);
-            std::vector<float> wf((size_t)4 * cout * cin);
-            const float* src = w.f32();
-            for (int ci = 0; ci < cin; ++ci)
-                for (int co = 0; co < cout; ++co)
-                    for (int dy = 0; dy < 2; ++dy)
-                        for (int dx = 0; dx < 2; ++dx)
-                            wf[((size_t)(dy * 2 + dx) * cout + co) * cin + ci] =
-                                src[(((size_t)ci * cout + co) * 2 + dy) * 2 + dx] * scale[co];
-            std::vector<float> bias(cout, 0.f);
-            if (!bname.empty()) {
-                const float* bs = ws_->get(bname).f32();
-                for (int co = 0; co < cout; ++co) bias[co] = bs[co] * scale[co];
-            }
-            for (int co = 0; co < cout; ++co) bias[co] += shift[co];
+            std::vector<float> wf, bias;
+            pack_deconv2x2(w.f32(), bname.empty() ? nullptr : ws_->get(bname).f32(), cin, cout, scale.data(), shift.data(), wf, bias);
             pb_->add(key + "#w", wf);
             pb_->add(key + "#b", bias);
             if (h3_ && fits_fp16_range(wf)) {

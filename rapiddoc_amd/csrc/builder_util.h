@@ -57,6 +57,23 @@ static inline void pack_det_head_tail(const float* w1, const float* b1, const fl
     for (int co = 0; co < cmid; ++co) ba[co] += shift[co];
 }
 
+// A ConvTranspose2d(.., 2, stride 2) weight in its checkpoint layout - w [cin][cout][2][2], b [cout] or null - as the OUT_DECONV2X2
+// epilogue of the implicit-GEMM kernels reads it: wf [4 cout][cin], row = tap * cout + co with tap = 2 dy + dx, and bias [cout], both with
+// the output channel's affine (a folded BatchNorm: scale, shift per channel) applied
+static inline void pack_deconv2x2(const float* w, const float* b, int cin, int cout, const float* scale, const float* shift, std::vector<float>& wf,
+                                  std::vector<float>& bias) {
+    wf.assign((size_t)4 * cout * cin, 0.f);
+    bias.assign(cout, 0.f);
+    for (int ci = 0; ci < cin; ++ci)
+        for (int co = 0; co < cout; ++co)
+            for (int dy = 0; dy < 2; ++dy)
+                for (int dx = 0; dx < 2; ++dx)
+                    wf[((size_t)(dy * 2 + dx) * cout + co) * cin + ci] = w[(((size_t)ci * cout + co) * 2 + dy) * 2 + dx] * scale[co];
+    if (b)
+        for (int co = 0; co < cout; ++co) bias[co] = b[co] * scale[co];
+    for (int co = 0; co < cout; ++co) bias[co] += shift[co];
+}
+
 // OpRecord::shape of a layer over the map x: "N<n>_<h>x<w>", then "_C<c>" per channel count given
 static inline std::string shape_str(const TView& x, std::initializer_list<int> channels = {}) {
     std::string s = "N" + std::to_string(x.n) + "_" + std::to_string(x.h) + "x" + std::to_string(x.w);

@@ -12,6 +12,7 @@
 // Activations are split on the fly while a K tile is staged into LDS (5 VALU ops per element, hidden under the
 // MFMAs); weights are split once at load time (rd_load_weights) and stored as two fp16 matrices [Ng][Kp], Kp = K rounded up to 32.
 #include <cstdlib>
+#include <stdexcept>
 #include <vector>
 
 #include "rd_device.h"
@@ -425,6 +426,8 @@ ConvRoute conv_split_route(const ConvParams& p, bool has_ascale) {
 
 void launch_conv_route(ConvRoute r, const ConvParams& p, hipStream_t s) {
     if (p.M <= 0) return;
+    // (as launch_dwconv on a planner / launcher disagreement: no kernel below reads p.ascale, the layer would run ungated)
+    if (p.ascale) throw std::runtime_error("launch_conv_route: ConvParams::ascale is set, and no dense-conv kernel applies it");
     switch (r) {
         case CONV_STREAM: launch_conv_stream_h3(p, s); break;
         case CONV_C3H1: launch_conv3x3_h1(p, s); break;

@@ -29,7 +29,8 @@ struct ConvParams {
     int OH, OW, Cout;
     int KH, KW, SH, SW, PT, PL;
     const float* res; int rld;      // added after the activation, same geometry as y
-    const float* ascale;            // optional [N][Cin] multiplier applied to X rows on load (1x1 only)
+    const float* ascale;            // must be null: once a [N][Cin] multiplier of the X rows on load (1x1 only), applied by NO kernel since
+                                    // round 2.  launch_conv_route throws on it and Builder::conv refuses it at plan time
     const float* ln_g; const float* ln_b;   // skinny path (M <= 32, K <= 512) only: LayerNorm(eps 1e-5) applied to every X row
                                             // before the product (fuses the pre-LN of a transformer decode step)
     int act, out_mode;
