@@ -289,6 +289,26 @@ typedef struct {
 } rd_table_decode_cfg;
 int rd_table_decode(rd_handle* h, const float* memory_dev, int B, int S, int max_new_tokens, const rd_table_decode_cfg* cfg, int64_t* ids_dev,
                     int32_t* n_tokens, void* stream);
+/* The same decode through refilled slots (model_kind "unitable_decoder"): the N tables of memory_dev [N,S,768] run through `slots` decode
+ * rows; a row whose table ends (eos_id, or max_new_tokens reached) takes the next waiting table on the device, inside the captured step -
+ * at position 0 and with the bbox counter at 0 -, so no row waits for the longest table of a batch.  Row i of ids_dev
+ * [N][max_new_tokens + 1] is exactly what rd_table_decode writes for table i alone: prefix_id, the emitted tokens, eos_id, pad_id behind
+ * it; lens_dev[i] (DEVICE int32 [N]) = the columns that count, prefix and EOS included (max_new_tokens + 1 for a table that never stopped).
+ * Limits: 1 <= slots <= RD_TABLE_STREAM_MAX_SLOTS (the rows of the decoder's weight-streaming GEMV), N >= 1, 1 <= S <= 1024,
+ * 1 <= max_new_tokens <= 1024, the id checks of rd_table_decode, and N * S <= RD_TABLE_STREAM_MAX_TOKENS: every memory row keeps its
+ * cross-attention K and V of the 4 layers on the device for the whole call, 4 x 2 x 768 x 4 B = 24 KiB per row, 1.5 GiB at the limit.
+ * Outside the limits the call returns non-zero with a message in rd_last_error that names the limit, launches nothing and leaves the
+ * outputs untouched.  stats (host, may be NULL) is filled before the call returns; the call synchronises `stream`. */
+#define RD_TABLE_STREAM_MAX_SLOTS 8
+#define RD_TABLE_STREAM_MAX_TOKENS 65536
+typedef struct rd_table_stream_stats {
+    int32_t steps;           /* step launches, the host loop's run-ahead included (it looks at the device state every 8 steps) */
+    int32_t live_slot_steps; /* slot-steps that produced a token = sum over the tables of lens - 1 */
+    int32_t slots;
+    int32_t admitted;        /* tables that were given a slot (= N) */
+} rd_table_stream_stats;
+int rd_table_decode_stream(rd_handle* h, const float* memory_dev, int N, int S, int max_new_tokens, int slots, const rd_table_decode_cfg* cfg,
+                           int64_t* ids_dev, int32_t* lens_dev, rd_table_stream_stats* stats, void* stream);
 /* The classifier's verdict applied on the device, between rd_line_warp_batch and rd_line_resize_norm_batch: every line with
  * prob[1] > prob[0] and prob[1] >= thresh has its packed uint8 crop in scratch_u8_dev turned by 180 degrees in place
  * (cv2.rotate(ROTATE_180): the pixel order reversed); flipped_out_dev[i] = 1 for those lines, 0 for the others.  The scratch holds the

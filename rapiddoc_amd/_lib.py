@@ -45,6 +45,7 @@ SYMBOLS = {
     "rd_cls_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rd_table_encoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rd_table_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rd_table_decode_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rd_line_flip180_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rd_ctc_collapse": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "rd_ctc_collapse_lines": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -91,6 +92,7 @@ DEBUG_SYMBOLS = {
     "rd_debug_det_forward_stages": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "rd_debug_cls_forward_stages": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "rd_debug_table_decode": (_I, [_P, _P, _I, _I, _I, _P] + [_P] * 7),
+    "rd_debug_table_decode_stream": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "rd_debug_table_encoder_taps": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "rd_debug_formula_decode": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(C.c_int32), _P, _P, _P]),
     "rd_debug_formula_decode_stream": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I]),

@@ -376,8 +376,12 @@ class TableOcr:
     _warned_line_level = False       # the use_word_box downgrade is reported once per process
 
     def __init__(self, pipeline, det_raw_fn=None, rec_fn=None, skip_text_in_image: bool = True, use_img2table: bool = False,
-                 table_formula_enable: bool = True, lang: str = "ch", use_word_box: bool = True):
-        self.pipe, self.rec_fn, self.use_word_box = pipeline, rec_fn, use_word_box
+                 table_formula_enable: bool = True, lang: str = "ch", use_word_box: bool = True, pooled: bool = False):
+        """`pooled`: when the table model has `predict_many` (table_unitable.Mi355RapidTable), collect the per-table work of the whole
+        page batch - crop, masked detection, recognition, fill images - and hand it over in ONE call, so that the structure model sees the
+        tables together; the answers land on the detections exactly as the per-table loop writes them.  Default off: the per-table
+        route is the reference's order of calls."""
+        self.pipe, self.rec_fn, self.use_word_box, self.pooled = pipeline, rec_fn, use_word_box, bool(pooled)
         self.det = RegionOcr(pipeline, box_thresh=0.5, unclip_ratio=1.6, lang=lang, det_raw_fn=det_raw_fn)
         self.skip_text_in_image, self.use_img2table, self.table_formula_enable = skip_text_in_image, use_img2table, table_formula_enable
 
@@ -457,6 +461,19 @@ class TableOcr:
         reference appends to the formulas everywhere in this stage (analyze_utils.py:318-321,411-415); their `checkbox` text travels
         to the table model like a formula's `latex`."""
         n = 0
+        pool = self.pooled and hasattr(table_model, "predict_many")
+        waiting = []                     # pooled: (detection, predict's arguments, formulas, fill, scale) of every table of the page batch
+
+        def write(t, html_code, formulas, fill, scale):
+            if html_code and "<table>" in html_code and "</table>" in html_code:
+                t["html"] = html_code[html_code.find("<table>"): html_code.rfind("</table>") + len("</table>")]
+                fboxes = [f["bbox"] for f in formulas if "bbox" in f]
+                if fboxes:
+                    t["formula_boxes"] = [[int(c / scale) for c in b] for b in fboxes]
+                iboxes = [f["ori_bbox"] for f in fill if "bbox" in f]
+                if iboxes:
+                    t["img_boxes"] = [[int(c / scale) for c in b] for b in iboxes]
+
         for p, dets in enumerate(layout_dets_per_page):
             _ocr, tables, formulas = layout_host.split_regions(dets)
             if mask_boxes_per_page is not None:
@@ -486,17 +503,20 @@ class TableOcr:
                 ocr_result = self.ocr_result(table, adjusted, override, None if page_langs is None else page_langs[p]) if table.numel() else []
                 fill = layout_host.table_fill_images(t, useful) if table_image_enable else []
                 t.pop("layout_image_list", None)
+                n += 1
+                if pool:
+                    waiting.append((t, (table.cpu().numpy(), ocr_result, fill, adjusted, self.skip_text_in_image, self.use_img2table, True),
+                                    formulas, fill, scale))
+                    continue
                 html_code = table_model.predict(table.cpu().numpy(), ocr_result, fill, adjusted, self.skip_text_in_image, self.use_img2table,
                                                 skip_table_orientation=True)
-                n += 1
-                if html_code and "<table>" in html_code and "</table>" in html_code:
-                    t["html"] = html_code[html_code.find("<table>"): html_code.rfind("</table>") + len("</table>")]
-                    fboxes = [f["bbox"] for f in formulas if "bbox" in f]
-                    if fboxes:
-                        t["formula_boxes"] = [[int(c / scale) for c in b] for b in fboxes]
-                    iboxes = [f["ori_bbox"] for f in fill if "bbox" in f]
-                    if iboxes:
-                        t["img_boxes"] = [[int(c / scale) for c in b] for b in iboxes]
+                write(t, html_code, formulas, fill, scale)
+        if waiting:
+            answers = table_model.predict_many([w[1] for w in waiting])
+            if len(answers) != len(waiting):
+                raise ValueError(f"predict_many returned {len(answers)} answers for {len(waiting)} tables")
+            for (t, _args, formulas, fill, scale), html_code in zip(waiting, answers):
+                write(t, html_code, formulas, fill, scale)
         return n
 
 
@@ -562,8 +582,8 @@ class PageAnalyzer:
                  formula_expand_px: int = 2, det_batch_num: Optional[int] = None, det_raw_fn=None, lang: str = "ch",
                  table_det_raw_fn=None, table_rec_fn=None, table_image_enable: bool = True, table_use_word_box: bool = True,
                  seal_model=None, seal_enable: bool = True, checkbox_fn=None, checkbox_enable: bool = False,
-                 orientation_model=None, use_doc_orientation_classify: bool = False):
-        """Batch sizes default to the reference's (layout_config['batch_num'] / formula_config['batch_num'] = 1,
+                 orientation_model=None, use_doc_orientation_classify: bool = False, table_pooled: bool = False):
+        """`table_pooled`: see TableOcr(pooled=...).  Batch sizes default to the reference's (layout_config['batch_num'] / formula_config['batch_num'] = 1,
         batch_analyze.py:66-71); `det_batch_num` / `det_raw_fn`: see RegionOcr."""
         self.layout_model, self.pipe = layout_model, pipeline
         self.formula_model, self.table_model, self.custom_ocr = formula_model, table_model, custom_ocr
@@ -571,7 +591,8 @@ class PageAnalyzer:
         self.formula_batch_size, self.formula_expand_px = formula_batch_size, formula_expand_px
         self.ocr = RegionOcr(pipeline, box_thresh, unclip_ratio, lang, det_batch_num, det_raw_fn)
         # table_config["use_word_box"], default True (analyze_utils.py:308): word-level OCR entries for the table model
-        self.table_ocr = TableOcr(pipeline, det_raw_fn=table_det_raw_fn, rec_fn=table_rec_fn, lang=lang, use_word_box=table_use_word_box)
+        self.table_ocr = TableOcr(pipeline, det_raw_fn=table_det_raw_fn, rec_fn=table_rec_fn, lang=lang, use_word_box=table_use_word_box,
+                                  pooled=table_pooled)
         self.table_image_enable = table_image_enable          # table_config["table_image_enable"], default True (batch_analyze.py:75)
         # 7. seal OCR (ocr_config["seal_enable"], default True, batch_analyze.py:62,150-151): `seal_model` = the RapidOcrModel-shaped object
         #    the reference obtains with get_atom_model(OCR, is_seal=True) - `.ocr(bgr crop, det=True, rec=True) -> [[(box, (text, score)), ...]]`.

@@ -124,6 +124,16 @@ int rd_table_decode(rd_handle* h, const float* memory, int B, int S, int max_new
                                  nullptr, nullptr);
     });
 }
+int rd_table_decode_stream(rd_handle* h, const float* memory, int N, int S, int max_new_tokens, int slots, const rd_table_decode_cfg* cfg, int64_t* ids,
+                           int32_t* lens, rd_table_stream_stats* stats, void* stream) {
+    return guarded(h, [&] {
+        RD_CHECK(h->kind == "unitable_decoder" && h->tdec, "handle is not a loaded table-structure decoder (unitable_decoder)");
+        int c[6];
+        table_cfg6(cfg, c);
+        rd::table_decoder_decode_stream(h->tdec, memory, N, S, max_new_tokens, slots, c, (long long*)ids, (int*)lens, stats, (hipStream_t)stream, nullptr,
+                                        nullptr, nullptr, 0);
+    });
+}
 
 int rd_line_flip180_batch(int device_id, const rd_line_crop_desc* descs, int n, const float* cls_prob, float thresh, uint8_t* scratch,
                           int32_t* flipped_out, void* stream) {

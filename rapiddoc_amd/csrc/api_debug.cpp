@@ -82,6 +82,22 @@ int rd_debug_table_decode(rd_handle* h, const float* memory, int B, int S, int s
     });
 }
 
+// developer entry ("unitable_decoder"): rd_table_decode_stream plus optional traces written inside the step (graph replay included), indexed
+// by what the slot holds: trace_logits [N][max_new_tokens][960] and trace_hidden [N][max_new_tokens][4][768] (the row after each block) by
+// (table, position), and trace_sched int32 [sched_steps][slots][2] = the (table or -1, position) of every slot at the start of every step
+// (steps past sched_steps are not recorded).  With all three null it enqueues exactly what rd_table_decode_stream enqueues.
+int rd_debug_table_decode_stream(rd_handle* h, const float* memory, int N, int S, int max_new_tokens, int slots, const rd_table_decode_cfg* cfg,
+                                 int64_t* ids, int32_t* lens, rd_table_stream_stats* stats, void* stream, float* trace_logits, float* trace_hidden,
+                                 int32_t* trace_sched, int sched_steps) {
+    return guarded(h, [&] {
+        RD_CHECK(h->kind == "unitable_decoder" && h->tdec, "handle is not a loaded table-structure decoder (unitable_decoder)");
+        int c[6];
+        table_cfg6(cfg, c);
+        rd::table_decoder_decode_stream(h->tdec, memory, N, S, max_new_tokens, slots, c, (long long*)ids, (int*)lens, stats, (hipStream_t)stream,
+                                        trace_logits, trace_hidden, (int*)trace_sched, sched_steps);
+    });
+}
+
 // developer entry ("unitable_encoder" only): rd_table_encoder_forward plus three taps, each [B,T,768], back to back in taps_dev: the patch
 // embedding (before the position rows) and the outputs of encoder layers 0 and 11.  The plan of the engine's VIT_WANT_TAPS variant; the
 // internal workspace.  Not part of the public header.

@@ -30,6 +30,10 @@ TableDecoder* table_decoder_create(int device, const void* blob, size_t nbytes);
 void table_decoder_destroy(TableDecoder* d);
 int table_decoder_decode(TableDecoder* d, const float* memory, int B, int S, int max_new, const int* cfg6, long long* ids, int* n_tokens, hipStream_t s,
                          const int* forced, float* trace_hidden, float* trace_logits, int* trace_chosen, int* trace_emitted);
+// the decode through refilled slots (rd_table_decode_stream); the traces (rd_debug_table_decode_stream) may each be null
+void table_decoder_decode_stream(TableDecoder* d, const float* memory, int N, int S, int max_new, int slots, const int* cfg6, long long* ids, int* lens,
+                                 rd_table_stream_stats* stats, hipStream_t s, float* trace_logits, float* trace_hidden, int* trace_sched,
+                                 int sched_steps);
 }  // namespace rd
 
 struct rd_handle {

@@ -11,6 +11,10 @@
 //                     (a counter per table that ONLY a bbox token raises and only its overflow clears), the per-table EOS latch (a
 //                     finished table keeps its slot and writes `pad`), and the next step's embedding + position row
 // No atomics: every table has its own flag, counter and token word.
+// rd_table_decode_stream (decode_stream below) runs N tables through `slots` <= 8 rows of the same step: per-slot state in device memory (the
+// table a slot holds, its position, its bbox counter), and a row whose table ended takes the next waiting table inside the captured step.
+//   td_stream_attn_kernel / td_stream_select_kernel   td_attn_kernel / td_select_kernel reading the slot's state where those read `step`
+//   td_stream_admit_kernel   one workgroup in td_advance_kernel's place: finished slots take the waiting tables in slot order, or go idle
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -213,6 +217,204 @@ __global__ void __launch_bounds__(1024) td_select_kernel(TdSelect p) {
     if (step + 1 < TD_MAXPOS) td_embed_row(p.emb, p.pos, next_tok, step + 1, p.x + (size_t)b * TD_D);
 }
 
+// ---- rd_table_decode_stream: the launches of a step that read per-row state.  Row b is a decode SLOT with a state of its own in device
+// memory: the table it holds (src, -1 = idle), that table's position (pos = its cached length) and its bbox counter.  The kernels above keep
+// their text (a body shared with them changed their generated code in the formula decoder: docs/notebook/formula_stream.md s2), so the
+// three below are copies with the per-slot reads put in; layernorm768 and td_gemv_kernel run unchanged at M = slots (a row's sums never see
+// another row, so an idle slot's row is computed, finite, and never looked at).
+struct TdStream {          // written by one lane with plain stores; cross-block reads only across a kernel boundary
+    int next;              // first table not yet admitted
+    int n_live;            // slots that hold a table
+    int steps;             // step launches so far
+    int live_slot_steps;   // slot-steps that produced a token
+    int src[TD_MAXB];      // table of the slot, -1 = idle
+    int pos[TD_MAXB];      // tokens generated so far for that table
+    int done[TD_MAXB];     // the select launch of this step ended the slot's table (cleared by the admission launch)
+    int box[TD_MAXB];      // the bbox counter of the slot's table
+};
+
+// td_attn_kernel with b = the slot: the self cache is the slot's (rows 0 .. pos - 1 were all written by the table that holds the slot now:
+// a refilled slot starts at length 0 and never reads its predecessor's rows), the cross K | V block is table src's.  An idle slot returns at once.
+__global__ void __launch_bounds__(256) td_stream_attn_kernel(TdAttn p, const TdStream* ss) {
+    __shared__ float sc[TD_MAXPOS];
+    __shared__ float qs[TD_HD];
+    __shared__ float red[4];
+    __shared__ float part[4][TD_HD];
+    const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int src = ss->src[b];
+    if (src < 0) return;               // idle (uniform over the block)
+    const bool self = p.kcur != nullptr;
+    const int pos = self ? min(ss->pos[b], TD_MAXPOS - 1) : 0;
+    const int T = self ? pos + 1 : p.fixed_T;
+    const int blk = self ? b : src;    // the block of the K / V buffers this row reads (and, self, appends to)
+    float* kb = p.kc + (size_t)blk * p.seq_stride + h * TD_HD;
+    float* vb = p.vc + (size_t)blk * p.seq_stride + h * TD_HD;
+    const float* kcur = self ? p.kcur + (size_t)b * p.ldcur + h * TD_HD : nullptr;
+    const float* vcur = self ? p.vcur + (size_t)b * p.ldcur + h * TD_HD : nullptr;
+    if (tid < TD_HD) {
+        qs[tid] = p.q[(size_t)b * p.ldq + h * TD_HD + tid] * 0.125f;
+        if (self) {
+            kb[(size_t)pos * p.ldkv + tid] = kcur[tid];
+            vb[(size_t)pos * p.ldkv + tid] = vcur[tid];
+        }
+    }
+    __syncthreads();
+    float m = -INFINITY;
+    for (int j = tid; j < T; j += 256) {
+        const float* kr = (self && j == pos) ? kcur : kb + (size_t)j * p.ldkv;
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < TD_HD; d += 4) {
+            const f32x4 kv = *reinterpret_cast<const f32x4*>(kr + d);
+            s = fmaf(qs[d], kv[0], s); s = fmaf(qs[d + 1], kv[1], s); s = fmaf(qs[d + 2], kv[2], s); s = fmaf(qs[d + 3], kv[3], s);
+        }
+        sc[j] = s;
+        m = fmaxf(m, s);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float l = 0.f;
+    for (int j = tid; j < T; j += 256) {
+        const float e = expf(sc[j] - m);
+        sc[j] = e;
+        l += e;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) l += __shfl_xor(l, o, 64);
+    if (lane == 0) red[wave] = l;
+    __syncthreads();
+    l = (red[0] + red[1]) + (red[2] + red[3]);
+    float acc = 0.f;
+    for (int j = wave; j < T; j += 4) {
+        const float* vr = (self && j == pos) ? vcur : vb + (size_t)j * p.ldkv;
+        acc = fmaf(sc[j], vr[lane], acc);
+    }
+    part[wave][lane] = acc;
+    __syncthreads();
+    if (tid < TD_HD) p.out[(size_t)b * p.ldo + h * TD_HD + tid] = ((part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid])) / l;
+}
+
+struct TdStreamSelect {
+    const float* logits; long long* ids; int ids_ld; int* lens; TdStream* ss; TdCfg cfg; int max_new;
+    const float* emb; const float* pos; float* x;
+};
+
+// td_select_kernel's whitelist argmax and bbox rule for the slot's table: ids[src][pos + 1]; EOS or the table's last column ends it
+// (lens[src], done[slot]); otherwise the position advances and the next step's input row is embedded.  Block `slot` is the only one that
+// touches the slot's words in this launch.
+__global__ void __launch_bounds__(1024) td_stream_select_kernel(TdStreamSelect p) {
+    __shared__ float bv[1024];
+    __shared__ int bi[1024];
+    __shared__ int next_tok;
+    const int slot = blockIdx.x, tid = threadIdx.x, src = p.ss->src[slot];
+    if (src < 0) return;               // idle (uniform over the block)
+    const int t = p.ss->pos[slot];
+    float v = -INFINITY;
+    if (tid < TD_VOCAB) {
+        v = td_whitelisted(tid) ? p.logits[(size_t)slot * TD_VOCAB + tid] : -1e9f;
+        if (!(v == v)) v = -INFINITY;          // NaN never wins
+    }
+    bv[tid] = v;
+    bi[tid] = tid < TD_VOCAB ? tid : TD_VOCAB - 1;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {        // the larger value, the lower id among equals
+        if (tid < s) {
+            const float a = bv[tid], c = bv[tid + s];
+            if (c > a || (c == a && bi[tid + s] < bi[tid])) { bv[tid] = c; bi[tid] = bi[tid + s]; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int chosen = bi[0];
+        int emitted = chosen;
+        if (chosen >= p.cfg.bbox_lo && chosen <= p.cfg.bbox_hi) {
+            int c = p.ss->box[slot] + 1;
+            if (c > 4) { emitted = p.cfg.close_id; c = 0; }
+            p.ss->box[slot] = c;
+        }
+        p.ids[(size_t)src * p.ids_ld + t + 1] = emitted;
+        const bool end = emitted == p.cfg.eos || t + 1 >= p.max_new;
+        if (end) {
+            p.lens[src] = t + 2;
+            p.ss->done[slot] = 1;
+        } else {
+            p.ss->pos[slot] = t + 1;
+        }
+        next_tok = end ? -1 : min(max(emitted, 0), TD_VOCAB - 1);
+    }
+    __syncthreads();
+    if (next_tok < 0) return;          // the admission launch behind this one writes the row of whatever takes the slot
+    td_embed_row(p.emb, p.pos, next_tok, t + 1, p.x + (size_t)slot * TD_D);
+}
+
+// Admission, one workgroup, in the launch behind the select launch (the kernel boundary is what makes every select block's stores visible
+// here).  In slot order every finished slot takes the first waiting table - position 0, bbox counter 0, input row = the prefix token's (x0) -
+// or goes idle: which slot a table lands in follows from the lengths alone (tests/stream_reference.py).  An idle slot's input row is put
+// back to x0 at every step, so the row the linears compute for it stays the same finite one however long the call runs.
+__global__ void __launch_bounds__(256) td_stream_admit_kernel(TdStream* ss, int N, int slots, const float* x0, float* x) {
+    __shared__ int reset[TD_MAXB];
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        int next = ss->next, n_live = ss->n_live, live = 0;
+        for (int s = 0; s < slots; ++s) {
+            reset[s] = 1;
+            if (ss->src[s] < 0) continue;
+            ++live;
+            if (!ss->done[s]) { reset[s] = 0; continue; }
+            ss->done[s] = 0;
+            ss->pos[s] = 0;
+            ss->box[s] = 0;
+            if (next < N) {
+                ss->src[s] = next++;
+            } else {
+                ss->src[s] = -1;
+                --n_live;
+            }
+        }
+        ss->next = next;
+        ss->n_live = n_live;
+        ss->steps += 1;
+        ss->live_slot_steps += live;
+    }
+    __syncthreads();
+    for (int s = 0; s < slots; ++s)
+        if (reset[s])
+            for (int c = tid; c < TD_D; c += 256) x[(size_t)s * TD_D + c] = x0[c];
+}
+
+// Once per call: the state (tables 0 .. min(N, slots) - 1 sit in the slots of their number), ids = prefix | pad, and the prefix token's
+// input row emb[prefix] + pos[0] into x0 and into every slot's row (block 0)
+__global__ void __launch_bounds__(256) td_stream_init_kernel(TdStream* ss, long long* ids, int ids_ld, int N, int slots, TdCfg cfg, const float* emb,
+                                                             const float* pos, float* x, float* x0) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int t0 = min(max(cfg.prefix, 0), TD_VOCAB - 1);
+    if (i == 0) { ss->next = min(N, slots); ss->n_live = min(N, slots); ss->steps = 0; ss->live_slot_steps = 0; }
+    if (i < TD_MAXB) { ss->src[i] = (i < slots && i < N) ? i : -1; ss->pos[i] = 0; ss->done[i] = 0; ss->box[i] = 0; }
+    for (long long k = i; k < (long long)N * ids_ld; k += (long long)gridDim.x * blockDim.x) ids[k] = (k % ids_ld == 0) ? t0 : cfg.pad;
+    if (blockIdx.x == 0)
+        for (int r = 0; r <= slots; ++r) td_embed_row(emb, pos, t0, 0, r < slots ? x + (size_t)r * TD_D : x0);
+}
+
+// developer traces (rd_debug_table_decode_stream): dst[(src * max_new + pos) * row_ld + i] = src_rows[slot][i], i < n
+__global__ void __launch_bounds__(256) td_stream_trace_kernel(const float* src_rows, float* dst, int n, long long row_ld, int max_new, const TdStream* ss) {
+    const int slot = blockIdx.x, src = ss->src[slot];
+    if (src < 0) return;
+    float* d = dst + ((size_t)src * max_new + ss->pos[slot]) * row_ld;
+    const float* r = src_rows + (size_t)slot * n;
+    for (int i = threadIdx.x; i < n; i += 256) d[i] = r[i];
+}
+// sched [sched_steps][slots][2] = (src, pos) of every slot at the start of step ss->steps
+__global__ void td_stream_sched_kernel(const TdStream* ss, int* sched, int sched_steps, int slots) {
+    const int s = threadIdx.x, t = ss->steps;
+    if (s >= slots || t >= sched_steps) return;
+    sched[((size_t)t * slots + s) * 2] = ss->src[s];
+    sched[((size_t)t * slots + s) * 2 + 1] = ss->pos[s];
+}
+
 // =================================================================================================
 class TableDecoder {
    public:
@@ -224,6 +426,10 @@ class TableDecoder {
     void load(const WeightStore& ws);
     int decode(const float* memory, int B, int S, int max_new, const TdCfg& cfg, long long* ids_out, int* n_tokens, hipStream_t s, const int* forced,
                float* trace_hidden, float* trace_logits, int* trace_chosen, int* trace_emitted);
+    // memory [N,S,768] through `slots` refilled decode rows -> ids [N][max_new+1], lens [N] (device); stats (host) may be null.  Traces (each
+    // may be null): logits [N][max_new][960], hidden [N][max_new][4][768], sched int [sched_steps][slots][2]
+    void decode_stream(const float* memory, int N, int S, int max_new, int slots, const TdCfg& cfg, long long* ids_out, int* lens_out,
+                       rd_table_stream_stats* stats, hipStream_t s, float* trace_logits, float* trace_hidden, int* trace_sched, int sched_steps);
 
    private:
     void gemm(const float* x, int M, int K, const std::string& key, int N, float* y, hipStream_t s);
@@ -438,6 +644,164 @@ int TableDecoder::decode(const float* memory, int B, int S, int max_new, const T
     return 0;
 }
 
+// rd_table_decode_stream.  decode() above is batch-synchronous: the tables of a batch share one step counter and the loop runs until the
+// longest table has ended, so on a page batch of mixed lengths most slot-steps write `pad`.  Here the step is the same launch sequence at
+// M = slots, but every row carries its own (table, position, bbox counter) in device memory (TdStream) and a one-workgroup admission launch
+// at the end of the captured step hands a finished row the next waiting table.  The host only replays the graph and looks at the state
+// every 8 steps.
+void TableDecoder::decode_stream(const float* memory, int N, int S, int max_new, int slots, const TdCfg& cfg, long long* ids_out, int* lens_out,
+                                 rd_table_stream_stats* stats, hipStream_t s, float* trace_logits, float* trace_hidden, int* trace_sched,
+                                 int sched_steps) {
+    // refusals first: nothing is launched and the outputs stay as they are
+    RD_CHECK(slots >= 1 && slots <= RD_TABLE_STREAM_MAX_SLOTS,
+             "table decode stream: slots must be 1 .. " + std::to_string(RD_TABLE_STREAM_MAX_SLOTS) + " (RD_TABLE_STREAM_MAX_SLOTS), got " + std::to_string(slots));
+    RD_CHECK(N >= 1, "table decode stream: N must be at least 1, got " + std::to_string(N));
+    RD_CHECK(S >= 1 && S <= TD_MAXPOS, "table decode stream: 1 <= S <= 1024 memory rows per table, got " + std::to_string(S));
+    RD_CHECK(max_new >= 1 && max_new <= TD_MAXPOS, "table decode stream: 1 <= max_new_tokens <= 1024, got " + std::to_string(max_new));
+    RD_CHECK((long long)N * S <= RD_TABLE_STREAM_MAX_TOKENS, "table decode stream: N * S = " + std::to_string((long long)N * S) +
+                                                                 " memory rows exceed RD_TABLE_STREAM_MAX_TOKENS (" +
+                                                                 std::to_string(RD_TABLE_STREAM_MAX_TOKENS) + "): decode in windows");
+    auto in_vocab = [](int v) { return v >= 0 && v < TD_VOCAB; };
+    RD_CHECK(in_vocab(cfg.prefix) && in_vocab(cfg.eos) && in_vocab(cfg.close_id), "table decode stream: prefix, eos and close ids must lie in 0 .. 959");
+    RD_CHECK(cfg.bbox_lo <= cfg.bbox_hi, "table decode stream: empty bbox id range");
+    RD_CHECK(memory && ids_out && lens_out, "table decode stream: null input/output");
+    RD_CHECK(!trace_sched || sched_steps > 0, "table decode stream: trace_sched needs sched_steps > 0");
+    static_assert(RD_TABLE_STREAM_MAX_SLOTS == TD_MAXB, "a slot is a row of td_gemv_kernel");
+    RD_HIP(hipSetDevice(device_));
+    const int ids_ld = max_new + 1, M = slots, Tc = max_new;      // Tc: rows of a slot's self cache (positions 0 .. max_new - 1)
+    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t f = sizeof(float);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    const size_t o_state = take(sizeof(TdStream));
+    const size_t o_ck = take((size_t)TD_LAYERS * N * S * TD_D * f), o_cv = take((size_t)TD_LAYERS * N * S * TD_D * f);          // [layer][N][S][768]
+    const size_t o_kc = take((size_t)TD_LAYERS * M * Tc * TD_D * f), o_vc = take((size_t)TD_LAYERS * M * Tc * TD_D * f);        // [layer][slots][Tc][768]
+    const size_t o_x0 = take((size_t)TD_D * f);
+    const size_t o_act = off;                                       // the step's activations: cleared once, so that an idle row reads nothing uninitialised
+    const size_t o_x = take((size_t)M * TD_D * f), o_x2 = take((size_t)M * TD_D * f), o_h = take((size_t)M * TD_D * f);
+    const size_t o_qkv = take((size_t)M * 3 * TD_D * f), o_a = take((size_t)M * TD_D * f), o_f = take((size_t)M * TD_FFN * f);
+    const size_t o_lg = take((size_t)M * TD_VOCAB * f);
+    if (off > buf_bytes_) {
+        RD_HIP(hipStreamSynchronize(s));
+        if (buf_) RD_HIP(hipFree(buf_));
+        buf_ = nullptr;
+        buf_bytes_ = 0;
+        RD_HIP(hipMalloc((void**)&buf_, off));
+        buf_bytes_ = off;
+    }
+    TdStream* ss = reinterpret_cast<TdStream*>(buf_ + o_state);
+    float* ck = reinterpret_cast<float*>(buf_ + o_ck);
+    float* cv = reinterpret_cast<float*>(buf_ + o_cv);
+    float* kc = reinterpret_cast<float*>(buf_ + o_kc);
+    float* vc = reinterpret_cast<float*>(buf_ + o_vc);
+    float* x0 = reinterpret_cast<float*>(buf_ + o_x0);
+    float* x = reinterpret_cast<float*>(buf_ + o_x);
+    float* x2 = reinterpret_cast<float*>(buf_ + o_x2);
+    float* h = reinterpret_cast<float*>(buf_ + o_h);
+    float* qkv = reinterpret_cast<float*>(buf_ + o_qkv);
+    float* a = reinterpret_cast<float*>(buf_ + o_a);
+    float* ff = reinterpret_cast<float*>(buf_ + o_f);
+    float* lg = reinterpret_cast<float*>(buf_ + o_lg);
+
+    RD_HIP(hipMemsetAsync(buf_ + o_act, 0, off - o_act, s));
+    hipLaunchKernelGGL(td_stream_init_kernel, dim3(64), dim3(256), 0, s, ss, ids_out, ids_ld, N, slots, cfg, params_.ptr("emb"), params_.ptr("pos"), x, x0);
+    // once per call: every layer's cross-attention K and V of all N tables, in consecutive groups of `slots` tables at the M decode() uses
+    // for such a batch: a table's K | V have the bits rd_table_decode gives them in a batch of `slots` and do not depend on N
+    for (int g0 = 0; g0 < N; g0 += slots) {
+        const int rows = std::min(slots, N - g0) * S;
+        const float* mem_g = memory + (size_t)g0 * S * TD_D;
+        for (int l = 0; l < TD_LAYERS; ++l) {
+            const std::string K = "l" + std::to_string(l) + ".";
+            gemm(mem_g, rows, TD_D, K + "ck", TD_D, ck + ((size_t)l * N + g0) * S * TD_D, s);
+            gemm(mem_g, rows, TD_D, K + "cv", TD_D, cv + ((size_t)l * N + g0) * S * TD_D, s);
+        }
+    }
+    const TdStreamSelect sel{lg, ids_out, ids_ld, lens_out, ss, cfg, max_new, params_.ptr("emb"), params_.ptr("pos"), x};
+    auto enqueue_step = [&]() {          // decode()'s chain at B = slots
+        if (trace_sched) hipLaunchKernelGGL(td_stream_sched_kernel, dim3(1), dim3(64), 0, s, ss, trace_sched, sched_steps, slots);
+        float* cur = x;
+        float* nxt = x2;
+        for (int l = 0; l < TD_LAYERS; ++l) {
+            const std::string K = "l" + std::to_string(l) + ".";
+            ln(cur, K + "ln1", h, M, s);
+            gemv(h, M, TD_D, K + "qkv", 3 * TD_D, qkv, ACT_NONE, nullptr, s);
+            TdAttn sp{};
+            sp.q = qkv; sp.ldq = 3 * TD_D;
+            sp.kc = kc + (size_t)l * M * Tc * TD_D; sp.vc = vc + (size_t)l * M * Tc * TD_D; sp.ldkv = TD_D; sp.seq_stride = (long long)Tc * TD_D;
+            sp.kcur = qkv + TD_D; sp.vcur = qkv + 2 * TD_D; sp.ldcur = 3 * TD_D;
+            sp.st = nullptr; sp.fixed_T = 0; sp.out = a; sp.ldo = TD_D;
+            hipLaunchKernelGGL(td_stream_attn_kernel, dim3(TD_HEADS, M), dim3(256), 0, s, sp, ss);
+            gemv(a, M, TD_D, K + "wo", TD_D, nxt, ACT_NONE, cur, s);
+            std::swap(cur, nxt);
+            ln(cur, K + "ln2", h, M, s);
+            gemv(h, M, TD_D, K + "cq", TD_D, qkv, ACT_NONE, nullptr, s);
+            TdAttn cp{};
+            cp.q = qkv; cp.ldq = TD_D;
+            cp.kc = ck + (size_t)l * N * S * TD_D; cp.vc = cv + (size_t)l * N * S * TD_D; cp.ldkv = TD_D; cp.seq_stride = (long long)S * TD_D;
+            cp.st = nullptr; cp.fixed_T = S; cp.out = a; cp.ldo = TD_D;
+            hipLaunchKernelGGL(td_stream_attn_kernel, dim3(TD_HEADS, M), dim3(256), 0, s, cp, ss);
+            gemv(a, M, TD_D, K + "co", TD_D, nxt, ACT_NONE, cur, s);
+            std::swap(cur, nxt);
+            ln(cur, K + "ln3", h, M, s);
+            gemv(h, M, TD_D, K + "fc1", TD_FFN, ff, ACT_GELU, nullptr, s);
+            gemv(ff, M, TD_FFN, K + "fc2", TD_D, nxt, ACT_NONE, cur, s);
+            std::swap(cur, nxt);
+            if (trace_hidden)
+                hipLaunchKernelGGL(td_stream_trace_kernel, dim3(M), dim3(256), 0, s, cur, trace_hidden + (size_t)l * TD_D, TD_D,
+                                   (long long)TD_LAYERS * TD_D, max_new, ss);
+        }
+        gemv(cur, M, TD_D, "gen", TD_VOCAB, lg, ACT_NONE, nullptr, s);
+        if (trace_logits) hipLaunchKernelGGL(td_stream_trace_kernel, dim3(M), dim3(256), 0, s, lg, trace_logits, TD_VOCAB, (long long)TD_VOCAB, max_new, ss);
+        RD_CHECK(cur == x, "table decode stream: the layer stack must end in the buffer the next embedding is written to");
+        hipLaunchKernelGGL(td_stream_select_kernel, dim3(M), dim3(1024), 0, s, sel);
+        hipLaunchKernelGGL(td_stream_admit_kernel, dim3(1), dim3(256), 0, s, ss, N, slots, x0, x);
+    };
+    struct StepGraph {          // the captured step; freed on every way out of this function, a throwing RD_HIP included
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        hipStream_t stream = nullptr;
+        ~StepGraph() {
+            if (exec) {
+                (void)hipStreamSynchronize(stream);
+                (void)hipGraphExecDestroy(exec);
+            }
+            if (graph) (void)hipGraphDestroy(graph);
+        }
+    } sg;
+    sg.stream = s;
+    if (s != nullptr) {          // one stream, no branches (the null stream cannot be captured: direct launches there)
+        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            enqueue_step();
+            if (hipStreamEndCapture(s, &sg.graph) != hipSuccess || hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0) != hipSuccess) {
+                if (sg.graph) (void)hipGraphDestroy(sg.graph);
+                sg.graph = nullptr;
+                sg.exec = nullptr;
+                (void)hipGetLastError();
+            }
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    // every live slot advances by one token per step and a table ends after max_new at the latest: N * max_new steps would decode the tables
+    // one after the other in a single slot.  The cap keeps a fault in the admission from spinning this loop
+    const long long cap = (long long)N * max_new + 8;
+    TdStream hs{};
+    bool ended = false;
+    for (long long t = 0; t < cap && !ended; ++t) {
+        if (sg.exec) RD_HIP(hipGraphLaunch(sg.exec, s));
+        else enqueue_step();
+        if ((t & 7) == 7) {        // one small D2H + sync every 8 steps
+            RD_HIP(hipMemcpyAsync(&hs, ss, sizeof(TdStream), hipMemcpyDeviceToHost, s));
+            RD_HIP(hipStreamSynchronize(s));
+            ended = hs.next >= N && hs.n_live == 0;
+        }
+    }
+    RD_HIP(hipStreamSynchronize(s));
+    RD_HIP(hipGetLastError());
+    RD_CHECK(ended, "table decode stream: the device state never reported the end of the queue");
+    if (stats) *stats = rd_table_stream_stats{hs.steps, hs.live_slot_steps, slots, hs.next};
+}
+
 TableDecoder* table_decoder_create(int device, const void* blob, size_t nbytes) {
     RD_HIP(hipSetDevice(device));
     WeightStore ws;
@@ -456,6 +820,12 @@ int table_decoder_decode(TableDecoder* d, const float* memory, int B, int S, int
                          const int* forced, float* trace_hidden, float* trace_logits, int* trace_chosen, int* trace_emitted) {
     TdCfg c{cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5]};
     return d->decode(memory, B, S, max_new, c, ids, n_tokens, s, forced, trace_hidden, trace_logits, trace_chosen, trace_emitted);
+}
+void table_decoder_decode_stream(TableDecoder* d, const float* memory, int N, int S, int max_new, int slots, const int* cfg6, long long* ids, int* lens,
+                                 rd_table_stream_stats* stats, hipStream_t s, float* trace_logits, float* trace_hidden, int* trace_sched,
+                                 int sched_steps) {
+    TdCfg c{cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5]};
+    d->decode_stream(memory, N, S, max_new, slots, c, ids, lens, stats, s, trace_logits, trace_hidden, trace_sched, sched_steps);
 }
 
 }  // namespace rd

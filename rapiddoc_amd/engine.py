@@ -22,10 +22,17 @@ CLS_WANT_AUX = 1            # ppocr_cls_mobile: also hand out [B, 2 logits | 200
 CLS_FEATURES = 200          # channels of the classifier's pooled features (conv2 of MobileNetV3 small scale 0.35)
 FORMULA_STREAM_MAX_TOKENS = 65536      # RD_FORMULA_STREAM_MAX_TOKENS: N * S of one rd_formula_decode_stream call
 FORMULA_STREAM_MAX_SLOTS = 32          # RD_FORMULA_STREAM_MAX_SLOTS
+TABLE_STREAM_MAX_TOKENS = 65536        # RD_TABLE_STREAM_MAX_TOKENS: N * S of one rd_table_decode_stream call
+TABLE_STREAM_MAX_SLOTS = 8             # RD_TABLE_STREAM_MAX_SLOTS
 
 
 class FormulaStreamStats(C.Structure):
     """rd_formula_stream_stats (include/rapiddoc_mi355.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("steps", "live_slot_steps", "slots", "admitted")]
+
+
+class TableStreamStats(C.Structure):
+    """rd_table_stream_stats (include/rapiddoc_mi355.h)"""
     _fields_ = [(n, C.c_int32) for n in ("steps", "live_slot_steps", "slots", "admitted")]
 
 
@@ -299,6 +306,34 @@ class RdEngine:
         cfg = cfg_struct(ids)
         self._chk(self._l.rd_table_decode(self._h, memory.data_ptr(), B, S, max_new_tokens, C.byref(cfg), out.data_ptr(), n, _stream_ptr()))
         return out, [int(v) for v in n]
+
+    def table_decode_stream(self, memory: torch.Tensor, ids, max_new_tokens: int = 1024, slots: int = 8, trace: Optional[dict] = None):
+        """memory [N,S,768] -> (ids [N, max_new_tokens + 1] int64, lens [N] int32, stats): the N tables run through `slots` decode rows, a
+        row whose table ends takes the next one (rd_table_decode_stream).  Row i is what `table_decode` gives table i alone - prefix,
+        tokens, EOS, `pad` behind it - and lens[i] the columns that count.  N * S may be at most TABLE_STREAM_MAX_TOKENS.
+        `trace` (developer, rd_debug_table_decode_stream): a dict with any of "logits" [N, max_new, 960], "hidden" [N, max_new, 4, 768]
+        (float32) and "sched" [max_steps, slots, 2] (int32) device tensors, written inside the step."""
+        from .table_unitable import cfg_struct
+        if self.kind != "unitable_decoder":
+            raise EngineError("table_decode_stream: the handle is not a unitable_decoder model")
+        if memory.dim() != 3 or memory.shape[2] != 768:
+            raise EngineError(f"table_decode_stream: memory must be [N, S, 768], got {tuple(memory.shape)}")
+        memory = self._prep(memory)
+        N, S, _ = memory.shape
+        out = torch.empty((N, max(max_new_tokens, 0) + 1), dtype=torch.int64, device=memory.device)
+        lens = torch.empty((N,), dtype=torch.int32, device=memory.device)
+        st, cfg = TableStreamStats(), cfg_struct(ids)
+        if trace is None:
+            rc = self._l.rd_table_decode_stream(self._h, memory.data_ptr(), N, S, max_new_tokens, slots, C.byref(cfg), out.data_ptr(), lens.data_ptr(),
+                                                C.byref(st), _stream_ptr())
+        else:
+            ptr = lambda k: trace[k].data_ptr() if trace.get(k) is not None else None
+            sched = trace.get("sched")
+            rc = self._l.rd_debug_table_decode_stream(self._h, memory.data_ptr(), N, S, max_new_tokens, slots, C.byref(cfg), out.data_ptr(),
+                                                      lens.data_ptr(), C.byref(st), _stream_ptr(), ptr("logits"), ptr("hidden"), ptr("sched"),
+                                                      int(sched.shape[0]) if sched is not None else 0)
+        self._chk(rc)
+        return out, lens, {"steps": st.steps, "live_slot_steps": st.live_slot_steps, "slots": st.slots, "admitted": st.admitted}
 
     def table_decode_debug(self, memory: torch.Tensor, ids, steps: int, forced: Optional[torch.Tensor] = None):
         """Developer (rd_debug_table_decode): `steps` steps with traces; forced int32 [B, steps] = the token fed to every step (EOS latch

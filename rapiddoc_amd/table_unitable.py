@@ -22,6 +22,7 @@ import torch
 IMG_SIZE = 448
 MAX_SEQ_LEN = 1024
 MAX_BATCH = 8
+MAX_SLOTS = 8                # RD_TABLE_STREAM_MAX_SLOTS
 # pre_process.py: transforms.Normalize on the RGB image scaled to [0, 1]
 NORM_MEAN = (0.86597056, 0.88463002, 0.87491087)
 NORM_STD = (0.20686628, 0.18201602, 0.18485524)
@@ -130,12 +131,20 @@ class Mi355UniTableStructure:
     """`UniTableStructure` on the engine.  encoder / decoder: path to / bytes of a .safetensors file, or a state dict."""
 
     def __init__(self, encoder, decoder, ids: TableIds, id_to_token: Sequence[str], device: int = 0, max_new_tokens: int = MAX_SEQ_LEN,
-                 resize: str = "linear"):
+                 resize: str = "linear", batching: str = "chunk", slots: int = MAX_SLOTS):
         """`resize`: "linear" = the engine's 2-tap linear resize (rd_preproc_resize_norm), "pil" = Pillow's antialiased bilinear, the
-        reference's transforms.Resize on a PIL image, bit for bit (rd_preproc_resize_aa_norm)."""
+        reference's transforms.Resize on a PIL image, bit for bit (rd_preproc_resize_aa_norm).
+        `batching`: "chunk" decodes every group of 8 tables as one batch, which runs until its longest table has ended; "stream" encodes
+        the groups, then decodes all tables through `slots` (1 .. 8) decode rows that take the next waiting table as soon as theirs ends
+        (`RdEngine.table_decode_stream`).  Both return the same contexts in the caller's order."""
         from .engine import RdEngine
         if resize not in ("linear", "pil"):
             raise ValueError("resize must be 'linear' or 'pil'")
+        if batching not in ("chunk", "stream"):
+            raise ValueError("batching must be 'chunk' or 'stream'")
+        if isinstance(slots, bool) or not isinstance(slots, (int, np.integer)) or not 1 <= int(slots) <= MAX_SLOTS:
+            raise ValueError(f"slots must be an integer in 1 .. {MAX_SLOTS}, got {slots!r}")
+        self.batching, self.slots, self.last_stream_stats = batching, int(slots), []
         self.ids, self.id_to_token, self.max_new_tokens, self.resize = ids, list(id_to_token), int(max_new_tokens), resize
         self.encoder = RdEngine("unitable_encoder", device).load_weights(encoder)
         self.decoder = RdEngine("unitable_decoder", device).load_weights(decoder)
@@ -163,6 +172,8 @@ class Mi355UniTableStructure:
 
     def decode_ids(self, x: torch.Tensor) -> List[List[int]]:
         """normalised [B,3,448,448] -> per table the context the reference's loop ends with (prefix ... eos)"""
+        if self.batching == "stream":
+            return self._decode_ids_stream(x)
         out: List[List[int]] = []
         for i in range(0, x.shape[0], MAX_BATCH):
             memory = self.encoder.table_encoder_forward(x[i:i + MAX_BATCH])
@@ -171,11 +182,37 @@ class Mi355UniTableStructure:
             out.extend(ids[b, :n[b]].tolist() for b in range(ids.shape[0]))
         return out
 
+    def _decode_ids_stream(self, x: torch.Tensor) -> List[List[int]]:
+        """batching="stream": encode in groups of 8 into one [N,S,768] buffer, decode every window of tables that fits the token limit
+        with one `table_decode_stream`, cut the rows by `lens`."""
+        from .engine import TABLE_STREAM_MAX_TOKENS
+        self.last_stream_stats = []
+        N = int(x.shape[0])
+        if N == 0:
+            return []
+        memory = None
+        for i in range(0, N, MAX_BATCH):
+            m = self.encoder.table_encoder_forward(x[i:i + MAX_BATCH])
+            if memory is None:
+                memory = torch.empty((N,) + tuple(m.shape[1:]), dtype=torch.float32, device=m.device)
+            memory[i:i + m.shape[0]] = m
+        out: List[List[int]] = []
+        for beg, end in stream_windows(N, int(memory.shape[1]), TABLE_STREAM_MAX_TOKENS):
+            ids, lens, stats = self.decoder.table_decode_stream(memory[beg:end], self.ids, self.max_new_tokens, self.slots)
+            self.last_stream_stats.append(stats)
+            ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
+            out.extend(ids[b, :int(lens[b])].tolist() for b in range(ids.shape[0]))
+        return out
+
     def forward_tensor(self, x: torch.Tensor, ori_shapes: Optional[List[Tuple[int, int]]] = None):
         """The pinned path: (struct_list, total_bboxes) as the reference's __call__ returns them, from an already normalised tensor"""
         ori_shapes = ori_shapes or [(IMG_SIZE, IMG_SIZE)] * x.shape[0]
+        return self.finish(self.decode_ids(x), ori_shapes)
+
+    def finish(self, contexts: List[List[int]], ori_shapes: List[Tuple[int, int]]):
+        """contexts of `decode_ids` -> (struct_list, total_bboxes): the host functions behind the loop"""
         struct_list, total_bboxes = [], []
-        for ctx, (h, w) in zip(self.decode_ids(x), ori_shapes):
+        for ctx, (h, w) in zip(contexts, ori_shapes):
             bboxes, html = decode_tokens(ctx, self.id_to_token)
             total_bboxes.append(rescale_bboxes(h, w, bboxes) if len(bboxes) else bboxes)
             struct_list.append((wrap_with_html_struct(html), 1.0))
@@ -190,6 +227,17 @@ class Mi355UniTableStructure:
     def __call__(self, imgs: List[np.ndarray]):
         x, shapes = self.preprocess(imgs)
         return self.forward_tensor(x, shapes)
+
+
+def stream_windows(n: int, S: int, max_tokens: int) -> list:
+    """(begin, end) windows over n tables of S memory rows each: as many tables per `table_decode_stream` call as its token limit takes
+    (N * S <= max_tokens, i.e. max_tokens // S tables).  One table alone must fit."""
+    if n <= 0:
+        return []
+    per = max_tokens // S
+    if per < 1:
+        raise ValueError(f"one table has {S} memory rows, the stream decode takes {max_tokens} per call")
+    return [(b, min(n, b + per)) for b in range(0, n, per)]
 
 
 # ------------------------------------------------------------------------------------------------------------------ the whole table path
@@ -223,6 +271,11 @@ class Mi355RapidTable:
         if not isinstance(bgr_images, list):
             bgr_images = [bgr_images]
         pred_structures, cell_bboxes = self.structure(bgr_images)
+        return self._match(bgr_images, ocr_results, pred_structures, cell_bboxes)
+
+    def _match(self, bgr_images: list, ocr_results, pred_structures: list, cell_bboxes: list) -> TableOutput:
+        """what `__call__` does behind the structure model"""
+        from . import table_match as TM
         logic_points = TM.decode_logic_points(pred_structures)
         dt_boxes, rec_res = [], []
         if ocr_results is not None:
@@ -241,6 +294,18 @@ class Mi355RapidTable:
         there) -> the table's HTML, or None (no OCR rows; anything the reference's try / except swallows, such as a structure without a
         cell).  The cell text goes through normalize_table_cell_text before the tokens are joined (the reference re-serialises the
         finished HTML through BeautifulSoup instead: restated, not pinned)."""
+        bgr = self._front(image, ocr_result, fill_image_res, mfd_res, skip_text_in_image, use_img2table, skip_table_orientation)
+        if bgr is None:
+            return None                  # (the reference would run its own OCR engine first; the page driver always hands the rows over)
+        try:
+            return self([bgr], [ocr_result]).pred_htmls[0]
+        except Exception:                # as the reference: logged there, None here
+            return None
+
+    def _front(self, image, ocr_result=None, fill_image_res=None, mfd_res=None, skip_text_in_image=True, use_img2table=False,
+               skip_table_orientation=None):
+        """`predict` in front of the structure model: the switches that are not built raise, the OCR list is prepared in place; returns
+        the BGR image, or None when there are no OCR rows"""
         from . import table_match as TM
         if use_img2table:
             raise NotImplementedError("use_img2table=True needs the img2table route and an OCR engine of RapidOcrTable's shape, which are not part of this package")
@@ -252,12 +317,39 @@ class Mi355RapidTable:
             raise NotImplementedError("the portrait-rotation check needs a text detector on the table image (ocr_engine.ocr(rec=False)); "
                                       "pass an ocr_result or skip_table_orientation=True")
         if not ocr_result:
-            return None                  # (the reference would run its own OCR engine first; the page driver always hands the rows over)
-        TM.prepare_ocr_list(bgr, ocr_result, fill_image_res, mfd_res, skip_text_in_image)
-        try:
-            return self([bgr], [ocr_result]).pred_htmls[0]
-        except Exception:                # as the reference: logged there, None here
             return None
+        TM.prepare_ocr_list(bgr, ocr_result, fill_image_res, mfd_res, skip_text_in_image)
+        return bgr
+
+    def predict_many(self, items: Sequence[tuple]) -> list:
+        """`[self.predict(*it) for it in items]` with ONE structure call over every table that has OCR rows (so that a structure model
+        built with batching="stream" sees the page batch's tables together); the matcher runs per table, each table under the same
+        try / except -> None as in `predict`.  If the pooled structure call itself raises, every table goes the way `predict` takes it."""
+        results: list = [None] * len(items)
+        live = []                        # (index, bgr, ocr_result) of the tables that reach the structure model
+        for i, it in enumerate(items):
+            bgr = self._front(*it)
+            if bgr is not None:
+                live.append((i, bgr, it[1]))
+        if not live:
+            return results
+        try:
+            x, shapes = self.structure.preprocess([bgr for _i, bgr, _o in live])
+            contexts = self.structure.decode_ids(x)
+            if len(contexts) != len(live):
+                raise RuntimeError("the structure model returned another number of tables")
+        except Exception:
+            contexts = None
+        for k, (i, bgr, ocr_result) in enumerate(live):
+            try:
+                if contexts is None:
+                    results[i] = self([bgr], [ocr_result]).pred_htmls[0]
+                else:
+                    structs, boxes = self.structure.finish([contexts[k]], [shapes[k]])
+                    results[i] = self._match([bgr], [ocr_result], structs, boxes).pred_htmls[0]
+            except Exception:            # as `predict`
+                results[i] = None
+        return results
 
     def batch_predict(self, images: list, ocr_result=None, fill_image_res=None, mfd_res=None, skip_text_in_image=True, use_img2table=False,
                       skip_table_orientation=None) -> list:
