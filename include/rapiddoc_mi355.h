@@ -16,6 +16,8 @@
  *                           rapid_doc/model/table/rapid_table_self/table_structure/unitable/pre_process.py
  *   rd_formula_margin_boxes, rd_formula_preproc_plan, rd_formula_preproc_batch <- UniMERNetImgDecode + UniMERNetTestTransform +
  *                           LatexImageFormat: .../model_handler/pp_formulanet_plus/pre_process.py:39-246
+ *   rd_region_canvases   <- crop_img + _apply_mask_boxes_to_image for a batch of regions: rapid_doc/utils/model_utils.py:90-124,
+ *                           rapid_doc/backend/pipeline/analyze_utils.py:82-103,131-145
  *   rd_load_weights      <- `_load_state_dict` + `load_state_dict`: rapid_doc/model/ocr/torch.py:82-110
  *
  * Conventions: every pointer named *_dev is a DEVICE pointer on the handle's GPU (PyTorch-ROCm
@@ -488,6 +490,35 @@ size_t rd_checkbox_workspace(int P, int H, int W, int max_runs, int max_cand, si
 int rd_checkbox_detect_device(int device_id, const uint8_t* pages_dev, int P, int H, int W, int bgr, int max_runs, int max_cand, void* ws_dev,
                               size_t ws_bytes, rd_checkbox_page* hdr_dev, rd_checkbox_cand* cands_dev, void* stream);
 int rd_checkbox_finish(const rd_checkbox_cand* cands, int n, int H, int W, rd_checkbox_box* out, int max_out, int32_t* n_out);
+
+/* Region composition on the device (csrc/kernels_region.hip, csrc/region_geom.h; docs/notebook/region_compose.md): the canvases that the
+ * OCR and table stages hand to the detector and the recogniser - crop_img (rapid_doc/utils/model_utils.py:90-124) with its polygon mask and
+ * _apply_mask_boxes_to_image (analyze_utils.py:82-103) - for n regions in one launch.  Every region names its own page, so the pages of a
+ * launch may differ in size.  Canvas k of canv_dev [n][gh][gw][3] u8 is
+ *     255 everywhere;
+ *     the page pixel where the canvas pixel maps into the region rectangle clipped to the page: x0c = max(0, x0), x1c = min(page_w, x1),
+ *     the same for y, at canvas offset paste + (clipped - unclipped);
+ *     with a polygon, 255 again wherever cv2.fillPoly's raster of the polygon - translated by the UNclipped (x0, y0), on a window of the
+ *     clipped size [y1c - y0c][x1c - x0c] - is not set (rd_fill_poly's pixels exactly; vertices are int32, truncated by the caller).
+ * det_canv_dev (may be NULL: not written) is the same canvas with every mask box of the region at 255.
+ * ws_dev: rd_region_canvases_workspace bytes of device scratch (0 on bad arguments) when any region has a polygon, else unused and may be
+ * NULL; pts_dev / boxes_dev may be NULL when no region has a polygon / a box.  The descriptors and the boxes are read back on `stream` and
+ * checked before anything is launched (64 bytes a region, 16 a box; the stream is synchronised).  Return 0 = ok, 1 = bad arguments -
+ * NULL pointers, n < 1, gh or gw outside 1 .. 16384, a polygon above RD_REGION_MAX_POLY, a box that is empty or leaves its canvas,
+ * coordinates beyond +-2^28, a workspace that is too small: nothing launched, the message is rd_create_error()'s. */
+#define RD_REGION_MAX_POLY 64
+typedef struct rd_region_desc {
+    const uint8_t* page;      /* device address of the page's pixel (0,0), channel 0 (3-channel u8 HWC) */
+    int64_t pitch;            /* bytes per page row (a page may be a window of a larger buffer) */
+    int32_t page_w, page_h;
+    int32_t x0, y0, x1, y1;   /* region rectangle in page coordinates, UNclipped (may overhang or miss the page) */
+    int32_t paste_x, paste_y; /* canvas position of (x0, y0) */
+    int32_t poly_off, poly_n; /* vertices in pts_dev (int32 x, y pairs, page coordinates); poly_n = 0: none */
+    int32_t box_off, box_n;   /* mask boxes in boxes_dev (int32 x0, y0, x1, y1 in CANVAS coordinates, already clipped, non-empty) */
+} rd_region_desc;
+size_t rd_region_canvases_workspace(int n, int gh, int gw);
+int rd_region_canvases(int device_id, const rd_region_desc* descs_dev, int n, const int32_t* pts_dev, const int32_t* boxes_dev,
+                       int gh, int gw, uint8_t* canv_dev, uint8_t* det_canv_dev /* may be NULL */, void* ws_dev, size_t ws_bytes, void* stream);
 
 /* Host: chunk sizes of the recogniser's THROUGHPUT mode (the engine's own scheduling; rapidocr's fixed rec_batch_num chunks,
  * rapid_doc/model/ocr/rapid_ocr.py:430-440, are the `strict` mode of rapiddoc_amd.pipeline.PagePipeline).  wpad_sorted[i] = padded

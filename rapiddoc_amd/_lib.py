@@ -67,6 +67,9 @@ SYMBOLS = {
     "rd_checkbox_detect_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
     "rd_checkbox_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "rd_region_canvases_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "rd_region_canvases": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     "rd_contour_area": (C.c_double, [C.c_void_p, C.c_int]),
     "rd_arc_length": (C.c_double, [C.c_void_p, C.c_int, C.c_int]),
     "rd_approx_poly_dp": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
@@ -98,6 +101,7 @@ DEBUG_SYMBOLS = {
     "rd_debug_formula_decode_stream": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I]),
     "rd_debug_resize_aa_coeffs": (_I, [_I, _I, _P, _P, C.c_int64]),
     "rd_debug_resample_coeffs": (_I, [_I, _I, C.c_double, C.c_double, _I, _P, _P, C.c_int64]),
+    "rd_debug_region_keep_mask": (_I, [_I, _I, _P, _I, _P]),
     "rd_debug_time_mixer": (_F, [_I] * 4 + [_P] * 6),
     "rd_debug_time_gemm": (_F, [_I] * 5 + [_P] * 6),
     "rd_debug_gemm_h1": (_F, [_I] * 5 + [_P, _I, _P, _P, _P, _I, _P, _I, _P]),

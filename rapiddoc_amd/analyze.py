@@ -20,18 +20,90 @@ reference's (one global argsort, chunks of 6), otherwise `rec_batch_num` is GPU 
 from __future__ import annotations
 
 import math
+import os
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import layout_host, layout_polygon, ocr_host, table_host
-from .engine import preproc_resize_norm_batch
+from .engine import REGION_MAX_POLY, Region, RegionStage, preproc_resize_norm_batch, region_canvases, region_polygon
 
 OCR_TEXT, LOW_SCORE_TEXT = 15, 16                 # utils/enum_class.py:103-104
 MIN_CONFIDENCE, MIN_WIDTH = 0.5, 3                # utils/ocr_utils.py:9-11
 PASTE = 50                                        # analyze_utils.py:131
 _SPECIAL = ("（204号", "（20", "（2", "（2号", "（20号", "号", "（204")   # analyze_utils.py:288
+# RD_REGION_COMPOSE (read once): "host" = the detector / recogniser canvases of the OCR and table stages are put together with torch calls
+# per region and host-rasterised polygon masks (the code before the device route, kept for A/B); "device" = device-resident pages take
+# `engine.region_canvases`, one launch per size group; unset = COMPOSE_DEVICE_BY_DEFAULT (docs/notebook/region_compose.md has the measurement).
+COMPOSE_SWITCH = os.environ.get("RD_REGION_COMPOSE", "").strip().lower()
+COMPOSE_DEVICE_BY_DEFAULT = True
+
+
+def compose_route(compose: Optional[str] = None) -> str:
+    """"host" | "device": `compose` (RegionOcr(compose=...)) overrides RD_REGION_COMPOSE, which overrides the default."""
+    if compose is not None:
+        if compose not in ("host", "device"):
+            raise ValueError(f"compose must be 'host' or 'device', not {compose!r}")
+        return compose
+    if COMPOSE_SWITCH in ("host", "device"):
+        return COMPOSE_SWITCH
+    return "device" if COMPOSE_DEVICE_BY_DEFAULT else "host"
+
+
+class PageSet:
+    """The page batch as the stages read it: today's [P, H, W, 3] uint8 tensor, or a sequence of [H_i, W_i, 3] uint8 tensors on one
+    device - the reference takes a list of page images of any sizes (batch_analyze.py:78-111)."""
+
+    def __init__(self, pages):
+        self.tensor: Optional[torch.Tensor] = None
+        self._packed: Dict[int, torch.Tensor] = {}
+        if isinstance(pages, torch.Tensor):
+            assert pages.dtype == torch.uint8 and pages.dim() == 4 and pages.shape[3] == 3
+            self.tensor = pages
+            self._pages = None
+        else:
+            self._pages = list(pages)
+            for t in self._pages:
+                assert isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3, "a page is a [H, W, 3] uint8 tensor"
+            assert len({t.device for t in self._pages}) <= 1, "the pages of a batch live on one device"
+
+    @property
+    def count(self) -> int:
+        return int(self.tensor.shape[0]) if self.tensor is not None else len(self._pages)
+
+    def page(self, p: int) -> torch.Tensor:
+        return self.tensor[p] if self.tensor is not None else self._pages[p]
+
+    def packed(self, p: int) -> torch.Tensor:
+        """page p with pixels and channels packed (strides [pitch, 3, 1]), as the kernels read a page; copied once if it is not"""
+        t = self.page(p)
+        if t.stride(2) == 1 and t.stride(1) == 3:
+            return t
+        if p not in self._packed:
+            self._packed[p] = t.contiguous()
+        return self._packed[p]
+
+    def hw(self, p: int):
+        t = self.page(p)
+        return int(t.shape[0]), int(t.shape[1])
+
+    def as_list(self) -> List[torch.Tensor]:
+        return [self.page(p) for p in range(self.count)]
+
+    @property
+    def device(self) -> torch.device:
+        if self.tensor is not None:
+            return self.tensor.device
+        return self._pages[0].device if self._pages else torch.device("cpu")
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.device.type == "cuda"
+
+
+def page_set(pages) -> PageSet:
+    return pages if isinstance(pages, PageSet) else PageSet(pages)
 
 
 def _formula_boxes_in_crop(formulas: Sequence[dict], useful: Sequence[int]) -> List[List[float]]:
@@ -83,18 +155,19 @@ def _int_box(b, h: int, w: int) -> Optional[List[int]]:
     return [x0, y0, x1, y1] if x1 > x0 and y1 > y0 else None
 
 
-def crop_region(pages: torch.Tensor, p: int, det: dict) -> Optional[np.ndarray]:
+def crop_region(pages, p: int, det: dict) -> Optional[np.ndarray]:
     """`crop_img(det, page)[0]` with no margin (utils/model_utils.py:90-124): the integer box of the detection on a white canvas - page
     pixels where the box lies on the page, white outside it and outside the detection's polygon, if it has one.  RGB u8 numpy; None
     for an inverted box (the reference's np.ones of a negative size raises)."""
-    _P, H, W, _ = pages.shape
+    pages = page_set(pages)
+    H, W = pages.hw(p)
     x0, y0, x1, y1 = (int(v) for v in (det["poly"][0], det["poly"][1], det["poly"][4], det["poly"][5]))
     if x1 < x0 or y1 < y0:
         return None
     crop = np.full((y1 - y0, x1 - x0, 3), 255, np.uint8)
     x0c, y0c, x1c, y1c = max(0, x0), max(0, y0), min(W, x1), min(H, y1)
     if x1c > x0c and y1c > y0c:
-        part = pages[p, y0c:y1c, x0c:x1c].cpu().numpy()
+        part = pages.page(p)[y0c:y1c, x0c:x1c].cpu().numpy()
         if det.get("polygon_points"):
             part = part.copy()
             part[~layout_polygon.polygon_keep_mask(part.shape[:2], det["polygon_points"], x0, y0)] = 255
@@ -102,7 +175,7 @@ def crop_region(pages: torch.Tensor, p: int, det: dict) -> Optional[np.ndarray]:
     return crop
 
 
-def attach_table_images(pages: torch.Tensor, p: int, dets: Sequence[dict]) -> None:
+def attach_table_images(pages, p: int, dets: Sequence[dict]) -> None:
     """Second half of get_res_list_from_layout_res (utils/model_utils.py:181-194): every image region lying inside a table is attached
     to that table's detection as `layout_image_list` = [{uuid, poly, pil_image}] (the table stage pops the field again; with tables
     switched off it stays in the output, as in the reference)."""
@@ -115,7 +188,7 @@ def attach_table_images(pages: torch.Tensor, p: int, dets: Sequence[dict]) -> No
         tb.setdefault("layout_image_list", []).append({"uuid": str(uuid.uuid4()), "poly": im["poly"], "pil_image": Image.fromarray(crop)})
 
 
-def recognise_formulas(pages: torch.Tensor, layout_dets_per_page: Sequence[Sequence[dict]], formula_model,
+def recognise_formulas(pages, layout_dets_per_page: Sequence[Sequence[dict]], formula_model,
                        expand_px: int = 2, batch_size: int = 16) -> int:
     """Formula branch of BatchAnalyze (batch_analyze.py:258-283): every formula region (category 8 / 13 / 14) is cropped
     - grown by `bbox_expand_px` where no neighbouring layout box is in the way - and handed to
@@ -126,10 +199,11 @@ def recognise_formulas(pages: torch.Tensor, layout_dets_per_page: Sequence[Seque
     RD_FORMULA_PREPROC keeps the pre-process on the host; every other model, and every region with `polygon_points` (the white-out is
     a host mask), gets numpy crops as before."""
     from . import formula_host
-    P, H, W, _ = pages.shape
+    pages = page_set(pages)
     targets, crops = [], []
     on_device = bool(getattr(formula_model, "accepts_device_images", False)) and pages.is_cuda and formula_host.device_preproc_enabled()
     for p, dets in enumerate(layout_dets_per_page):
+        H, W = pages.hw(p)                                                   # the page's own size: the batch may mix sizes
         for d in dets:
             if int(d["category_id"]) not in layout_host.FORMULA_CATEGORY_IDS:
                 continue
@@ -140,9 +214,9 @@ def recognise_formulas(pages: torch.Tensor, layout_dets_per_page: Sequence[Seque
                 continue
             targets.append(d)
             if on_device and not c.get("polygon_points"):                # the window itself: pre-processed on the device with its chunk
-                crops.append(pages[p, y0:y1, x0:x1])
+                crops.append(pages.page(p)[y0:y1, x0:x1])
                 continue
-            crop = pages[p, y0:y1, x0:x1].cpu().numpy()                  # RGB crop, no margin (crop_img with paste 0)
+            crop = pages.page(p)[y0:y1, x0:x1].cpu().numpy()                  # RGB crop, no margin (crop_img with paste 0)
             if c.get("polygon_points"):                                  # crop_img whites out what lies outside the polygon
                 crop = crop.copy()
                 crop[~layout_polygon.polygon_keep_mask(crop.shape[:2], c["polygon_points"], int(c["poly"][0]), int(c["poly"][1]))] = 255
@@ -156,7 +230,7 @@ def recognise_formulas(pages: torch.Tensor, layout_dets_per_page: Sequence[Seque
 
 class RegionOcr:
     def __init__(self, pipeline, box_thresh: float = 0.3, unclip_ratio: float = 1.8, lang: str = "ch",
-                 det_batch_num: Optional[int] = None, det_raw_fn=None):
+                 det_batch_num: Optional[int] = None, det_raw_fn=None, compose: Optional[str] = None):
         """`pipeline`: a `rapiddoc_amd.pipeline.PagePipeline` (its det / rec engines and streams are reused).  box_thresh 0.3 /
         unclip 1.8 are the page-OCR settings of backend/pipeline/model_init.py:73.
 
@@ -165,10 +239,13 @@ class RegionOcr:
         is, the number only reaches `det_raw_fn`.
         `det_raw_fn(canvases [b,H64,W64,3] u8 RGB, batch_size) -> [raw boxes [n,4,2] per image]` replaces the detector
         (pre-process, network, DB post-process) of a size group - the seam `ocr_model.det_batch_predict` is in the reference
-        (analyze_utils.py:187).  Used by tests/test_analyze_trace.py to replay traces of the reference's own driver."""
+        (analyze_utils.py:187).  Used by tests/test_analyze_trace.py to replay traces of the reference's own driver.
+        `compose`: "host" | "device", where the canvases of device-resident pages are put together (`compose_route`; default: the
+        RD_REGION_COMPOSE switch).  Pages in host memory are always composed on the host."""
         self.pipe = pipeline
         self.box_thresh, self.unclip_ratio, self.lang = box_thresh, unclip_ratio, lang
         self.det_batch_num, self.det_raw_fn = det_batch_num, det_raw_fn
+        self.compose = compose_route(compose)
 
     def _pipe_for(self, lang: str):
         """`pipeline` may be one PagePipeline (every page is of language `lang`) or a dict {language: PagePipeline} - the reference
@@ -208,11 +285,63 @@ class RegionOcr:
         q = ocr_host.merge_det_boxes(ocr_host.sorted_boxes(np.asarray(raw_boxes, dtype=np.float32)))
         return np.asarray(q, dtype=np.float32).reshape(-1, 4, 2)
 
+    # ------------------------------------------------------------------ the canvases of one size group
+    @staticmethod
+    def _compose_host(pages: PageSet, regions, members, gh: int, gw: int):
+        """(canv, det_canv) of a size group with torch calls per region - the "host" route, and the route of pages in host memory."""
+        canv = torch.full((len(members), gh, gw, 3), 255, dtype=torch.uint8, device=pages.device)
+        for k, ridx in enumerate(members):
+            p, _r, (px, py, x0, y0, x1, y1, _nw, _nh), fboxes = regions[ridx]
+            H, W = pages.hw(p)
+            x0c, y0c, x1c, y1c = max(0, x0), max(0, y0), min(W, x1), min(H, y1)      # numpy slicing clips the same way
+            if x1c > x0c and y1c > y0c:
+                dst = canv[k, py + (y0c - y0): py + (y0c - y0) + (y1c - y0c), px + (x0c - x0): px + (x0c - x0) + (x1c - x0c)]
+                dst[:] = pages.page(p)[y0c:y1c, x0c:x1c]
+                if _r.get("polygon_points"):       # crop_img (model_utils.py:109-118): outside the region's polygon -> white,
+                    keep = layout_polygon.polygon_keep_mask((y1c - y0c, x1c - x0c), _r["polygon_points"], x0, y0)   # for det AND rec
+                    dst[~torch.from_numpy(keep).to(dst.device)] = 255
+        det_canv = canv.clone() if any(regions[ridx][3] for ridx in members) else canv
+        for k, ridx in enumerate(members):
+            nh, nw = regions[ridx][2][7], regions[ridx][2][6]
+            for fb in regions[ridx][3]:             # _apply_mask_boxes_to_image (analyze_utils.py:82-103)
+                ib = _int_box(fb, nh, nw)
+                if ib:
+                    det_canv[k, ib[1]:ib[3], ib[0]:ib[2]] = 255
+        return canv, det_canv
+
+    @staticmethod
+    def _device_groups(pages: PageSet, regions, groups):
+        """The "device" route's regions (host only): (indices of the size groups the device composes, their engine.Region lists).
+        A group that holds a polygon above the kernel's vertex cap is left out - it is composed by `_compose_host`, whole."""
+        chosen, lists = [], []
+        for gi, (_lang, _hw, members, _bs) in enumerate(groups):
+            rs = []
+            for ridx in members:
+                p, r, (px, py, x0, y0, x1, y1, nw, nh), fboxes = regions[ridx]
+                poly = region_polygon(r["polygon_points"]) if r.get("polygon_points") else None
+                if poly is not None and len(poly) > REGION_MAX_POLY:
+                    break
+                boxes = [ib for ib in (_int_box(fb, nh, nw) for fb in fboxes) if ib]
+                rs.append(Region(pages.packed(p), (x0, y0, x1, y1), (px, py), poly, boxes))
+            else:
+                chosen.append(gi)
+                lists.append(rs)
+        return chosen, lists
+
+    @staticmethod
+    def _stage_groups(pages: PageSet, regions, groups) -> dict:
+        """{group index: (engine.RegionStage, position in it)}: the descriptors of `_device_groups` in one staging buffer, one upload."""
+        chosen, lists = RegionOcr._device_groups(pages, regions, groups)
+        if not chosen:
+            return {}
+        stage = RegionStage(lists, pages.device)
+        return {gi: (stage, at) for at, gi in enumerate(chosen)}
+
     # ------------------------------------------------------------------ whole batch
-    def __call__(self, pages: torch.Tensor, layout_dets_per_page: Sequence[Sequence[dict]], det_maps_fn=None,
+    def __call__(self, pages, layout_dets_per_page: Sequence[Sequence[dict]], det_maps_fn=None,
                  page_langs: Optional[Sequence[str]] = None, mask_boxes_per_page: Optional[Sequence[Sequence[dict]]] = None,
                  page_keys: Optional[Sequence[int]] = None, all_langs: Optional[Sequence[str]] = None) -> List[List[dict]]:
-        """pages [P,H,W,3] u8 RGB (GPU); returns, per page, the layout detections followed by their OcrText spans
+        """pages [P,H,W,3] u8 RGB (GPU), or a sequence of [H_i,W_i,3] pages of any sizes; returns, per page, the layout detections followed by their OcrText spans
         (`layout_res` of the reference after both OCR stages).  `det_maps_fn(regions, (gh, gw), (dh, dw))` may supply the
         det maps of a size group (see `_detect_group`); regions = [(page, region dict, useful_list)].
         `page_langs[p]`: the language of page p (the `lang` of the reference's input tuples); regions are grouped by language first
@@ -224,8 +353,9 @@ class RegionOcr:
         those of the unsharded batch; `all_langs` = every language of the global batch in one agreed order (default: this
         object's language) - each rank makes one pooled recogniser call per language, also for a language it holds no region of,
         so the exchanges pair up across ranks."""
-        assert pages.dtype == torch.uint8 and (pages.is_cuda or self.det_raw_fn is not None)
-        P, H, W, _ = pages.shape
+        pages = page_set(pages)                          # the tensor, or a sequence of [H_i, W_i, 3] pages of any sizes
+        assert pages.is_cuda or self.det_raw_fn is not None
+        P = pages.count
         assert page_keys is None or len(page_keys) == P
         pipes = list(self.pipe.values()) if isinstance(self.pipe, dict) else [self.pipe]
         synced = any(getattr(pp, "rec_width_sync", None) is not None for pp in pipes)
@@ -247,27 +377,18 @@ class RegionOcr:
         langs = [self.lang if page_langs is None else page_langs[p] for p, _r, _u, _f in regions]
         groups = ocr_host.det_buckets([(u[7], u[6]) for _, _, u, _ in regions], langs, det_batch_num=len(regions))
         pending = []                                   # per size group: (unmasked canvases, quads, spans, page of each image)
-        for _lang, (gh, gw), members, _bs in groups:
-            canv = torch.full((len(members), gh, gw, 3), 255, dtype=torch.uint8, device=pages.device)
-            # The reference whites the formula boxes out of a COPY that only the detector sees (`det_image`,
-            # analyze_utils.py:136-145); the line crops for the recogniser come from the unmasked region image
-            # (`bgr_image`, analyze_utils.py:199 -> ocr_utils.py:361-383).  Two canvases: `canv` unmasked, `det_canv` masked.
-            for k, ridx in enumerate(members):
-                p, _r, (px, py, x0, y0, x1, y1, _nw, _nh), fboxes = regions[ridx]
-                x0c, y0c, x1c, y1c = max(0, x0), max(0, y0), min(W, x1), min(H, y1)      # numpy slicing clips the same way
-                if x1c > x0c and y1c > y0c:
-                    dst = canv[k, py + (y0c - y0): py + (y0c - y0) + (y1c - y0c), px + (x0c - x0): px + (x0c - x0) + (x1c - x0c)]
-                    dst[:] = pages[p, y0c:y1c, x0c:x1c]
-                    if _r.get("polygon_points"):       # crop_img (model_utils.py:109-118): outside the region's polygon -> white,
-                        keep = layout_polygon.polygon_keep_mask((y1c - y0c, x1c - x0c), _r["polygon_points"], x0, y0)   # for det AND rec
-                        dst[~torch.from_numpy(keep).to(dst.device)] = 255
-            det_canv = canv.clone() if any(regions[ridx][3] for ridx in members) else canv
-            for k, ridx in enumerate(members):
-                nh, nw = regions[ridx][2][7], regions[ridx][2][6]
-                for fb in regions[ridx][3]:             # _apply_mask_boxes_to_image (analyze_utils.py:82-103)
-                    ib = _int_box(fb, nh, nw)
-                    if ib:
-                        det_canv[k, ib[1]:ib[3], ib[0]:ib[2]] = 255
+        # The reference whites the formula boxes out of a COPY that only the detector sees (`det_image`,
+        # analyze_utils.py:136-145); the line crops for the recogniser come from the unmasked region image
+        # (`bgr_image`, analyze_utils.py:199 -> ocr_utils.py:361-383).  Two canvases: `canv` unmasked, `det_canv` masked.
+        # Device-resident pages on the "device" route: every group's descriptors in one staging buffer, then one launch per group.
+        staged = self._stage_groups(pages, regions, groups) if self.compose == "device" and pages.is_cuda else {}
+        for gi, (_lang, (gh, gw), members, _bs) in enumerate(groups):
+            if gi in staged:
+                stage, at = staged[gi]
+                canv, det_canv = region_canvases(stage.groups[at], (gh, gw), any(r.boxes for r in stage.groups[at]), stage, at)
+                det_canv = canv if det_canv is None else det_canv
+            else:
+                canv, det_canv = self._compose_host(pages, regions, members, gh, gw)
             override = None
             if det_maps_fn is not None:
                 override = det_maps_fn([regions[i][:3] for i in members], (gh, gw), ocr_host.det_resize_shape(gh, gw, 960, "max"))
@@ -376,13 +497,14 @@ class TableOcr:
     _warned_line_level = False       # the use_word_box downgrade is reported once per process
 
     def __init__(self, pipeline, det_raw_fn=None, rec_fn=None, skip_text_in_image: bool = True, use_img2table: bool = False,
-                 table_formula_enable: bool = True, lang: str = "ch", use_word_box: bool = True, pooled: bool = False):
+                 table_formula_enable: bool = True, lang: str = "ch", use_word_box: bool = True, pooled: bool = False,
+                 compose: Optional[str] = None):
         """`pooled`: when the table model has `predict_many` (table_unitable.Mi355RapidTable), collect the per-table work of the whole
         page batch - crop, masked detection, recognition, fill images - and hand it over in ONE call, so that the structure model sees the
         tables together; the answers land on the detections exactly as the per-table loop writes them.  Default off: the per-table
-        route is the reference's order of calls."""
+        route is the reference's order of calls.  `compose`: see RegionOcr."""
         self.pipe, self.rec_fn, self.use_word_box, self.pooled = pipeline, rec_fn, use_word_box, bool(pooled)
-        self.det = RegionOcr(pipeline, box_thresh=0.5, unclip_ratio=1.6, lang=lang, det_raw_fn=det_raw_fn)
+        self.det = RegionOcr(pipeline, box_thresh=0.5, unclip_ratio=1.6, lang=lang, det_raw_fn=det_raw_fn, compose=compose)
         self.skip_text_in_image, self.use_img2table, self.table_formula_enable = skip_text_in_image, use_img2table, table_formula_enable
 
     def ocr_result(self, table: torch.Tensor, adjusted: Optional[List[dict]], maps_override: Optional[torch.Tensor] = None,
@@ -392,7 +514,13 @@ class TableOcr:
         h, w, _ = table.shape
         canvas = table.unsqueeze(0)
         det_canvas = canvas
-        if adjusted:
+        if self.det.compose == "device" and table.is_cuda and h > 0 and w > 0:
+            # the crop as ONE region with paste 0 on a canvas of its own size: `canvas` and the masked copy in one launch
+            boxes = [ib for ib in (_int_box(f["bbox"], h, w) for f in adjusted or ()) if ib]
+            view = table if table.stride(2) == 1 and table.stride(1) == 3 else table.contiguous()
+            canvas, det_canvas = region_canvases([Region(view, (0, 0, w, h), (0, 0), None, boxes)], (h, w), bool(boxes))
+            det_canvas = canvas if det_canvas is None else det_canvas
+        elif adjusted:
             det_canvas = canvas.clone()
             for f in adjusted:                          # _apply_mask_boxes_to_image
                 ib = _int_box(f["bbox"], h, w)
@@ -452,7 +580,7 @@ class TableOcr:
             out.extend([wr[2], table_host.normalize_table_ocr_text(wr[0]), wr[1]] for wr in res[2])
         return [list(x) for x in zip(*out)] if out else []
 
-    def __call__(self, pages: torch.Tensor, layout_dets_per_page: Sequence[Sequence[dict]], table_model,
+    def __call__(self, pages, layout_dets_per_page: Sequence[Sequence[dict]], table_model,
                  page_scales: Optional[Sequence[float]] = None, det_maps_fn=None, table_image_enable: bool = True,
                  page_langs: Optional[Sequence[str]] = None, mask_boxes_per_page: Optional[Sequence[Sequence[dict]]] = None) -> int:
         """Writes `html` (and `formula_boxes` / `img_boxes`) into the table detections IN PLACE; returns the number of tables handed to
@@ -461,6 +589,7 @@ class TableOcr:
         reference appends to the formulas everywhere in this stage (analyze_utils.py:318-321,411-415); their `checkbox` text travels
         to the table model like a formula's `latex`."""
         n = 0
+        pages = page_set(pages)
         pool = self.pooled and hasattr(table_model, "predict_many")
         waiting = []                     # pooled: (detection, predict's arguments, formulas, fill, scale) of every table of the page batch
 
@@ -484,7 +613,7 @@ class TableOcr:
                 if rect is None:
                     continue
                 x0, y0, x1, y1 = rect
-                table = pages[p, y0:y1, x0:x1]
+                table = pages.page(p)[y0:y1, x0:x1]
                 useful = [0, 0, x0, y0, x1, y1, int(table.shape[1]), int(table.shape[0])]
                 adjusted = None
                 if self.table_formula_enable:
@@ -582,17 +711,18 @@ class PageAnalyzer:
                  formula_expand_px: int = 2, det_batch_num: Optional[int] = None, det_raw_fn=None, lang: str = "ch",
                  table_det_raw_fn=None, table_rec_fn=None, table_image_enable: bool = True, table_use_word_box: bool = True,
                  seal_model=None, seal_enable: bool = True, checkbox_fn=None, checkbox_enable: bool = False,
-                 orientation_model=None, use_doc_orientation_classify: bool = False, table_pooled: bool = False):
+                 orientation_model=None, use_doc_orientation_classify: bool = False, table_pooled: bool = False,
+                 compose: Optional[str] = None):
         """`table_pooled`: see TableOcr(pooled=...).  Batch sizes default to the reference's (layout_config['batch_num'] / formula_config['batch_num'] = 1,
-        batch_analyze.py:66-71); `det_batch_num` / `det_raw_fn`: see RegionOcr."""
+        batch_analyze.py:66-71); `det_batch_num` / `det_raw_fn` / `compose`: see RegionOcr."""
         self.layout_model, self.pipe = layout_model, pipeline
         self.formula_model, self.table_model, self.custom_ocr = formula_model, table_model, custom_ocr
         self.layout_batch_size, self.formula_level = layout_batch_size, formula_level
         self.formula_batch_size, self.formula_expand_px = formula_batch_size, formula_expand_px
-        self.ocr = RegionOcr(pipeline, box_thresh, unclip_ratio, lang, det_batch_num, det_raw_fn)
+        self.ocr = RegionOcr(pipeline, box_thresh, unclip_ratio, lang, det_batch_num, det_raw_fn, compose=compose)
         # table_config["use_word_box"], default True (analyze_utils.py:308): word-level OCR entries for the table model
         self.table_ocr = TableOcr(pipeline, det_raw_fn=table_det_raw_fn, rec_fn=table_rec_fn, lang=lang, use_word_box=table_use_word_box,
-                                  pooled=table_pooled)
+                                  pooled=table_pooled, compose=compose)
         self.table_image_enable = table_image_enable          # table_config["table_image_enable"], default True (batch_analyze.py:75)
         # 7. seal OCR (ocr_config["seal_enable"], default True, batch_analyze.py:62,150-151): `seal_model` = the RapidOcrModel-shaped object
         #    the reference obtains with get_atom_model(OCR, is_seal=True) - `.ocr(bgr crop, det=True, rec=True) -> [[(box, (text, score)), ...]]`.
@@ -615,31 +745,42 @@ class PageAnalyzer:
             raise ValueError("use_doc_orientation_classify needs an orientation_model (ONNX-only in the reference, not part of this build)")
         self.last_rotate_labels: List[str] = []
 
-    def __call__(self, pages: torch.Tensor, det_maps_fn=None, page_scales: Optional[Sequence[float]] = None,
+    def __call__(self, pages, det_maps_fn=None, page_scales: Optional[Sequence[float]] = None,
                  table_det_maps_fn=None, page_langs: Optional[Sequence[str]] = None,
                  page_keys: Optional[Sequence[int]] = None, all_langs: Optional[Sequence[str]] = None) -> List[List[dict]]:
-        """`page_keys` / `all_langs`: page-sharded runs, see RegionOcr.__call__ (the OCR stage's pooled recogniser call is the one step
+        """`pages`: the [P, H, W, 3] uint8 tensor, or a sequence of [H_i, W_i, 3] uint8 tensors of any sizes on one device (`PageSet`) -
+        then the layout model gets that list, the checkbox stage one `detect_pages` call per page, and the orientation stage turns every
+        sideways page by itself, so a list may mix upright and sideways pages (a tensor that mixes them is refused, as before).
+        `page_keys` / `all_langs`: page-sharded runs, see RegionOcr.__call__ (the OCR stage's pooled recogniser call is the one step
         of the batch whose result depends on the other pages; tables, formulas and layout are per region / per page).
         `page_scales[p]`: the render scale the reference carries with every page (the `scale` of its input tuples); only the
         `formula_boxes` written next to a table's `html` use it (analyze_utils.py:405-418).  Default 1."""
-        assert pages.dtype == torch.uint8 and pages.dim() == 4 and (pages.is_cuda or self.ocr.det_raw_fn is not None)
+        as_tensor = isinstance(pages, torch.Tensor)      # else: a sequence of [H_i, W_i, 3] pages, any sizes, one device
+        if as_tensor:
+            assert pages.dtype == torch.uint8 and pages.dim() == 4
+        assert page_set(pages).is_cuda or self.ocr.det_raw_fn is not None
         # 0. page orientation (off by default): classify every page, turn the 90 / 270 ones upright (get_rotate_image, utils/boxbase.py:
         #    312-326: "270" -> cv2.ROTATE_90_CLOCKWISE, "90" -> counter-clockwise; 0 and 180 are left as they are)
         orig_hw_label = []
         if self.use_doc_orientation_classify:
-            labels = [self.orientation_model.predict(pages[i].cpu().numpy()) for i in range(pages.shape[0])]
+            given = page_set(pages)
+            labels = [self.orientation_model.predict(given.page(i).cpu().numpy()) for i in range(given.count)]
             turned = [lb in ("90", "270") for lb in labels]
-            if any(turned) and not all(turned):
+            if as_tensor and any(turned) and not all(turned):
                 raise NotImplementedError("a batch that mixes upright and sideways pages: the page tensor is one [P,H,W,3] array - "
-                                          "hand the two groups over as separate batches")
-            orig_hw_label = [(int(pages.shape[1]), int(pages.shape[2]), lb) for lb in labels]
-            if all(turned) and labels:
+                                          "hand the two groups over as separate batches, or the pages as a list")
+            orig_hw_label = [(*given.hw(i), lb) for i, lb in enumerate(labels)]
+            if as_tensor and all(turned) and labels:
                 pages = torch.stack([torch.rot90(pages[i], 1 if lb == "90" else -1, dims=(0, 1)) for i, lb in enumerate(labels)]).contiguous()
+            elif not as_tensor:                          # every sideways page is turned by itself: a list may mix the two kinds
+                pages = [torch.rot90(given.page(i), 1 if lb == "90" else -1, dims=(0, 1)).contiguous() if t else given.page(i)
+                         for i, (lb, t) in enumerate(zip(labels, turned))]
             self.last_rotate_labels = list(labels)
-        P, H, W, _ = pages.shape
+        pages = page_set(pages)
+        P = pages.count
         use_custom = self.custom_ocr is not None
         # 1. layout (+ overlap filter, formula level)
-        dets = self.layout_model.batch_predict([pages[i] for i in range(P)], self.layout_batch_size)
+        dets = self.layout_model.batch_predict(pages.as_list(), self.layout_batch_size)
         dets = [layout_host.filter_overlap_boxes(d, use_custom) for d in dets]
         if self.formula_model is None or self.formula_level == 1:
             inline = layout_host.CATEGORY_ID["InlineEquation"]
@@ -652,7 +793,10 @@ class PageAnalyzer:
         checkbox_res: Optional[List[List[dict]]] = None
         checkbox_found = None
         if self.checkbox_enable and getattr(self.checkbox_fn, "accepts_device_pages", False):
-            checkbox_found = [list(found) for found in self.checkbox_fn.detect_pages(pages)]      # the tensor itself: nothing leaves the device
+            if pages.tensor is not None:
+                checkbox_found = [list(found) for found in self.checkbox_fn.detect_pages(pages.tensor)]      # the tensor itself: nothing leaves the device
+            else:                                        # pages of their own sizes: one call each
+                checkbox_found = [list(self.checkbox_fn.detect_pages(pages.page(p).unsqueeze(0))[0]) for p in range(P)]
         for p, page in enumerate(dets):
             layout_host.split_regions(page)
             attach_table_images(pages, p, page)
@@ -660,7 +804,7 @@ class PageAnalyzer:
                 if checkbox_res is None:
                     checkbox_res = []
                 found = checkbox_found[p] if checkbox_found is not None else \
-                    list(self.checkbox_fn(np.ascontiguousarray(pages[p].cpu().numpy()[:, :, ::-1])))
+                    list(self.checkbox_fn(np.ascontiguousarray(pages.page(p).cpu().numpy()[:, :, ::-1])))
                 checkbox_res.append(found)
                 for res in found:
                     b = res["bbox"]
@@ -701,7 +845,7 @@ class PageAnalyzer:
                 for t in tables:
                     rect = table_crop_rect(t)                  # snapped outwards to multiples of 5 px (batch_analyze.py:235-243)
                     if rect is not None:
-                        crop = pages[p, rect[1]:rect[3], rect[0]:rect[2]].cpu().numpy()
+                        crop = pages.page(p)[rect[1]:rect[3], rect[0]:rect[2]].cpu().numpy()
                         useful = [0, 0, rect[0], rect[1], rect[2], rect[3], crop.shape[1], crop.shape[0]]
                         fills.append(layout_host.table_fill_images(t, useful) if self.table_image_enable else [])
                         crops.append(crop)
@@ -734,7 +878,7 @@ class PageAnalyzer:
         return self.seal_model is not None or (self.custom_ocr is not None and
                                                "is_seal" in inspect.signature(self.custom_ocr.batch_predict).parameters)
 
-    def _run_seal_ocr(self, pages: torch.Tensor, out: List[List[dict]]) -> int:
+    def _run_seal_ocr(self, pages, out: List[List[dict]]) -> int:
         """`BatchAnalyze._run_seal_ocr` (batch_analyze.py:415-470): every region the layout model labelled `seal` is cropped (crop_img, no
         margin, polygon whited out), handed over as BGR and gets `text` = the LIST of the lines read in it - from the custom OCR model when
         its batch_predict takes `is_seal` (one string, split at newlines), else from the seal OCR model (malformed / empty items skipped one

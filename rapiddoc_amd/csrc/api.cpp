@@ -301,6 +301,17 @@ int rd_checkbox_finish(const rd_checkbox_cand* cands, int n, int H, int W, rd_ch
     return rc;
 }
 
+size_t rd_region_canvases_workspace(int n, int gh, int gw) { return rd::region_canvases_workspace_bytes(n, gh, gw); }
+
+int rd_region_canvases(int device_id, const rd_region_desc* descs_dev, int n, const int32_t* pts_dev, const int32_t* boxes_dev, int gh, int gw,
+                       uint8_t* canv_dev, uint8_t* det_canv_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+    std::string err;
+    const int rc = rd::launch_region_canvases(device_id, descs_dev, n, pts_dev, boxes_dev, gh, gw, canv_dev, det_canv_dev, ws_dev, ws_bytes,
+                                              (hipStream_t)stream, err);
+    if (rc != 0) g_create_err = err;
+    return rc;
+}
+
 int rd_crop_resize_norm_batch(int device_id, const uint8_t* pages, int P, int H, int W, const rd_crop_desc* descs, int n,
                               int out_h, int out_w_padded, const float mean[3], const float std[3], float scale, int swap_rb,
                               float* out, void* stream) {

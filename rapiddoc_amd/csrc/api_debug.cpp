@@ -8,6 +8,7 @@
 
 #include "api_handle.h"
 #include "builder_util.h"
+#include "region_geom.h"
 
 extern "C" {
 
@@ -163,6 +164,21 @@ int rd_debug_resample_coeffs(int filter, int in, double box0, double box1, int o
     std::copy(bounds.begin(), bounds.end(), bounds_out);
     std::copy(kk.begin(), kk.end(), kk_out);
     return ksize;
+}
+
+// developer entry (host only, no HIP call): the keep mask of rd_region_canvases for ONE polygon on an h x w window, from the functions of
+// region_geom.h that the device evaluates - out_u8 [h][w] = 1 where cv2.fillPoly(mask, [pts], 1) sets the pixel.  pts int32 [n][2] in
+// window coordinates.  Returns 0, or -1 on bad arguments (n above RD_REGION_MAX_POLY included).
+int rd_debug_region_keep_mask(int h, int w, const int32_t* pts, int n, uint8_t* out_u8) {
+    if (h < 1 || w < 1 || n < 0 || n > RD_REGION_MAX_POLY || (n > 0 && !pts) || !out_u8) return -1;
+    rd_region::Edge edges[rd_region::kMaxPoly];
+    for (int t = 0; t < n; ++t) {
+        const int32_t* p = pts + 2 * (t == 0 ? n - 1 : t - 1);
+        edges[t] = rd_region::make_edge(p[0], p[1], pts[2 * t], pts[2 * t + 1]);
+    }
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) out_u8[(size_t)y * w + x] = rd_region::keep(edges, n, x, y) ? 1 : 0;
+    return 0;
 }
 
 // ---- developer micro-benchmarks (not part of the public header): time one kernel on caller-provided buffers

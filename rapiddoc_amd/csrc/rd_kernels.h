@@ -548,6 +548,11 @@ int launch_checkbox_detect(int device, const uint8_t* pages, int P, int H, int W
 void launch_checkbox_bin(const uint8_t* pages, int P, int H, int W, int bgr, uint64_t* bin, hipStream_t s);      // the threshold kernel alone
 // its host half (checkbox_host.cpp): 0, or 1 / 2 / 3 as rd_checkbox_finish documents, the message in `err`
 int checkbox_finish(const rd_checkbox_cand* cands, int n, int H, int W, rd_checkbox_box* out, int max_out, int32_t* n_out, std::string& err);
+// region composition on the device (kernels_region.hip): include/rapiddoc_mi355.h rd_region_canvases_workspace / rd_region_canvases.
+// The launcher returns 0, or 1 with the message in `err` and nothing launched.
+size_t region_canvases_workspace_bytes(int n, int gh, int gw);
+int launch_region_canvases(int device, const rd_region_desc* descs, int n, const int32_t* pts, const int32_t* boxes, int gh, int gw, uint8_t* canv,
+                           uint8_t* det, void* ws, size_t ws_bytes, hipStream_t s, std::string& err);
 // polygon_ops.cpp: the external contours of a u8 mask, last found first; `none` = CHAIN_APPROX_NONE, else CHAIN_APPROX_SIMPLE
 void find_external_contours(const uint8_t* mask, int h, int w, bool none, std::vector<std::vector<int32_t>>& xy_out);
 

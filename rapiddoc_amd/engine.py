@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import json
 import os
-from typing import Dict, List, Optional, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -768,3 +768,100 @@ def formula_preprocess(crops: list, return_u8: bool = False):
             if u8 is not None:
                 u8[i].copy_(torch.from_numpy(d))
     return (x, routes, u8) if return_u8 else (x, routes)
+
+
+# ---------------------------------------------------------------------------------------------------------------- region composition
+REGION_MAX_POLY = 64                                                                                        # RD_REGION_MAX_POLY
+REGION_DESC_DTYPE = np.dtype([("page", "<u8"), ("pitch", "<i8")] + [(n, "<i4") for n in (
+    "page_w", "page_h", "x0", "y0", "x1", "y1", "paste_x", "paste_y", "poly_off", "poly_n", "box_off", "box_n")])      # rd_region_desc
+
+
+class Region(NamedTuple):
+    """One region of `region_canvases`: `page` a [H, W, 3] uint8 tensor (a window of a larger buffer is fine: pixels and channels packed,
+    any row pitch), `rect` the UNclipped (x0, y0, x1, y1) in page coordinates, `paste` the canvas position of (x0, y0), `polygon` the
+    region's polygon_points in page coordinates or None, `boxes` the integer mask boxes in CANVAS coordinates (clipped, non-empty)."""
+    page: torch.Tensor
+    rect: Tuple[int, int, int, int]
+    paste: Tuple[int, int] = (0, 0)
+    polygon: Optional[Sequence] = None
+    boxes: Sequence[Sequence[int]] = ()
+
+
+def region_polygon(polygon_points) -> np.ndarray:
+    """polygon_points as the raster takes them: int32 [n, 2], truncated towards zero (crop_img's np.array(..., dtype=np.int32))."""
+    return np.array(polygon_points, dtype=np.int32).reshape(-1, 2)
+
+
+def pack_regions(groups: Sequence[Sequence[Region]]):
+    """Host only: the descriptors of every region of every group, group after group, and the vertex and box lists they index ->
+    (descs [total] REGION_DESC_DTYPE, pts int32 [*, 2], boxes int32 [*, 4], first descriptor of every group)."""
+    total = sum(len(g) for g in groups)
+    descs = np.zeros(total, dtype=REGION_DESC_DTYPE)
+    pts: List[np.ndarray] = []
+    boxes: List[Sequence[int]] = []
+    firsts, k, n_pts = [], 0, 0
+    for g in groups:
+        firsts.append(k)
+        for r in g:
+            t = r.page
+            if not (t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3 and t.stride(2) == 1 and t.stride(1) == 3):
+                raise EngineError("region_canvases: a page must be a uint8 [H, W, 3] tensor with packed pixels")
+            H, W_ = int(t.shape[0]), int(t.shape[1])
+            poly = region_polygon(r.polygon) if r.polygon is not None and len(r.polygon) else np.zeros((0, 2), np.int32)
+            descs[k] = (t.data_ptr(), t.stride(0) if H > 1 else 3 * W_, W_, H, *(int(v) for v in r.rect), int(r.paste[0]), int(r.paste[1]),
+                        n_pts, len(poly), len(boxes), len(r.boxes))
+            pts.append(poly)
+            n_pts += len(poly)
+            boxes.extend([int(v) for v in b] for b in r.boxes)
+            k += 1
+    return (descs, np.concatenate(pts).astype(np.int32).reshape(-1, 2) if pts else np.zeros((0, 2), np.int32),
+            np.asarray(boxes, dtype=np.int32).reshape(-1, 4), firsts)
+
+
+class RegionStage:
+    """The descriptors of all size groups of a batch on the device: packed into ONE pinned staging buffer, uploaded by ONE asynchronous
+    copy on the current stream; `region_canvases` then makes one launch per group out of it."""
+
+    def __init__(self, groups: Sequence[Sequence[Region]], device):
+        self.groups = [list(g) for g in groups]
+        descs, pts, boxes, self.firsts = pack_regions(self.groups)
+        parts = [descs.view(np.uint8).reshape(-1), pts.view(np.uint8).reshape(-1), boxes.view(np.uint8).reshape(-1)]
+        offs, n = [], 0
+        for part in parts:
+            offs.append(n)
+            n += (part.size + 15) // 16 * 16
+        self.host = torch.empty(max(n, 16), dtype=torch.uint8, pin_memory=True)
+        for o, part in zip(offs, parts):
+            if part.size:
+                self.host[o:o + part.size] = torch.from_numpy(part)
+        self.dev = self.host.to(device, non_blocking=True)
+        base = self.dev.data_ptr()
+        self.descs_ptr, self.pts_ptr, self.boxes_ptr = base + offs[0], (base + offs[1]) if len(pts) else None, (base + offs[2]) if len(boxes) else None
+        self.any_poly = [any(r.polygon is not None and len(r.polygon) for r in g) for g in self.groups]
+
+
+def region_canvases(regions: Sequence[Region], group_hw: Tuple[int, int], want_masked: bool, stage: Optional[RegionStage] = None, group: int = 0):
+    """The canvases of one size group, composed on the device (rd_region_canvases; include/rapiddoc_mi355.h has the semantics) ->
+    (canv [n, gh, gw, 3] uint8, det_canv or None): `canv` the regions on white, `det_canv` - when `want_masked` - the same with every
+    region's mask boxes at 255.  `stage` / `group`: the batch's RegionStage and this group's position in it; without one the group is
+    staged by itself.  Bad arguments raise EngineError; nothing is launched."""
+    lib = _lib.load()
+    if stage is None:
+        if not regions:
+            raise EngineError("region_canvases: no regions")
+        stage, group = RegionStage([regions], regions[0].page.device), 0
+    n = len(stage.groups[group])
+    gh, gw = int(group_hw[0]), int(group_hw[1])
+    dev = stage.dev.device
+    if n < 1 or gh < 1 or gw < 1 or not all(r.page.is_cuda and r.page.device == dev for r in stage.groups[group]):
+        raise EngineError("region_canvases: needs at least one region, a canvas of at least 1 x 1 and pages on the staging device")
+    canv = torch.empty((n, gh, gw, 3), dtype=torch.uint8, device=dev)
+    det = torch.empty((n, gh, gw, 3), dtype=torch.uint8, device=dev) if want_masked else None
+    ws_bytes = int(lib.rd_region_canvases_workspace(n, gh, gw)) if stage.any_poly[group] else 0
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    rc = lib.rd_region_canvases(dev.index or 0, stage.descs_ptr + REGION_DESC_DTYPE.itemsize * stage.firsts[group], n, stage.pts_ptr, stage.boxes_ptr,
+                                gh, gw, canv.data_ptr(), det.data_ptr() if det is not None else None, ws.data_ptr() if ws is not None else None,
+                                ws_bytes, _stream_ptr())
+    if rc != 0:
+        raise EngineError(lib.rd_create_error().decode())
+    return canv, det
