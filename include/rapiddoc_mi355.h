@@ -18,6 +18,8 @@
  *                           LatexImageFormat: .../model_handler/pp_formulanet_plus/pre_process.py:39-246
  *   rd_region_canvases   <- crop_img + _apply_mask_boxes_to_image for a batch of regions: rapid_doc/utils/model_utils.py:90-124,
  *                           rapid_doc/backend/pipeline/analyze_utils.py:82-103,131-145
+ *   rd_stage_pack, rd_stage_canvases <- the numpy crops BatchAnalyze hands to a `custom_model` (batch_analyze.py:258-331) and the white
+ *                           canvases of `_run_ocr_det_batch` (analyze_utils.py:150-189), for a whole call: pack, one upload, one launch
  *   rd_load_weights      <- `_load_state_dict` + `load_state_dict`: rapid_doc/model/ocr/torch.py:82-110
  *
  * Conventions: every pointer named *_dev is a DEVICE pointer on the handle's GPU (PyTorch-ROCm
@@ -519,6 +521,41 @@ typedef struct rd_region_desc {
 size_t rd_region_canvases_workspace(int n, int gh, int gw);
 int rd_region_canvases(int device_id, const rd_region_desc* descs_dev, int n, const int32_t* pts_dev, const int32_t* boxes_dev,
                        int gh, int gw, uint8_t* canv_dev, uint8_t* det_canv_dev /* may be NULL */, void* ws_dev, size_t ws_bytes, void* stream);
+
+/* Host images behind the plugin seam (csrc/stage_pack.cpp, csrc/kernels_stage.hip; docs/notebook/plugin_seams.md): the crops an
+ * unmodified RapidDoc hands to a `custom_model` are numpy arrays in pageable host memory.  rd_stage_pack gathers them into ONE pinned
+ * buffer, the caller uploads that buffer with one copy, rd_stage_canvases composes the detector canvases of every size group of the
+ * call from the uploaded bytes in ONE launch.
+ *
+ * rd_stage_pack (host only, no device call): image i is u8 [hs[i]][ws[i]][3] at srcs[i], rows pitches[i] bytes apart, pixels 3 bytes
+ * apart, channels 1 byte apart; its rows are copied, packed (row pitch 3 * ws[i]), to dst + offsets[i].  The rows of all images are
+ * shared out by bytes among at most n_threads threads (capped at 16; fewer for a small total).  Everything is checked before the first
+ * byte is written.  Return 0 = ok (n = 0 included), 1 = bad arguments - a NULL array or dst, n < 0, dst_bytes < 0, a negative size or
+ * offset, an image with pixels whose source is NULL or whose pitch is below 3 * ws[i] while it has more than one row, an image that
+ * overruns dst_bytes: nothing written.  Images may not overlap in dst; that is the caller's layout and is not checked. */
+int rd_stage_pack(const uint8_t* const* srcs, const int64_t* pitches, const int32_t* hs, const int32_t* ws, const int64_t* offsets, int n,
+                  uint8_t* dst, int64_t dst_bytes, int n_threads);
+
+/* rd_stage_canvases: canvas k (u8 [gh][gw][3] at `canvas`, a device address that is a multiple of 4) is 255 everywhere and crop k
+ * (u8 [h][w][3] at `src`, any byte address, rows `pitch` bytes apart) at (0, 0), its first and third channel exchanged when bit 0 of
+ * `flags` is set - the canvases analyze.RegionTextModel hands to the detector.  Every canvas byte is written exactly once, nothing
+ * outside the canvases is written, and no byte outside [src + y * pitch, src + y * pitch + 3 * w) of a row y < h is read.  The canvases
+ * of a launch may differ in size.  descs_host and descs_dev hold the same n descriptors, on the host and on the device (uploaded on
+ * `stream` by the caller): the checks read the host copy, so nothing is read back and the stream is not synchronised.  Return 0 = ok,
+ * 1 = bad arguments - a NULL array, n outside 1 .. 65535, a NULL or misaligned canvas, gh or gw outside 1 .. 16384, gw % 4 != 0,
+ * w > gw, h > gh, a negative size, a crop with pixels whose src is NULL or whose pitch is below 3 * w while it has more than one row:
+ * nothing launched, the message is rd_create_error()'s. */
+#define RD_STAGE_SWAP_RB 1u
+typedef struct rd_stage_desc {
+    const uint8_t* src;       /* device address of the crop's pixel (0,0), channel 0 */
+    int64_t pitch;            /* bytes per crop row */
+    uint8_t* canvas;          /* device address of this crop's canvas */
+    int32_t w, h;             /* crop size */
+    int32_t gh, gw;           /* canvas size */
+    uint32_t flags;           /* RD_STAGE_SWAP_RB */
+    uint32_t reserved;        /* 0 */
+} rd_stage_desc;
+int rd_stage_canvases(int device_id, const rd_stage_desc* descs_host, const rd_stage_desc* descs_dev, int n, void* stream);
 
 /* Host: chunk sizes of the recogniser's THROUGHPUT mode (the engine's own scheduling; rapidocr's fixed rec_batch_num chunks,
  * rapid_doc/model/ocr/rapid_ocr.py:430-440, are the `strict` mode of rapiddoc_amd.pipeline.PagePipeline).  wpad_sorted[i] = padded

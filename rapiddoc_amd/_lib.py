@@ -70,6 +70,8 @@ SYMBOLS = {
     "rd_region_canvases_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "rd_region_canvases": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
+    "rd_stage_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int]),
+    "rd_stage_canvases": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "rd_contour_area": (C.c_double, [C.c_void_p, C.c_int]),
     "rd_arc_length": (C.c_double, [C.c_void_p, C.c_int, C.c_int]),
     "rd_approx_poly_dp": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),

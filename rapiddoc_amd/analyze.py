@@ -657,22 +657,52 @@ class RegionTextModel:
     Here a region is read the conventional way - det, box sort / merge, rec - on the GPU, and its lines with a
     confidence >= 0.5 are joined in reading order."""
 
-    def __init__(self, pipeline, box_thresh: float = 0.3, unclip_ratio: float = 1.8):
+    def __init__(self, pipeline, box_thresh: float = 0.3, unclip_ratio: float = 1.8, host_images: str = "copy"):
+        """`host_images`: how the numpy crops of a call reach the detector's canvases.  "copy" (default): a `torch.full` per size group and,
+        per region, a channel-reversed host copy and a synchronous upload into its canvas.  "stage": the crops are packed into one pinned
+        buffer and uploaded by ONE copy (`host_stage.HostImageStage`), then ONE `rd_stage_canvases` launch composes the canvases of all
+        size groups - the same bytes.  `last_canvases`: the canvases of the last call, one [n, gh, gw, 3] tensor per size group."""
+        if host_images not in ("copy", "stage"):
+            raise ValueError("host_images must be 'copy' or 'stage'")
         self._ocr = RegionOcr(pipeline, box_thresh, unclip_ratio)
+        self.host_images = host_images
+        self._stage = None
+        self.last_canvases: List[torch.Tensor] = []
+
+    def _canvases(self, image_list, shapes, keep, groups) -> List[torch.Tensor]:
+        """the RGB canvases of every size group, white outside the crop"""
+        pipe = self._ocr.pipe
+        if self.host_images == "stage" and groups:
+            from . import host_stage
+            if self._stage is None:
+                self._stage = host_stage.HostImageStage(pipe.tdev)
+            staged = self._stage.upload([image_list[i] for i in keep])
+            canvases = host_stage.stage_canvases(staged, [((gh, gw), members) for _lang, (gh, gw), members, _bs in groups], swap_rb=True)
+            self._stage.release()
+            return canvases
+        canvases = []
+        for _lang, (gh, gw), members, _bs in groups:
+            canv = torch.full((len(members), gh, gw, 3), 255, dtype=torch.uint8, device=pipe.tdev)
+            for k, m in enumerate(members):
+                i = keep[m]
+                rgb = np.ascontiguousarray(np.asarray(image_list[i], dtype=np.uint8)[:, :, ::-1])     # BGR -> RGB
+                canv[k, : shapes[i][0], : shapes[i][1]] = torch.from_numpy(rgb).to(pipe.tdev)
+            canvases.append(canv)
+        return canvases
 
     def batch_predict(self, image_list: Sequence[np.ndarray], det_maps_fn=None, **kwargs) -> List[str]:
+        """`**kwargs` takes the `batch_size=` the reference passes (batch_analyze.py:313).  `is_seal` is deliberately NOT a parameter: the
+        reference sends seal crops to a custom OCR model only when its signature names it (batch_analyze.py:432-434), and there is no
+        seal reader here."""
         pipe = self._ocr.pipe
         texts = [""] * len(image_list)
         shapes = [(int(im.shape[0]), int(im.shape[1])) for im in image_list]
         keep = [i for i, (h, w) in enumerate(shapes) if h > 0 and w > 0]
         groups = ocr_host.det_buckets([shapes[i] for i in keep], ["_"] * len(keep), det_batch_num=max(1, len(keep)))
+        self.last_canvases = self._canvases(image_list, shapes, keep, groups)
         pending = []
-        for _lang, (gh, gw), members, _bs in groups:
+        for (_lang, (gh, gw), members, _bs), canv in zip(groups, self.last_canvases):
             ids = [keep[m] for m in members]
-            canv = torch.full((len(ids), gh, gw, 3), 255, dtype=torch.uint8, device=pipe.tdev)
-            for k, i in enumerate(ids):
-                rgb = np.ascontiguousarray(np.asarray(image_list[i], dtype=np.uint8)[:, :, ::-1])     # BGR -> RGB
-                canv[k, : shapes[i][0], : shapes[i][1]] = torch.from_numpy(rgb).to(pipe.tdev)
             override = det_maps_fn(ids, (gh, gw), ocr_host.det_resize_shape(gh, gw, 960, "max")) if det_maps_fn else None
             boxes = [self._ocr._sort_merge(r) for r in self._ocr._detect_group(canv, override)]
             quads = [np.asarray([q for q in b if q[2][0] - q[0][0] >= MIN_WIDTH], dtype=np.float32).reshape(-1, 4, 2) for b in boxes]

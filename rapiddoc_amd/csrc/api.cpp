@@ -312,6 +312,13 @@ int rd_region_canvases(int device_id, const rd_region_desc* descs_dev, int n, co
     return rc;
 }
 
+int rd_stage_canvases(int device_id, const rd_stage_desc* descs_host, const rd_stage_desc* descs_dev, int n, void* stream) {
+    std::string err;
+    const int rc = rd::launch_stage_canvases(device_id, descs_host, descs_dev, n, (hipStream_t)stream, err);
+    if (rc != 0) g_create_err = err;
+    return rc;
+}
+
 int rd_crop_resize_norm_batch(int device_id, const uint8_t* pages, int P, int H, int W, const rd_crop_desc* descs, int n,
                               int out_h, int out_w_padded, const float mean[3], const float std[3], float scale, int swap_rb,
                               float* out, void* stream) {

@@ -553,6 +553,9 @@ int checkbox_finish(const rd_checkbox_cand* cands, int n, int H, int W, rd_check
 size_t region_canvases_workspace_bytes(int n, int gh, int gw);
 int launch_region_canvases(int device, const rd_region_desc* descs, int n, const int32_t* pts, const int32_t* boxes, int gh, int gw, uint8_t* canv,
                            uint8_t* det, void* ws, size_t ws_bytes, hipStream_t s, std::string& err);
+// canvases from uploaded host crops (kernels_stage.hip): include/rapiddoc_mi355.h rd_stage_canvases.  `host` / `dev`: the same descriptors on
+// the host (checked here) and on the device (read by the kernel).  Returns 0, or 1 with the message in `err` and nothing launched.
+int launch_stage_canvases(int device, const rd_stage_desc* host, const rd_stage_desc* dev, int n, hipStream_t s, std::string& err);
 // polygon_ops.cpp: the external contours of a u8 mask, last found first; `none` = CHAIN_APPROX_NONE, else CHAIN_APPROX_SIMPLE
 void find_external_contours(const uint8_t* mask, int h, int w, bool none, std::vector<std::vector<int32_t>>& xy_out);
 

@@ -128,8 +128,13 @@ class FormulaRecognizer:
     def __init__(self, weights, device: int = 0, max_new_tokens: Optional[int] = None,
                  token_decoder: Optional[Callable[[List[int]], str]] = None,
                  bpe_decode: Optional[Callable[[List[int]], str]] = None,
-                 fix_text: Optional[Callable[[str], str]] = None, tokenizer_json=None, batching: str = "chunk", slots: int = 16):
-        """`batching`: "chunk" decodes every chunk of `batch_size` formulas as one batch, which runs until its longest formula has ended;
+                 fix_text: Optional[Callable[[str], str]] = None, tokenizer_json=None, batching: str = "chunk", slots: int = 16,
+                 host_images: str = "host"):
+        """`host_images`: what happens to NUMPY images (what an unmodified RapidDoc hands over).  "host" (default): each is pre-processed on
+        the host with Pillow.  "stage": the uint8 [h, w, 3] arrays of a call are uploaded by one copy (`host_stage.HostImageStage`) and their
+        device views take the device pre-process chunk by chunk, like device tensors - the same bits; RD_FORMULA_PREPROC=host keeps
+        everything on the host.
+        `batching`: "chunk" decodes every chunk of `batch_size` formulas as one batch, which runs until its longest formula has ended;
         "stream" encodes the chunks, then decodes all formulas through `slots` decode rows that take the next waiting formula as soon as
         theirs ends (`RdEngine.formula_decode_stream`).  Both return the same strings in the caller's order."""
         import torch  # noqa: F401  (device memory + stream only)
@@ -137,6 +142,9 @@ class FormulaRecognizer:
         from .engine import RdEngine
         if batching not in ("chunk", "stream"):
             raise ValueError("batching must be 'chunk' or 'stream'")
+        if host_images not in ("host", "stage"):
+            raise ValueError("host_images must be 'host' or 'stage'")
+        self.host_images, self._stage = host_images, None
         self.batching, self.slots = batching, int(slots)
         if isinstance(weights, (str, bytes)):
             blob = weights if isinstance(weights, bytes) else open(weights, "rb").read()
@@ -161,14 +169,20 @@ class FormulaRecognizer:
     def batch_predict(self, image_list: Sequence, batch_size: int = 16, **kwargs) -> list:
         """numpy images are pre-processed on the host exactly as before.  Device tensors take `engine.formula_preprocess` per chunk (one
         device-to-host copy of the margin boxes per chunk; a crop it declines is copied and pre-processed on the host: the same bits),
-        unless RD_FORMULA_PREPROC says "host".  `self.last_routes[i]`: "numpy", "device", "host" or "empty" for image i."""
+        unless RD_FORMULA_PREPROC says "host".  `self.last_routes[i]`: "numpy", "device", "host" or "empty" for image i.
+        With host_images="stage" the numpy images travel in one upload and are then treated like device tensors: "staged" where the device
+        pre-processed the upload's view, "host" where its plan declined (the view is copied back: the same bits), "empty"."""
         import torch
         from .engine import formula_preprocess
         results: list = [None] * len(image_list)
         on_device = device_preproc_enabled()
         inputs: list = [None] * len(image_list)
         routes = ["numpy"] * len(image_list)
+        staged_ids = self._stage_numpy(image_list) if self.host_images == "stage" and on_device else {}
         for i, im in enumerate(image_list):
+            if i in staged_ids:
+                inputs[i], routes[i] = staged_ids[i], "device" if staged_ids[i] is not None else "empty"
+                continue
             if isinstance(im, torch.Tensor) and on_device and im.is_cuda and im.numel() > 0:
                 inputs[i] = im                                            # pre-processed with its chunk
                 routes[i] = "device"
@@ -205,8 +219,26 @@ class FormulaRecognizer:
                 if 2 in toks:
                     toks = toks[: toks.index(2)]          # UniMERNetDecode cuts at EOS (post_process.py:277-296)
                 results[i] = self.token_decoder(toks) if self.token_decoder else toks
+        if any(v is not None for v in staged_ids.values()):
+            self._stage.release()                                         # every pre-process that reads the upload is enqueued
+            for i in staged_ids:
+                routes[i] = "staged" if routes[i] == "device" else routes[i]
         self.last_routes = routes
         return [r if r is not None else ([] if self.token_decoder is None else "") for r in results]
+
+    def _stage_numpy(self, image_list: Sequence) -> dict:
+        """host_images="stage": {index: device view} of the images of the call that are uint8 [h, w, 3] numpy arrays, uploaded by ONE copy
+        (None for one without pixels: nothing to read, route "empty"); every other image keeps its route"""
+        mine = [i for i, im in enumerate(image_list) if isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3]
+        ids = [i for i in mine if image_list[i].size > 0]
+        if not ids:
+            return {i: None for i in mine}
+        if self._stage is None:
+            import torch
+            from .host_stage import HostImageStage
+            self._stage = HostImageStage(torch.device("cuda", self.encoder.device))
+        staged = self._stage.upload([image_list[i] for i in ids])
+        return {**{i: None for i in mine}, **dict(zip(ids, staged.views))}
 
     def _predict_stream(self, valid: list, inputs: list, routes: list, results: list, batch_size: int) -> None:
         """batching="stream": pre-process and encode the valid crops in chunks of `batch_size` (the chunk path's routes), decode every
