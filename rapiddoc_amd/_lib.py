@@ -145,6 +145,9 @@ DEBUG_SYMBOLS = {
     "rd_debug_dec_gemv": (_I, [_I] * 4 + [_P] * 7),
     "rd_debug_dec_attention": (_I, [_I] * 4 + [_P, _P, _I, C.c_longlong] + [_P] * 5 + [_P, _I, _P, _P, _I, _P, _I]),
     "rd_debug_dec_select": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _I] + [_P] * 6),
+    "rd_debug_td_gemv": (_I, [_I] * 4 + [_P] * 5),
+    "rd_debug_td_attention": (_I, [_I] * 4 + [_P, _P, _I, C.c_longlong, _P, _I, _P, _P, _I, _P, _I, _P, _P]),
+    "rd_debug_td_select": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I] + [_P] * 6),
 }
 
 

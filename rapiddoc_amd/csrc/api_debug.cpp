@@ -1103,4 +1103,25 @@ int rd_debug_dec_select(int mode, const float* logits, int V, int B, int step, i
                                 b, x, state_out);
 }
 
+// developer entries for the UniTable decoder's kernels (csrc/table_decoder.hip): one synchronised launch each, through the launch functions of
+// decode() / decode_stream(), on caller-provided device buffers.  0 = launched; -1 = arguments the launch cannot take (nothing launched, the
+// outputs untouched).  The state words - src / pos of rd_debug_td_attention, and finished .. slot_done of rd_debug_td_select - are HOST int32
+// arrays of B entries (forced: [B][forced_ld]) that the entry copies into device state of its own and, for select, back out behind the launch.
+int rd_debug_td_gemv(int B, int K, int N, int act, const float* x, const float* w, const float* bias, const float* res, float* y) {
+    return rd::debug_td_gemv(B, K, N, act, x, w, bias, res, y);
+}
+int rd_debug_td_attention(int stream_form, int self, int B, int T, float* kc, float* vc, int ldkv, long long seq_stride, const float* q, int ldq,
+                          const float* kcur, const float* vcur, int ldcur, float* out, int ldo, const int32_t* src, const int32_t* pos) {
+    return rd::debug_td_attention(stream_form, self, B, T, kc, vc, ldkv, seq_stride, q, ldq, kcur, vcur, ldcur, out, ldo, src, pos);
+}
+int rd_debug_td_select(int stream_form, const float* logits, int B, const rd_table_decode_cfg* cfg, int max_new, int64_t* ids, int ids_ld,
+                       const float* emb, const float* pos, float* x, int step, int32_t* finished, int32_t* boxcount, int32_t* tok,
+                       const int32_t* forced, int forced_ld, int32_t* chosen, const int32_t* slot_src, int32_t* slot_pos, int32_t* slot_box,
+                       int32_t* slot_done, int32_t* lens) {
+    if (!cfg) return -1;
+    const int c[6] = {cfg->prefix_id, cfg->eos_id, cfg->pad_id, cfg->bbox_close_id, cfg->bbox_first_id, cfg->bbox_last_id};
+    return rd::debug_td_select(stream_form, logits, B, c, max_new, reinterpret_cast<long long*>(ids), ids_ld, emb, pos, x, step, finished, boxcount,
+                               tok, forced, forced_ld, chosen, slot_src, slot_pos, slot_box, slot_done, lens);
+}
+
 }  // extern "C"

@@ -34,6 +34,13 @@ int table_decoder_decode(TableDecoder* d, const float* memory, int B, int S, int
 void table_decoder_decode_stream(TableDecoder* d, const float* memory, int N, int S, int max_new, int slots, const int* cfg6, long long* ids, int* lens,
                                  rd_table_stream_stats* stats, hipStream_t s, float* trace_logits, float* trace_hidden, int* trace_sched,
                                  int sched_steps);
+// one synchronised launch of a decode step's kernel on caller-provided buffers (rd_debug_td_*; table_decoder.hip)
+int debug_td_gemv(int B, int K, int N, int act, const float* x, const float* w, const float* bias, const float* res, float* y);
+int debug_td_attention(int stream_form, int self, int B, int T, float* kc, float* vc, int ldkv, long long seq_stride, const float* q, int ldq,
+                       const float* kcur, const float* vcur, int ldcur, float* out, int ldo, const int* src, const int* pos);
+int debug_td_select(int stream_form, const float* logits, int B, const int* cfg6, int max_new, long long* ids, int ids_ld, const float* emb,
+                    const float* pos, float* x, int step, int* finished, int* boxcount, int* tok, const int* forced, int forced_ld, int* chosen,
+                    const int* slot_src, int* slot_pos, int* slot_box, int* slot_done, int* lens);
 }  // namespace rd
 
 struct rd_handle {

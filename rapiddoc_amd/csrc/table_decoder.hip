@@ -7,7 +7,9 @@
 //                     a (row, column) sum has the same order whatever B is
 //   td_attn_kernel    one workgroup per (table, head): scores into LDS, max, exp, sum, P V; the self form appends the step's K / V row to
 //                     the cache (1024 rows, fp32) and attends rows 0 .. step (the causal mask at input_pos)
-//   td_select_kernel  whitelist argmax (ids 1 and 12 .. 509; NaN counts as -inf, so the winner is always an id below 960), the bbox rule
+//   td_select_kernel  whitelist argmax (ids 1 and 12 .. 509; every other id sits at -1e9; NaN counts as -inf; the lowest id wins among
+//                     equals - so the winner is always an id below 960, and a row whose whitelisted logits are ALL NaN or -inf names
+//                     id 0, outside the whitelist, because -1e9 beats -inf: tests/test_gpu_td_select.py pins both), the bbox rule
 //                     (a counter per table that ONLY a bbox token raises and only its overflow clears), the per-table EOS latch (a
 //                     finished table keeps its slot and writes `pad`), and the next step's embedding + position row
 // No atomics: every table has its own flag, counter and token word.
@@ -131,12 +133,13 @@ __global__ void __launch_bounds__(256) td_attn_kernel(TdAttn p) {
     float m = -INFINITY;
     for (int j = tid; j < T; j += 256) {
         const float* kr = (self && j == pos) ? kcur : kb + (size_t)j * p.ldkv;
-        float s = 0.f;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;      // four partial sums: one chain of 64 roundings put few-hot scores outside the fp64 bound
 #pragma unroll
         for (int d = 0; d < TD_HD; d += 4) {
             const f32x4 kv = *reinterpret_cast<const f32x4*>(kr + d);
-            s = fmaf(qs[d], kv[0], s); s = fmaf(qs[d + 1], kv[1], s); s = fmaf(qs[d + 2], kv[2], s); s = fmaf(qs[d + 3], kv[3], s);
+            s0 = fmaf(qs[d], kv[0], s0); s1 = fmaf(qs[d + 1], kv[1], s1); s2 = fmaf(qs[d + 2], kv[2], s2); s3 = fmaf(qs[d + 3], kv[3], s3);
         }
+        const float s = (s0 + s1) + (s2 + s3);
         sc[j] = s;
         m = fmaxf(m, s);
     }
@@ -262,12 +265,13 @@ __global__ void __launch_bounds__(256) td_stream_attn_kernel(TdAttn p, const TdS
     float m = -INFINITY;
     for (int j = tid; j < T; j += 256) {
         const float* kr = (self && j == pos) ? kcur : kb + (size_t)j * p.ldkv;
-        float s = 0.f;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;      // four partial sums: one chain of 64 roundings put few-hot scores outside the fp64 bound
 #pragma unroll
         for (int d = 0; d < TD_HD; d += 4) {
             const f32x4 kv = *reinterpret_cast<const f32x4*>(kr + d);
-            s = fmaf(qs[d], kv[0], s); s = fmaf(qs[d + 1], kv[1], s); s = fmaf(qs[d + 2], kv[2], s); s = fmaf(qs[d + 3], kv[3], s);
+            s0 = fmaf(qs[d], kv[0], s0); s1 = fmaf(qs[d + 1], kv[1], s1); s2 = fmaf(qs[d + 2], kv[2], s2); s3 = fmaf(qs[d + 3], kv[3], s3);
         }
+        const float s = (s0 + s1) + (s2 + s3);
         sc[j] = s;
         m = fmaxf(m, s);
     }
@@ -415,6 +419,20 @@ __global__ void td_stream_sched_kernel(const TdStream* ss, int* sched, int sched
     sched[((size_t)t * slots + s) * 2 + 1] = ss->pos[s];
 }
 
+// The launches of a step: decode(), decode_stream() and the developer entries rd_debug_td_* (below) all launch through these four.
+// `ss` given = the stream form (per-slot state), null = the batch form (p.st).
+static void launch_td_gemv(const float* x, const float* w, const float* bias, const float* res, float* y, int B, int K, int N, int act, hipStream_t s) {
+    hipLaunchKernelGGL(td_gemv_kernel, dim3((N + 3) / 4), dim3(256), 0, s, x, w, bias, res, y, B, K, N, act);
+}
+static void launch_td_attention(const TdAttn& p, int B, const TdStream* ss, hipStream_t s) {
+    if (ss) hipLaunchKernelGGL(td_stream_attn_kernel, dim3(TD_HEADS, B), dim3(256), 0, s, p, ss);
+    else hipLaunchKernelGGL(td_attn_kernel, dim3(TD_HEADS, B), dim3(256), 0, s, p);
+}
+static void launch_td_select(const TdSelect& p, hipStream_t s) { hipLaunchKernelGGL(td_select_kernel, dim3(p.B), dim3(1024), 0, s, p); }
+static void launch_td_stream_select(const TdStreamSelect& p, int slots, hipStream_t s) {
+    hipLaunchKernelGGL(td_stream_select_kernel, dim3(slots), dim3(1024), 0, s, p);
+}
+
 // =================================================================================================
 class TableDecoder {
    public:
@@ -434,7 +452,7 @@ class TableDecoder {
    private:
     void gemm(const float* x, int M, int K, const std::string& key, int N, float* y, hipStream_t s);
     void gemv(const float* x, int B, int K, const std::string& key, int N, float* y, int act, const float* res, hipStream_t s) {
-        hipLaunchKernelGGL(td_gemv_kernel, dim3((N + 3) / 4), dim3(256), 0, s, x, params_.ptr(key + "#w"), params_.ptr(key + "#b"), res, y, B, K, N, act);
+        launch_td_gemv(x, params_.ptr(key + "#w"), params_.ptr(key + "#b"), res, y, B, K, N, act, s);
     }
     void ln(const float* x, const std::string& key, float* y, int M, hipStream_t s) {
         launch_layernorm768(x, TD_D, y, TD_D, params_.ptr(key + ".weight"), params_.ptr(key + ".bias"), M, 1e-5f, s);
@@ -563,7 +581,7 @@ int TableDecoder::decode(const float* memory, int B, int S, int max_new, const T
             sp.kc = kc + (size_t)l * B * TD_MAXPOS * TD_D; sp.vc = vc + (size_t)l * B * TD_MAXPOS * TD_D; sp.ldkv = TD_D; sp.seq_stride = (long long)TD_MAXPOS * TD_D;
             sp.kcur = qkv + TD_D; sp.vcur = qkv + 2 * TD_D; sp.ldcur = 3 * TD_D;
             sp.st = st; sp.fixed_T = 0; sp.out = a; sp.ldo = TD_D;
-            hipLaunchKernelGGL(td_attn_kernel, dim3(TD_HEADS, B), dim3(256), 0, s, sp);
+            launch_td_attention(sp, B, nullptr, s);
             gemv(a, B, TD_D, K + "wo", TD_D, nxt, ACT_NONE, cur, s);
             std::swap(cur, nxt);
             ln(cur, K + "ln2", h, B, s);
@@ -572,7 +590,7 @@ int TableDecoder::decode(const float* memory, int B, int S, int max_new, const T
             cp.q = qkv; cp.ldq = TD_D;
             cp.kc = ck + (size_t)l * B * S * TD_D; cp.vc = cv + (size_t)l * B * S * TD_D; cp.ldkv = TD_D; cp.seq_stride = (long long)S * TD_D;
             cp.st = st; cp.fixed_T = S; cp.out = a; cp.ldo = TD_D;
-            hipLaunchKernelGGL(td_attn_kernel, dim3(TD_HEADS, B), dim3(256), 0, s, cp);
+            launch_td_attention(cp, B, nullptr, s);
             gemv(a, B, TD_D, K + "co", TD_D, nxt, ACT_NONE, cur, s);
             std::swap(cur, nxt);
             ln(cur, K + "ln3", h, B, s);
@@ -588,7 +606,7 @@ int TableDecoder::decode(const float* memory, int B, int S, int max_new, const T
         RD_CHECK(cur == x, "table decode: the layer stack must end in the buffer the next embedding is written to");
         TdSelect sel{lg, ids_out, ids_ld, fin, box, tok, st, cfg, max_new, forced, forced_ld, trace_chosen, trace_emitted, B, params_.ptr("emb"),
                      params_.ptr("pos"), x};
-        hipLaunchKernelGGL(td_select_kernel, dim3(B), dim3(1024), 0, s, sel);
+        launch_td_select(sel, s);
         hipLaunchKernelGGL(td_advance_kernel, dim3(1), dim3(1), 0, s, st);
     };
     struct StepGraph {          // the captured step; freed on every way out of this function, a throwing RD_HIP included
@@ -730,7 +748,7 @@ void TableDecoder::decode_stream(const float* memory, int N, int S, int max_new,
             sp.kc = kc + (size_t)l * M * Tc * TD_D; sp.vc = vc + (size_t)l * M * Tc * TD_D; sp.ldkv = TD_D; sp.seq_stride = (long long)Tc * TD_D;
             sp.kcur = qkv + TD_D; sp.vcur = qkv + 2 * TD_D; sp.ldcur = 3 * TD_D;
             sp.st = nullptr; sp.fixed_T = 0; sp.out = a; sp.ldo = TD_D;
-            hipLaunchKernelGGL(td_stream_attn_kernel, dim3(TD_HEADS, M), dim3(256), 0, s, sp, ss);
+            launch_td_attention(sp, M, ss, s);
             gemv(a, M, TD_D, K + "wo", TD_D, nxt, ACT_NONE, cur, s);
             std::swap(cur, nxt);
             ln(cur, K + "ln2", h, M, s);
@@ -739,7 +757,7 @@ void TableDecoder::decode_stream(const float* memory, int N, int S, int max_new,
             cp.q = qkv; cp.ldq = TD_D;
             cp.kc = ck + (size_t)l * N * S * TD_D; cp.vc = cv + (size_t)l * N * S * TD_D; cp.ldkv = TD_D; cp.seq_stride = (long long)S * TD_D;
             cp.st = nullptr; cp.fixed_T = S; cp.out = a; cp.ldo = TD_D;
-            hipLaunchKernelGGL(td_stream_attn_kernel, dim3(TD_HEADS, M), dim3(256), 0, s, cp, ss);
+            launch_td_attention(cp, M, ss, s);
             gemv(a, M, TD_D, K + "co", TD_D, nxt, ACT_NONE, cur, s);
             std::swap(cur, nxt);
             ln(cur, K + "ln3", h, M, s);
@@ -753,7 +771,7 @@ void TableDecoder::decode_stream(const float* memory, int N, int S, int max_new,
         gemv(cur, M, TD_D, "gen", TD_VOCAB, lg, ACT_NONE, nullptr, s);
         if (trace_logits) hipLaunchKernelGGL(td_stream_trace_kernel, dim3(M), dim3(256), 0, s, lg, trace_logits, TD_VOCAB, (long long)TD_VOCAB, max_new, ss);
         RD_CHECK(cur == x, "table decode stream: the layer stack must end in the buffer the next embedding is written to");
-        hipLaunchKernelGGL(td_stream_select_kernel, dim3(M), dim3(1024), 0, s, sel);
+        launch_td_stream_select(sel, M, s);
         hipLaunchKernelGGL(td_stream_admit_kernel, dim3(1), dim3(256), 0, s, ss, N, slots, x0, x);
     };
     struct StepGraph {          // the captured step; freed on every way out of this function, a throwing RD_HIP included
@@ -826,6 +844,109 @@ void table_decoder_decode_stream(TableDecoder* d, const float* memory, int N, in
                                  int sched_steps) {
     TdCfg c{cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5]};
     d->decode_stream(memory, N, S, max_new, slots, c, ids, lens, stats, s, trace_logits, trace_hidden, trace_sched, sched_steps);
+}
+
+// ---- developer entries (api_debug.cpp rd_debug_td_*): ONE synchronised launch of a step's kernel through the launch functions above, on
+// caller-provided device buffers; no weight file.  0 = launched and synchronised; -1 = arguments the launch cannot take (nothing launched,
+// the outputs untouched) or a HIP error.  The state words (step, per-slot src / pos / box / done, finished, boxcount, tok) are HOST arrays:
+// the entry puts them into device state of its own and copies them back out behind the launch.
+namespace {
+bool td_debug_sync() { return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess; }
+struct TdDebugBuf {      // `bytes` of device memory of the entry's own: a copy of `host`, or zeros
+    void* d = nullptr;
+    size_t bytes;
+    TdDebugBuf(size_t n, const void* host) : bytes(n) {
+        if (hipMalloc(&d, bytes) != hipSuccess) { d = nullptr; return; }
+        if ((host ? hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) : hipMemset(d, 0, bytes)) != hipSuccess) { (void)hipFree(d); d = nullptr; }
+    }
+    ~TdDebugBuf() { if (d) (void)hipFree(d); }
+    bool read(void* host) const { return hipMemcpy(host, d, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
+    template <class T> T* as() const { return static_cast<T*>(d); }
+};
+}  // namespace
+
+// y [B][N] = act(x [B][K] w [N][K]^T + bias) + res [B][N] by td_gemv_kernel; bias and res may be null
+int debug_td_gemv(int B, int K, int N, int act, const float* x, const float* w, const float* bias, const float* res, float* y) {
+    if (B < 1 || B > TD_MAXB || K <= 0 || K % 256 != 0 || N <= 0 || !x || !w || !y || act < ACT_NONE || act > ACT_HSIG_PADDLE) return -1;
+    launch_td_gemv(x, w, bias, res, y, B, K, N, act, nullptr);
+    return td_debug_sync() ? 0 : -1;
+}
+
+// td_attn_kernel (stream_form 0) or td_stream_attn_kernel (1) over B rows.  Batch form: self != 0: the step is T, rows 0 .. T - 1 of
+// the cache are read and this step's kcur / vcur appended as row T (T in 0 .. 1023); self == 0: T keys (1 .. 1024).  Stream form: src [B] and
+// pos [B] (host int32) are the slots' tables (-1 = idle) and positions; self: row b's cache block is b and its step pos[b]; cross: T keys of
+// block src[b] - kc / vc must hold max(src) + 1 blocks.  seq_stride must cover the rows a sequence reads and appends.
+int debug_td_attention(int stream_form, int self, int B, int T, float* kc, float* vc, int ldkv, long long seq_stride, const float* q, int ldq,
+                       const float* kcur, const float* vcur, int ldcur, float* out, int ldo, const int* src, const int* pos) {
+    if (B < 1 || B > TD_MAXB || !kc || !vc || !q || !out || ldkv < TD_D || (ldkv & 3) || (seq_stride & 3) || ldq < TD_D || ldo < TD_D) return -1;
+    if (self && (!kcur || !vcur || ldcur < TD_D || (ldcur & 3))) return -1;
+    if (stream_form && (!src || !pos)) return -1;
+    int rows = 0;          // cache rows of a sequence that the launch reads or appends
+    if (!self) {
+        if (T < 1 || T > TD_MAXPOS) return -1;
+        rows = T;
+    } else if (!stream_form) {
+        if (T < 0 || T >= TD_MAXPOS) return -1;
+        rows = T + 1;
+    }
+    TdStream hs{};
+    for (int b = 0; b < TD_MAXB; ++b) hs.src[b] = -1;
+    if (stream_form)
+        for (int b = 0; b < B; ++b) {
+            if (src[b] < -1 || pos[b] < 0 || pos[b] >= TD_MAXPOS) return -1;
+            hs.src[b] = src[b];
+            hs.pos[b] = pos[b];
+            if (self && src[b] >= 0) rows = std::max(rows, pos[b] + 1);
+        }
+    if (seq_stride < (long long)rows * ldkv) return -1;
+    const TdState hst{self ? T : 0};
+    TdDebugBuf st(sizeof(TdState), &hst), ss(sizeof(TdStream), &hs);
+    if (!st.d || !ss.d) return -1;
+    TdAttn p{};
+    p.q = q; p.ldq = ldq; p.kc = kc; p.vc = vc; p.ldkv = ldkv; p.seq_stride = seq_stride;
+    if (self) { p.kcur = kcur; p.vcur = vcur; p.ldcur = ldcur; }
+    p.st = stream_form ? nullptr : st.as<TdState>(); p.fixed_T = self ? 0 : T; p.out = out; p.ldo = ldo;
+    launch_td_attention(p, B, stream_form ? ss.as<TdStream>() : nullptr, nullptr);
+    return td_debug_sync() ? 0 : -1;
+}
+
+// td_select_kernel (stream_form 0) or td_stream_select_kernel (1) over B rows of logits [B][960] (device).  Device: ids [.][ids_ld], emb
+// [960][768], pos [1024][768], x [B][768], lens (stream form: one word per table).  Host, int32, in and out: batch form finished / boxcount /
+// tok [B], forced [B][forced_ld] or null (in only), chosen [B] or null (out only: the whitelist argmax in front of the bbox rule); stream form
+// slot_src (in only) / slot_pos / slot_box / slot_done [B].
+int debug_td_select(int stream_form, const float* logits, int B, const int* cfg6, int max_new, long long* ids, int ids_ld, const float* emb,
+                    const float* pos, float* x, int step, int* finished, int* boxcount, int* tok, const int* forced, int forced_ld, int* chosen,
+                    const int* slot_src, int* slot_pos, int* slot_box, int* slot_done, int* lens) {
+    if (B < 1 || B > TD_MAXB || !logits || !cfg6 || max_new < 1 || max_new > TD_MAXPOS || !ids || ids_ld < 1 || !emb || !pos || !x) return -1;
+    const TdCfg cfg{cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5]};
+    const size_t words = (size_t)B * sizeof(int);
+    if (!stream_form) {
+        if (step < 0 || step >= TD_MAXPOS || !finished || !boxcount || !tok || (forced && forced_ld < 1)) return -1;
+        const TdState hst{step};
+        TdDebugBuf st(sizeof(TdState), &hst), fin(words, finished), box(words, boxcount), tk(words, tok);
+        TdDebugBuf fo(forced ? words * forced_ld : sizeof(int), forced), ch(words * (step + 1), nullptr);
+        if (!st.d || !fin.d || !box.d || !tk.d || !fo.d || !ch.d) return -1;
+        const TdSelect sel{logits, ids, ids_ld, fin.as<int>(), box.as<int>(), tk.as<int>(), st.as<TdState>(), cfg, max_new,
+                           forced ? fo.as<int>() : nullptr, forced_ld, ch.as<int>(), nullptr, B, emb, pos, x};
+        launch_td_select(sel, nullptr);
+        if (!td_debug_sync() || !fin.read(finished) || !box.read(boxcount) || !tk.read(tok)) return -1;
+        if (chosen && hipMemcpy(chosen, ch.as<int>() + (size_t)step * B, words, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        return 0;
+    }
+    if (!slot_src || !slot_pos || !slot_box || !slot_done || !lens) return -1;
+    TdStream hs{};
+    for (int b = 0; b < TD_MAXB; ++b) hs.src[b] = -1;
+    for (int b = 0; b < B; ++b) {          // a live slot writes ids[src][pos + 1]
+        if (slot_src[b] < -1 || slot_pos[b] < 0 || (slot_src[b] >= 0 && slot_pos[b] + 1 >= ids_ld)) return -1;
+        hs.src[b] = slot_src[b]; hs.pos[b] = slot_pos[b]; hs.box[b] = slot_box[b]; hs.done[b] = slot_done[b];
+    }
+    TdDebugBuf ss(sizeof(TdStream), &hs);
+    if (!ss.d) return -1;
+    const TdStreamSelect sel{logits, ids, ids_ld, lens, ss.as<TdStream>(), cfg, max_new, emb, pos, x};
+    launch_td_stream_select(sel, B, nullptr);
+    if (!td_debug_sync() || !ss.read(&hs)) return -1;
+    for (int b = 0; b < B; ++b) { slot_pos[b] = hs.pos[b]; slot_box[b] = hs.box[b]; slot_done[b] = hs.done[b]; }
+    return 0;
 }
 
 }  // namespace rd

@@ -104,5 +104,6 @@ def test_the_library_exports_the_entries():
     rd_build.build(verbose=False)
     from rapiddoc_amd import _lib
     lib = _lib.load()
-    for name in ("rd_table_encoder_forward", "rd_debug_table_encoder_taps", "rd_debug_vit_attention"):
+    for name in ("rd_table_encoder_forward", "rd_debug_table_encoder_taps", "rd_debug_vit_attention", "rd_debug_td_gemv", "rd_debug_td_attention",
+                 "rd_debug_td_select"):
         assert hasattr(lib, name), name
