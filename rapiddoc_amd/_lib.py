@@ -113,6 +113,7 @@ DEBUG_SYMBOLS = {
     "rd_debug_conv_ex": (_F, [_I] * 22 + [_P] * 10 + [C.c_char_p, _P, _I, _P]),
     "rd_debug_conv": (_F, [_I] * 14 + [_P] * 8),
     "rd_debug_stem34": (_F, [_I] * 11 + [_P] * 7),
+    "rd_debug_stem_front": (_F, [_I] * 8 + [_P] * 10),
     "rd_debug_dwconv_ex": (_F, [_I] * 17 + [_P] * 10 + [_I]),
     "rd_debug_dwconv": (_F, [_I] * 8 + [_P] * 8),
     "rd_debug_dw_route": (_I, [_I] * 9 + [_P, _I, _P]),

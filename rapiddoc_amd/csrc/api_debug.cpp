@@ -614,6 +614,47 @@ float rd_debug_stem34(int N, int H, int W, int Cin, int xld, int N1, int N2, int
     return ms;
 }
 
+// developer entry: the stem front alone.  route 1: the fused kernel (kernels_stem_fused.hip) - x NCHW fp32 [N][in_ch][H][W] (in_ch 1 or 3);
+// w1 [27][C1] in the stem layout (row (kh * 3 + kw) * 3 + ci, co fastest), w2a folded [C1/2][4 C1] with k = tap * C1 + c, w2b folded
+// [C1][4 (C1/2)], biases [C1] / [C1/2] / [C1] (device pointers, BN folded); y = cat NHWC [N][H2][W2][yld >= 2 C1] = [pool | stem2b];
+// line_tab int32 [N][4] (rd_kernels.h LineTab) or null; range_flag or null.  The weight image and the bias vector are built here the way
+// Builder::stem_front builds them (fits_fp16_range, prepare_stem_fused_weights, bias [C1 | C1/2 | C1]).  route 0: launch_stem_conv3x3s2
+// alone (the fp32 kernel of the four-kernel plan): y = e NHWC [N][H2][W2][yld >= C1] with ReLU; w2a .. b2b, line_tab and range_flag are
+// not read.  Returns ms per launch, -1 with nothing launched for an unsupported C1 / in_ch / yld or weights beyond the fp16 range.
+float rd_debug_stem_front(int route, int N, int H, int W, int in_ch, int C1, int yld, int iters, float* x, float* w1, float* b1, float* w2a,
+                          float* b2a, float* w2b, float* b2b, float* y, const int32_t* line_tab, unsigned* range_flag) {
+    if ((route != 0 && route != 1) || N <= 0 || H <= 0 || W <= 0 || (in_ch != 1 && in_ch != 3) || !rd::stem_fused_supported(C1)) return -1.f;
+    if (!x || !w1 || !b1 || !y || yld % 4 != 0 || yld < (route == 1 ? 2 * C1 : C1)) return -1.f;
+    if (route == 0) {
+        rd::StemParams p{};
+        p.x = x; p.N = N; p.H = H; p.W = W; p.in_ch = in_ch; p.w = w1; p.bias = b1; p.y = y; p.yld = yld;
+        p.OH = (H - 1) / 2 + 1; p.OW = (W - 1) / 2 + 1; p.Cout = C1; p.act = rd::ACT_RELU;
+        return rd_debug_time(iters, [&] { rd::launch_stem_conv3x3s2(p, nullptr); });
+    }
+    if (!w2a || !b2a || !w2b || !b2b) return -1.f;
+    const int na = C1 / 2;
+    std::vector<float> h1((size_t)27 * C1), h2a((size_t)na * 4 * C1), h2b((size_t)C1 * 4 * na), bias((size_t)C1 + na + C1);
+    if (hipMemcpy(h1.data(), w1, h1.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    if (hipMemcpy(h2a.data(), w2a, h2a.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    if (hipMemcpy(h2b.data(), w2b, h2b.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    if (hipMemcpy(bias.data(), b1, (size_t)C1 * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    if (hipMemcpy(bias.data() + C1, b2a, (size_t)na * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    if (hipMemcpy(bias.data() + C1 + na, b2b, (size_t)C1 * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
+    if (!rd::fits_fp16_range(h1) || !rd::fits_fp16_range(h2a) || !rd::fits_fp16_range(h2b)) return -1.f;
+    std::vector<uint16_t> img;
+    rd::prepare_stem_fused_weights(C1, h1.data(), h2a.data(), h2b.data(), img);
+    void *dimg = nullptr, *dbias = nullptr;
+    if (hipMalloc(&dimg, img.size() * 2) != hipSuccess) return -1.f;
+    if (hipMalloc(&dbias, bias.size() * 4) != hipSuccess) { (void)hipFree(dimg); return -1.f; }
+    (void)hipMemcpy(dimg, img.data(), img.size() * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(dbias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice);
+    const float ms = rd_debug_time(iters, [&] {
+        rd::launch_stem_fused(C1, x, N, H, W, in_ch, (const uint16_t*)dimg, (const float*)dbias, y, yld, range_flag, nullptr, line_tab);
+    });
+    (void)hipFree(dimg); (void)hipFree(dbias);
+    return ms;
+}
+
 // "lds1" .. "lds5" = dwconv_lds_variant, "kxk_lds5" / "7", "tiled4" / "8", "col", "pixel": what rd_debug_dw_route and rd_debug_dwconv_ex report
 static std::string debug_dw_route_name(const rd::DwRoute& r) {
     static const char* const kernels[] = {"pixel", "lds", "kxk_lds", "col", "tiled"};

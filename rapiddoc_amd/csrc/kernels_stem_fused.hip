@@ -157,6 +157,14 @@ __global__ void __launch_bounds__(SF_NT, 2) stem_fused_kernel(StemFusedParams p)
             pre[k] = img[p_ci[k] + iy * p.W + ix];
         }
     };
+    // The range guard.  The OPERANDS of the three products are x, e and a; one at or beyond 65504 splits into hi = +-inf, lo = -+inf and its
+    // products are NaN - which the ReLU epilogues of stem1 and stem2a (v_max_f32 v, 0, v in IEEE mode) turn into 0.0, a finite wrong
+    // answer.  So x and e are tested where they are touched anyway, as bit patterns (inf and NaN sort above every finite value):
+    //   omax: |x| of every patch element (store_patch) and the pool's outputs = the maximum over e (e >= 0, every e of the map is pooled)
+    //         -> raised at 65504 (0x477fe000) like kernels_stem34.hip
+    //   emax: stem2b's pre-activations -> raised when non-finite only: an `a` beyond the range makes them NaN, while b itself is
+    //         written, not split, and may lie beyond the fp16 range
+    unsigned emax = 0, omax = 0;
     auto store_patch = [&](int ty0, int tx0) {    // (zero outside the image: the conv's padding)
         const int iy0 = 2 * ty0 - 1, ix0 = 2 * tx0 - 1;
 #pragma unroll
@@ -164,13 +172,13 @@ __global__ void __launch_bounds__(SF_NT, 2) stem_fused_kernel(StemFusedParams p)
             const int iy = iy0 + (p_rc[k] >> 16), ix = ix0 + (p_rc[k] & 0xffff);
             const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
             if (p_rc[k] >= 0) As[p_lds[k]] = ok ? pre[k] : 0.f;
+            omax = max(omax, __float_as_uint(pre[k]) & 0x7fffffffu);      // (a clamped address: a pixel of this image either way)
         }
         // the slots behind the last real column of every row and behind the last row are read with zero weights: keep them finite
         if (tid < SF_PH) As[tid * SF_PROW + SF_PW * 3] = 0.f;
         if (tid >= 64 && tid < 80) As[SF_PH * SF_PROW + tid - 64] = 0.f;
     };
 
-    unsigned emax = 0;      // largest |pre-activation| bit pattern of stem2b's outputs / the pool's: inf and NaN sort above every finite value
     int t = blockIdx.x;
     if (t < ntiles) load_patch(t);
     __syncthreads();
@@ -187,7 +195,7 @@ __global__ void __launch_bounds__(SF_NT, 2) stem_fused_kernel(StemFusedParams p)
         const bool inner = ty0 + SF_EH <= p.H2 && tx0 + SF_EW <= W2n;
 
         // ---------------- stem1: e = ReLU(conv3x3 s2 (patch)) on the matrix cores, K = 3 kernel rows x 16 slots.  The bias rides in
-        // the accumulator init; non-finite values are not tested here: they reach stem2b's outputs and the pool, which are
+        // the accumulator init; the range of e is tested at the pool, which reads every e of the map (omax above)
         for (int mb = wave; mb < G::MB1 && !(p.dbg & 1); mb += 8) {
             const int m = min(mb * 32 + l31, SF_EH * SF_EW - 1);
             const int ey = m / SF_EW, ex = m - ey * SF_EW;
@@ -332,7 +340,7 @@ __global__ void __launch_bounds__(SF_NT, 2) stem_fused_kernel(StemFusedParams p)
                     f32x4 o;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) o[k] = fmaxf(fmaxf(a[k], b[k]), fmaxf(c[k], d[k]));
-                    emax = max(emax, __float_as_uint(o[0] + o[1] + o[2] + o[3]) & 0x7fffffffu);      // (e >= 0: the sum is non-finite iff a term is)
+                    omax = max(omax, __float_as_uint(fmaxf(fmaxf(o[0], o[1]), fmaxf(o[2], o[3]))) & 0x7fffffffu);      // (e >= 0 or +inf, never NaN)
                     __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(p.y + (((size_t)n * p.H2 + gy) * p.W2 + gx) * p.yld + 4 * cg));
                 }
             }
@@ -432,7 +440,7 @@ __global__ void __launch_bounds__(SF_NT, 2) stem_fused_kernel(StemFusedParams p)
         }
         __syncthreads();        // e / a are free for the next tile
     }
-    if (emax >= 0x7f800000u && p.range_flag) rd_raise_flag(p.range_flag);
+    if ((emax >= 0x7f800000u || omax >= 0x477fe000u) && p.range_flag) rd_raise_flag(p.range_flag);
 }
 
 bool stem_fused_supported(int c1) { return c1 == 24 || c1 == 32 || c1 == 48; }
