@@ -20,6 +20,8 @@
  *                           rapid_doc/backend/pipeline/analyze_utils.py:82-103,131-145
  *   rd_stage_pack, rd_stage_canvases <- the numpy crops BatchAnalyze hands to a `custom_model` (batch_analyze.py:258-331) and the white
  *                           canvases of `_run_ocr_det_batch` (analyze_utils.py:150-189), for a whole call: pack, one upload, one launch
+ *   rd_line_warp_sources <- get_rotate_crop_image for the text lines of MANY region images at once (rapid_doc/utils/ocr_utils.py:494-537,
+ *                           called per line by get_ocr_result_list, :361-432): every line names its own source image, one launch
  *   rd_load_weights      <- `_load_state_dict` + `load_state_dict`: rapid_doc/model/ocr/torch.py:82-110
  *
  * Conventions: every pointer named *_dev is a DEVICE pointer on the handle's GPU (PyTorch-ROCm
@@ -266,6 +268,28 @@ int rd_line_warp_batch(int device_id, const uint8_t* pages_u8_dev, int P, int H,
                        int64_t max_crop_pixels, uint8_t* scratch_u8_dev, void* stream);
 int rd_line_resize_norm_batch(int device_id, const rd_line_crop_desc* descs_dev, int n, const uint8_t* scratch_u8_dev, int out_h,
                               int out_w_padded, int swap_rb, float* out_nchw_dev, void* stream);
+
+/* rd_line_warp_batch for lines that come from MANY source images of different sizes (the region images behind RapidDoc's OCR-model
+ * seam, rapiddoc_amd/ocr_model.py: every text region is an image of its own): each line names its source, so ONE launch warps all lines
+ * of a rec launch.  Line k: the crop_w x crop_h crop whose pixel (x, y, 1) maps to source position m * (x, y, 1) is written, packed
+ * [crop_h][crop_w][3], to scratch_u8_dev + scratch_off - the arithmetic of rd_line_warp_batch (1/32-pixel positions, the 15-bit cubic
+ * weight table, border replicate), byte for byte.  The source is u8 [H][W][3] at `src`, ANY byte address, rows `pitch` >= 3 * W bytes
+ * apart (a window of a larger image).  No byte outside [src + y * pitch, src + y * pitch + 3 * W) of a row y < H is read, nothing outside
+ * the crops is written.  descs_host and descs_dev hold the same n descriptors on the host and on the device (uploaded on `stream` by the
+ * caller): the checks read the host copy, so nothing is read back and the stream is not synchronised.  Return 0 = ok, 1 = bad arguments -
+ * a NULL array or scratch, n outside 1 .. 65535, a NULL src, pitch < 3 * W, a source or crop size that is not positive, a negative
+ * scratch_off, a crop that overruns scratch_bytes: nothing launched, the message is rd_create_error()'s. */
+typedef struct rd_line_source_desc {
+    const uint8_t* src;       /* device address of the source's pixel (0,0), channel 0 */
+    int64_t pitch;            /* bytes per source row */
+    int32_t W, H;             /* source size */
+    int32_t crop_w, crop_h;   /* rectified crop size */
+    int32_t scratch_off;      /* byte offset of this crop in scratch_u8_dev */
+    int32_t reserved;         /* 0 */
+    double m[9];              /* crop (x, y, 1) -> source (X, Y, W) homography, row-major, float64 like cv2's */
+} rd_line_source_desc;
+int rd_line_warp_sources(int device_id, const rd_line_source_desc* descs_host, const rd_line_source_desc* descs_dev, int n,
+                         uint8_t* scratch_u8_dev, int64_t scratch_bytes, void* stream);
 
 /* Text-line direction classifier ("ppocr_cls_mobile"): x [B,3,H,W] (rapidocr's classifier pre-process gives 48 x 192) -> the head's softmax
  * [B,2] = (P(0 deg), P(180 deg)), the tensor the reference session returns for this graph.  flags 0, or RD_CLS_WANT_AUX: aux_dev also

@@ -563,16 +563,7 @@ class TableOcr:
         else:
             raw = self.det._pipe_for(lang or self.det.lang).rec_forward_sources([(canvas.contiguous(), [quads])], image_keys=[[0]],
                                                                                 want_words=True, pooled=False)[0][0]
-            # lines the recogniser marked degenerate (no homography: `ws` None) or read nothing in carry no words: they never reach the
-            # box arithmetic (whose inverse rotation would divide by a zero side / solve a singular system) and drop out below
-            good = [i for i, (t, _s, ws) in enumerate(raw) if ws and t]
-            infos = [WB.decode_word_info(raw[i][0], raw[i][2]["cols"], raw[i][2]["confs"], raw[i][2]["n_steps"], raw[i][2]["wh_ratio"],
-                                         raw[i][2]["max_wh_ratio"]) for i in good]
-            word_good = WB.cal_rec_boxes([raw[i][2]["crop_hw"] for i in good], [quads[i] for i in good], [raw[i][0] for i in good], infos)
-            word_lines: List[list] = [[] for _ in raw]
-            for i, wl in zip(good, word_good):
-                word_lines[i] = wl
-            lines = [(t, s, wl) for (t, s, _w), wl in zip(raw, word_lines)]
+            lines = WB.lines_with_words(raw, quads)      # (degenerate or empty lines carry no words and drop out below)
         origin = WB.calc_word_boxes([wl for _t, _s, wl in lines], h, w)     # (lines without words drop out: rapid_ocr.py:325-326)
         rec_res = list(zip([t for t, _s, _w in lines], [s for _t, s, _w in lines], origin))      # rapid_ocr.py:295 - zip, as it is
         out = []

@@ -360,6 +360,13 @@ int rd_line_warp_batch(int device_id, const uint8_t* pages, int P, int H, int W,
     if (rd::launch_line_warp(p, (hipStream_t)stream) != 0) return 1;
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
+int rd_line_warp_sources(int device_id, const rd_line_source_desc* descs_host, const rd_line_source_desc* descs_dev, int n,
+                         uint8_t* scratch, int64_t scratch_bytes, void* stream) {
+    std::string err;
+    const int rc = rd::launch_line_warp_sources(device_id, descs_host, descs_dev, n, scratch, scratch_bytes, (hipStream_t)stream, err);
+    if (rc != 0) g_create_err = err;
+    return rc;
+}
 int rd_line_resize_norm_batch(int device_id, const rd_line_crop_desc* descs, int n, const uint8_t* scratch, int out_h, int out_w_padded,
                               int swap_rb, float* out, void* stream) {
     if (!descs || !scratch || !out || n < 0 || out_h <= 0 || out_w_padded <= 0) return 1;

@@ -4,6 +4,7 @@
 //                               (PPPreProcess pp_doclayout/pre_process.py:22-42; rapidocr DetPreProcess, rapid_ocr.py:517-518)
 //   line_warp_kernel .......... cv2.warpPerspective(INTER_CUBIC, BORDER_REPLICATE) of every text line of a rec batch into a
 //                               packed uint8 scratch (utils/ocr_utils.py:494-536 get_rotate_crop_image)
+//   line_warp_sources_kernel .. the same warp for lines whose source images differ from line to line (rd_line_warp_sources)
 //   line_resize_norm_kernel ... np.rot90 for tall crops, cv2.resize (linear) to height 48, /255, (x - 0.5) / 0.5, zero right
 //                               padding (rapidocr resize_norm_img, called from rapid_ocr.py:436-440)
 // The arithmetic restated here (11-bit resize coefficients rounded half-to-even from float32, int32 rows, the two vertical
@@ -14,11 +15,15 @@
 #pragma clang fp contract(off)
 #include <cmath>
 #include <mutex>
+#include <string>
 #include <vector>
 
+#include "line_sources_check.h"
 #include "rd_device.h"
 
 namespace rd {
+
+static_assert(sizeof(rd_line_source_desc) == 112, "rd_line_source_desc layout");
 
 static inline int img_grid(long total, int cap = 16384) {
     long g = (total + 255) / 256;
@@ -291,6 +296,62 @@ int launch_line_flip180(const LineCropDesc* descs, int n, const float* prob, flo
 int launch_line_crops(const LineCropParams& p, hipStream_t s) {
     if (launch_line_warp(p, s) != 0) return 1;
     return launch_line_resize_norm(p, s);
+}
+
+// ---- text lines of one rec launch from ANY number of source images (include/rapiddoc_mi355.h rd_line_warp_sources): every line carries
+// its own source - device address, row pitch, size - so the lines of hundreds of region images of different sizes are warped by ONE
+// launch instead of one launch per image.  The arithmetic is line_warp_kernel's, expression for expression (a copy on purpose: the two
+// kernels share no body, so this one cannot move the other's generated code); only the addressing differs: rows are `pitch` bytes apart
+// (a source may be a window of a larger buffer) and the source starts at any byte address - every load is a single byte.
+// grid = (blocks along the largest crop, lines): blockIdx.y names the line, its descriptor is wave-uniform (scalar loads); the blocks of a
+// row of the grid stride over the crop's pixels, blocks past a smaller crop's end leave at once.  Stores are plain byte stores.
+__global__ void __launch_bounds__(256) line_warp_sources_kernel(const rd_line_source_desc* __restrict__ descs, uint8_t* __restrict__ scratch,
+                                                                const int16_t* __restrict__ tab) {
+    const rd_line_source_desc d = descs[blockIdx.y];
+    const long total = (long)d.crop_w * d.crop_h;
+    const uint8_t* src = d.src;
+    uint8_t* dst = scratch + d.scratch_off;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int x = (int)(idx % d.crop_w), y = (int)(idx / d.crop_w);
+        double w = d.m[6] * x + d.m[7] * y + d.m[8];
+        w = w != 0.0 ? 32.0 / w : 0.0;
+        const double fx = fmax(-2147483648.0, fmin(2147483647.0, (d.m[0] * x + d.m[1] * y + d.m[2]) * w));
+        const double fy = fmax(-2147483648.0, fmin(2147483647.0, (d.m[3] * x + d.m[4] * y + d.m[5]) * w));
+        const int X = __double2int_rn(fx), Y = __double2int_rn(fy);
+        const int sx = X >> 5, sy = Y >> 5;
+        const int16_t* wt = tab + (size_t)(((Y & 31) << 5) + (X & 31)) * 16;
+        int acc[3] = {0, 0, 0};
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int yy = min(max(sy - 1 + a, 0), d.H - 1);
+            const uint8_t* row = src + (size_t)yy * (size_t)d.pitch;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int xx = min(max(sx - 1 + b, 0), d.W - 1);
+                const int wv = wt[a * 4 + b];
+                acc[0] += (int)row[xx * 3 + 0] * wv;
+                acc[1] += (int)row[xx * 3 + 1] * wv;
+                acc[2] += (int)row[xx * 3 + 2] * wv;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dst[idx * 3 + c] = (uint8_t)min(max((acc[c] + (1 << 14)) >> 15, 0), 255);
+    }
+}
+
+int launch_line_warp_sources(int device, const rd_line_source_desc* host, const rd_line_source_desc* dev, int n, uint8_t* scratch,
+                             int64_t scratch_bytes, hipStream_t s, std::string& err) {
+    const std::string who = "rd_line_warp_sources: ";
+    int64_t max_pixels = 0;
+    if (check_line_sources(host, dev, n, scratch, scratch_bytes, max_pixels, err) != 0) return 1;
+    hipError_t rc = hipSetDevice(device);
+    if (rc != hipSuccess) { err = who + "hipSetDevice: " + hipGetErrorString(rc); return 1; }
+    const int16_t* tab = cubic_remap_table_dev();
+    if (!tab) { err = who + "no device memory for the cubic table"; return 1; }
+    hipLaunchKernelGGL(line_warp_sources_kernel, dim3(img_grid((long)max_pixels, 256), n), dim3(256), 0, s, dev, scratch, tab);
+    rc = hipGetLastError();
+    if (rc != hipSuccess) { err = who + "kernel launch: " + hipGetErrorString(rc); return 1; }
+    return 0;
 }
 
 }  // namespace rd

@@ -535,6 +535,11 @@ struct LineCropParams {
 int launch_line_crops(const LineCropParams& p, hipStream_t s);
 int launch_line_warp(const LineCropParams& p, hipStream_t s);          // stage 1 only (pages -> uint8 crops in the scratch buffer)
 int launch_line_resize_norm(const LineCropParams& p, hipStream_t s);   // stage 2 only (scratch crops -> fp32 rec batch tensor)
+// stage 1 for lines that each name their own source image: include/rapiddoc_mi355.h rd_line_warp_sources.  `host` / `dev`: the same
+// descriptors on the host (checked here, line_sources_check.h) and on the device (read by the kernel).  Returns 0, or 1 with the message
+// in `err` and nothing launched.
+int launch_line_warp_sources(int device, const rd_line_source_desc* host, const rd_line_source_desc* dev, int n, uint8_t* scratch,
+                             int64_t scratch_bytes, hipStream_t s, std::string& err);
 // CTC greedy decode on the device: idx / prob [B][T] -> per line (row stride row_bytes): int32 n_text_bytes, float32
 // confidence (numpy float32 mean of the kept probabilities), int32 n_kept, int32 0, UTF-8 text.  ctab: [n_classes][1 + max_len]
 // bytes (length, then the entry's UTF-8 bytes).

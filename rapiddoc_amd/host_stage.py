@@ -100,7 +100,9 @@ class HostImageStage:
         self._event = None
         self.uploads = 0
 
-    def upload(self, images: Sequence) -> Staged:
+    def upload(self, images: Sequence, tail_bytes: int = 0) -> Staged:
+        """`tail_bytes`: room the device buffer keeps BEHIND the uploaded images (from byte `sum of the aligned image sizes` on) for what
+        the consumer writes next to them - ocr_model's warped line crops, addressed from the same base as the uploaded ones."""
         import torch
         arrs = [as_stage_image(im) for im in images]
         shapes = [(int(a.shape[0]), int(a.shape[1])) for a in arrs]
@@ -111,7 +113,9 @@ class HostImageStage:
         if self._pin is None or self._pin.numel() < total:
             grown = max(total, 2 * (self._pin.numel() if self._pin is not None else 0), 1 << 16)
             self._pin = torch.empty(grown, dtype=torch.uint8, pin_memory=True)
-            self._dev = torch.empty(grown, dtype=torch.uint8, device=self.tdev)
+            self._dev = torch.empty(max(grown, total + int(tail_bytes)), dtype=torch.uint8, device=self.tdev)
+        elif self._dev.numel() < total + int(tail_bytes):
+            self._dev = torch.empty(max(total + int(tail_bytes), 2 * self._dev.numel()), dtype=torch.uint8, device=self.tdev)
         pack_images(arrs, offsets, self._pin.data_ptr(), total, self.n_threads)
         if total:
             self._dev[:total].copy_(self._pin[:total], non_blocking=True)

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib, ocr_host
 from .engine import RdEngine, preproc_resize_norm, preproc_resize_norm_batch
-from .rec_plan import (CLS_IMG_H, CLS_IMG_W, LINE_DTYPE, RecPlan, plan_rec,     # noqa: F401  (the crop helpers are imported from here)
+from .rec_plan import (CLS_IMG_H, CLS_IMG_W, LINE_DTYPE, LINE_SOURCE_DTYPE, RecPlan, plan_lines, plan_rec,     # noqa: F401  (the crop helpers are imported from here)
                        quad_to_crop_matrix, quads_to_crop_matrices)
 
 LAYOUT_SIZE = 800          # PP-DocLayout-L/plus-L/V2/V3 input (pp_doclayout/main.py:17-29)
@@ -209,6 +209,7 @@ class PagePipeline:
         self._width_sync_epoch, self._in_run_batch = 0, False
         self.keep_rec_inputs = False      # tests: keep every rec batch's input tensor and raw (idx, prob) in last_rec_batches
         self.last_rec_batches: List[Tuple[np.ndarray, torch.Tensor, torch.Tensor, torch.Tensor]] = []
+        self._raw_scores = False          # True inside rec_forward_crops: the scores as the recogniser gives them, not as analyze_utils.py:280 prints them
         self._lib = _lib.load()
         self.stats: Dict[str, float] = {}
 
@@ -278,6 +279,64 @@ class PagePipeline:
             out = self._rec_forward_sources_once(sources, image_keys, want_words)
         return out
 
+    def rec_forward_crops(self, crop_w, crop_h, rot90, ok, scratch_off, scratch: int, scratch_bytes: int, src_descs: Optional[np.ndarray] = None,
+                          want_words: bool = False) -> list:
+        """The recogniser on lines that are given as CROPS in a scratch buffer the caller owns (ocr_model.Mi355RapidOcrModel: the crops an
+        unmodified RapidDoc pools into one `ocr(det=False)` call), pooled as ONE list - the strict mode then batches them exactly as the
+        reference's loop does (rapid_ocr.py:404-472).  Line i is the packed uint8 [crop_h[i]][crop_w[i]][3] image at `scratch +
+        scratch_off[i]` (BGR, as rapidocr takes it), read by rd_line_resize_norm_batch directly; `rot90[i]`: the recogniser sees np.rot90
+        of it; `ok[i]` False: no crop, the line gets ("", 0.0).  `src_descs` (LINE_SOURCE_DTYPE [n], or None): a line whose `src` is
+        not 0 is not in the scratch yet - it is warped there from its source image, all such lines of a rec launch by ONE
+        rd_line_warp_sources launch (`stats["warp_source_launches"]` counts them).  Returns per line (text, score) in the caller's order,
+        the score as the recogniser gives it (with `want_words`: (text, score, words), see rec_forward_sources).  Carries the range guard
+        of rec_forward_sources.  `use_cls` pipelines are refused: a turned crop would stay turned in the caller's buffer."""
+        if self.use_cls:
+            raise ValueError("rec_forward_crops: not available on a use_cls pipeline")
+        n = len(crop_w)
+        cw, ch = np.asarray(crop_w, dtype=np.float64), np.asarray(crop_h, dtype=np.float64)
+        offs = np.asarray(scratch_off, dtype=np.int64)
+        if n and (int(scratch_bytes) >= 2 ** 31 or int(offs.max()) >= 2 ** 31):
+            raise RuntimeError("rec_forward_crops: the crops of one call must lie inside 2 GB (scratch_off is an int32)")
+        pooling = dict(n_img=[1], src_of=np.zeros(n, np.int32), page_of=np.zeros(n, np.int32), perm=None, n_all=n)
+        self._sync_this_call = False
+        if not self._in_run_batch:
+            self._width_sync_epoch += 1
+
+        def once():
+            t0 = time.perf_counter()
+            self.last_cls = None
+            plan = plan_lines(pooling, np.zeros((n, 9)), cw, ch, np.asarray(rot90, dtype=np.int32), np.asarray(ok, dtype=bool), None, 0,
+                              **self._plan_modes(self.rec_mode == "strict"), want_words=want_words)
+            if plan.n:
+                lines = plan.keep[plan.order_all]
+                plan.descs["page"] = 0
+                plan.descs["scratch_off"] = offs[lines].astype(np.int32)
+                plan.batch_base = np.zeros(len(plan.batches) + 1, np.int64)       # every launch reads the caller's buffer from its start
+                plan.src_descs = np.zeros(0, LINE_SOURCE_DTYPE)
+                plan.src_jobs = [(0, 0)] * len(plan.batches)
+                plan.src_scratch_bytes = int(scratch_bytes)
+                plan.swap_rb = 0                                                  # the caller's crops are BGR already
+                if src_descs is not None:
+                    sd = np.ascontiguousarray(src_descs, dtype=LINE_SOURCE_DTYPE)[lines]
+                    sd["scratch_off"] = plan.descs["scratch_off"]
+                    warp = sd["src"] != 0
+                    first = np.concatenate([[0], np.cumsum(warp)])
+                    plan.src_descs = np.ascontiguousarray(sd[warp])
+                    plan.src_jobs = [(int(first[a]), int(first[e] - first[a])) for a, e in zip(plan.starts[:-1], plan.starts[1:])]
+            return self._run_rec_plan(plan, None, want_words, t0, scratch=int(scratch))[0][0]
+
+        self._raw_scores = True
+        try:
+            out = once()
+            for _ in range(3):
+                if not any([e.check_range_and_fallback() for e in self.rec_engines + [self.rec_tail]]):
+                    break
+                self.stats["range_fallbacks"] = self.stats.get("range_fallbacks", 0) + 1
+                out = once()
+        finally:
+            self._raw_scores = False
+        return out
+
     def _synced_widths(self, sync, keys: np.ndarray, ratios: np.ndarray):
         """One collective per recogniser CALL (per page batch inside run_batch): a range-guard repeat (same lines) re-uses the first
         pass's answer - a rank that repeats must not make a collective call its peers do not make."""
@@ -345,21 +404,32 @@ class PagePipeline:
         sync = None         # the width collective: a pooled call of the strict two-stage mode of a page-sharded run
         if self.rec_width_sync is not None and strict and self.rec_two_stage and self._sync_this_call:
             sync = lambda keys, ratios: self._synced_widths(self.rec_width_sync, keys, ratios)      # noqa: E731
-        plan = plan_rec([(imgs.shape[0], quads) for imgs, quads in sources], image_keys, strict=strict, two_stage=self.rec_two_stage,
-                        lines_in_launch=self.rec_lines_in_launch, chunking=self.rec_chunking, rec_batch_num=self.rec_batch_num,
-                        rec_width_multiple=self.rec_width_multiple, n_cu=self.n_cu, n_streams=len(self.rec_engines), use_cls=self.use_cls,
-                        host_native=self.host_native, want_words=want_words, width_sync=sync)
+        plan = plan_rec([(imgs.shape[0], quads) for imgs, quads in sources], image_keys, **self._plan_modes(strict), want_words=want_words,
+                        width_sync=sync)
+        return self._run_rec_plan(plan, sources, want_words, t0)
+
+    def _plan_modes(self, strict: bool) -> dict:
+        """what rec_plan.plan_rec / plan_lines need to know about this pipeline"""
+        return dict(strict=strict, two_stage=self.rec_two_stage, lines_in_launch=self.rec_lines_in_launch, chunking=self.rec_chunking,
+                    rec_batch_num=self.rec_batch_num, rec_width_multiple=self.rec_width_multiple, n_cu=self.n_cu,
+                    n_streams=len(self.rec_engines), use_cls=self.use_cls, host_native=self.host_native)
+
+    def _run_rec_plan(self, plan: RecPlan, sources, want_words: bool, t0: float, scratch: Optional[int] = None):
+        """enqueue, decode, scatter of a planned call.  `scratch`: device address of a crop scratch the CALLER owns (rec_forward_crops);
+        default: the pipeline's own, grown to the plan's size."""
         scatter = lambda per_line: self._scatter_texts(per_line, plan.src_of, plan.page_of, plan.n_img, plan.perm)      # noqa: E731
         cls_of: List[tuple] = [(False, 0, 0.0)] * plan.n_all
         if plan.n == 0:                 # nothing to recognise: degenerate quads get ("", 0.0)
             if self.use_cls and plan.n_all:
                 self.last_cls = scatter(cls_of)
             return scatter([("", 0.0, None) if want_words else ("", 0.0)] * plan.n_all)
-        if getattr(self, "_crop_scratch", None) is None or self._crop_scratch.numel() < plan.scratch_bytes:
-            self._crop_scratch = torch.empty(int(plan.scratch_bytes * 1.25) + 1024, dtype=torch.uint8, device=sources[0][0].device)
+        if scratch is None:
+            if getattr(self, "_crop_scratch", None) is None or self._crop_scratch.numel() < plan.scratch_bytes:
+                self._crop_scratch = torch.empty(int(plan.scratch_bytes * 1.25) + 1024, dtype=torch.uint8, device=sources[0][0].device)
+            scratch = self._crop_scratch.data_ptr()
         self.stats["t_descs_ms"] = (time.perf_counter() - t0) * 1e3
         main = torch.cuda.current_stream()
-        launches = self._enqueue_rec(plan, sources, want_words)
+        launches = self._enqueue_rec(plan, sources, want_words, scratch)
         self.stats["t_rec_enqueue_ms"] = (time.perf_counter() - t0) * 1e3 - self.stats["t_descs_ms"]
         hook, self._after_rec_enqueue = self._after_rec_enqueue, None
         if hook is not None:
@@ -384,11 +454,12 @@ class PagePipeline:
             self.last_cls_prob = (plan.line_ids, ph)      # tests: pooled line ids and the raw probabilities
         return scatter(texts)
 
-    def _enqueue_rec(self, plan: RecPlan, sources, want_words: bool) -> List[_RecLaunch]:
+    def _enqueue_rec(self, plan: RecPlan, sources, want_words: bool, scratch_base: int) -> List[_RecLaunch]:
         """Everything the stage puts on the GPU, in launch order: the descriptor uploads, then per launch `bi` on stream `bi % S` the warp
         jobs, the optional classifier, the recogniser's resize and its forward; with the two-stage recogniser `_enqueue_tail(g)` directly
-        after the last launch of group g."""
-        dev, S, lib = sources[0][0].device, len(self.rec_engines), self._lib
+        after the last launch of group g.  A plan of rec_forward_crops has no warp jobs and carries `src_descs` / `src_jobs` instead: ONE
+        rd_line_warp_sources launch per rec launch that has lines to warp."""
+        dev, S, lib = (sources[0][0].device if sources else self.tdev), len(self.rec_engines), self._lib
         keep_inputs = self.keep_rec_inputs
         upload = lambda descs: torch.from_numpy(descs.view(np.uint8)).to(dev, non_blocking=True)      # noqa: E731
         descs_dev = upload(plan.descs)
@@ -397,6 +468,7 @@ class PagePipeline:
             cls = (upload(plan.descs_cls), self._buf("cls_prob", 2 * plan.n).view(plan.n, 2), self._buf("cls_flip", plan.n, torch.int32),
                    torch.empty((plan.n, 2), dtype=torch.float32, pin_memory=True), torch.empty((plan.n,), dtype=torch.int32, pin_memory=True))
         descs_warp_dev = upload(plan.descs_warp) if plan.descs_warp is not None else descs_dev
+        src_descs_dev = upload(plan.src_descs) if plan.src_descs is not None and len(plan.src_descs) else None
         if keep_inputs:          # tests: the descriptors in launch order, every batch's scratch base and first line; the classifier's inputs
             self.last_rec_descs = (plan.descs.copy(), np.asarray(plan.batch_base, dtype=np.int64), np.asarray(plan.starts, dtype=np.int64))
             self.last_cls_inputs = []
@@ -428,7 +500,15 @@ class PagePipeline:
             with torch.cuda.stream(st):
                 # one input buffer per stream (batches bi, bi + S, ... of a stream run one after the other)
                 x = self._buf(("rec_x", k), nb * 3 * ocr_host.REC_IMG_H * wpad).view(nb, 3, ocr_host.REC_IMG_H, wpad)
-                scratch = self._crop_scratch.data_ptr() + int(plan.batch_base[bi])
+                scratch = scratch_base + int(plan.batch_base[bi])
+                if plan.src_jobs is not None and plan.src_jobs[bi][1]:       # stage 1, every line from a source of its own: one launch
+                    first, cnt = plan.src_jobs[bi]
+                    off = first * LINE_SOURCE_DTYPE.itemsize
+                    rc = lib.rd_line_warp_sources(self.device, plan.src_descs.ctypes.data + off, src_descs_dev.data_ptr() + off, cnt, scratch,
+                                                  int(plan.src_scratch_bytes), st.cuda_stream)
+                    if rc != 0:
+                        raise RuntimeError(lib.rd_create_error().decode())
+                    self.stats["warp_source_launches"] = self.stats.get("warp_source_launches", 0) + 1
                 for si, first, cnt, max_px in plan.warp_jobs[bi]:            # stage 1: page / canvas -> rectified uint8 crops
                     imgs = sources[si][0]
                     rc = lib.rd_line_warp_batch(self.device, imgs.data_ptr(), imgs.shape[0], imgs.shape[1], imgs.shape[2],
@@ -439,7 +519,7 @@ class PagePipeline:
                 if cls is not None:           # classify the crops and turn the upside-down ones in the scratch, before the recogniser reads it
                     self._enqueue_cls(launch, cls, descs_dev, k, pos, nb, scratch, plan.line_ids[pos: pos + nb])
                 rc = lib.rd_line_resize_norm_batch(self.device, descs_dev.data_ptr() + pos * LINE_DTYPE.itemsize, nb, scratch,
-                                                   ocr_host.REC_IMG_H, wpad, 1, x.data_ptr(), st.cuda_stream)   # stage 2
+                                                   ocr_host.REC_IMG_H, wpad, plan.swap_rb, x.data_ptr(), st.cuda_stream)   # stage 2
                 if rc != 0:
                     raise RuntimeError("rd_line_resize_norm_batch failed")
                 if plan.lines_in_launch:
@@ -516,9 +596,12 @@ class PagePipeline:
     def _texts_from_rows(self, rows_np: np.ndarray, line_ids: np.ndarray, texts: list) -> None:
         """Collapsed CTC rows -> texts[pooled line] = (text, score as analyze_utils.py:280 prints it), in the library or in Python."""
         if self.host_native:
-            txt, _conf, conf3 = ocr_host.parse_ctc_rows_native(rows_np)
-            for i, t, s in zip(line_ids.tolist(), txt, conf3):
+            txt, conf, conf3 = ocr_host.parse_ctc_rows_native(rows_np)
+            for i, t, s in zip(line_ids.tolist(), txt, conf if self._raw_scores else conf3):
                 texts[i] = (t, s)
+        elif self._raw_scores:
+            for i, ts in zip(line_ids.tolist(), ocr_host.parse_ctc_rows(rows_np)):
+                texts[i] = ts
         else:
             for i, (t, s) in zip(line_ids.tolist(), ocr_host.parse_ctc_rows(rows_np)):
                 texts[i] = (t, ocr_host.format_score(s))

@@ -21,6 +21,10 @@ CLS_IMG_H, CLS_IMG_W = 48, 192       # the text-line classifier's input (PaddleO
 LINE_DTYPE = np.dtype([("page", "<i4"), ("out_w", "<i4"), ("crop_w", "<i4"), ("crop_h", "<i4"), ("rot90", "<i4"),
                        ("scratch_off", "<i4"), ("m", "<f8", (9,))])
 assert LINE_DTYPE.itemsize == 96
+# rd_line_source_desc: a line that names its own source image (rd_line_warp_sources)
+LINE_SOURCE_DTYPE = np.dtype([("src", "<u8"), ("pitch", "<i8"), ("W", "<i4"), ("H", "<i4"), ("crop_w", "<i4"), ("crop_h", "<i4"),
+                              ("scratch_off", "<i4"), ("reserved", "<i4"), ("m", "<f8", (9,))])
+assert LINE_SOURCE_DTYPE.itemsize == 112
 
 
 def quad_to_crop_matrix(quad: np.ndarray) -> Tuple[np.ndarray, float, float]:
@@ -118,6 +122,12 @@ class RecPlan:
     descs_cls: Optional[np.ndarray] = None                      # the classifier's resize (use_cls), else None
     descs_warp: Optional[np.ndarray] = None                     # several sources: every launch's descriptors grouped by source, else None
     warp_jobs: Optional[List[List[Tuple[int, int, int, int]]]] = None   # per launch: (source, first desc, count, max crop pixels)
+    # lines that name their own source (PagePipeline.rec_forward_crops; no warp jobs then): LINE_SOURCE_DTYPE of the lines to warp
+    # in launch order, per launch (first desc, count), the size of the scratch buffer they are written into
+    src_descs: Optional[np.ndarray] = None
+    src_jobs: Optional[List[Tuple[int, int]]] = None
+    src_scratch_bytes: int = 0
+    swap_rb: int = 1                    # the recogniser's resize exchanges channels 0 and 2 (the crops are RGB; rapidocr works on BGR)
     batch_base: Optional[np.ndarray] = None                     # first scratch byte of every launch, and the total
     # two-stage: tokens per line, the groups of S launches that share a tail call, their real and padded (engine.pad_tail_lengths)
     # line lengths, every group's first token, every line's first token, every launch's, the line table of the backbone
@@ -174,13 +184,28 @@ def plan_rec(sources: Sequence[Tuple[int, Sequence[np.ndarray]]], image_keys: Op
         perm = np.argsort(key, kind="stable")
         quads, src_of, page_of, key = quads[perm], src_of[perm], page_of[perm], key[perm]
     mats, cws_a, chs_a, ok = quads_to_crop_matrices(quads)
+    rots_a = (chs_a / cws_a >= 2.0).astype(np.int32)  # ocr_utils.py:531-534 rotates crops with h/w >= 2
+    return plan_lines(dict(n_img=n_img, src_of=src_of, page_of=page_of, perm=perm, n_all=len(quads)), mats, cws_a, chs_a, rots_a, ok,
+                      key if image_keys is not None else None, len(sources), strict=strict, two_stage=two_stage,
+                      lines_in_launch=lines_in_launch, chunking=chunking, rec_batch_num=rec_batch_num, rec_width_multiple=rec_width_multiple,
+                      n_cu=n_cu, n_streams=n_streams, use_cls=use_cls, host_native=host_native, want_words=want_words, width_sync=width_sync)
+
+
+def plan_lines(pooling: dict, mats: np.ndarray, cws_a: np.ndarray, chs_a: np.ndarray, rots_a: np.ndarray, ok: np.ndarray,
+               key: Optional[np.ndarray], n_sources: int, *, strict: bool, two_stage: bool, lines_in_launch: bool, chunking: str,
+               rec_batch_num: int, rec_width_multiple: int, n_cu: int, n_streams: int, use_cls: bool = False, host_native: bool = True,
+               want_words: bool = False, width_sync: Optional[Callable] = None) -> RecPlan:
+    """The plan of a pooled line list that is given as crops: per pooled line its crop -> source homography `mats` [n, 9], crop size
+    `cws_a` x `chs_a`, `rots_a` (1: the recogniser sees np.rot90 of the crop) and `ok` (False: no crop exists, the line gets ("", 0.0)).
+    `pooling`: n_img, src_of, page_of, perm, n_all of the RecPlan; `key`: the pooling key per line, or None.  `plan_rec` ends here;
+    `n_sources` = 0 (ocr_model.Mi355RapidOcrModel: every line names its own source, rd_line_warp_sources) lists no warp launches."""
+    src_of, page_of = pooling["src_of"], pooling["page_of"]
     keep = np.nonzero(ok)[0]                      # degenerate quads (zero-area / collinear corners) get ("", 0.0)
     n = len(keep)
-    pooling = dict(n_img=n_img, src_of=src_of, page_of=page_of, perm=perm, keep=keep, n_all=len(quads))
+    pooling = dict(pooling, keep=keep)
     if n == 0:
         return _no_lines(width_sync, **pooling)
-    mats, cws_a, chs_a = mats[keep], cws_a[keep], chs_a[keep]
-    rots_a = (chs_a / cws_a >= 2.0).astype(np.int32)  # ocr_utils.py:531-534 rotates crops with h/w >= 2
+    mats, cws_a, chs_a, rots_a = mats[keep], cws_a[keep], chs_a[keep], rots_a[keep]
     eff_w = np.where(rots_a == 1, chs_a, cws_a)
     eff_h = np.where(rots_a == 1, cws_a, chs_a)
     ratios = (eff_w / eff_h).tolist()
@@ -191,7 +216,7 @@ def plan_rec(sources: Sequence[Tuple[int, Sequence[np.ndarray]]], image_keys: Op
     if lines_mode:
         given = None
         if width_sync is not None:  # the widths come from the pooled lines of every rank; key = the image key (global page index)
-            line_keys = key[keep] if image_keys is not None else page_of[keep].astype(np.int64)
+            line_keys = key[keep] if key is not None else page_of[keep].astype(np.int64)
             given = width_sync(line_keys, np.asarray(ratios, dtype=np.float64))
         batches, line_w, line_ratio = ocr_host.rec_batches_lines(ratios, n_cu=n_cu, with_ratio=True, given=given, native=host_native)
         if not lines_in_launch:
@@ -233,7 +258,9 @@ def plan_rec(sources: Sequence[Tuple[int, Sequence[np.ndarray]]], image_keys: Op
     # pipeline) needs no second descriptor array: the batch's own descriptors are the launch's.
     crop_px = descs["crop_w"].astype(np.int64) * descs["crop_h"]
     plan.warp_jobs = []
-    if len(sources) > 1:
+    if n_sources == 0:
+        plan.warp_jobs = [[] for _ in range(nb)]
+    elif n_sources > 1:
         src_sorted = src_of[keep][order_all]
         warp_order = np.concatenate([starts[b] + np.argsort(src_sorted[starts[b]:starts[b + 1]], kind="stable") for b in range(nb)])
         plan.descs_warp = descs[warp_order]

@@ -267,3 +267,18 @@ def cal_rec_boxes(crop_hw: Sequence[Tuple[int, int]], dt_boxes: Sequence[np.ndar
         boxes = reverse_rotate_crop_image(copy.deepcopy(np.asarray(box, dtype=np.float32)), boxes, get_box_direction(np.asarray(box, dtype=np.float32)))
         out.append(list(zip(contents, confs, boxes)))
     return out
+
+
+def lines_with_words(raw: Sequence[tuple], quads: Sequence[np.ndarray]) -> List[tuple]:
+    """The recogniser's `want_words` lines (text, score, words = {cols, confs, n_steps, wh_ratio, max_wh_ratio, crop_hw} or None) with the
+    boxes `quads` they were cropped from -> [(text, score, [(word, conf, box) ...])], what rapidocr's cal_rec_boxes leaves per line.  Lines
+    the recogniser marked degenerate (no homography: words None) or read nothing in carry no words: they never reach the box arithmetic
+    (whose inverse rotation would divide by a zero side / solve a singular system)."""
+    good = [i for i, (t, _s, ws) in enumerate(raw) if ws and t]
+    infos = [decode_word_info(raw[i][0], raw[i][2]["cols"], raw[i][2]["confs"], raw[i][2]["n_steps"], raw[i][2]["wh_ratio"],
+                              raw[i][2]["max_wh_ratio"]) for i in good]
+    word_good = cal_rec_boxes([raw[i][2]["crop_hw"] for i in good], [quads[i] for i in good], [raw[i][0] for i in good], infos)
+    word_lines: List[list] = [[] for _ in raw]
+    for i, wl in zip(good, word_good):
+        word_lines[i] = wl
+    return [(t, s, wl) for (t, s, _w), wl in zip(raw, word_lines)]
