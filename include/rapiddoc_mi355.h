@@ -170,6 +170,27 @@ int rd_preproc_resize_norm(int device_id, const uint8_t* hwc_u8_dev, int H, int 
 int rd_preproc_resize_norm_batch(int device_id, const uint8_t* pages_u8_dev, int P, int H, int W, int OH, int OW, const float mean[3],
                                  const float std[3], float scale, int interp, int swap_rb, float* out_nchw_dev, void* stream);
 
+/* rd_preproc_resize_norm for n source images of ANY sizes, each to its own output size, in ONE launch (the pages of a batch whose sizes
+ * differ: the reference slices the pages of many documents into one batch, pipeline_analyze.py:135,197-201).  Source k: u8 [H][W][3] at
+ * `src`, ANY byte address, rows `pitch` >= 3 * W bytes apart (a window of a larger image); its [3][OH][OW] float32 planes are written to
+ * out_dev + out_off - bit for bit what rd_preproc_resize_norm writes for a contiguous copy of the source with the same mean, std, scale,
+ * interp and swap_rb (which all sources of a call share).  No byte outside [src + y * pitch, src + y * pitch + 3 * W) of a row y < H is
+ * read, nothing outside the slots is written.  descs_host and descs_dev hold the same n descriptors on the host and on the device
+ * (uploaded on `stream` by the caller): the checks read the host copy, so nothing is read back and the stream is not synchronised.
+ * Return 0 = ok, 1 = bad arguments - a NULL array or NULL out_dev, n outside 1 .. 65535, a NULL src, pitch < 3 * W, a side outside
+ * 1 .. 32768, interp other than 1 / 2, a negative out_off, a slot that overruns out_floats, two slots that overlap: nothing launched,
+ * the message is rd_create_error()'s. */
+typedef struct rd_resize_source_desc {
+    const uint8_t* src;       /* device address of pixel (0, 0), 3-channel uint8 HWC, any byte alignment */
+    int64_t pitch;            /* bytes between rows, >= 3 * W */
+    int64_t out_off;          /* offset in floats of this source's [3][OH][OW] planes inside out_dev */
+    int32_t W, H, OW, OH;
+    int32_t reserved[2];      /* 0 */
+} rd_resize_source_desc;
+int rd_preproc_resize_norm_sources(int device_id, const rd_resize_source_desc* descs_host, const rd_resize_source_desc* descs_dev, int n,
+                                   const float mean[3], const float std[3], float scale, int interp, int swap_rb, float* out_dev,
+                                   int64_t out_floats, void* stream);
+
 /* u8 HWC (3 channels) device image -> Pillow's antialiased bilinear resample to OHxOW -> ((v / 255) - mean[c]) / std[c] -> CHW float32:
  * transforms.Resize((OH, OW)) on a PIL image, ToTensor and Normalize, as UniTable's TablePreprocess runs them
  * (rapid_table_self/table_structure/unitable/pre_process.py).  The resample is Pillow's 8-bit path bit for bit (Resample.c): per axis

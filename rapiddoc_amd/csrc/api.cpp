@@ -252,6 +252,16 @@ int rd_preproc_resize_norm_batch(int device_id, const uint8_t* src, int P, int H
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+int rd_preproc_resize_norm_sources(int device_id, const rd_resize_source_desc* descs_host, const rd_resize_source_desc* descs_dev, int n,
+                                   const float mean[3], const float std[3], float scale, int interp, int swap_rb, float* out_dev,
+                                   int64_t out_floats, void* stream) {
+    std::string err;
+    const int rc = rd::launch_preproc_resize_norm_sources(device_id, descs_host, descs_dev, n, mean, std, scale, interp, swap_rb, out_dev,
+                                                          out_floats, (hipStream_t)stream, err);
+    if (rc != 0) g_create_err = err;
+    return rc;
+}
+
 int rd_preproc_resize_aa_norm(int device_id, const uint8_t* src, int H, int W, int OH, int OW, const float mean[3], const float std[3],
                               int swap_rb, float* out, uint8_t* out_u8, void* stream) {
     std::string err;

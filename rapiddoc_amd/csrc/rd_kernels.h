@@ -540,6 +540,12 @@ int launch_line_resize_norm(const LineCropParams& p, hipStream_t s);   // stage 
 // in `err` and nothing launched.
 int launch_line_warp_sources(int device, const rd_line_source_desc* host, const rd_line_source_desc* dev, int n, uint8_t* scratch,
                              int64_t scratch_bytes, hipStream_t s, std::string& err);
+// resize + normalise of n sources of any sizes in one launch (kernels_resize_sources.hip): include/rapiddoc_mi355.h
+// rd_preproc_resize_norm_sources.  `host` / `dev`: the same descriptors on the host (checked, resize_sources_check.h) and on the device
+// (read by the kernel).  Returns 0, or 1 with the message in `err` and nothing launched.
+int launch_preproc_resize_norm_sources(int device, const rd_resize_source_desc* host, const rd_resize_source_desc* dev, int n, const float mean[3],
+                                       const float std[3], float scale, int interp, int swap_rb, float* out, int64_t out_floats, hipStream_t s,
+                                       std::string& err);
 // CTC greedy decode on the device: idx / prob [B][T] -> per line (row stride row_bytes): int32 n_text_bytes, float32
 // confidence (numpy float32 mean of the kept probabilities), int32 n_kept, int32 0, UTF-8 text.  ctab: [n_classes][1 + max_len]
 // bytes (length, then the entry's UTF-8 bytes).

@@ -639,6 +639,85 @@ def preproc_resize_norm_batch(imgs_u8_nhwc: torch.Tensor, out_hw: Tuple[int, int
     return out
 
 
+# rd_resize_source_desc: a source image that names its own address, pitch, sizes and destination (rd_preproc_resize_norm_sources)
+RESIZE_SOURCE_DTYPE = np.dtype([("src", "<u8"), ("pitch", "<i8"), ("out_off", "<i8"), ("W", "<i4"), ("H", "<i4"), ("OW", "<i4"), ("OH", "<i4"),
+                                ("reserved", "<i4", (2,))])
+
+
+def pack_resize_sources(ptrs: Sequence[int], pitches: Sequence[int], hws: Sequence[Tuple[int, int]], out_hws: Sequence[Tuple[int, int]],
+                        out_offs: Sequence[int]) -> np.ndarray:
+    """Host only: one rd_resize_source_desc per source.  `ptrs[k]` / `pitches[k]`: device address of pixel (0, 0) and bytes between rows of
+    source k, `hws[k]` = (H, W) its size, `out_hws[k]` = (OH, OW) its output size, `out_offs[k]` the offset in FLOATS of its planes."""
+    n = len(ptrs)
+    if not (len(pitches) == len(hws) == len(out_hws) == len(out_offs) == n):
+        raise ValueError("pack_resize_sources: one pitch, size, output size and offset per source")
+    descs = np.zeros(n, dtype=RESIZE_SOURCE_DTYPE)
+    for k in range(n):
+        (h, w), (oh, ow) = hws[k], out_hws[k]
+        descs[k] = (int(ptrs[k]), int(pitches[k]), int(out_offs[k]), int(w), int(h), int(ow), int(oh), (0, 0))
+    return descs
+
+
+def resize_source_view(t: torch.Tensor) -> Tuple[int, int]:
+    """(device address, row pitch in bytes) of a uint8 [H, W, 3] device image as rd_preproc_resize_norm_sources reads it: channels 1 byte
+    and pixels 3 bytes apart, rows at a pitch of at least 3 * W - a window of a larger image is read where it lies."""
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3 and t.shape[0] >= 1 and t.shape[1] >= 1):
+        raise EngineError(f"a resize source must be a uint8 [H, W, 3] device image, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    h, w = int(t.shape[0]), int(t.shape[1])
+    if not (t.stride(2) == 1 and (w == 1 or t.stride(1) == 3) and (h == 1 or t.stride(0) >= 3 * w)):
+        raise EngineError(f"a resize source must have packed pixels and a row pitch of at least 3 * W, got strides {tuple(t.stride())}")
+    return t.data_ptr(), (int(t.stride(0)) if h > 1 else 3 * w)
+
+
+def launch_resize_sources(descs: np.ndarray, device: torch.device, out_ptr: int, out_floats: int, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0),
+                          scale: float = 1.0 / 255.0, interp: int = 2, swap_rb: bool = False) -> None:
+    """rd_preproc_resize_norm_sources on a descriptor array: its device copy is uploaded here (pinned, asynchronous, current stream).  Bad
+    arguments raise EngineError with the library's message; nothing is launched then."""
+    lib = _lib.load()
+    descs = np.ascontiguousarray(descs, dtype=RESIZE_SOURCE_DTYPE)
+    host = torch.empty(max(descs.nbytes, 16), dtype=torch.uint8, pin_memory=True)
+    host[: descs.nbytes] = torch.from_numpy(descs.view(np.uint8).reshape(-1))
+    dev = host.to(device, non_blocking=True)
+    rc = lib.rd_preproc_resize_norm_sources(device.index or 0, descs.ctypes.data, dev.data_ptr(), len(descs), (C.c_float * 3)(*mean),
+                                            (C.c_float * 3)(*std), scale, int(interp), 1 if swap_rb else 0, out_ptr, C.c_int64(int(out_floats)),
+                                            _stream_ptr())
+    if rc != 0:
+        raise EngineError(lib.rd_create_error().decode())
+
+
+def preproc_resize_norm_sources(sources: Sequence[torch.Tensor], out_hws: Sequence[Tuple[int, int]], mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0),
+                                scale: float = 1.0 / 255.0, interp: int = 2, swap_rb: bool = False,
+                                out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """`preproc_resize_norm` for uint8 [H_k, W_k, 3] device images of DIFFERENT sizes, source k to out_hws[k] = (OH_k, OW_k), in ONE launch
+    (rd_preproc_resize_norm_sources) -> one [3, OH_k, OW_k] float32 tensor per source, bit for bit what `preproc_resize_norm` gives for a
+    contiguous copy.  A source may be a window of a larger image (row pitch above 3 * W).  `out`: one contiguous float32 [3, OH_k, OW_k]
+    destination per source, anywhere on the sources' device (rows of per-shape batch tensors, say) as long as no two overlap; default:
+    views of one new buffer.  Bad arguments raise EngineError; nothing is launched then."""
+    n = len(sources)
+    if n == 0:
+        return []
+    if len(out_hws) != n or (out is not None and len(out) != n):
+        raise EngineError("preproc_resize_norm_sources: one output size (and one `out` tensor) per source")
+    device = sources[0].device
+    views = [resize_source_view(t) for t in sources]
+    if any(t.device != device for t in sources):
+        raise EngineError("preproc_resize_norm_sources: the sources must lie on one device")
+    out_hws = [(int(oh), int(ow)) for oh, ow in out_hws]
+    if out is None:
+        offs = np.concatenate([[0], np.cumsum([3 * oh * ow for oh, ow in out_hws])]).astype(np.int64)
+        flat = torch.empty(int(offs[-1]), dtype=torch.float32, device=device)
+        out = [flat[int(o): int(o) + 3 * oh * ow].view(3, oh, ow) for o, (oh, ow) in zip(offs[:-1], out_hws)]
+    for t, (oh, ow) in zip(out, out_hws):
+        if not (t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (3, oh, ow)):
+            raise EngineError(f"preproc_resize_norm_sources: an `out` tensor does not match [3, {oh}, {ow}] float32 on {device}")
+    base = min(t.data_ptr() for t in out)          # one base address for the call: every destination is a float offset from it
+    offs = [(t.data_ptr() - base) // 4 for t in out]
+    out_floats = max(o + t.numel() for o, t in zip(offs, out))
+    descs = pack_resize_sources([p for p, _ in views], [q for _, q in views], [(int(t.shape[0]), int(t.shape[1])) for t in sources], out_hws, offs)
+    launch_resize_sources(descs, device, base, out_floats, mean, std, scale, interp, swap_rb)
+    return list(out)
+
+
 def preproc_resize_aa_norm(img_u8_hwc: torch.Tensor, out_hw: Tuple[int, int], mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), swap_rb: bool = False,
                            return_u8: bool = False, out: Optional[torch.Tensor] = None):
     """u8 HWC device image -> Pillow's antialiased bilinear resample (bit for bit) -> ((v / 255) - mean) / std -> CHW float32

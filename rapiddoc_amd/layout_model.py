@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import layout_host
-from .engine import preproc_resize_norm
+from .engine import preproc_resize_norm, preproc_resize_norm_sources
+from .host_stage import HostImageStage
 
 _TABLES = {k: {int(c): v for c, v in t.items()}
            for k, t in json.loads((Path(__file__).resolve().parent / "data" / "layout_model_tables.json").read_text()).items()}
@@ -117,7 +118,38 @@ class LayoutModel:
     # ------------------------------------------------------------------ PPPreProcess on the GPU (pre_process.py:22-42)
     def preprocess(self, pages: Sequence[Union[np.ndarray, torch.Tensor]]) -> Tuple[torch.Tensor, np.ndarray]:
         """u8 HWC pages (host arrays or device tensors, RGB as the pipeline hands them over, load_image.py:76-79) ->
-        f32 [B,3,S,S] on the device + scale_factor f32[B,2] = [S / H, S / W] (main.py:46-52)."""
+        f32 [B,3,S,S] on the device + scale_factor f32[B,2] = [S / H, S / W] (main.py:46-52).  `PREPROCESS_ROUTE`: "sources" stages the
+        host pages once and resizes all pages in one launch, "loop" copies and launches page by page; the same bits either way."""
+        if self.PREPROCESS_ROUTE == "sources" and len(pages):
+            return self.preprocess_sources(pages)
+        return self.preprocess_loop(pages)
+
+    PREPROCESS_ROUTE = "loop"          # profiles/mb_mixed_pages.txt (c): the one-launch route loses on host pages (its pinned pack), so the loop stays
+
+    def preprocess_sources(self, pages: Sequence[Union[np.ndarray, torch.Tensor]]) -> Tuple[torch.Tensor, np.ndarray]:
+        """`preprocess` with ONE pinned pack + ONE copy for the host pages (HostImageStage) and ONE rd_preproc_resize_norm_sources launch
+        for all pages, whatever their sizes."""
+        S = self.m["S"]
+        mean, std = self.m["norm"]
+        x = torch.empty((len(pages), 3, S, S), dtype=torch.float32, device=self.device)
+        host = [i for i, pg in enumerate(pages) if not (isinstance(pg, torch.Tensor) and pg.device.type == "cuda")]
+        # (a device page is read where it lies - a window of a larger image too; only unpacked pixels need a copy)
+        srcs = [pg if i in host or (pg.stride(2) == 1 and pg.stride(1) == 3 and pg.stride(0) >= 3 * pg.shape[1]) else pg.contiguous()
+                for i, pg in enumerate(pages)]
+        if host:
+            if getattr(self, "_stage", None) is None:
+                self._stage = HostImageStage(self.device)
+            staged = self._stage.upload([pages[i].numpy() if isinstance(pages[i], torch.Tensor) else pages[i] for i in host])
+            for i, v in zip(host, staged.views):
+                srcs[i] = v
+        sf = np.asarray([(S / t.shape[0], S / t.shape[1]) for t in srcs], dtype=np.float32).reshape(len(srcs), 2)
+        preproc_resize_norm_sources(srcs, [(S, S)] * len(srcs), mean=mean, std=std, interp=2, out=list(x))
+        if host:
+            self._stage.release()
+        return x, sf
+
+    def preprocess_loop(self, pages: Sequence[Union[np.ndarray, torch.Tensor]]) -> Tuple[torch.Tensor, np.ndarray]:
+        """`preprocess` page by page: one copy per host page, one rd_preproc_resize_norm launch per page."""
         S = self.m["S"]
         mean, std = self.m["norm"]
         x = torch.empty((len(pages), 3, S, S), dtype=torch.float32, device=self.device)

@@ -19,7 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib, ocr_host
-from .engine import RdEngine, preproc_resize_norm, preproc_resize_norm_batch
+from .engine import RdEngine, preproc_resize_norm, preproc_resize_norm_batch, preproc_resize_norm_sources, resize_source_view
+from .host_stage import HostImageStage, as_stage_image, pack_images, plan_offsets
 from .rec_plan import (CLS_IMG_H, CLS_IMG_W, LINE_DTYPE, LINE_SOURCE_DTYPE, RecPlan, plan_lines, plan_rec,     # noqa: F401  (the crop helpers are imported from here)
                        quad_to_crop_matrix, quads_to_crop_matrices)
 
@@ -52,6 +53,47 @@ assert CROP_DTYPE.itemsize == C.sizeof(CropDesc)
 def boxes_to_quads(boxes_xyxy: np.ndarray) -> np.ndarray:
     b = np.asarray(boxes_xyxy, dtype=np.float32).reshape(-1, 4)
     return np.stack([b[:, [0, 1]], b[:, [2, 1]], b[:, [2, 3]], b[:, [0, 3]]], axis=1)
+
+
+def page_det_shape(H: int, W: int) -> Tuple[int, int]:
+    """The det input shape of an H x W page, by the rule of `PagePipeline.det_preprocess`: 64-px bucket of the page with its 50-px
+    margins, then DetResizeForTest with limit 960 / "max"."""
+    bh, bw = -(-(int(H) + 100) // 64) * 64, -(-(int(W) + 100) // 64) * 64
+    return ocr_host.det_resize_shape(bh, bw, DET_LIMIT, "max")
+
+
+def group_pages_by_det_shape(page_hws: Sequence[Tuple[int, int]]):
+    """Pages of different sizes -> (det shape per page, groups, inverse): `groups` = [((dh, dw), page indices)] of the pages that share a
+    det input shape, in order of first appearance (members in page order); `inverse[i]` = position of page i in the concatenation of
+    the groups' members, so that `grouped[inverse[i]]` is page i again."""
+    shapes = [page_det_shape(h, w) for h, w in page_hws]
+    members: Dict[Tuple[int, int], List[int]] = {}
+    for i, s in enumerate(shapes):
+        members.setdefault(s, []).append(i)         # dicts keep insertion order: first appearance
+    groups = list(members.items())
+    inverse = np.zeros(len(shapes), np.int64)
+    inverse[[i for _s, m in groups for i in m]] = np.arange(len(shapes))
+    return shapes, groups, inverse
+
+
+def split_page_list(pages: Sequence) -> Tuple[str, list]:
+    """A list of [H_i, W_i, 3] uint8 pages -> ("device", the tensors) or ("host", numpy arrays as rd_stage_pack takes them).  A list that
+    mixes device and host pages, an empty list and a page of another dtype or rank raise ValueError."""
+    if len(pages) == 0:
+        raise ValueError("a page list must hold at least one page")
+    on_dev = [isinstance(p, torch.Tensor) and p.is_cuda for p in pages]
+    if any(on_dev) and not all(on_dev):
+        raise ValueError("a page list must be all device tensors or all host pages (numpy arrays / CPU tensors), not a mix")
+    out = []
+    for p in pages:
+        if tuple(p.shape[2:]) != (3,) or len(p.shape) != 3 or p.shape[0] < 1 or p.shape[1] < 1:
+            raise ValueError(f"a page of a list must be [H, W, 3], got shape {tuple(p.shape)}")
+        if p.dtype != (torch.uint8 if isinstance(p, torch.Tensor) else np.uint8):
+            raise ValueError(f"a page of a list must be uint8, got {p.dtype}")
+        out.append(p if on_dev[0] else as_stage_image(p.numpy() if isinstance(p, torch.Tensor) else p))
+    if on_dev[0] and any(p.device != out[0].device for p in out):
+        raise ValueError("the device pages of a list must lie on one device")
+    return ("device" if on_dev[0] else "host"), out
 
 
 @dataclass
@@ -757,7 +799,16 @@ class PagePipeline:
         enqueued as soon as this batch's det maps have been consumed, so they run under this batch's recognition instead of in
         front of the next batch's; the next `run_batch` call on that very tensor picks them up (any other call drops them).  The
         tensor is recognised by address and shape: its CONTENTS must not change between the two calls.  Results are the same with or
-        without it (the same kernels on the same inputs); `last_det` then already belongs to the next batch when this call returns."""
+        without it (the same kernels on the same inputs); `last_det` then already belongs to the next batch when this call returns.
+
+        `pages` may also be a SEQUENCE of [H_i, W_i, 3] uint8 pages of different sizes (`_run_list_once`): all device tensors, used
+        where they lie, or all host pages, which go through one pinned pack and one copy; a mix raises ValueError.  Pages of equal det
+        input shape form a group (one det forward and one DB post-process per group), one rd_preproc_resize_norm_sources launch
+        writes every group's det input, and every line of every page is pooled into ONE recogniser plan, so the strict mode's padded
+        widths are the reference's for the whole batch.  `det_maps_override` is then a sequence of one [1, 1, dh_i, dw_i] map per page,
+        `prefetch` may be a list of device pages, and `last_det` is a list of (maps, det_hw, page indices) per group."""
+        if isinstance(pages, (list, tuple)):
+            return self._run_batch_list(pages, quads_per_page, det_maps_override, prefetch, page_keys)
         if isinstance(pages, np.ndarray) or not pages.is_cuda:
             src = torch.from_numpy(np.ascontiguousarray(pages)) if isinstance(pages, np.ndarray) else pages.contiguous()
             pages = src.to(self.tdev, non_blocking=src.is_pinned())
@@ -846,10 +897,7 @@ class PagePipeline:
             src = det_maps_override if det_maps_override is not None else prob_maps
             quads_per_page = self.boxes_from_maps_device(src.contiguous(), (H, W)) if self.device_db else self._boxes_via_host_maps(src, (H, W))
         if prefetch is not None:
-            assert prefetch.is_cuda and prefetch.dtype == torch.uint8 and prefetch.dim() == 4
-
-            def front_next(gate):
-                self._prefetched = self._front(prefetch, prefetch.shape[0], gate)
+            front_next = self._front_next_hook(prefetch)
             self._after_rec_enqueue = front_next
         try:
             keys = getattr(self, "_page_keys", None)
@@ -870,6 +918,233 @@ class PagePipeline:
             if self.use_cls and self.last_cls is not None:
                 results[i].cls = list(self.last_cls[0][i])
         return results
+
+
+    def _front_next_hook(self, prefetch):
+        """The hook that enqueues the NEXT batch's det and layout forwards: for a [P,H,W,3] tensor or a list of device pages."""
+        if isinstance(prefetch, (list, tuple)):
+            kind, nxt = split_page_list(prefetch)
+            if kind != "device":
+                raise ValueError("prefetch takes device pages: upload a list of host pages first (PageUploader.submit)")
+
+            def front_next(gate):
+                self._prefetched = self._front_list(nxt, gate)
+        else:
+            assert prefetch.is_cuda and prefetch.dtype == torch.uint8 and prefetch.dim() == 4
+
+            def front_next(gate):
+                self._prefetched = self._front(prefetch, prefetch.shape[0], gate)
+        return front_next
+
+    # ---------------------------------------------------------------- whole batch, pages of different sizes
+    @staticmethod
+    def _front_key_list(pages: Sequence[torch.Tensor]) -> tuple:
+        return tuple((p.data_ptr(), tuple(p.shape)) for p in pages)
+
+    def _run_batch_list(self, pages, quads_per_page, det_maps_override, prefetch, page_keys) -> List[PageResult]:
+        """`run_batch` for a sequence of pages: the upload of host pages (one pack, one copy), then `_run_list_once` under the same range
+        guard as `_run_batch_guarded`."""
+        kind, pages = split_page_list(pages)
+        if kind == "host":
+            if getattr(self, "_page_stage", None) is None:
+                self._page_stage = HostImageStage(self.tdev)
+            pages = self._page_stage.upload(pages).views
+        P = len(pages)
+        self._page_keys = None if page_keys is None else [int(k) for k in page_keys]
+        if self._page_keys is not None and len(self._page_keys) != P:
+            raise ValueError("page_keys: one key per page")
+        if quads_per_page is not None and len(quads_per_page) != P:
+            raise ValueError("quads_per_page: one array of quads per page")
+        if det_maps_override is not None and len(det_maps_override) != P:
+            raise ValueError("det_maps_override: for a list of pages, one [1, 1, dh, dw] map per page")
+        if self.rec_width_sync is not None and page_keys is None and getattr(self.rec_width_sync, "world_size", 1) > 1:
+            raise ValueError("rec_width_sync over more than one rank needs page_keys: the pages' positions in the GLOBAL page list")
+        self._width_sync_epoch += 1
+        self._in_run_batch = True
+        try:
+            results = self._run_list_once(pages, quads_per_page, det_maps_override, prefetch)
+            engines = [self.det] + ([self.layout] if self.layout is not None else [])
+            if os.environ.get("RD_DEV_SKIP_RANGE_CHECK") == "1":
+                engines = []
+            if any([e.check_range_and_fallback() for e in engines]):
+                self.stats["range_fallbacks"] = self.stats.get("range_fallbacks", 0) + 1
+                self._prefetched = None
+                results = self._run_list_once(pages, quads_per_page, det_maps_override, prefetch)
+            return results
+        finally:
+            self._in_run_batch = False
+            if kind == "host":
+                self._page_stage.release()          # everything that reads the uploaded pages has been enqueued
+
+    def _front_list(self, pages: Sequence[torch.Tensor], gate: Sequence[torch.cuda.Event] = ()) -> dict:
+        """`_front` for pages of different sizes: ONE rd_preproc_resize_norm_sources launch writes the det input of every group of pages
+        that share a det shape (buffers per shape, so addresses repeat), then one det forward per group; behind them, on the layout
+        stream, one launch brings all pages to 800 x 800 and ONE backbone forward runs over the whole batch."""
+        cur = torch.cuda.current_stream()
+        P = len(pages)
+        hws = [(int(p.shape[0]), int(p.shape[1])) for p in pages]
+        shapes, groups, _inverse = group_pages_by_det_shape(hws)
+        h = {"key": self._front_key_list(pages), "feats": None, "layout_done": None, "groups": groups, "hws": hws, "preproc_launches": 1}
+        self.front_stream.wait_stream(cur)
+        for ev in gate:
+            self.front_stream.wait_event(ev)
+        with torch.cuda.stream(self.front_stream):
+            xs = [self._buf(("det_x", dh, dw), len(m) * 3 * dh * dw).view(len(m), 3, dh, dw) for (dh, dw), m in groups]
+            dst: List[Optional[torch.Tensor]] = [None] * P
+            for x, (_shape, members) in zip(xs, groups):
+                for j, i in enumerate(members):
+                    dst[i] = x[j]
+            preproc_resize_norm_sources(pages, shapes, mean=ocr_host.DET_MEAN, std=ocr_host.DET_STD, interp=1, swap_rb=True, out=dst)
+            h["prob_maps"] = [self.det.det_forward(x) for x in xs]
+            h["det_done"] = torch.cuda.Event()
+            h["det_done"].record(self.front_stream)
+        if self.layout is not None:
+            self.layout_stream.wait_event(h["det_done"])
+            with torch.cuda.stream(self.layout_stream):
+                x = self._buf("layout_x", P * 3 * LAYOUT_SIZE * LAYOUT_SIZE).view(P, 3, LAYOUT_SIZE, LAYOUT_SIZE)
+                preproc_resize_norm_sources(pages, [(LAYOUT_SIZE, LAYOUT_SIZE)] * P, interp=2, out=list(x))
+                h["preproc_launches"] += 1
+                feats = self.layout.backbone_forward(x)
+                if self.keep_feats:
+                    h["feats"] = [[f[i].clone() for f in feats] for i in range(P)]
+                h["layout_done"] = torch.cuda.Event()
+                h["layout_done"].record(self.layout_stream)
+        return h
+
+    def _boxes_device_sizes(self, maps_dev: torch.Tensor, page_hws: Sequence[Tuple[int, int]], box_thresh: float = 0.3,
+                            unclip_ratio: float = 1.8) -> List[np.ndarray]:
+        """`boxes_from_maps_device` for maps of one det shape whose pages differ in size: the post-process takes a size per image."""
+        res = ocr_host.db_postprocess_device(maps_dev, list(page_hws), thresh=0.3, box_thresh=box_thresh, unclip_ratio=unclip_ratio,
+                                             stats=self.stats, cache=self.db_ws, raw=self.host_native)
+        if self.host_native:
+            return ocr_host.order_merge_boxes_native(*res)
+        out = []
+        for boxes, _scores in res:
+            if len(boxes) == 0:
+                out.append(np.zeros((0, 4, 2), np.float32))
+                continue
+            b = ocr_host.merge_det_boxes(ocr_host.sorted_boxes(boxes.astype(np.float32)))
+            out.append(np.asarray(b, dtype=np.float32).reshape(-1, 4, 2))
+        return out
+
+    def _run_list_once(self, pages: Sequence[torch.Tensor], quads_per_page, det_maps_override, prefetch) -> List[PageResult]:
+        """`_run_batch_once` for device pages of different sizes; results in the caller's page order."""
+        P = len(pages)
+        results = [PageResult() for _ in range(P)]
+        cur = torch.cuda.current_stream()
+        h, self._prefetched = self._prefetched, None
+        if h is None or h["key"] != self._front_key_list(pages):
+            h = self._front_list(pages)
+            self.stats["front_prefetched"] = 0.0
+        else:
+            self.stats["front_prefetched"] = 1.0
+        cur.wait_event(h["det_done"])
+        if self.rec_width_sync is not None and self.det.precision != "fp32" and os.environ.get("RD_DEV_SKIP_RANGE_CHECK") != "1":
+            if self.det.check_range_and_fallback():       # settled before the recogniser stage, as in _run_batch_once
+                self.stats["range_fallbacks"] = self.stats.get("range_fallbacks", 0) + 1
+                h = self._front_list(pages)
+                self.stats["front_prefetched"] = 0.0
+                cur.wait_event(h["det_done"])
+        groups, hws = h["groups"], h["hws"]
+        self.last_det = [(maps, shape, list(members)) for maps, (shape, members) in zip(h["prob_maps"], groups)]
+        self.stats["det_groups"] = len(groups)
+        self.stats["preproc_launches"] = h["preproc_launches"]
+        if quads_per_page is None:
+            if not self.device_db:
+                raise ValueError("a list of pages needs the device DB post-process (device_db=True)")
+            quads_per_page = [None] * P
+            for maps, ((dh, dw), members) in zip(h["prob_maps"], groups):
+                src = maps
+                if det_maps_override is not None:
+                    for i in members:
+                        if tuple(det_maps_override[i].shape) != (1, 1, dh, dw):
+                            raise ValueError(f"det_maps_override[{i}] must be [1, 1, {dh}, {dw}], got {tuple(det_maps_override[i].shape)}")
+                    src = torch.cat([det_maps_override[i] for i in members])
+                for i, q in zip(members, self._boxes_device_sizes(src.contiguous(), [hws[i] for i in members])):
+                    quads_per_page[i] = q
+        if prefetch is not None:
+            front_next = self._front_next_hook(prefetch)
+            self._after_rec_enqueue = front_next
+        try:
+            keys = getattr(self, "_page_keys", None)
+            texts = self._rec_forward_pages(pages, quads_per_page, list(range(P)) if keys is None else keys)
+        except BaseException:
+            self._after_rec_enqueue = None
+            raise
+        if self._after_rec_enqueue is not None:        # no line to recognise: the hook was not reached
+            self._after_rec_enqueue = None
+            front_next(())
+        if h["layout_done"] is not None:
+            cur.wait_event(h["layout_done"])
+        for i in range(P):
+            qs = np.asarray(quads_per_page[i], dtype=np.float32).reshape(-1, 4, 2)
+            results[i].lines = [(qs[j], t, s) for j, (t, s) in enumerate(texts[i])]
+            if h["feats"] is not None:
+                results[i].layout_feats = h["feats"][i]
+            if self.use_cls and self.last_cls is not None:
+                results[i].cls = list(self.last_cls[i][0])
+        return results
+
+    def _rec_forward_pages(self, pages: Sequence[torch.Tensor], quads_per_page: Sequence[np.ndarray], keys: Sequence[int]):
+        """`rec_forward_sources` with one source per page, every line pooled into ONE plan (pooling key = `keys[page]`), and every rec
+        launch's lines warped by ONE rd_line_warp_sources launch: each line names its page.  -> per page [(text, score)].  Carries the
+        range guard of rec_forward_sources."""
+        self._sync_this_call = True
+        if not self._in_run_batch:
+            self._width_sync_epoch += 1
+        out = self._rec_pages_once(pages, quads_per_page, keys)
+        for _ in range(3):
+            if not any([e.check_range_and_fallback() for e in self.rec_engines + [self.rec_tail] + self.cls_engines]):
+                break
+            self.stats["range_fallbacks"] = self.stats.get("range_fallbacks", 0) + 1
+            out = self._rec_pages_once(pages, quads_per_page, keys)
+        return out
+
+    def _rec_pages_once(self, pages, quads_per_page, keys):
+        t0 = time.perf_counter()
+        self.last_cls = None
+        self.stats["warp_source_launches"] = 0
+        strict = self.rec_mode == "strict"
+        sync = None
+        if self.rec_width_sync is not None and strict and self.rec_two_stage and self._sync_this_call:
+            sync = lambda k, ratios: self._synced_widths(self.rec_width_sync, k, ratios)      # noqa: E731
+        plan = plan_rec([(1, [q]) for q in quads_per_page], [[int(k)] for k in keys], **self._plan_modes(strict), width_sync=sync)
+        scratch = None
+        if plan.n:
+            lines_name_their_sources(plan, [resize_source_view(p) for p in pages], [(int(p.shape[0]), int(p.shape[1])) for p in pages])
+            if getattr(self, "_crop_scratch", None) is None or self._crop_scratch.numel() < plan.src_scratch_bytes:
+                self._crop_scratch = torch.empty(int(plan.src_scratch_bytes * 1.25) + 1024, dtype=torch.uint8, device=self.tdev)
+            scratch = self._crop_scratch.data_ptr()
+        per_source = self._run_rec_plan(plan, None, False, t0, scratch=scratch)
+        return [s[0] for s in per_source]
+
+
+def lines_name_their_sources(plan: RecPlan, views: Sequence[Tuple[int, int]], hws: Sequence[Tuple[int, int]]) -> None:
+    """Host only: turns a `plan_rec` plan over one-image sources of different sizes into one whose lines name their source
+    (LINE_SOURCE_DTYPE), so that ONE rd_line_warp_sources launch per rec launch replaces a rd_line_warp_batch launch per source.
+    `views[s]` = (device address, row pitch) and `hws[s]` = (H, W) of source s.  The crops keep their places: a launch's region of the
+    scratch starts where it did, the offsets become offsets from the buffer's start (as in rec_forward_crops)."""
+    starts, total = plan.starts, int(plan.batch_base[-1])
+    if total >= 2 ** 31:
+        raise RuntimeError("the crops of one call must lie inside 2 GB (scratch_off is an int32): split the page list")
+    base_of = np.repeat(np.asarray(plan.batch_base[:-1], dtype=np.int64), np.diff(starts))
+    plan.descs["scratch_off"] = (plan.descs["scratch_off"].astype(np.int64) + base_of).astype(np.int32)
+    if plan.descs_cls is not None:
+        plan.descs_cls["scratch_off"] = plan.descs["scratch_off"]
+    src = plan.src_of[plan.line_ids]                          # source of every line, in launch order
+    sd = np.zeros(plan.n, LINE_SOURCE_DTYPE)
+    sd["src"] = np.asarray([v[0] for v in views], dtype=np.uint64)[src]
+    sd["pitch"] = np.asarray([v[1] for v in views], dtype=np.int64)[src]
+    sd["H"] = np.asarray([hw[0] for hw in hws], dtype=np.int32)[src]
+    sd["W"] = np.asarray([hw[1] for hw in hws], dtype=np.int32)[src]
+    for f in ("crop_w", "crop_h", "scratch_off", "m"):
+        sd[f] = plan.descs[f]
+    plan.src_descs = sd
+    plan.src_jobs = [(int(a), int(e - a)) for a, e in zip(starts[:-1], starts[1:])]
+    plan.src_scratch_bytes = total
+    plan.warp_jobs = [[] for _ in plan.batches]
+    plan.descs_warp = None
+    plan.batch_base = np.zeros(len(plan.batches) + 1, np.int64)
 
 
 def render_text_maps(boxes_per_page: Sequence[np.ndarray], page_hw: Tuple[int, int], map_hw: Tuple[int, int],
@@ -927,7 +1202,45 @@ class PageUploader:
         """A pinned uint8 host buffer to render pages into (its upload needs no staging copy)."""
         return torch.empty(tuple(shape), dtype=torch.uint8, pin_memory=True)
 
+    @staticmethod
+    def plan_list(shapes: Sequence[Tuple[int, int]]) -> Tuple[List[int], int]:
+        """Where the [h, w, 3] pages of a LIST lie in the upload: (byte offset per page, total bytes) - 16-byte aligned page starts, in
+        order (host_stage.plan_offsets)."""
+        return plan_offsets(shapes)
+
+    def _submit_list(self, pages_host: Sequence) -> Tuple[List[torch.Tensor], torch.cuda.Event, int]:
+        """`submit` for a list of host pages of different sizes: ONE pinned pack (rd_stage_pack) and ONE copy; the ticket's first entry is
+        the list of device views, which `wait` returns."""
+        kind, arrs = split_page_list(pages_host)
+        if kind != "host":
+            raise ValueError("PageUploader.submit takes host pages")
+        shapes = [(int(a.shape[0]), int(a.shape[1])) for a in arrs]
+        offsets, total = self.plan_list(shapes)
+        k = self._i % self.n
+        self._i += 1
+        if self._dev[k] is None or self._dev[k].numel() < total:
+            self._dev[k] = torch.empty(int(total * 1.1) + 256, dtype=torch.uint8, device=self.tdev)
+        if self._consumer[k] is not None:
+            rel = torch.cuda.Event()
+            rel.record(self._consumer[k])
+            self._released[k], self._consumer[k] = rel, None
+        if self._released[k] is not None:
+            self.stream.wait_event(self._released[k])
+        if self._pin[k] is None or self._pin[k].numel() < total:
+            self._pin[k] = torch.empty(int(total * 1.1) + 256, dtype=torch.uint8, pin_memory=True)
+        self.stream.synchronize()                                  # the staging buffer's previous copy has left the host
+        pack_images(arrs, offsets, self._pin[k].data_ptr(), total)
+        with torch.cuda.stream(self.stream):
+            self._dev[k][:total].copy_(self._pin[k][:total], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self.bytes_uploaded += total
+        views = [self._dev[k][o: o + 3 * h * w].view(h, w, 3) for o, (h, w) in zip(offsets, shapes)]
+        return views, ev, k
+
     def submit(self, pages_host) -> Tuple[torch.Tensor, torch.cuda.Event, int]:
+        if isinstance(pages_host, (list, tuple)):
+            return self._submit_list(pages_host)
         src = torch.from_numpy(pages_host) if isinstance(pages_host, np.ndarray) else pages_host
         assert not src.is_cuda and src.dtype == torch.uint8 and src.dim() == 4 and src.is_contiguous()
         k = self._i % self.n

@@ -157,6 +157,8 @@ class Mi355UniTableStructure:
         from .engine import preproc_resize_aa_norm, preproc_resize_norm
         imgs = [img for img in imgs if img is not None]
         x = torch.empty((len(imgs), 3, IMG_SIZE, IMG_SIZE), dtype=torch.float32, device=self._dev)
+        if self.resize == "linear" and self.LINEAR_ROUTE == "sources" and len(imgs):
+            return self._preprocess_linear_sources(imgs, x)
         shapes = []
         for i, img in enumerate(imgs):
             shapes.append(tuple(int(v) for v in img.shape[:2]))
@@ -168,6 +170,27 @@ class Mi355UniTableStructure:
                 preproc_resize_aa_norm(u8, (IMG_SIZE, IMG_SIZE), mean=NORM_MEAN, std=NORM_STD, swap_rb=True, out=x[i])
             else:
                 preproc_resize_norm(u8, (IMG_SIZE, IMG_SIZE), mean=NORM_MEAN, std=NORM_STD, swap_rb=True, out=x[i])
+        return x, shapes
+
+    LINEAR_ROUTE = "sources"           # "loop": one copy and one launch per table; profiles/mb_mixed_pages.txt (d) decides it
+
+    def _preprocess_linear_sources(self, imgs: list, x: torch.Tensor) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
+        """resize="linear" for all tables of a call at once: the host images staged by ONE pinned pack and ONE copy, then ONE
+        rd_preproc_resize_norm_sources launch writes every table's row of `x` - the bits of the per-table loop."""
+        from .engine import preproc_resize_norm_sources
+        from .host_stage import HostImageStage
+        shapes = [tuple(int(v) for v in img.shape[:2]) for img in imgs]
+        host = [i for i, img in enumerate(imgs) if not isinstance(img, torch.Tensor)]
+        srcs = [img if i in host else img.to(self._dev, non_blocking=True).contiguous() for i, img in enumerate(imgs)]
+        if host:
+            if getattr(self, "_stage", None) is None:
+                self._stage = HostImageStage(self._dev)
+            for i, v in zip(host, self._stage.upload([imgs[i] for i in host]).views):
+                srcs[i] = v
+        # (no `interp`: the same default as the loop's preproc_resize_norm call, so the two routes cannot drift apart)
+        preproc_resize_norm_sources(srcs, [(IMG_SIZE, IMG_SIZE)] * len(srcs), mean=NORM_MEAN, std=NORM_STD, swap_rb=True, out=list(x))
+        if host:
+            self._stage.release()
         return x, shapes
 
     def decode_ids(self, x: torch.Tensor) -> List[List[int]]:
