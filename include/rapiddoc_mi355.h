@@ -87,6 +87,10 @@ int rd_det_forward_ex(rd_handle* h, const float* x_nchw_dev, int B, int H, int W
 int rd_rec_forward(rd_handle* h, const float* x_nchw_dev, int B, int W, int32_t* idx_bt_dev, float* prob_bt_dev,
                    float* full_btc_dev, int flags, void* ws_dev, size_t ws_bytes, void* stream);
 int rd_rec_num_classes(rd_handle* h);
+/* The backbone the loaded weights picked, for the two kinds that serve two: "ppocrv5_det_server" and "ppocrv5_rec_server" return
+ * "pphgnetv2_b4" (the PP-OCRv5 server files) or "pphgnet_small" (the PP-OCRv4 server files, ch_PP-OCRv4_det_server / _rec_server, handed
+ * over as a state dict: their tensors resolve to these kinds).  "" for every other kind and before rd_load_weights; never NULL. */
+const char* rd_backbone_name(rd_handle* h);
 /* The same network in two stages, for a pipeline that recognises the lines of many batches (rapid_ocr.py:430-449 loops over
  * `rec_batch_num` chunks and calls the session once per chunk): the neck and the CTC head of one chunk are ~25 launches on a few
  * thousand tokens - launch latency - so the chunks run only the backbone, each writing its tokens into ONE buffer, and the tail

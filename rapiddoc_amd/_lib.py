@@ -21,6 +21,7 @@ SYMBOLS = {
     "rd_det_forward_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rd_rec_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rd_rec_num_classes": (C.c_int, [C.c_void_p]),
+    "rd_backbone_name": (C.c_char_p, [C.c_void_p]),
     "rd_rec_token_dim": (C.c_int, [C.c_void_p]),
     "rd_rec_backbone_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rd_rec_backbone_forward_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -113,6 +114,7 @@ DEBUG_SYMBOLS = {
     "rd_debug_det_local": (_F, [_I] * 5 + [_P] * 5 + [_F, _P, C.POINTER(C.c_int)]),
     "rd_debug_conv_route": (_I, [_I] * 17 + [_P, _I]),
     "rd_debug_conv_ex": (_F, [_I] * 22 + [_P] * 10 + [C.c_char_p, _P, _I, _P]),
+    "rd_debug_conv3x3_wide": (_F, [_I] * 10 + [_P] * 5 + [_I, _P]),
     "rd_debug_conv": (_F, [_I] * 14 + [_P] * 8),
     "rd_debug_stem34": (_F, [_I] * 11 + [_P] * 7),
     "rd_debug_stem_front": (_F, [_I] * 8 + [_P] * 10),
@@ -138,6 +140,8 @@ DEBUG_SYMBOLS = {
     "rd_debug_attention_limits": (_I, [_I, _P, _P]),
     "rd_debug_layernorm": (_I, [_I, _I, _P, _I, _P, _I, _P, _P, _F]),
     "rd_debug_se_chain": (_I, [_I] * 7 + [_F] + [_I] * 3 + [_P] * 9),
+    "rd_debug_ese": (_I, [_I] * 7 + [_P] * 8),
+    "rd_debug_maxpool3x3s2": (_I, [_I] * 6 + [_P] * 2),
     "rd_debug_maxpool2x2s1": (_I, [_I] * 6 + [_P] * 2),
     "rd_debug_avgpool3x2": (_I, [_I] * 6 + [_P] * 3),
     "rd_debug_mask_cols": (_I, [_I] * 5 + [_P, _P, _I]),

@@ -187,6 +187,7 @@ int rd_rec_seq_len(int W) {
     const int w1 = (W - 1) / 2 + 1, w2 = (w1 - 1) / 2 + 1;
     return (w2 - 2) / 2 + 1;
 }
+const char* rd_backbone_name(rd_handle* h) { return (h && h->eng) ? h->eng->backbone().c_str() : ""; }
 int rd_rec_num_classes(rd_handle* h) { return (h && h->eng) ? h->eng->n_classes() : -1; }
 
 int rd_backbone_forward(rd_handle* h, const float* x, int B, int H, int W, float* const feats[4], void* ws, size_t ws_bytes,

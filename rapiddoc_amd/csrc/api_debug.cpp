@@ -387,7 +387,8 @@ static void debug_copy_name(const char* s, char* name, int name_len) {
 }
 
 // developer entry, host only (no HIP call): the route of a dense convolution as the planner decides it.  Geometry as rd_debug_conv with a dense
-// input (xld = Cin), N images; images: bit 0 the (hi, lo) split weights, 1 the one-accumulator GEMM image, 2 the 3x3 image, 3 the 9x9 image
+// input (xld = Cin), N images; images: bit 0 the (hi, lo) split weights, 1 the one-accumulator GEMM image, 2 the 3x3 image, 3 the 9x9 image,
+// 4 the wide 3x3 image a builder's opt-in hands out (Builder::set_conv3x3_wide; asked without a residual, as those layers are)
 // (only bits are looked at: the images themselves are not); split = 0 asks conv_f32_route, with allow_skinny.  The route's name goes to
 // name[name_len]; returns the code rd_debug_conv reports for the route in *used_direct, -1 on a bad argument.
 int rd_debug_conv_route(int N, int H, int W, int Cin, int Cout, int KH, int KW, int S, int PT, int PL, int PB, int PR, int act, int images,
@@ -404,6 +405,7 @@ int rd_debug_conv_route(int N, int H, int W, int Cin, int Cout, int KH, int KW, 
     if (images & 2) { p.w1 = image; p.w1_inv = 1.f; }
     if (images & 4) { p.w3 = image; p.w3_inv = 1.f; }
     if (images & 8) { p.w9 = image; p.w9_inv = 1.f; }
+    if (images & 16) { p.w3w = image; p.w3w_inv = 1.f; p.rld = 0; }
     const rd::ConvRoute r = split ? rd::conv_split_route(p, has_ascale != 0) : rd::conv_f32_route(p);
     debug_copy_name(rd::conv_route_name(r), name, name_len);
     return debug_conv_code(r);
@@ -514,6 +516,12 @@ static float debug_conv_run(int N, int H, int W, int Cin, int Cout, int KH, int 
             if (!upload(img, &d)) return done(-1.f);
             p.w9 = (const uint16_t*)d;
         }
+        if ((images & 16) && !deconv && rd::conv3x3_wide_shape_ok(KH, KW, Cin, Cout)) {      // (the opt-in a PPHGNet_small layer carries)
+            p.w3w_inv = rd::prepare_conv3x3_wide_weights(hw.data(), Cout, Cin, img);
+            d = nullptr;
+            if (!upload(img, &d)) return done(-1.f);
+            p.w3w = (const uint16_t*)d;
+        }
         if (range_out) {
             if (hipHostMalloc((void**)&flag, sizeof(unsigned), hipHostMallocMapped) != hipSuccess) { flag = nullptr; return done(-1.f); }
             *flag = 0;
@@ -565,6 +573,41 @@ float rd_debug_conv_ex(int N, int H, int W, int Cin, int Cout, int KH, int KW, i
     const float ms = debug_conv_run(N, H, W, Cin, Cout, KH, KW, SH, SW, PT, PL, PB, PR, act, xld, yld, rld, out_mode, split, images, allow_skinny, iters,
                                     x, w, bias, res, y, dscale, dshift, ln_g, ln_b, ascale, force, nullptr, &route, range_out);
     if (ms != -1.f) debug_copy_name(rd::conv_route_name(route), name, name_len);
+    return ms;
+}
+
+// developer entry: one 3x3 / stride 1 / pad 1 convolution of PPHGNet_small's widths on one of the three routes tools/mb_v4_server.py compares,
+// operands prepared as the engine prepares them.  route 0: conv3x3_wide_h1 (kernels_conv3x3_wide.hip); 1: what conv_split_route gives the layer
+// without the builder's opt-in (the generic split implicit GEMM); 2: conv3x3_h1 launched over pieces of <= 96 output channels (Cin <= 512).
+// x NHWC [N][H][W][xld >= Cin], w folded [Cout][9 Cin], bias [Cout] or null, y [N][H][W][yld >= Cout]; name receives the route launched
+// (of the last piece), *range_out (optional) the range flag.  Returns ms per launch (the pieces' sum), -1: the route does not take the layer
+// (nothing launched), -2: a launcher threw.
+float rd_debug_conv3x3_wide(int route, int N, int H, int W, int Cin, int Cout, int act, int xld, int yld, int iters, float* x, float* w, float* bias,
+                            float* y, char* name, int name_len, int* range_out) {
+    debug_copy_name("", name, name_len);
+    if (route < 0 || route > 2 || !rd::conv3x3_wide_shape_ok(3, 3, Cin, Cout)) return -1.f;
+    rd::ConvRoute r = rd::CONV_F32_128x128;
+    float ms = 0.f;
+    if (route == 2) {
+        if (!rd::conv3x3_h1_shape_ok(3, 3, Cin, 96)) return -1.f;
+        int any = 0;
+        for (int n0 = 0; n0 < Cout; n0 += 96) {
+            const int nn = std::min(96, Cout - n0);
+            int flag = 0;
+            const float t = debug_conv_run(N, H, W, Cin, nn, 3, 3, 1, 1, 1, 1, 1, 1, act, xld, yld, 0, rd::OUT_NHWC, 1, 4, 0, iters, x, w + (size_t)n0 * 9 * Cin,
+                                           bias ? bias + n0 : nullptr, nullptr, y + n0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &r,
+                                           range_out ? &flag : nullptr);
+            if (t < 0.f || r != rd::CONV_C3H1) return t < 0.f ? t : -1.f;
+            ms += t;
+            any |= flag;
+        }
+        if (range_out) *range_out = any;
+    } else {
+        ms = debug_conv_run(N, H, W, Cin, Cout, 3, 3, 1, 1, 1, 1, 1, 1, act, xld, yld, 0, rd::OUT_NHWC, 1, route == 0 ? 16 : 0, 0, iters, x, w, bias, nullptr, y,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &r, range_out);
+        if (ms >= 0.f && route == 0 && r != rd::CONV_C3WIDE) return -1.f;      // (refused by conv3x3_wide_applies: the generic route ran instead)
+    }
+    if (ms != -1.f) debug_copy_name(rd::conv_route_name(r), name, name_len);
     return ms;
 }
 
@@ -1041,6 +1084,30 @@ int rd_debug_se_chain(int N, int H, int W, int C, int Cr, int chunks, int gate_a
     if (line_w) { f.line_w = line_w; f.line_w_stride = 1; }
     rd::launch_se_fc(f, nullptr);
     if (y) rd::launch_scale_channels(x, xld, y, yld, gate_out, alpha, N, hw, C, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
+
+// developer entry: the ESE gate of PPHGNet_small (kernels_ese.hip) as the engine chains it: launch_gap_partial (ese_gap_chunks(H W) chunks) ->
+// launch_ese_gate -> launch_ese_apply, synchronised.  x NHWC [N][H][W][xld >= C], w [C][C], b [C], partial [N][chunks][C] scratch, gate_out
+// [N][C], idn [N][H][W][ild >= C] or null, y [N][H][W][yld >= C] (may be x).  *chunks_out (optional) receives the chunk count.  Returns 0,
+// -1 on a bad argument or a width ese_shape_ok declines (nothing launched).
+int rd_debug_ese(int N, int H, int W, int C, int xld, int ild, int yld, float* x, float* w, float* b, float* idn, float* partial, float* gate_out,
+                 float* y, int* chunks_out) {
+    if (N <= 0 || H <= 0 || W <= 0 || !rd::ese_shape_ok(C) || !x || !w || !b || !gate_out || !y) return -1;
+    if (xld < C || xld % 4 || yld < C || yld % 4 || (idn && (ild < C || ild % 4))) return -1;
+    const int hw = H * W, chunks = rd::ese_gap_chunks(hw);
+    if (chunks_out) *chunks_out = chunks;
+    if (!partial) return chunks_out ? 0 : -1;          // (a size query)
+    rd::launch_gap_partial(x, xld, N, hw, C, partial, chunks, nullptr);
+    rd::launch_ese_gate(partial, chunks, N, C, 1.f / (float)hw, w, b, gate_out, nullptr);
+    rd::launch_ese_apply(x, xld, gate_out, idn, ild, y, yld, N, hw, C, nullptr);
+    return debug_finish(nullptr, nullptr);
+}
+
+// developer entry: MaxPool2d(3, stride 2, padding 1) (kernels_ese.hip): y [N][(H - 1) / 2 + 1][(W - 1) / 2 + 1][yld >= C] of x [N][H][W][xld >= C]
+int rd_debug_maxpool3x3s2(int N, int H, int W, int C, int xld, int yld, float* x, float* y) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 || !x || !y || xld < C || xld % 4 || yld < C || yld % 4) return -1;
+    rd::launch_maxpool3x3s2(x, xld, y, yld, N, H, W, C, nullptr);
     return debug_finish(nullptr, nullptr);
 }
 

@@ -142,7 +142,10 @@ TView Builder::conv(const std::string& wname, const std::string& bname, const st
                     const ConvGeom& g, int act, const TView* out, const TView* res, const TView* ascale) {
     const HostTensor& w = ws_->get(wname);
     RD_CHECK(w.shape.size() == 4 || w.shape.size() == 2, "conv weight rank: " + wname);
-    const int cout = (int)w.shape[0], cin = (int)w.shape[1];
+    // (set_conv_rows: this op computes output channels [row0, row0 + rows) of the layer only)
+    RD_CHECK(rows_n_ == 0 || (rows_0_ >= 0 && rows_0_ + rows_n_ <= (int)w.shape[0]), "conv: output-channel piece out of range: " + wname);
+    const int row0 = rows_n_ ? rows_0_ : 0;
+    const int cout = rows_n_ ? rows_n_ : (int)w.shape[0], cin = (int)w.shape[1];
     const int kh = w.shape.size() == 4 ? (int)w.shape[2] : 1, kw = w.shape.size() == 4 ? (int)w.shape[3] : 1;
     RD_CHECK(kh == g.kh && kw == g.kw, "conv kernel size mismatch: " + wname);
     RD_CHECK(cin == x.c, "conv Cin mismatch: " + wname + " expects " + std::to_string(cin) + " got " + std::to_string(x.c));
@@ -155,9 +158,9 @@ TView Builder::conv(const std::string& wname, const std::string& bname, const st
     RD_CHECK(y.n == x.n && y.h == oh && y.w == ow && y.c == cout, "conv output view mismatch: " + wname);
     if (res) RD_CHECK(res->n == y.n && res->h == oh && res->w == ow && res->c == cout, "conv residual mismatch: " + wname);
     const int K = kh * kw * cin;
-    const std::string key = wname + "|" + bn;
+    const std::string key = wname + "|" + bn + conv_rows_suffix(row0, rows_n_);
     if (!planning()) {
-        fold_conv(wname, bname, bn);
+        fold_conv(wname, bname, bn, row0, rows_n_);
         return y;
     }
     ConvParams p{};
@@ -173,7 +176,7 @@ TView Builder::conv(const std::string& wname, const std::string& bname, const st
     p.out_mode = OUT_NHWC;
     p.M = x.n * oh * ow; p.K = K; p.Ng = cout;
     OpRecord r;
-    r.name = wname;
+    r.name = wname + conv_rows_suffix(row0, rows_n_);
     r.kind = (kh == 1 && kw == 1) ? "conv1x1" : "conv" + std::to_string(kh) + "x" + std::to_string(kw);
     r.shape = "M" + std::to_string(p.M) + "_K" + std::to_string(K) + "_N" + std::to_string(cout);
     r.flops = 2.0 * p.M * (double)K * cout;
@@ -199,6 +202,10 @@ TView Builder::conv(const std::string& wname, const std::string& bname, const st
             p.w9 = reinterpret_cast<const uint16_t*>(pb_->ptr(key + "#w9"));
             p.w9_inv = *pb_->host_ptr(key + "#w9s");
         }
+        if (wide3x3_ && !h3_ && pb_->has(key + "#w3w")) {           // (the explicit h3 mode keeps these layers on the generic split route)
+            p.w3w = reinterpret_cast<const uint16_t*>(pb_->ptr(key + "#w3w"));
+            p.w3w_inv = *pb_->host_ptr(key + "#w3ws");
+        }
         p.range_flag = range_flag_;
     }
     const ConvRoute route = h3 ? conv_split_route(p, has_as) : conv_f32_route(p);
@@ -215,17 +222,24 @@ TView Builder::conv(const std::string& wname, const std::string& bname, const st
     return y;
 }
 
-void Builder::fold_conv(const std::string& wname, const std::string& bname, const std::string& bn) {
-    const std::string key = wname + "|" + bn;
+std::string Builder::conv_rows_suffix(int row0, int nrows) { return nrows ? "@" + std::to_string(row0) + "+" + std::to_string(nrows) : std::string(); }
+
+void Builder::fold_conv(const std::string& wname, const std::string& bname, const std::string& bn, int row0, int nrows) {
+    const std::string key = wname + "|" + bn + conv_rows_suffix(row0, nrows);
     if (pb_->has(key + "#w")) return;
     const HostTensor& w = ws_->get(wname);
-    const int cout = (int)w.shape[0], cin = (int)w.shape[1];
+    const int call = (int)w.shape[0], cin = (int)w.shape[1];
+    const int cout = nrows ? nrows : call;
     const int kh = w.shape.size() == 4 ? (int)w.shape[2] : 1, kw = w.shape.size() == 4 ? (int)w.shape[3] : 1;
     const int K = kh * kw * cin;
     std::vector<float> shift;
-    std::vector<float> scale = bn_scale_shift(bn, cout, shift);
+    std::vector<float> scale = bn_scale_shift(bn, call, shift);
+    if (nrows) {        // a piece: rows [row0, row0 + nrows) of the layer, folded exactly as the whole layer's rows are
+        scale = std::vector<float>(scale.begin() + row0, scale.begin() + row0 + nrows);
+        shift = std::vector<float>(shift.begin() + row0, shift.begin() + row0 + nrows);
+    }
     std::vector<float> wf((size_t)cout * K);
-    const float* src = w.f32();
+    const float* src = w.f32() + (size_t)row0 * cin * kh * kw;
     for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci)
             for (int a = 0; a < kh; ++a)
@@ -234,7 +248,7 @@ void Builder::fold_conv(const std::string& wname, const std::string& bname, cons
     std::vector<float> bias(cout, 0.f);
     bool any_bias = !bn.empty();
     if (!bname.empty()) {
-        const float* bs = ws_->get(bname).f32();
+        const float* bs = ws_->get(bname).f32() + row0;
         for (int co = 0; co < cout; ++co) bias[co] = bs[co] * scale[co];
         any_bias = true;
     }
@@ -251,6 +265,12 @@ void Builder::fold_conv(const std::string& wname, const std::string& bname, cons
             const float inv = prepare_conv3x3_h1_weights(wf.data(), cout, cin, img);
             pb_->add_u16(key + "#w3", img);
             pb_->add(key + "#w3s", std::vector<float>{inv});
+        }
+        if (wide3x3_ && conv3x3_wide_shape_ok(kh, kw, cin, cout)) { // one-accumulator direct 3x3 to 128 .. 256 channels, where the builder asked
+            std::vector<uint16_t> img;
+            const float inv = prepare_conv3x3_wide_weights(wf.data(), cout, cin, img);
+            pb_->add_u16(key + "#w3w", img);
+            pb_->add(key + "#w3ws", std::vector<float>{inv});
         }
         if (conv9x9_h1_shape_ok(kh, kw, cin, cout)) {               // one-accumulator direct 9x9 (LKPAN): slab-ordered fragment image
             std::vector<uint16_t> img;
@@ -925,6 +945,83 @@ void Builder::maxpool2x2s1(const TView& x, const TView& out) {
         launch_maxpool2x2s1(pl.vptr(xv, c), pl.ld(xv), pl.vptr(yv, c), pl.ld(yv), xv.n, xv.h, xv.w, xv.c, c.stream);
     };
     emit(std::move(r));
+}
+
+TView Builder::maxpool3x3s2(const TView& x, const TView* out) {
+    RD_CHECK(x.c % 4 == 0, "maxpool3x3s2: C % 4");
+    const int oh = (x.h - 1) / 2 + 1, ow = (x.w - 1) / 2 + 1;
+    TView y = out ? *out : alloc(x.n, oh, ow, x.c);
+    RD_CHECK(y.n == x.n && y.h == oh && y.w == ow && y.c == x.c, "maxpool3x3s2: output view mismatch");
+    if (!planning()) return y;
+    OpRecord r;
+    r.name = "maxpool3x3s2";
+    r.kind = "pool";
+    r.bytes = 4.0 * (x.pixels() * x.c + y.pixels() * y.c);
+    const TView xv = x, yv = y;
+    r.run = [xv, yv](const Plan& pl, const RunCtx& c) {
+        launch_maxpool3x3s2(pl.vptr(xv, c), pl.ld(xv), pl.vptr(yv, c), pl.ld(yv), xv.n, xv.h, xv.w, xv.c, c.stream);
+    };
+    emit(std::move(r));
+    return y;
+}
+
+void Builder::ese(const std::string& prefix, const TView& x, const TView& out, const TView* idn) {
+    const std::string wn = prefix + ".weight", bnm = prefix + ".bias";
+    const HostTensor& w = ws_->get(wn);
+    const int c = (int)w.shape[0];
+    RD_CHECK(w.numel() == (size_t)c * c && c == x.c && ese_shape_ok(c), "ESE gate: a [C][C][1][1] weight with C % 4 == 0, C <= 1024: " + wn);
+    RD_CHECK(out.n == x.n && out.h == x.h && out.w == x.w && out.c == c, "ESE gate: output view mismatch");
+    if (idn) RD_CHECK(idn->n == x.n && idn->h == x.h && idn->w == x.w && idn->c == c, "ESE gate: identity view mismatch");
+    const int hw = x.h * x.w, chunks = ese_gap_chunks(hw);         // (from the layer's map alone, never from the batch)
+    if (!planning()) {
+        if (!pb_->has(wn)) {
+            pb_->add(wn, std::vector<float>(w.f32(), w.f32() + w.numel()));
+            pb_->add(bnm, std::vector<float>(ws_->get(bnm).f32(), ws_->get(bnm).f32() + c));
+        }
+        return;
+    }
+    TView partial = alloc_raw((size_t)x.n * chunks * c);
+    TView gate = alloc(x.n, 1, 1, c);
+    const TView xv = x, pv = partial, gv = gate, yv = out;
+    {
+        OpRecord r;
+        r.name = wn + ":gap";
+        r.kind = "gap";
+        r.bytes = 4.0 * x.pixels() * c;
+        r.run = [xv, pv, hw, c, chunks](const Plan& pl, const RunCtx& cx) {
+            launch_gap_partial(pl.vptr(xv, cx), pl.ld(xv), xv.n, hw, c, pl.vptr(pv, cx), chunks, cx.stream);
+        };
+        emit(std::move(r));
+    }
+    {
+        OpRecord r;
+        r.name = wn + ":fc";
+        r.kind = "ese_gate";
+        r.flops = 2.0 * x.n * c * c;
+        r.bytes = 4.0 * c * c;
+        const float* wp = pb_->ptr(wn);
+        const float* bp = pb_->ptr(bnm);
+        const float inv = 1.f / (float)hw;
+        r.run = [pv, gv, wp, bp, inv, c, chunks](const Plan& pl, const RunCtx& cx) {
+            launch_ese_gate(pl.vptr(pv, cx), chunks, gv.n, c, inv, wp, bp, pl.vptr(gv, cx), cx.stream);
+        };
+        emit(std::move(r));
+    }
+    {
+        OpRecord r;
+        r.name = wn + ":apply";
+        r.kind = "ese_apply";
+        r.bytes = 4.0 * x.pixels() * c * (idn ? 3 : 2);
+        const bool has_id = idn != nullptr;
+        const TView iv = idn ? *idn : TView{};
+        r.run = [xv, gv, yv, iv, has_id, hw, c](const Plan& pl, const RunCtx& cx) {
+            launch_ese_apply(pl.vptr(xv, cx), pl.ld(xv), pl.vptr(gv, cx), has_id ? pl.vptr(iv, cx) : nullptr, has_id ? pl.ld(iv) : 0, pl.vptr(yv, cx),
+                             pl.ld(yv), xv.n, hw, c, cx.stream);
+        };
+        emit(std::move(r));
+    }
+    release(partial);
+    release(gate);
 }
 
 TView Builder::avgpool3x2(const TView& x, const TView* out) {

@@ -271,6 +271,7 @@ void Engine::load_weights(const void* blob, size_t nbytes) {
         rec_token_dim_ = (int)store_.get(model_->token_dim_tensor).shape[1];
     }
     if (model_->derive) model_->derive(store_);
+    if (kind_ == "ppocrv5_det_server" || kind_ == "ppocrv5_rec_server") backbone_ = store_.has(pphgnet_small_marker()) ? "pphgnet_small" : "pphgnetv2_b4";
     Plan dummy;
     h3_prepared_ = precision_ == PREC_H3;
     // the range flag: one word of pinned host memory mapped into the device's address space (rd_device.h rd_raise_flag) - reading

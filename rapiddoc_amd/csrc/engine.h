@@ -179,7 +179,12 @@ class Builder {
     // true when, in THIS plan, the channel mixer of `prefix` will run on the kernel that can take the block's depthwise conv along
     bool mixer_takes_dw(const std::string& prefix, int C) const;
     static std::string dw_key(const std::string& wname, const std::string& bn) { return wname + "|" + bn + "|dw"; }
-    void fold_conv(const std::string& wname, const std::string& bname, const std::string& bn);
+    void fold_conv(const std::string& wname, const std::string& bname, const std::string& bn, int row0 = 0, int nrows = 0);
+    // From here on (until set back to 0, 0) Builder::conv computes output channels [row0, row0 + nrows) of its layer only: weight rows, BatchNorm
+    // and bias of that piece, folded under their own key; `out` is the piece's channel slot.  A wide 3x3 layer as two launches of the
+    // <= 96-channel direct kernel (PPHGNet_small's 160- and 192-channel layers: docs/notebook/v4_server.md)
+    void set_conv_rows(int row0, int nrows) { rows_0_ = row0; rows_n_ = nrows; }
+    static std::string conv_rows_suffix(int row0, int nrows);
     TView linear(const std::string& prefix, const TView& x, int act, const TView* out = nullptr,
                  const TView* res = nullptr);
     // ConvTranspose2d(2, 2) + BN + ReLU -> ConvTranspose2d(2, 2) to ONE channel -> sigmoid, fused when the widths allow (DB head tail)
@@ -266,6 +271,13 @@ class Builder {
     GapOut lcv3_gap(const TView& x, int lt_col);          // SE pooling partial sums of x, one chunk per row
     TView lcv3_pool(const TView& x, Affine post, const TView* out = nullptr);   // the deferred hardswish, avg_pool2d([3, 2]), the deferred affine
     void maxpool2x2s1(const TView& x, const TView& out);
+    TView maxpool3x3s2(const TView& x, const TView* out = nullptr);                // MaxPool2d(3, stride 2, padding 1), -inf padding (kernels_ese.hip)
+    // ESE gate of an HG_Block (kernels_ese.hip): out = x sigmoid(conv1x1(mean_hw(x)) + bias) (+ idn); `prefix`.weight [C][C][1][1], `prefix`.bias;
+    // out may be x itself or a channel slot of another buffer
+    void ese(const std::string& prefix, const TView& x, const TView& out, const TView* idn = nullptr);
+    // From here on (until switched off again) the 3x3 layers that conv3x3_wide_shape_ok serves get that kernel's weight image and ask for
+    // its route in the "auto" precision.  A builder-side opt-in (PPHGNet_small): no layer moves onto the kernel by its shape alone
+    void set_conv3x3_wide(bool on) { wide3x3_ = on; }
     TView avgpool3x2(const TView& x, const TView* out = nullptr);
     // squeeze-excite gate s[n][c]; `w1/b1/w2/b2` full tensor names
     TView se_gate(const std::string& w1, const std::string& b1, const std::string& w2, const std::string& b2,
@@ -307,6 +319,8 @@ class Builder {
     std::vector<Block> blocks_;
     TView lt_;
     bool has_lt_ = false;
+    bool wide3x3_ = false;
+    int rows_0_ = 0, rows_n_ = 0;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -359,6 +373,9 @@ class Engine {
     std::string profile_json() const;
     int n_classes() const { return n_classes_; }
     int rec_token_dim() const { return rec_token_dim_; }   // channels of the rec backbone's pooled tokens (two-stage form)
+    // the backbone the loaded weights picked, for the kinds that serve two ("ppocrv5_det_server", "ppocrv5_rec_server": "pphgnetv2_b4" or
+    // "pphgnet_small", the PP-OCRv4 server files); "" for every other kind and before load_weights
+    const std::string& backbone() const { return backbone_; }
     bool h3() const { return precision_ == PREC_H3; }
     int device() const { return device_; }
     // Arithmetic of the dense layers.  Every mode returns fp32 results with fp32-level error:
@@ -387,6 +404,7 @@ class Engine {
     unsigned* range_flag_host_ = nullptr;     // ... this word of pinned, mapped host memory
     int n_classes_ = 0;
     int rec_token_dim_ = 0;
+    std::string backbone_;
     ParamBlock params_;
     WeightStore store_;
     std::map<std::tuple<int, int, int, int>, std::unique_ptr<Plan>> plans_;
@@ -434,6 +452,9 @@ bool mv1e_dw_strip_default(int sh, int sw, int c);
 // DET_WANT_NECK: ext[2] = the neck output `fuse` NCHW [B,256,H/4,W/4]
 enum DetFlags : int { DET_WANT_NECK = 1, DET_WANT_STAGES = 2 };   // DET_WANT_STAGES: ppocrv3_det_mobile only, developer (rd_debug_det_forward_stages): ext[3..6] = its four stage features NCHW
 void build_ppocrv5_det_server(Builder& b, int B, int H, int W, int flags);
+// The two server kinds take their backbone from the weights: PPHGNet_small (the PP-OCRv4 server files, rec_hgnet.py) when this tensor is
+// among them, PPHGNetV2-B4 otherwise
+inline const char* pphgnet_small_marker() { return "backbone.stages.0.blocks.0.att.conv.weight"; }
 // tensors build_ppocrv5_det_server reads that are not in the file: the three branches of every IntraCL level folded into one k x k convolution
 void derive_ppocrv5_det_server_weights(WeightStore& ws);
 // PP-OCRv5 mobile detector (PPLCNetV3 scale 0.75 det + RSEFPN 96 + DBHead): externals as the server detector; DET_WANT_NECK: ext[2] = `fuse`

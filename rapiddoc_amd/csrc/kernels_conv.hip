@@ -226,7 +226,7 @@ ConvRoute conv_f32_route(const ConvParams& p) {
 }
 
 const char* conv_route_name(ConvRoute r) {
-    static const char* const names[] = {"stream", "c3h1", "c9h1", "direct", "h1w256x128", "dma16w256x128", "dma256x128",
+    static const char* const names[] = {"stream", "c3h1", "c3w", "c9h1", "direct", "h1w256x128", "dma16w256x128", "dma256x128",
                                         "256x128", "128x96", "256x64", "128x32", "128x64", "f32",
                                         "skinny", "128x32", "128x64", "128x96", "128x128"};
     static_assert(sizeof(names) / sizeof(names[0]) == CONV_F32_128x128 + 1, "one name per ConvRoute");

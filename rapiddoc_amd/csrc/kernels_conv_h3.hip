@@ -411,6 +411,7 @@ ConvRoute conv_split_route(const ConvParams& p, bool has_ascale) {
     if (!has_ascale) {      // none of the specialised kernels scales its rows on load: a gated layer goes to the tiles below
         if (conv_stream_h3_applies(p)) return CONV_STREAM;    // small K (stems): HBM-bound, operands streamed from global memory at high occupancy
         if (conv3x3_h1_applies(p)) return CONV_C3H1;          // 3x3 stride 1 pad 1, <= 96 output channels: one accumulator set, two workgroups per CU (round 6)
+        if (conv3x3_wide_applies(p)) return CONV_C3WIDE;      // 3x3 stride 1 pad 1 to 128 .. 256 output channels, only where the builder asked (p.w3w): PPHGNet_small
         if (conv9x9_h1_applies(p)) return CONV_C9H1;          // 9x9 stride 1 pad 4 to 33 .. 64 output channels (LKPAN): the same scheme with a 16 x 40 patch
         if (conv_direct_h3_applies(p)) return CONV_DIRECT;    // 2x2 / 3x3 stride 1, <= 96 output channels: patch in LDS, taps as address offsets
         if (gemm_h1_applies(p)) return CONV_GEMM_H1;          // pointwise, K % 32 == 0, wide: single-accumulator split, two workgroups per CU (kernels_gemm_h1.hip)
@@ -431,6 +432,7 @@ void launch_conv_route(ConvRoute r, const ConvParams& p, hipStream_t s) {
     switch (r) {
         case CONV_STREAM: launch_conv_stream_h3(p, s); break;
         case CONV_C3H1: launch_conv3x3_h1(p, s); break;
+        case CONV_C3WIDE: launch_conv3x3_wide(p, s); break;
         case CONV_C9H1: launch_conv9x9_h1(p, s); break;
         case CONV_DIRECT: launch_conv_direct_h3(p, s); break;
         case CONV_GEMM_H1: launch_gemm_h1(p, s); break;

@@ -407,6 +407,115 @@ static void build_pphgnetv2(Builder& b, const TView& x, const HgStageCfg (&cfg)[
 }
 
 // ---------------------------------------------------------------------------------------------------
+// PPHGNet_small (rec_hgnet.py:255-290): the backbone of the PP-OCRv4 server detector and recogniser, served under the two v5 server kinds
+// when the weights carry it (pphgnet_small_marker).  Stem = three 3x3 ConvBN + ReLU (3 -> 64 stride 2, 64 -> 64, 64 -> 128), det only:
+// MaxPool2d(3, 2, 1).  A stage = optional depthwise 3x3 + BN downsample, then HG_Blocks: six 3x3 + BN + ReLU layers (the first from the
+// block input, the others from their predecessor), a 1x1 + BN + ReLU aggregation over the concatenation, the ESE gate, and - every block
+// but a stage's first - the identity.  The concatenation is never copied: one [B,H,W,in + 6 mid] buffer, block input in slot 0.
+// Each 3x3 layer of 128 .. 224 output channels takes the route hg_small_conv_route gives it; the opt-in to conv3x3_wide_h1
+// (Builder::set_conv3x3_wide) lives here, nowhere else.
+// ---------------------------------------------------------------------------------------------------
+struct HgSmallStageCfg { int cin, mid, cout, blocks; bool down; int sh, sw; };
+static const HgSmallStageCfg kHgSmallDet[4] = {{128, 128, 256, 1, false, 2, 2}, {256, 160, 512, 1, true, 2, 2}, {512, 192, 768, 2, true, 2, 2}, {768, 224, 1024, 1, true, 2, 2}};
+static const HgSmallStageCfg kHgSmallRec[4] = {{128, 128, 256, 1, true, 2, 1}, {256, 160, 512, 1, true, 1, 2}, {512, 192, 768, 2, true, 2, 1}, {768, 224, 1024, 1, true, 2, 1}};
+static const int kHgSmallLayers = 6;
+
+// The route of one wide 3x3 layer, by the LAYER (never by the batch or the map), from the per-layer A/B of tools/mb_v4_server.py at the
+// detector's and the recogniser's map sizes (profiles/mb_v4_server.txt, docs/notebook/v4_server.md):
+//   WIDE     conv3x3_wide_h1: 64 -> 128, 128 -> 128 and 768 -> 192 (1.36 - 1.77 x the generic route, level with the pieces where those exist);
+//   PIECES   two launches of conv3x3_h1 over <= 96 output channels (Cin <= 512): the 160- and 192-channel layers, where they measure
+//            1.05 - 1.33 x the new kernel (two independent workgroups per CU hide the patch staging that its one workgroup exposes);
+//   GENERIC  the split implicit GEMM: the 224-channel layers of stage 4, whose 1/32 maps (30 x 22 per page, 3 x 272 per line) leave
+//            much of an 8 x 32 tile empty - the new kernel measures 0.64 x (recogniser) to 0.99 x (detector) of it there.
+enum HgSmallConvRoute { HG_CONV_WIDE, HG_CONV_PIECES, HG_CONV_GENERIC };
+static HgSmallConvRoute hg_small_conv_route(int cin, int cout) {
+    if (cout >= 224) return HG_CONV_GENERIC;
+    if (cout > 128 && conv3x3_h1_shape_ok(3, 3, cin, 96)) return HG_CONV_PIECES;
+    return HG_CONV_WIDE;
+}
+static void hg_small_conv3x3(Builder& b, const std::string& w, const std::string& bn, const TView& x, const TView& out) {
+    const HgSmallConvRoute route = hg_small_conv_route(x.c, out.c);
+    if (route == HG_CONV_PIECES) {
+        for (int r0 = 0; r0 < out.c; r0 += 96) {
+            const int n = std::min(96, out.c - r0);
+            TView piece = b.slice(out, r0, n);
+            b.set_conv_rows(r0, n);
+            b.conv(w, "", bn, x, geom(3), ACT_RELU, &piece);
+        }
+        b.set_conv_rows(0, 0);
+        return;
+    }
+    b.set_conv3x3_wide(route == HG_CONV_WIDE);      // the opt-in: only here does a layer ask for the new kernel
+    b.conv(w, "", bn, x, geom(3), ACT_RELU, &out);
+    b.set_conv3x3_wide(false);
+}
+
+template <typename Emit>
+static void build_pphgnet_small(Builder& b, const TView& x, bool det, const std::string& pre, Emit emit) {
+    const HgSmallStageCfg (&cfg)[4] = det ? kHgSmallDet : kHgSmallRec;
+    const int B = x.n;
+    auto cw = [&](const std::string& p) { return pre + p + ".conv.weight"; };
+    auto bn = [&](const std::string& p) { return pre + p + ".bn"; };
+    TView e = b.stem3x3s2(cw("stem.0"), bn("stem.0"), x, ACT_RELU);
+    TView s1 = b.conv(cw("stem.1"), "", bn("stem.1"), e, geom(3), ACT_RELU);
+    b.release(e);
+    TView cur_cat = b.alloc(B, s1.h, s1.w, 128);
+    hg_small_conv3x3(b, cw("stem.2"), bn("stem.2"), s1, cur_cat);
+    b.release(s1);
+    TView cur = cur_cat;
+    for (int si = 0; si < 4; ++si) {
+        const HgSmallStageCfg& c = cfg[si];
+        const std::string sp = "stages." + std::to_string(si);
+        RD_CHECK(c.down || (det && si == 0), "PPHGNet_small: only the detector's first stage has no downsample (the stem's max-pool feeds it)");
+        {   // the stage input goes straight into slot 0 of the first block's concat buffer
+            const int oh = (cur.h + 2 - 3) / c.sh + 1, ow = (cur.w + 2 - 3) / c.sw + 1;
+            TView ncat = b.alloc(B, oh, ow, c.cin + kHgSmallLayers * c.mid);
+            TView nin = b.slice(ncat, 0, c.cin);
+            if (c.down) {
+                G gd = geom(3, 2);
+                gd.sh = c.sh;
+                gd.sw = c.sw;
+                b.dwconv(cw(sp + ".downsample"), "", bn(sp + ".downsample"), cur, gd, ACT_NONE, &nin);
+            } else {
+                b.maxpool3x3s2(cur, &nin);
+            }
+            b.release(cur_cat);
+            cur_cat = ncat;
+            cur = nin;
+        }
+        for (int bi = 0; bi < c.blocks; ++bi) {
+            const std::string bp = sp + ".blocks." + std::to_string(bi);
+            const int cin = bi == 0 ? c.cin : c.cout;
+            TView prev = cur;
+            for (int li = 0; li < kHgSmallLayers; ++li) {
+                const std::string lp = bp + ".layers." + std::to_string(li);
+                TView slot = b.slice(cur_cat, cin + li * c.mid, c.mid);
+                hg_small_conv3x3(b, cw(lp), bn(lp), prev, slot);
+                prev = slot;
+            }
+            TView agg = b.conv(cw(bp + ".aggregation_conv"), "", bn(bp + ".aggregation_conv"), cur_cat, geom(1), ACT_RELU);
+            const bool identity = bi > 0;
+            if (bi + 1 < c.blocks) {     // the gated output is the next block's input: slot 0 of its concat buffer
+                TView ncat = b.alloc(B, cur.h, cur.w, c.cout + kHgSmallLayers * c.mid);
+                TView nout = b.slice(ncat, 0, c.cout);
+                b.ese(pre + bp + ".att.conv", agg, nout, identity ? &cur : nullptr);
+                b.release(agg);
+                b.release(cur_cat);
+                cur_cat = ncat;
+                cur = nout;
+            } else {
+                b.ese(pre + bp + ".att.conv", agg, agg, identity ? &cur : nullptr);
+                b.release(cur_cat);
+                cur_cat = agg;
+                cur = agg;
+            }
+        }
+        emit(si, cur);
+    }
+    b.release(cur_cat);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // PP-OCRv5 server det (arch_config.yaml ch_PP-OCRv5_det_server): PPHGNetV2_B4(det=True) -> LKPAN(256, mode large, intracl) -> PFHeadLocal
 // (mode large).  ext[0] = x NCHW [B,3,H,W]; ext[1] = maps [B,1,H,W]; DET_WANT_NECK: ext[2] = fuse NCHW [B,256,H/4,W/4].
 // head.thresh.* is in the file and unused in eval mode: never asked for.
@@ -456,7 +565,9 @@ void build_ppocrv5_det_server(Builder& b, int B, int H, int W, int flags) {
 
     // backbone; ins_conv[i] (1x1 to 256) runs while stage i's buffer is live
     TView in[4];
-    build_pphgnetv2(b, x, kB4Det, "backbone.", [&](int si, const TView& v) { in[si] = b.conv(idx("neck.ins_conv", si), "", "", v, geom(1), ACT_NONE); });
+    auto ins = [&](int si, const TView& v) { in[si] = b.conv(idx("neck.ins_conv", si), "", "", v, geom(1), ACT_NONE); };
+    if (b.has_weight(std::string(pphgnet_small_marker()))) build_pphgnet_small(b, x, true, "backbone.", ins);      // the PP-OCRv4 server file
+    else build_pphgnetv2(b, x, kB4Det, "backbone.", ins);
     for (int i = 2; i >= 0; --i) b.upsample(in[i + 1], in[i], 2, true);          // out4, out3, out2 in place
     TView f[4];
     for (int i = 3; i >= 0; --i) {
@@ -553,7 +664,7 @@ static int rec_tokens_of_width(int W) {      // rd_rec_seq_len
 static TView pphgnetv2_rec_tokens(Builder& b, const TView& x, int B, int Cb, bool backbone_only) {
     TView h;
     // the height collapse avg_pool2d([3, 2]) runs while the last stage's buffer is live
-    build_pphgnetv2(b, x, kB4Rec, "backbone.", [&](int si, const TView& v) {
+    auto pool = [&](int si, const TView& v) {
         if (si != 3) return;
         RD_CHECK(v.c == Cb, "rec server: backbone width");
         if (backbone_only) {
@@ -562,7 +673,9 @@ static TView pphgnetv2_rec_tokens(Builder& b, const TView& x, int B, int Cb, boo
         } else {
             h = b.avgpool3x2(v);
         }
-    }, 1);
+    };
+    if (b.has_weight(std::string(pphgnet_small_marker()))) build_pphgnet_small(b, x, false, "backbone.", pool);   // the PP-OCRv4 server file (1024-wide tokens)
+    else build_pphgnetv2(b, x, kB4Rec, "backbone.", pool, 1);
     return h;
 }
 

@@ -50,6 +50,10 @@ struct ConvParams {
     const uint16_t* w9 = nullptr;
     float w9_inv = 0.f;
     int fast_epi = 1;               // interior tiles of the split implicit-GEMM kernels store through buffer accesses (round 5; RD_CONV_FAST_EPI=0: A/B)
+    // one-accumulator direct 3x3 to 128 .. 256 output channels (kernels_conv3x3_wide.hip): set only for the layers of a builder that asked for
+    // the route (Builder::set_conv3x3_wide), so no other layer of that shape moves
+    const uint16_t* w3w = nullptr;
+    float w3w_inv = 0.f;
 };
 // The kernel a dense convolution runs on.  The route of an op is decided ONCE - by conv_split_route (ops that carry p.wh / p.wl) or
 // conv_f32_route - from the geometry, the weight-image pointers, the mode fields (act, out_mode, allow_skinny, ln_g) and the RD_* switches;
@@ -57,7 +61,7 @@ struct ConvParams {
 // multiplies its rows by `ascale` is passed in.  The builder names the op with conv_route_name and launches with launch_conv_route.
 enum ConvRoute : int {
     // split-fp16 path, in the order conv_split_route asks (the *_applies predicate next to each kernel)
-    CONV_STREAM, CONV_C3H1, CONV_C9H1, CONV_DIRECT, CONV_GEMM_H1, CONV_DMA16, CONV_DMA8,
+    CONV_STREAM, CONV_C3H1, CONV_C3WIDE, CONV_C9H1, CONV_DIRECT, CONV_GEMM_H1, CONV_DMA16, CONV_DMA8,
     CONV_H3_256x128, CONV_H3_128x96, CONV_H3_256x64, CONV_H3_128x32, CONV_H3_128x64,   // the staged implicit-GEMM tiles (kernels_conv_h3.hip)
     CONV_H3_TO_F32,       // a tensor beyond the staged kernels' 32-bit offsets: whatever conv_f32_route says, at launch
     // fp32 MFMA path (kernels_conv.hip)
@@ -107,6 +111,14 @@ bool conv3x3_h1_shape_ok(int kh, int kw, int cin, int cout);   // host-side: whi
 bool conv3x3_h1_applies(const ConvParams& p);
 void launch_conv3x3_h1(const ConvParams& p, hipStream_t s);
 float prepare_conv3x3_h1_weights(const float* w, int N, int Cin, std::vector<uint16_t>& img);   // returns the inverse scale
+// direct 3x3 / stride 1 / pad 1 to 128 .. 256 output channels (multiples of 32) from 64 .. 768 input channels, one accumulator set, eight
+// wavefronts on one staged patch (kernels_conv3x3_wide.hip): PPHGNet_small's HG_Block layers.  Needs p.w3w / p.w3w_inv, which only a builder
+// that opted in sets; refuses (and the layer takes the generic route) an image of 2^31 bytes or more, and a layer with a residual (p.rld != 0:
+// the planner sets rld only with one).  RD_CONV3X3_WIDE=0: A/B switch
+bool conv3x3_wide_shape_ok(int kh, int kw, int cin, int cout);
+bool conv3x3_wide_applies(const ConvParams& p);
+void launch_conv3x3_wide(const ConvParams& p, hipStream_t s);
+float prepare_conv3x3_wide_weights(const float* w, int N, int Cin, std::vector<uint16_t>& img);   // returns the inverse scale
 // direct 9x9 / stride 1 / pad 4 to 33 .. 64 output channels, one accumulator set, two workgroups per CU (kernels_conv9x9_h1.hip): LKPAN
 bool conv9x9_h1_shape_ok(int kh, int kw, int cin, int cout);   // host-side: which layers get a weight image
 bool conv9x9_h1_applies(const ConvParams& p);
@@ -409,6 +421,14 @@ void launch_det_local(const DetLocalParams& p, hipStream_t s);
 float prepare_det_local_weights(const float* w3_folded, std::vector<float>& img32, std::vector<uint16_t>& img16);   // returns the inverse scale
 void launch_scale_channels(const float* x, int xld, float* y, int yld, const float* scale, float alpha,
                            int N, int HW, int C, hipStream_t s);
+// ESE gate of PPHGNet_small's HG_Block (kernels_ese.hip): s[n][c] = sigmoid(b[c] + sum_k w[c][k] mean[n][k]) from launch_gap_partial's sums
+// (chunks = ese_gap_chunks(H W): from the layer's map alone), C % 4 == 0 up to 1024; then y = x s (+ idn), in place or into a channel slot
+bool ese_shape_ok(int c);
+int ese_gap_chunks(int hw);
+void launch_ese_gate(const float* partial, int chunks, int N, int C, float inv_hw, const float* w, const float* b, float* s, hipStream_t st);
+void launch_ese_apply(const float* x, int xld, const float* s, const float* idn, int ild, float* y, int yld, int N, int HW, int C, hipStream_t st);
+// MaxPool2d(3, stride 2, padding 1) with torch's -inf padding: y [N][(H - 1) / 2 + 1][(W - 1) / 2 + 1][C], C % 4 == 0
+void launch_maxpool3x3s2(const float* x, int xld, float* y, int yld, int N, int H, int W, int C, hipStream_t st);
 
 // y[n,h,w,:] (+)= x[n,h/f,w/f,:]   (nearest-neighbour upsample by integer factor f)
 void launch_upsample(const float* x, int xld, float* y, int yld, int N, int H, int W, int C, int f, int accumulate,

@@ -397,6 +397,13 @@ class RdEngine:
         self._guarded(launch)
         return idx, prob, (full if want_full else None)
 
+    @property
+    def backbone(self) -> str:
+        """The backbone the loaded weights picked (read-only): "pphgnetv2_b4" or "pphgnet_small" for the two server kinds - a PP-OCRv4
+        server state dict (ch_PP-OCRv4_det_server / _rec_server) loads under "ppocrv5_det_server" / "ppocrv5_rec_server" with PPHGNet_small;
+        "" for every other kind."""
+        return (self._l.rd_backbone_name(self._h) or b"").decode()
+
     # two-stage form of the recogniser (include/rapiddoc_mi355.h: rd_rec_backbone_forward / rd_rec_tail_forward)
     @property
     def rec_token_dim(self) -> int:

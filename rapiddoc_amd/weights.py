@@ -65,6 +65,13 @@ _KIND_GAINS["ppocrv3_det_mobile"] = (
 _KIND_GAINS["ppocr_cls_mobile"] = (
     (lambda n: n == "head.fc.weight", 300.0),
 )
+# PP-OCRv4 server detector / recogniser (PPHGNet_small): under the plain rule every ESE gate of the backbone sits near 0.5 (pre-sigmoid
+# logits of std 0.2 - 0.9) and a wrong gate would hardly show in the outputs.  A gain per HG_Block on `att.conv.weight` brings the logits
+# of every block to a std of 1.2 - 1.9 on the fixtures' inputs (tests/golden/summary_v4_server.json records them); the biases keep the plain draw
+_KIND_GAINS["ppocrv4_server"] = tuple(
+    (lambda n, blk=blk: n == "backbone.%s.att.conv.weight" % blk, g)
+    for blk, g in (("stages.0.blocks.0", 2.0), ("stages.1.blocks.0", 3.0), ("stages.2.blocks.0", 4.0), ("stages.2.blocks.1", 6.0),
+                   ("stages.3.blocks.0", 5.0)))
 _KIND_OFFSETS = {
     "ppocr_cls_mobile": (
         (lambda n: n == "head.fc.bias", (-11.6, 11.6)),
